@@ -6,12 +6,17 @@ proposal, multinomial resampling EVERY step, T = --steps time steps.  One bench 
 filter time step over all particles = pf_resample!(state, :multinomial) + pf_update!(state, ...).
 Metric: particle-steps/sec = (particles on all GPUs) * steps / wall seconds, inputs resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0) with the extra objects `roofline` (dominant kernel, HIP-event timed on
-the handle's stream) and `cpu_baseline` (the C oracle = a port of the reference algorithm, timed on
-this box's host cores on a bounded sample; rank 0, N=1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, runs W warm-up and K timed steps, writes the
+outputs of the last timed step if --dump-outputs is given, and prints the line: `value`, `ms_per_step`
+and the filter's log-ML estimate.  --full adds everything else, each in passes of its own behind the
+timed loop: `roofline` (dominant kernel, HIP-event timed on the handle's stream), `cpu_baseline` (the
+C oracle = a port of the reference algorithm, timed on the host cores on a bounded sample; rank 0,
+N=1 only), the stand-alone gather leg, the named variants and, with several ranks, the exchange plans,
+phases and transport calibration; the exact log-ML of the Kalman recursion beside the estimate.
+Without --full those fields are null.
 """
 import argparse
 import gc
@@ -28,6 +33,8 @@ AUX_STEPS = 30             # steps of the stand-alone gather leg
 CPU_STEPS = 80             # steps of the cpu_baseline sample: ~13 s on one host core at N = 1e6 (a bounded sample of the same workload)
 SEED = 1
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_BYTES = 64_000_000    # --dump-outputs: all files of all ranks together, .npy headers included, stay within this
+NPY_HEADER = 128           # bytes np.save puts in front of a 1-D or 2-D float64 array
 
 
 def kernel_sources_sha16() -> str:
@@ -53,6 +60,28 @@ def algorithmic_bytes(d: int, W: int):
         "k_search": 8 + 4,                 # R cdf cell, W ancestor (k_search_multi reads 2-byte offsets instead: fewer bytes, same figure kept)
         "k_gather": 4 + row + row + 8,     # R ancestor, R row, W row, W lw  (16d + 12)
     }
+
+
+def dump_outputs(out_dir: str, state, lml: float, rank: int, world: int) -> None:
+    """--dump-outputs: what a caller of the timed path holds after its last step, as DIR/<name>.npy in float64 -- the particles
+    (get_traces rows), their log-weights, the ancestors of the last resample (int64 ids, exact in float64) and the log-ML estimate.
+    With several ranks every rank writes its own shard as <name>_rank<r>.npy.  A shard over its share of DUMP_BYTES keeps the same
+    fixed, seeded sample of particles in every array; sample_index holds their sorted indices."""
+    import numpy as np
+    arrays = {"traces": state.traces, "log_weights": state.log_weights, "parents": state.parents.astype(np.float64)}
+    n = state.n_particles
+    per_particle = sum(a.nbytes for a in arrays.values()) // n
+    budget = DUMP_BYTES // world - 8 - 5 * NPY_HEADER               # (the log-ML scalar; at most five files)
+    if n * per_particle > budget:
+        m = budget // (per_particle + 8)
+        idx = np.sort(np.random.default_rng(SEED).choice(n, m, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    arrays["log_ml_estimate"] = np.array([lml], np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a, np.float64))
 
 
 def _free_port() -> int:
@@ -129,17 +158,26 @@ def main():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--particles-per-gpu", type=int, default=N_PER_GPU)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step (particles, log-weights, ancestors, log-ML estimate) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: roofline, stand-alone gather leg, named variants, CPU baseline, exact log-ML (multi-rank: plans, "
+                         "phases, transports); a plain run only times the headline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the headline loop (no stand-alone gather leg, no named variants, no CPU baseline): what the PMC passes profile, so that "
-                         "a kernel's mean counters are not mixed with the variants' launches of the same kernel")
+                    help="--full with only the headline loop and its roofline (no stand-alone gather leg, no named variants, no CPU baseline): what "
+                         "the PMC passes profile, so that a kernel's mean counters are not mixed with the variants' launches of the same kernel")
     ap.add_argument("--launch-timeout", type=float, default=float(os.environ.get("GPF_BENCH_LAUNCH_TIMEOUT", "1500")),
                     help="wall-clock bound (s) of the self-launched multi-rank job")
     args = ap.parse_args()
+    args.full = args.full or args.no_cpu_baseline or args.headline_only    # (both shape the --full run)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # BEFORE torch is imported or any GPU call is made
-        sys.exit(launch_ranks(args.gpus, sys.argv[1:], args.launch_timeout))
+        argv = sys.argv[1:]
+        if args.dump_outputs:                                    # the ranks start in ROOT: the directory as this process sees it
+            argv += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
+        sys.exit(launch_ranks(args.gpus, argv, args.launch_timeout))
 
     import numpy as np
     import torch
@@ -270,7 +308,7 @@ def main():
         step(t); t += 1
     barrier()
     headline_traffic = None
-    if sharded_mode and getattr(state.backend, "lib_comm", False):
+    if args.full and sharded_mode and getattr(state.backend, "lib_comm", False):
         state.backend.traffic(reset=True)
     t0 = time.perf_counter()
     for _ in range(K):
@@ -278,7 +316,7 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
-    if sharded_mode and getattr(state.backend, "lib_comm", False):
+    if args.full and sharded_mode and getattr(state.backend, "lib_comm", False):
         headline_traffic = state.backend.traffic(reset=True)
     if dist is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if one_device else "cuda")
@@ -286,67 +324,70 @@ def main():
         elapsed = float(tt.item())
     value = n_global * K / elapsed
     lml = sharded.get_lml_est(state) if sharded_mode else g.get_lml_est(state)
+    local = state.local if sharded_mode else state
+    if args.dump_outputs:                                        # before any --full pass below moves the filter on
+        dump_outputs(args.dump_outputs, local, lml, rank, world)
     # BASELINE.json's metric also names the log-ML error: the model is linear-Gaussian, so the exact log p(y_1:T) of the
     # observations consumed so far is a Kalman recursion away (host, NumPy)
-    lml_exact = g.models.kalman_loglik(model, ys[:t]) if rank == 0 else None
+    lml_exact = g.models.kalman_loglik(model, ys[:t]) if rank == 0 and args.full else None
 
     # ---- roofline of the dominant kernel: HIP events around every launch, on the handle's stream ----
     roofline = None
-    local = state.local if sharded_mode else state
     kid_names = g._lib.KERNEL_NAMES
     kids = [g._lib.K_STEP, g._lib.K_MAX, g._lib.K_SCAN, g._lib.K_SEARCH, g._lib.K_GATHER]
-    n_ev = min(K, 200)
-    for kid in kids:
-        local.kernel_timing(kid, True)
-    tt_ = 1
-    for _ in range(n_ev):
-        step(tt_); tt_ += 1
-    per = {}
-    for kid in kids:
-        ms, cnt = local.kernel_time(kid)
-        local.kernel_timing(kid, False)
-        if cnt:
-            per[kid_names[kid]] = (ms / cnt * 1e3, cnt)          # us per launch
-    if sharded_mode:
-        # the sharded resample times its two kernels under the search / gather ids: k_push_scan (every shard evaluates the
-        # targets of ALL output slots and stages its hits: W 16 B per hit) and k_push (R staged hit, R cdf cell, R row, W packed row)
-        per = {{"k_search": "k_push_scan", "k_gather": "k_push"}.get(k, k): v for k, v in per.items()}
-    if per and rank == 0:
-        ab = algorithmic_bytes(model.dim, local.row_width)
-        ab["k_push_scan"] = 16
-        ab["k_push"] = 16 + 8 + 8 * local.row_width + 8 * local.row_width + 8
-        share = {k: v[0] * v[1] for k, v in per.items()}
-        dom = max(share, key=share.get)
-        us = per[dom][0]
-        achieved = ab[dom] * n_local / (us * 1e-6) / 1e9
-        # HBM-side bytes per launch from the committed rocprofv3 PMC passes (profiles/pmc_traffic.json; FETCH_SIZE +
-        # WRITE_SIZE collected in separate runs and corrected as MI355X_MICROARCH.md §HBM prescribes); only valid for
-        # the workload they were measured on
-        traffic, traffic_source = None, None
-        try:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
-            sha = kernel_sources_sha16()
-            if n_local != N_PER_GPU or dom not in pmc["kernels"]:
-                traffic_source = "none: no PMC pass for this kernel / size"
-            elif pmc.get("kernel_sources_sha16") != sha:
-                # the counters were collected on other kernel sources than the ones being timed: do not quote them
-                traffic_source = (f"stale: profiles/pmc_traffic.json (tag {pmc.get('tag')}) was collected on kernel sources "
-                                  f"{pmc.get('kernel_sources_sha16')}, this build is {sha}")
-            else:
-                traffic = pmc["kernels"][dom]["traffic_bytes"]
-                traffic_source = {"file": "profiles/pmc_traffic.json", "tag": pmc.get("tag"), "kernel_sources_sha16": sha,
-                                  "passes": f"profiles/{pmc.get('tag')}_pmc_FETCH_SIZE.csv, profiles/{pmc.get('tag')}_pmc_WRITE_SIZE.csv"}
-        except Exception as e:                                   # noqa: BLE001
-            traffic, traffic_source = None, f"none: {e!r}"
-        roofline = {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                    "algorithmic_bytes_per_launch": ab[dom] * n_local, "avg_launch_us": round(us, 2),
-                    "all_kernels_us": {k: round(v[0], 2) for k, v in per.items()}}
+    if args.full:
+        n_ev = min(K, 200)
+        for kid in kids:
+            local.kernel_timing(kid, True)
+        tt_ = 1
+        for _ in range(n_ev):
+            step(tt_); tt_ += 1
+        per = {}
+        for kid in kids:
+            ms, cnt = local.kernel_time(kid)
+            local.kernel_timing(kid, False)
+            if cnt:
+                per[kid_names[kid]] = (ms / cnt * 1e3, cnt)          # us per launch
+        if sharded_mode:
+            # the sharded resample times its two kernels under the search / gather ids: k_push_scan (every shard evaluates the
+            # targets of ALL output slots and stages its hits: W 16 B per hit) and k_push (R staged hit, R cdf cell, R row, W packed row)
+            per = {{"k_search": "k_push_scan", "k_gather": "k_push"}.get(k, k): v for k, v in per.items()}
+        if per and rank == 0:
+            ab = algorithmic_bytes(model.dim, local.row_width)
+            ab["k_push_scan"] = 16
+            ab["k_push"] = 16 + 8 + 8 * local.row_width + 8 * local.row_width + 8
+            share = {k: v[0] * v[1] for k, v in per.items()}
+            dom = max(share, key=share.get)
+            us = per[dom][0]
+            achieved = ab[dom] * n_local / (us * 1e-6) / 1e9
+            # HBM-side bytes per launch from the committed rocprofv3 PMC passes (profiles/pmc_traffic.json; FETCH_SIZE +
+            # WRITE_SIZE collected in separate runs and corrected for the MI355X's HBM accounting); only valid for
+            # the workload they were measured on
+            traffic, traffic_source = None, None
+            try:
+                pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
+                sha = kernel_sources_sha16()
+                if n_local != N_PER_GPU or dom not in pmc["kernels"]:
+                    traffic_source = "none: no PMC pass for this kernel / size"
+                elif pmc.get("kernel_sources_sha16") != sha:
+                    # the counters were collected on other kernel sources than the ones being timed: do not quote them
+                    traffic_source = (f"stale: profiles/pmc_traffic.json (tag {pmc.get('tag')}) was collected on kernel sources "
+                                      f"{pmc.get('kernel_sources_sha16')}, this build is {sha}")
+                else:
+                    traffic = pmc["kernels"][dom]["traffic_bytes"]
+                    traffic_source = {"file": "profiles/pmc_traffic.json", "tag": pmc.get("tag"), "kernel_sources_sha16": sha,
+                                      "passes": f"profiles/{pmc.get('tag')}_pmc_FETCH_SIZE.csv, profiles/{pmc.get('tag')}_pmc_WRITE_SIZE.csv"}
+            except Exception as e:                                   # noqa: BLE001
+                traffic, traffic_source = None, f"none: {e!r}"
+            roofline = {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                        "algorithmic_bytes_per_launch": ab[dom] * n_local, "avg_launch_us": round(us, 2),
+                        "all_kernels_us": {k: round(v[0], 2) for k, v in per.items()}}
 
     # ---- the stand-alone resample gather (BASELINE.json names it): the hot loop above fuses the gather into the next
     #      propagate, so time k_gather itself on the same state by asking for the ESS between resample and update
     gather = None
-    if not sharded_mode and rank == 0 and not args.headline_only:
+    if args.full and not sharded_mode and rank == 0 and not args.headline_only:
         gather = {}
         W = state.row_width
         gbytes = (4 + 8 * W + 8 * W + 8) * n_local                # R anc, R row (random), W row, W lw = 16d + 12
@@ -423,7 +464,7 @@ def main():
                 "ms_per_step": round(seconds / k * 1e3, 5)}
 
     strat = island = plans = sorted_variant = strat_sorted = links = exchange_modes = calibration = headline_phases = None
-    if not sharded_mode and not args.headline_only:
+    if args.full and not sharded_mode and not args.headline_only:
         # the OPT-IN sorted form of the multinomial resampler (gpf.h GPF_RESAMPLE_MULTINOMIAL_SORTED): same offspring-count
         # law, ancestors in non-decreasing order -- NOT the reference's slot order, so a named variant beside the unchanged headline
         kv = min(K, 200)
@@ -457,7 +498,7 @@ def main():
             g.pf_update(state, (tq + 1,), (None,), ys[1 + tq % (n_obs - 1)])
         strat_sorted = variant_line("same filter, stratified resample every step with the reference's default sort_particles=true",
                                     kv, variant(strat_sorted_step, kv))
-    if sharded_mode:
+    if args.full and sharded_mode:
         kv = min(K, 200)
 
         def step_of(method, **kw):
@@ -612,7 +653,7 @@ def main():
 
     # ---- CPU baseline: the oracle (port of the reference algorithm), bounded sample, rank 0 / N=1 only ----
     cpu = cpu_all = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.headline_only:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.headline_only:
         from oracle import oracle as o          # cpu_baseline leg: the only place bench.py touches oracle/
         o.lib()
         n_cpu, k_cpu = n_local, CPU_STEPS
@@ -661,7 +702,7 @@ def main():
                               if getattr(state.backend, "lib_comm", False) else
                               f"python: sharded.py composes the phases over torch.distributed ({dist.get_backend() if dist is not None and dist.is_initialized() else 'no'} backend, {world} rank(s))"
                               + (f"; {engine_note}" if engine_note else ""))),
-            "log_ml_estimate": lml, "log_ml_exact_kalman": lml_exact, "log_ml_abs_error": abs(lml - lml_exact),
+            "log_ml_estimate": lml, "log_ml_exact_kalman": lml_exact, "log_ml_abs_error": None if lml_exact is None else abs(lml - lml_exact),
             "rccl_ranks": rccl_ranks,
             "shard_summaries": (state.backend.summary_mode() if sharded_mode and hasattr(state.backend, "summary_mode") else None),
             "roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_multithread": cpu_all, "resample_gather_kernel": gather,

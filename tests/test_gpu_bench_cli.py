@@ -1,5 +1,6 @@
 """The driver's own bench command on the GPU box: `python bench.py --gpus 1 --steps 20 --warmup 5` must exit 0 and its
-LAST stdout line must be the JSON line with roofline + cpu_baseline (BENCH_r01 had rc 1 on exactly this command)."""
+LAST stdout line must be the JSON line (BENCH_r01 had rc 1 on exactly this command); with --full it carries roofline +
+cpu_baseline, and --dump-outputs writes the same arrays with and without --full."""
 import json
 import os
 import subprocess
@@ -11,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("argv", [["--gpus", "1", "--steps", "20", "--warmup", "5"], ["--steps", "1", "--warmup", "0", "--no-cpu-baseline"]])
+@pytest.mark.parametrize("argv", [["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], ["--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--full"]])
 def test_driver_command_line(built, argv):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -28,6 +29,32 @@ def test_driver_command_line(built, argv):
     assert out["log_ml_abs_error"] < 1.0
 
 
+@pytest.mark.gpu
+def test_plain_command_line_dumps_what_the_full_run_computes(built, tmp_path):
+    """the plain command times the headline and nothing else; its --dump-outputs arrays (the state after the last timed step) are
+    the ones a --full run of the same arguments writes, bit for bit: same seeded inputs, same filter, in two processes"""
+    import numpy as np
+    outs = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--headline-only"])):
+        argv = ["--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(tmp_path / name)] + extra
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-2000:]
+        outs[name] = json.loads(p.stdout.strip().splitlines()[-1])
+    out = outs["plain"]
+    assert out["steps"] == 20 and out["warmup"] == 5 and out["dtype"] == "f64" and out["value"] > 5e7
+    assert abs(out["value"] - 1e6 * 1e3 / out["ms_per_step"]) < 1e-3 * out["value"]
+    assert out["roofline"] is None and out["cpu_baseline"] is None and out["multinomial_sorted_variant"] is None and out["log_ml_abs_error"] is None
+    assert outs["full"]["roofline"]["kernel"] and outs["full"]["log_ml_estimate"] == out["log_ml_estimate"]
+    names = {"traces.npy", "log_weights.npy", "parents.npy", "log_ml_estimate.npy"}
+    assert {f.name for f in (tmp_path / "plain").iterdir()} == names
+    assert sum(f.stat().st_size for f in (tmp_path / "plain").iterdir()) <= 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)
+        assert a.dtype == np.float64 and np.array_equal(a, b), n
+    assert np.load(tmp_path / "plain" / "traces.npy").shape == (1_000_000, 2)
+    assert np.load(tmp_path / "plain" / "log_ml_estimate.npy").tolist() == [out["log_ml_estimate"]]
+
+
 def _last_json(stdout):
     return json.loads([ln for ln in stdout.strip().splitlines() if ln.startswith("{")][-1])
 
@@ -39,7 +66,7 @@ def test_two_ranks_one_device_smoke(built):
     env = dict(os.environ, GPF_BENCH_ONE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29731", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-           "--particles-per-gpu", "200000"]
+           "--particles-per-gpu", "200000", "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     out = _last_json(p.stdout)
@@ -54,7 +81,7 @@ def test_sharded_path_with_rccl_one_rank(built):
     """one rank, the sharded code path, every collective issued by the library on a real (1-rank) RCCL communicator"""
     env = dict(os.environ, GPF_BENCH_FORCE_SHARDED="1", GPF_SHARD_FORCE_COLLECTIVES="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29733",
                RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline"], cwd=ROOT, env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--full"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     out = _last_json(p.stdout)
@@ -95,19 +122,24 @@ def test_two_ranks_library_engine_over_loopback(built, tmp_path):
 
 
 @pytest.mark.gpu
-def test_plain_command_self_launches_two_ranks(built):
+def test_plain_command_self_launches_two_ranks(built, tmp_path):
     """the driver's scaling command as the driver types it -- plain `python bench.py --gpus 2 ...`, no torchrun, no WORLD_SIZE:
     bench.py starts the two ranks itself as a child job (round 2: SystemExit, rc 1).  Both ranks on cuda:0 here."""
     env = dict(os.environ, GPF_BENCH_ONE_DEVICE="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-                        "--particles-per-gpu", "200000"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--particles-per-gpu", "200000", "--dump-outputs", "dumps"], cwd=tmp_path, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads(p.stdout.strip().splitlines()[-1])                      # the LAST stdout line, nothing after it
     assert out["n_gpus"] == 2 and out["steps"] == 20 and out["warmup"] == 5 and out["config"]["particles_total"] == 400000
     assert out["rccl_ranks"] == 0 and out["shard_engine"].startswith("python")      # gloo staging: no RCCL in this run, and the line says so
     assert out["value"] > 0 and out["scaling"] == "weak"
+    # --dump-outputs relative to the caller's directory, one shard per rank
+    import numpy as np
+    for r in (0, 1):
+        assert np.load(tmp_path / "dumps" / f"traces_rank{r}.npy").shape == (200_000, 2)
+        assert np.load(tmp_path / "dumps" / f"log_ml_estimate_rank{r}.npy").tolist() == [out["log_ml_estimate"]]
 
 
 @pytest.mark.gpu
@@ -123,7 +155,7 @@ def test_two_ranks_line_explains_itself(built, tmp_path):
                     "-o", str(lib)], check=True)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29739", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "2",
-           "--particles-per-gpu", "100000"]
+           "--particles-per-gpu", "100000", "--full"]
     ests = {}
     for plan in ("push", "pull"):
         env = dict(os.environ, GPF_BENCH_ONE_DEVICE="1", GPF_SHARD_ENGINE="library", GPF_RCCL_LIBRARY=str(lib), GPF_SHARD_PLAN=plan)

@@ -7,7 +7,7 @@
 #   tests[:EXPR]          pytest -m gpu (optionally -k EXPR) -> gpurun_out/TAG_pytest.log
 #   soak                  pytest -m "gpu or gpu_soak": the driver's set PLUS the wide multi-process matrices (tests/conftest.py soak_grid) -> TAG_pytest_soak.log
 #   file:PATH[:EXPR]      pytest -m gpu on one test file
-#   bench[:STEPS]         python bench.py --steps STEPS (default 1000) --warmup 20 -> TAG_bench.json
+#   bench[:STEPS]         python bench.py --full --steps STEPS (default 1000) --warmup 20 (the whole line: roofline, CPU baseline, variants) -> TAG_bench.json
 #   driver                the driver's own command: python bench.py --gpus 1 --steps 20 --warmup 5 -> TAG_bench_driver_cmd.json
 #   prof                  rocprofv3 --kernel-trace --stats of bench.py --headline-only (200 steps) -> TAG_kernel_stats.csv, and of
 #                         tools/resample_loop.py for every named variant -> TAG_<variant>_kernel_stats.csv
@@ -19,12 +19,13 @@
 #   sharded               one-rank sharded table (tools/sharded_loop.py; no communicator / 1-rank RCCL) -> TAG_sharded_one_rank.txt
 #   essloop               the ESS-triggered loop of BASELINE configs[3] through the sharded path on one rank (tools/sharded_ess_loop.py): separate calls / one call,
 #                         no communicator / 1-rank RCCL + mailboxes, ESS < N/2 / always / never; and without the summary reuse / the lazy move -> TAG_sharded_ess_loop.txt
-#   tworanks              bench.py --gpus 2 --steps 20 with both ranks on this GPU over tests/loopback_rccl: the SHAPE of a multi-GPU line -> TAG_bench_2ranks_one_gpu_loopback.json
+#   tworanks              bench.py --gpus 2 --steps 20 --full with both ranks on this GPU over tests/loopback_rccl: the SHAPE of a multi-GPU line -> TAG_bench_2ranks_one_gpu_loopback.json
 #   variant:OUT:METHOD:DEFS   tools/variant_stats.sh OUT METHOD DEFS (DEFS: comma-separated -D sets, alternating A/B rocprofv3 runs)
 #   py:SCRIPT:ARGS        python3 tools/SCRIPT.py ARGS -> TAG_SCRIPT.txt
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=${GPF_TAG:-r06}
 mkdir -p $R/gpurun_out
+OUTDIR=$_                # (the folder just made: where every step writes)
 export TMPDIR=/tmp
 stats_of() {   # stats_of DIR OUT: copy the kernel-stats csv of a rocprofv3 output directory
   f=$(find "$1" -name "*kernel_stats.csv" | head -1)
@@ -39,7 +40,7 @@ for STEP in "$@"; do
     tests)   ( time timeout 3000 python -m pytest tests -m gpu -q --durations=25 ${A1:+-k "$A1"} ) > gpurun_out/${TAG}_pytest.log 2>&1; tail -15 gpurun_out/${TAG}_pytest.log | cut -c1-220 ;;
     soak)    timeout 3000 python -m pytest tests -m "gpu or gpu_soak" -q > gpurun_out/${TAG}_pytest_soak.log 2>&1; tail -8 gpurun_out/${TAG}_pytest_soak.log | cut -c1-220 ;;
     file)    timeout 3000 python -m pytest "$A1" -m gpu -x -q ${A2:+-k "$A2"} > gpurun_out/${TAG}_pytest_$(basename $A1 .py).log 2>&1; tail -25 gpurun_out/${TAG}_pytest_$(basename $A1 .py).log | cut -c1-220 ;;
-    bench)   python bench.py --steps ${A1:-1000} --warmup 20 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err; cut -c1-3000 gpurun_out/${TAG}_bench.json; tail -3 gpurun_out/${TAG}_bench.err ;;
+    bench)   python bench.py --full --steps ${A1:-1000} --warmup 20 > $OUTDIR/${TAG}_bench.json 2> $OUTDIR/${TAG}_bench.err; cut -c1-3000 $OUTDIR/${TAG}_bench.json; tail -3 $OUTDIR/${TAG}_bench.err ;;
     driver)  python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${TAG}_bench_driver_cmd.json 2> gpurun_out/${TAG}_bench_driver_cmd.err; cut -c1-600 gpurun_out/${TAG}_bench_driver_cmd.json ;;
     prof)    # the headline loop ALONE (k_step<...GATHER> is also launched by the sorted variants: a mixed file misstates its average), then one
              # stats file per named variant
@@ -98,7 +99,7 @@ for STEP in "$@"; do
              done
              cat $OUT ;;
     tworanks) hipcc -O2 -std=c++17 -fPIC -shared tests/loopback_rccl/loopback_rccl.cpp -o /tmp/libloopback_rccl.so
-             GPF_BENCH_ONE_DEVICE=1 GPF_SHARD_ENGINE=library GPF_RCCL_LIBRARY=/tmp/libloopback_rccl.so python bench.py --gpus 2 --steps 20 --warmup 5 --particles-per-gpu 500000 \
+             GPF_BENCH_ONE_DEVICE=1 GPF_SHARD_ENGINE=library GPF_RCCL_LIBRARY=/tmp/libloopback_rccl.so python bench.py --gpus 2 --steps 20 --warmup 5 --particles-per-gpu 500000 --full \
                > gpurun_out/${TAG}_bench_2ranks_one_gpu_loopback.json 2> gpurun_out/${TAG}_bench_2ranks.err; cut -c1-700 gpurun_out/${TAG}_bench_2ranks_one_gpu_loopback.json; tail -2 gpurun_out/${TAG}_bench_2ranks.err ;;
     variant) bash tools/variant_stats.sh $R/gpurun_out/${TAG}_$A1 $A2 ${A3//,/ } 2>&1 | tail -30 | cut -c1-200 ;;
     py)      python3 tools/$A1.py ${A2//,/ } > gpurun_out/${TAG}_$A1.txt 2> gpurun_out/${TAG}_$A1.err; cut -c1-220 gpurun_out/${TAG}_$A1.txt | tail -40; tail -3 gpurun_out/${TAG}_$A1.err ;;
