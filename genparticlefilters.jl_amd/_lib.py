@@ -83,6 +83,8 @@ SYMBOLS = [
     ("gpf_resize", C.c_int, [_H, C.c_int64, C.c_int32, C.c_double, C.c_int32, _pi32]),
     ("gpf_replicate", C.c_int, [_H, C.c_int32, C.c_int32]),
     ("gpf_dereplicate", C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32]),
+    ("gpf_coalesce", C.c_int, [_H, C.c_uint64, C.POINTER(C.c_int64)]),
+    ("gpf_introduce", C.c_int, [_H, _pd, C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
     ("gpf_history_enable", C.c_int, [_H, C.c_int32]),
     ("gpf_history_steps", C.c_int, [_H, _pi32]),
     ("gpf_history_column", C.c_int, [_H, C.c_int32, C.c_int32, _pd, C.c_int64]),

@@ -7,6 +7,7 @@ is spelled `f` here; the Julia glue in julia/GenParticleFiltersAMD.jl keeps the 
     pf_update(state, new_args, argdiffs, observations)                 src/update.jl:12-25
     pf_resample(state, method; priority_fn, check[, sort_particles])   src/resample.jl:19-175
     pf_rejuvenate(state, kern, kern_args, n_iters; method)             src/rejuvenate.jl:18-90
+    pf_coalesce(state; by) / pf_introduce(state, ..., n)               src/resize.jl:309-421
     effective_sample_size / get_ess / log_ml_estimate / get_lml_est /
     get_log_weights / get_log_norm_weights / get_norm_weights          src/utils.jl:148-186
     mean / var                                                         src/statistics.jl:13-14,48-50
@@ -698,6 +699,81 @@ def pf_dereplicate(state, n_replicates: int, *, layout: str = "contiguous", meth
     if method not in ("keepfirst", "sample"):
         raise ErrorException(f"Method {method} not recognized.")
     state._check(state._L.gpf_dereplicate(state._h, int(n_replicates), int(layout != "contiguous"), int(method == "sample")))
+    _refresh_count(state)
+    return state
+
+
+_COALESCE_ALL = (None, "get_choices", "identity")
+
+
+def _coalesce_mask(state, by) -> int:
+    """the key columns of pf_coalesce as gpf_coalesce's bit mask (0 = every state column)"""
+    msg = ("native coalescing accepts by = None / 'get_choices' / 'identity' (every state column), a current-step column "
+           "or a tuple of current-step columns")
+    if isinstance(by, str) or by is None:
+        if by not in _COALESCE_ALL:
+            raise ErrorException(f"{msg}; got {by!r}")
+        return 0
+    if callable(by):
+        raise ErrorException(f"{msg}; a Python callable has no native form")
+    cols = by if isinstance(by, (tuple, list)) else (by,)
+    mask = 0
+    for c in cols:
+        if isinstance(c, tuple):
+            raise ErrorException(f"{msg}; the past-step address {c!r} is not")
+        if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < state.dim:
+            raise ErrorException(f"{msg}; got {c!r}")
+        mask |= 1 << int(c)
+    if mask == 0:
+        raise ErrorException(f"{msg}; got an empty key")
+    return mask
+
+
+def pf_coalesce(state, by=None):
+    """src/resize.jl:309-334 (gpf.h gpf_coalesce): particles whose key columns are bitwise equal become one particle -- the group's first
+    member, weight logsumexp(group) + log(n_new / n_old).  Groups come out in ascending order of first occurrence (the reference: Dict
+    order), so `state.parents` is strictly increasing.  by: None / 'get_choices' / 'identity' = every state column (with keep_prev the
+    previous state too), a column, or a tuple of columns of the current step."""
+    mask = _coalesce_mask(state, by)
+    n = C.c_int64(0)
+    st = state._L.gpf_coalesce(state._h, mask, C.byref(n))
+    state._check(st)
+    _refresh_count(state)
+    return state
+
+
+def pf_introduce(state, *args):
+    """src/resize.jl:351-421 (gpf.h gpf_introduce): append n_particles trajectories generated over the whole observation history.
+        pf_introduce(state, observations, n_particles)
+        pf_introduce(state, model, model_args, observations, n_particles)
+        pf_introduce(state, observations, proposal, proposal_args, n_particles)
+        pf_introduce(state, model, model_args, observations, proposal, proposal_args, n_particles)
+    observations: the per-step data vectors of steps 1..t (a (t, obs_dim) array; one vector = t = 1).  proposal: a native proposal
+    (`locally_optimal`, `line_fixed`), applied at the last step.  model / model_args are accepted for signature parity; the model must
+    be the state's own."""
+    model = None
+    if len(args) == 2:
+        obs, proposal, n = args[0], None, args[1]
+    elif len(args) == 4 and isinstance(args[0], NativeModel):
+        model, obs, proposal, n = args[0], args[2], None, args[3]
+    elif len(args) == 4:
+        obs, proposal, n = args[0], args[1], args[3]
+    elif len(args) == 6:
+        model, obs, proposal, n = args[0], args[2], args[3], args[5]
+    else:
+        raise TypeError("pf_introduce(state, [model, model_args,] observations, [proposal, proposal_args,] n_particles)")
+    if model is not None:
+        mp = np.ascontiguousarray(model.params, np.float64)
+        if model.model_id != state.model.model_id or mp.shape != state._params.shape or mp.tobytes() != state._params.tobytes():
+            raise ErrorException("pf_introduce: a device filter introduces particles of its own model (same model id and parameters)")
+    pid = 0 if proposal is None else _proposal_id(proposal)
+    ob = np.asarray(obs, np.float64)
+    if ob.ndim == 1:
+        ob = ob[None, :]
+    if ob.ndim != 2 or ob.shape[0] < 1:
+        raise ErrorException("pf_introduce: observations must be the data vectors of steps 1..t, t >= 1")
+    ob = np.ascontiguousarray(ob)
+    state._check(state._L.gpf_introduce(state._h, _pd(ob), ob.shape[1], ob.shape[0], int(n), pid))
     _refresh_count(state)
     return state
 

@@ -1,6 +1,7 @@
 // libgpf_aux.hip -- what widened around the hot path: block-wise operations on many small filters, weighted statistics,
-// sub-state views (src/view.jl), the resize family (src/resize.jl), the trajectory store.
+// sub-state views (src/view.jl), the resize family with coalesce / introduce (src/resize.jl), the trajectory store.
 #include "gpf_host.hpp"
+#include "gpf_k_coalesce.hpp"
 
 using namespace gpf;
 using namespace gpfh;
@@ -656,14 +657,15 @@ static gpf_status view_create_impl(gpf_handle parent, int64_t start, int64_t ste
 }
 
 // =================================================================================== resize family (src/resize.jl)
-static gpf_status resize_ready(gpf_handle h)
+// bump = false (gpf_coalesce): the caller makes the views stale itself, once the call can no longer be refused
+static gpf_status resize_ready(gpf_handle h, bool bump = true)
 {
     gpf_status s = check_ready(h);
     if (s) return s;
     if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, "resizing a sharded filter is not supported");
     if (h->hist_on) return fail(h, GPF_ERR_STATE, "resizing a filter with a trajectory store is not supported");
     if (h->parent) return fail(h, GPF_ERR_STATE, "a sub-state view cannot be resized");
-    h->generation += 1;                  // views of this filter become stale
+    if (bump) h->generation += 1;        // views of this filter become stale
     return materialize(h);
 }
 // after the particle count changed: unsharded bookkeeping
@@ -852,6 +854,144 @@ gpf_status gpf_dereplicate(gpf_handle h, int32_t n_replicates, int32_t interleav
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     free_bufs(old);
     HIP_TRY(h, hipGetLastError());
+    return GPF_OK;
+}
+
+// pf_coalesce! (resize.jl:309-334) -- gpf.h gpf_coalesce.  Four passes (gpf_k_coalesce.hpp) and one host read of the group count.
+} // extern "C"
+namespace gpfh {
+// device scratch of ONE call (hash table, slots, tile counts / the observation history): freed on every return path -- hipFree waits
+// for the device, so no kernel of the call still reads it -- and never kept on the handle (46 MB at n = 10^6)
+struct CallScratch {
+    void* p = nullptr;
+    ~CallScratch() { if (p) (void)hipFree(p); }
+};
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+template <int W>
+void launch_coal(gpf_filter* h, const CoalArgs& a, int stage, double log_ratio = 0.0)
+{
+    const unsigned nt = (unsigned)a.ntiles;
+    if (stage == 0) {
+        GPF_LAUNCH((k_coal_insert<W>), dim3(grid_for(h, a.n, 8)), dim3(BLOCK), 0, h->stream, a);
+        GPF_LAUNCH(k_coal_sum, dim3(nt), dim3(BLOCK), 0, h->stream, a);
+        GPF_LAUNCH(k_coal_scan, dim3(1), dim3(BLOCK), 0, h->stream, a);
+    } else {
+        GPF_LAUNCH((k_coal_emit<W>), dim3(nt), dim3(BLOCK), 0, h->stream, a, log_ratio, h->rows[0], h->lw, h->anc);
+    }
+}
+static void launch_coal_w(gpf_filter* h, const CoalArgs& a, int stage, double log_ratio = 0.0)
+{
+    switch (h->W) {
+        case 2: launch_coal<2>(h, a, stage, log_ratio); break;
+        case 4: launch_coal<4>(h, a, stage, log_ratio); break;
+        case 8: launch_coal<8>(h, a, stage, log_ratio); break;
+    }
+}
+template <int M, bool KEEP, bool PROP>
+void launch_introduce(gpf_filter* h, uint64_t seed, const double* obs, int T, int64_t n_old, int64_t n_add)
+{
+    using Mo = Model<M>;
+    constexpr int Wc = row_width(Mo::D, KEEP);
+    if constexpr (PROP && !Mo::HAS_PROPOSAL) { (void)h; (void)seed; (void)obs; (void)T; (void)n_old; (void)n_add; return; }
+    else GPF_LAUNCH((k_introduce<M, Wc, KEEP, PROP>), dim3(grid_for(h, n_add, 8)), dim3(BLOCK), 0, h->stream, h->args, seed, obs, T, n_old, n_add,
+                    h->rows[0], h->lw, h->anc);
+}
+static bool model_proposal_ok(const gpf_filter* h, int32_t proposal)
+{
+    bool has = false;
+    DISPATCH_MODEL(h, (has = Model<MM>::HAS_PROPOSAL));
+    if (proposal == GPF_PROPOSAL_LOCALLY_OPTIMAL) return has && h->cfg.model != MODEL_LINE;
+    if (proposal == GPF_PROPOSAL_LINE_FIXED) return h->cfg.model == MODEL_LINE;
+    return false;
+}
+} // namespace gpfh
+extern "C" {
+
+gpf_status gpf_coalesce(gpf_handle h, uint64_t key_mask, int64_t* n_out)
+{
+    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+    const int ncols = h->cfg.keep_prev ? 2 * h->d : h->d;          // the padding column of odd widths is never part of the key
+    const uint64_t all = ((uint64_t)1 << ncols) - 1;
+    if (key_mask & ~all) return fail(h, GPF_ERR_INVALID_ARGUMENT, "coalesce: the key names a column beyond the " + std::to_string(ncols) + " state columns");
+    gpf_status s = resize_ready(h, false);
+    if (s) return s;
+    const int64_t n = h->n;
+    uint64_t T = 64;                                              // T <= 2^32 (n < 2^31): slots fit in uint32
+    while (T < 2 * (uint64_t)n) T <<= 1;
+    const int64_t ntl = (n + COAL_TILE - 1) / COAL_TILE;
+    const size_t b_claim = align256(T * 4), b_gm = align256(T * 16), b_slot = align256((size_t)n * 4), b_tile = align256((size_t)ntl * 4);
+    CallScratch scr;
+    HIP_TRY(h, hipMalloc(&scr.p, b_claim + b_gm + b_slot + 2 * b_tile + 256));
+    char* p = static_cast<char*>(scr.p);
+    CoalArgs a{};
+    a.rows = h->rows[h->cur]; a.lw = h->lw; a.n = n; a.mask = (uint32_t)(key_mask ? key_mask : all);
+    a.claim = reinterpret_cast<uint32_t*>(p); p += b_claim;
+    a.gm = reinterpret_cast<unsigned long long*>(p); p += b_gm;
+    a.slot_of = reinterpret_cast<uint32_t*>(p); p += b_slot;
+    a.tile_cnt = reinterpret_cast<uint32_t*>(p); p += b_tile;
+    a.tile_off = reinterpret_cast<uint32_t*>(p); p += b_tile;
+    a.misc = reinterpret_cast<unsigned long long*>(p);
+    a.tmask = T - 1; a.K = fix_K(n); a.ntiles = ntl;
+    HIP_TRY(h, hipMemsetAsync(a.claim, 0xff, T * 4, h->stream));
+    HIP_TRY(h, hipMemsetAsync(a.gm, 0, T * 16, h->stream));
+    HIP_TRY(h, hipMemsetAsync(a.misc, 0, 2 * sizeof(unsigned long long), h->stream));
+    launch_coal_w(h, a, 0);
+    unsigned long long misc[2] = {0, 0};
+    HIP_TRY(h, hipMemcpyAsync(misc, a.misc, sizeof(misc), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipGetLastError());
+    if (misc[0]) return fail(h, GPF_ERR_INVALID_WEIGHTS, "Invalid weights.");     // NaN / +Inf: nothing changed, views stay valid
+    h->generation += 1;                                                           // views of this filter become stale
+    const int64_t n_new = (int64_t)misc[1];
+    const double log_ratio = log_((double)n_new) - log_((double)n);               // log(n_particles) - log(n_old), resize.jl:326
+    Bufs old = take_particle_buffers(h);
+    set_count(h, n_new);
+    if ((s = alloc_particle_buffers(h))) { free_bufs(old); return s; }
+    a.rows = old.rows[old.cur]; a.lw = old.lw;
+    launch_coal_w(h, a, 1, log_ratio);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    free_bufs(old);
+    HIP_TRY(h, hipGetLastError());
+    if (n_out) *n_out = n_new;
+    return GPF_OK;
+}
+
+// pf_introduce! (resize.jl:351-421) -- gpf.h gpf_introduce.  One k_introduce launch for the whole history.
+gpf_status gpf_introduce(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int64_t n_particles, int32_t proposal)
+{
+    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_steps < 1 || !obs) return fail(h, GPF_ERR_INVALID_ARGUMENT, "introduce: need observations of at least one step");
+    if (n_obs != model_obs_dim(h->cfg.model))
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model takes " + std::to_string(model_obs_dim(h->cfg.model)) + " observation values per step");
+    if (n_particles < 1 || h->n + n_particles >= ((int64_t)1 << 31)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "introduce: bad n_particles");
+    if (proposal != 0 && !model_proposal_ok(h, proposal)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "unknown proposal id for this model");
+    gpf_status s = resize_ready(h);
+    if (s) return s;
+    const int64_t n_old = h->n;
+    std::vector<double> hobs((size_t)n_steps * MAX_OBS, 0.0);
+    for (int32_t e = 0; e < n_steps; ++e)
+        for (int k = 0; k < n_obs; ++k) hobs[(size_t)e * MAX_OBS + k] = obs[(size_t)e * n_obs + k];
+    CallScratch scr;
+    HIP_TRY(h, hipMalloc(&scr.p, hobs.size() * sizeof(double)));
+    double* dobs = static_cast<double*>(scr.p);
+    HIP_TRY(h, hipMemcpyAsync(dobs, hobs.data(), hobs.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const uint64_t seed = intro_seed(h->cfg.seed, h->epoch);
+    Bufs old = take_particle_buffers(h);
+    set_count(h, n_old + n_particles);
+    if ((s = alloc_particle_buffers(h))) { free_bufs(old); return s; }
+    HIP_TRY(h, hipMemcpyAsync(h->rows[0], old.rows[old.cur], (size_t)n_old * h->W * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->anc, old.anc, (size_t)n_old * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+    GPF_LAUNCH(k_intro_old, dim3(grid_for(h, n_old, 8)), dim3(BLOCK), 0, h->stream, old.lw, h->sc, n_old, h->lw);
+    HIP_TRY(h, hipMemsetAsync(reinterpret_cast<char*>(h->sc) + offsetof(Scalars, lml_est), 0, sizeof(double), h->stream));   // log_ml_est = 0
+    const bool keep = h->cfg.keep_prev != 0;
+    if (proposal) { if (keep) { DISPATCH_MODEL(h, (launch_introduce<MM, true, true>(h, seed, dobs, n_steps, n_old, n_particles))); }
+                    else      { DISPATCH_MODEL(h, (launch_introduce<MM, false, true>(h, seed, dobs, n_steps, n_old, n_particles))); } }
+    else          { if (keep) { DISPATCH_MODEL(h, (launch_introduce<MM, true, false>(h, seed, dobs, n_steps, n_old, n_particles))); }
+                    else      { DISPATCH_MODEL(h, (launch_introduce<MM, false, false>(h, seed, dobs, n_steps, n_old, n_particles))); } }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                 // (the old buffers and the host copy of the history are read above)
+    free_bufs(old);
+    HIP_TRY(h, hipGetLastError());
+    h->epoch += 1;
     return GPF_OK;
 }
 

@@ -326,6 +326,43 @@ gpf_status gpf_resize(gpf_handle h, int64_t n_particles, int32_t method, double 
 gpf_status gpf_replicate(gpf_handle h, int32_t n_replicates, int32_t interleaved);
 /* pf_dereplicate!(state, n_replicates; layout, method)                 src/resize.jl:267-297  (sample=0 :keepfirst, 1 :sample) */
 gpf_status gpf_dereplicate(gpf_handle h, int32_t n_replicates, int32_t interleaved, int32_t sample);
+/* pf_coalesce!(state; by)                                               src/resize.jl:309-334
+ * Groups the particles whose key columns are equal BITWISE (Julia's isequal on Float64 apart from NaN payloads: -0.0 != 0.0) and
+ * replaces every group by its first member.  key_mask: bit c = column c of the row (gpf_get_rows) is part of the key; 0 = every
+ * state column -- the d latent columns, plus the d previous-state columns with keep_prev (by = get_choices / identity).  The
+ * padding column of odd widths is never part of the key; a bit beyond the state columns is GPF_ERR_INVALID_ARGUMENT.
+ *   row of group g       = the row of its first member;  parents[g] = that member's index + 1
+ *   lw[g]                = lse_g + (log(n_new) - log(n_old)),  lse_g = lse_from(m_g, S_g, K, flags_g): m_g the group's maximum,
+ *                          K = fix_K(n_old), S_g = sum of exp_fix(w_i - m_g, K) as an exact u64 sum, flags_g = ALL_NEGINF iff m_g = -Inf
+ *                          (the fixed-point logsumexp of the summaries; log = the library's log, gpf_host_log)
+ *   *n_out               = n_new, the number of groups (may be NULL)
+ * log_ml_est, the RNG epoch and everything else are unchanged; all rows distinct: n_new = n_old and the state comes back bit for bit
+ * (m + log(1.0) + 0.0; parents 1:n).  Views of the filter become stale (not when the call is refused).  Refused (GPF_ERR_STATE) on
+ * sharded filters, views and filters with a trajectory store.  Device scratch of about 20 B x 2n + 4 B x n (a hash table of 2^k >= 2n
+ * slots) is allocated by the call and freed before it returns; nothing stays on the handle.
+ * Deviations from the reference:
+ *   - order: the reference emits groups in Dict iteration order (unspecified); here in ASCENDING ORDER OF FIRST OCCURRENCE, so parents
+ *     is strictly increasing and the result does not depend on the thread schedule.
+ *   - sum: the reference's unshifted sum of exp(w) underflows to -Inf below about -745; the shifted fixed-point sum does not.  Because
+ *     it is an integer sum, the result does not depend on summation order (device atomics are bit-reproducible).
+ *   - a NaN or +Inf weight anywhere returns GPF_ERR_INVALID_WEIGHTS and leaves the state and its views untouched (the reference
+ *     propagates NaN).
+ *   - `by` is a set of current-step columns; closures and past-step addresses have no native form. */
+gpf_status gpf_coalesce(gpf_handle h, uint64_t key_mask, int64_t* n_out);
+/* pf_introduce!(state, [model, model_args,] observations, [proposal, proposal_args,] n_particles)   src/resize.jl:351-421
+ * obs = [n_steps][n_obs] row-major: the per-step data vectors of steps 1..t (t = n_steps >= 1) that the reference's choicemap
+ * constrains, e.g. line_choicemap(10).  Appends n_particles new particles generated over the whole history in ONE launch:
+ *   new particle j = particle j of gpf_initialize's kernel at step 1 followed by t - 1 propagates from the prior (gpf_update), with
+ *   RNG counter n_old + j, epochs 0 .. t-1 and the seed s' = mix(cfg.seed, epoch at the call); weight = the sum of the step
+ *   log-likelihoods in step order.  proposal = GPF_PROPOSAL_* (0: none): the native proposal of the LAST step
+ *   (gpf_initialize_proposal's when t = 1, else gpf_update_proposal's), earlier steps from the prior.
+ *   mix(s, e): z = s ^ (e * 0x9e3779b97f4a7c15 + 0xd1b54a32d192ed03); z = (z ^ z >> 30) * 0xbf58476d1ce4e5b9;
+ *              z = (z ^ z >> 27) * 0x94d049bb133111eb; mix = z ^ z >> 31   (64-bit wrap-around arithmetic)
+ * The existing particles: lw += log_ml_est where log_ml_est != 0 (on the device), then log_ml_est = 0; their parents are kept; the new
+ * particles' parents read 0 (no ancestor; no kernel gathers through them: the pending-resample flags are cleared with the count).  Then
+ * n = n_old + n_particles and epoch += 1.  Views become stale; the same refusals as gpf_coalesce.  The reference leaves the new parents
+ * undefined; the model / model_args of the reference's signature are the handle's own (checked by the bindings). */
+gpf_status gpf_introduce(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int64_t n_particles, int32_t proposal);
 
 /* ---- trajectory store ------------------------------------------------------------------
  * Gen traces are persistent, so the reference can ask for a PAST choice of every surviving particle:

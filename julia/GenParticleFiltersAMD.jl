@@ -7,10 +7,12 @@
 module GenParticleFiltersAMD
 
 import GenParticleFilters: pf_resize!, pf_multinomial_resize!, pf_residual_resize!, pf_optimal_resize!, pf_replicate!, pf_dereplicate!
+import GenParticleFilters: pf_coalesce!, pf_introduce!
 import GenParticleFilters: pf_initialize, pf_update!, pf_resample!, pf_multinomial_resample!,
     pf_residual_resample!, pf_stratified_resample!, pf_rejuvenate!, pf_move_accept!, pf_move_reweight!,
     get_log_norm_weights, get_norm_weights, get_ess, get_lml_est
 import Gen: effective_sample_size, log_ml_estimate, get_log_weights, sample_unweighted_traces
+using Gen: get_choices
 import Statistics: mean, var
 
 const libgpf = get(ENV, "LIBGPF_HIP", "libgpf_hip.so")
@@ -309,6 +311,41 @@ end
 function pf_dereplicate!(s::DeviceParticleFilterState, k::Int; layout::Symbol=:contiguous, method::Symbol=:keepfirst)
     _status(s, ccall((:gpf_dereplicate, libgpf), Cint, (Ptr{Cvoid}, Cint, Cint, Cint), s.handle, k, layout != :contiguous, method == :sample)); _refresh!(s)
 end
+# src/resize.jl:309-334 (gpf.h gpf_coalesce): by = get_choices / identity -> every state column; a column or a tuple of columns of the current step
+# (0-based, as gpf_get_column).  Groups come out in ascending order of first occurrence.
+function pf_coalesce!(s::DeviceParticleFilterState; by=get_choices)
+    mask = UInt64(0)
+    if !(by === get_choices || by === identity)
+        cols = by isa Integer ? (by,) : by
+        (cols isa Tuple && !isempty(cols) && all(c -> c isa Integer && 0 <= c < s.model.dim, cols)) ||
+            error("native coalescing accepts by = get_choices / identity, a current-step column or a tuple of current-step columns")
+        for c in cols; mask |= UInt64(1) << c; end
+    end
+    n_new = Ref{Int64}(0)
+    _status(s, ccall((:gpf_coalesce, libgpf), Cint, (Ptr{Cvoid}, UInt64, Ref{Int64}), s.handle, mask, n_new))
+    _refresh!(s)
+end
+# src/resize.jl:351-421 (gpf.h gpf_introduce): observations = one column per step 1..t (obs_dim x t); the proposal (native id, 0 = none)
+# applies at the last step.  model / model_args are the state's own.
+function _introduce!(s::DeviceParticleFilterState, model, observations::AbstractMatrix{<:Real}, proposal_id::Integer, n::Int)
+    model === nothing || (model.id == s.model.id && model.params == s.model.params) ||
+        error("pf_introduce!: a device filter introduces particles of its own model")
+    obs = Matrix{Float64}(observations)                          # column-major: step e's data vector is column e, i.e. [t][obs_dim] row-major
+    _status(s, ccall((:gpf_introduce, libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Int64, Cint),
+                     s.handle, obs, size(obs, 1), size(obs, 2), n, proposal_id))
+    _refresh!(s)
+end
+_steps(observations::AbstractVector{<:Real}) = reshape(Vector{Float64}(observations), :, 1)
+_steps(observations::AbstractMatrix{<:Real}) = observations
+_proposal_id(::LocallyOptimal) = 1
+_proposal_id(id::Integer) = id                                  # 2: line_model's fixed proposals (GPF_PROPOSAL_LINE_FIXED)
+pf_introduce!(s::DeviceParticleFilterState, observations::AbstractVecOrMat, n::Int) = _introduce!(s, nothing, _steps(observations), 0, n)
+pf_introduce!(s::DeviceParticleFilterState, model::NativeModel, model_args::Tuple, observations::AbstractVecOrMat, n::Int) =
+    _introduce!(s, model, _steps(observations), 0, n)
+pf_introduce!(s::DeviceParticleFilterState, observations::AbstractVecOrMat, proposal, proposal_args::Tuple, n::Int) =
+    _introduce!(s, nothing, _steps(observations), _proposal_id(proposal), n)
+pf_introduce!(s::DeviceParticleFilterState, model::NativeModel, model_args::Tuple, observations::AbstractVecOrMat, proposal, proposal_args::Tuple, n::Int) =
+    _introduce!(s, model, _steps(observations), _proposal_id(proposal), n)
 
 # src/utils.jl:148-186
 function _scalar(s, sym)
