@@ -500,13 +500,58 @@ def _block_obs(state, observations, block_size: int) -> np.ndarray:
     return obs
 
 
+def block_params_rows(model: NativeModel, params, n_particles: int, block_size: int) -> np.ndarray:
+    """the [n_blocks][n_params] rows gpf_set_block_params takes, checked on the host: `params` is an array with one parameter vector per block
+    (the layout of csrc/gpf_models.hpp, derived constants included) or a list of NativeModel descriptors of `model`'s kind, whose `params` --
+    built by the model constructors, derived constants and all -- become the rows"""
+    if int(block_size) < 1:
+        raise ErrorException("block_size < 1")
+    bs = min(int(block_size), max(int(n_particles), 1))                 # (clamped to the particle count, as in the C ABI)
+    nb = (int(n_particles) + bs - 1) // bs
+    if isinstance(params, (list, tuple)) and any(isinstance(m, NativeModel) for m in params):
+        if not all(isinstance(m, NativeModel) for m in params):
+            raise ErrorException("per-block parameters: a list of NativeModel descriptors or an array, not a mixture")
+        bad = [m.name for m in params if m.model_id != model.model_id]
+        if bad:
+            raise ErrorException(f"per-block parameters: the state's model is {model.name}, got descriptors of {sorted(set(bad))}")
+        vecs = [np.asarray(m.params, np.float64).ravel() for m in params]
+        if any(v.size != vecs[0].size for v in vecs):
+            raise ErrorException("per-block parameters: the descriptors' parameter vectors differ in length")
+        rows = np.stack(vecs) if vecs else np.zeros((0, 0))
+    else:
+        rows = np.asarray(params, np.float64)
+    if rows.ndim != 2 or rows.shape[0] != nb:
+        raise ErrorException(f"one parameter vector per block expected: {nb} rows, got an array of shape {rows.shape}")
+    if rows.shape[1] != np.asarray(model.params).size:
+        raise ErrorException(f"{model.name} takes {np.asarray(model.params).size} parameters per block, got {rows.shape[1]}")
+    return np.ascontiguousarray(rows, np.float64)
+
+
+def set_block_params(state, params, block_size: int | None = None):
+    """for b in blocks: the model arguments of state[b] -- pf_update!(state[b], new_args_b, argdiffs, observations[b]) with a parameter vector PER
+    BLOCK (gpf.h gpf_set_block_params).  params: (n_blocks, n_params) array or a list of NativeModel descriptors of the state's model (see
+    block_params_rows); None clears them.  While they are set, the block-wise calls use row b for block b, with this block_size only, and every
+    call that would use the state's one parameter vector (pf_update, pf_initialize, the resize family, ...) raises.  Uploaded once."""
+    if params is None:
+        state._check(state._L.gpf_set_block_params(state._h, None, 0, 0))
+        return state
+    if block_size is None:
+        raise ErrorException("set_block_params needs the block_size of the block-wise calls")
+    rows = block_params_rows(state.model, params, state.n_particles, block_size)
+    state._check(state._L.gpf_set_block_params(state._h, _pd(rows), rows.shape[1], int(block_size)))
+    return state
+
+
 def pf_initialize_blocks(model: NativeModel, model_args: tuple, observations, n_particles: int, block_size: int, *, seed: int = 1,
-                         keep_prev: bool = False, device: int = 0, strata=None, layout: str = "contiguous"):
+                         keep_prev: bool = False, device: int = 0, strata=None, layout: str = "contiguous", params=None):
     """many small filters in one state, each with its own data: block b (block_size consecutive particles) is initialised with
     observations[b] -- the batched form of per-view initialisation (gpf.h gpf_initialize_blocks).  strata: every block is initialised
-    stratified by itself (src/initialize.jl:92-109 per sub-state, gpf.h gpf_initialize_blocks_strata), the same strata for all blocks"""
+    stratified by itself (src/initialize.jl:92-109 per sub-state, gpf.h gpf_initialize_blocks_strata), the same strata for all blocks.
+    params: per-block model parameters (set_block_params) in force from this call on; `model` gives the model kind and the rows' length"""
     state = DeviceParticleFilterState(model, n_particles, seed=seed, keep_prev=keep_prev, device=device)
     obs = _block_obs(state, observations, block_size)
+    if params is not None:
+        set_block_params(state, params, block_size)
     if strata is not None:
         v = _strata_values(model, strata, "initialize")
         state._check(state._L.gpf_initialize_blocks_strata(state._h, _pd(obs), obs.shape[1], int(block_size), _pd(v), v.size, int(_layout_id(layout))))

@@ -201,6 +201,10 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     int64_t blk_stage_next = 0;                                                        // staging copies issued so far (ticket of the next one - 1)
     int64_t* h_blk_done = nullptr; unsigned int* blk_stage_counter = nullptr;          // pinned: ticket of the last finished staging copy; device: its workgroup counter
     int64_t blk_obs_size = 0;                                                          // > 0: the latest observations are per block, blocks of this size
+    // gpf_set_block_params: every block's own model parameters, [n_blocks][MAX_PARAMS] on the device (ModelArgs::blk_params), uploaded once;
+    // bp_size > 0: the rows are in force for blocks of this (clamped) size -- the block-wise steps run their BP kernels, everything that would
+    // read cfg.params is refused (bp_refused)
+    double* blk_params = nullptr; int64_t blk_params_cap = 0, bp_size = 0;
     // the pull plan (gpf_comm_set_plan): request lists [G][n], their counters, the dense / gathered request matrix and its pinned mirror
     int shard_plan_kind = 0;
     ulonglong2* pull_req = nullptr; int64_t pull_req_cap = 0;
@@ -247,6 +251,15 @@ inline gpf_status fail(gpf_handle h, gpf_status s, const std::string& msg)
 {
     if (h) h->err = msg; else g_err = msg;
     return s;
+}
+
+// gpf_set_block_params: while the rows are set on a filter, a call on it or on a view of it that would use the filter's one parameter vector fails
+inline gpf_status bp_refused(gpf_filter* h, const char* who)
+{
+    const gpf_filter* root = (h->parent && !h->orphaned) ? h->parent : h;
+    if (root->bp_size > 0)
+        return fail(h, GPF_ERR_STATE, std::string(who) + ": per-block model parameters are set (gpf_set_block_params): use the block-wise calls, or clear them first");
+    return GPF_OK;
 }
 
 constexpr int row_width(int D, bool keep) { return ((keep ? 2 * D : D) + 1) & ~1; }

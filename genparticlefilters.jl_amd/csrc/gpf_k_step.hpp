@@ -107,7 +107,8 @@ __device__ __forceinline__ void wave_rows_store(double* __restrict__ rows_out, i
 // row out, lw += log p(y|x).  Counter-based RNG: no RNG state in memory.
 // MODE 0: the model's own sampler; 1: native custom proposal; 2: stratified (the discrete latent constrained per stratum);
 // 3 (k_init only): stratified with a native proposal for the other choice
-template <int M, int MODE = 0, bool BLK = false>
+// BP (gpf_set_block_params, BLK only): every block's particles use the block's own parameter row (params_of) instead of a.P
+template <int M, int MODE = 0, bool BLK = false, bool BP = false>
 __global__ __launch_bounds__(BLOCK) void k_init(ModelArgs a, uint64_t seed, uint32_t epoch, int64_t gid0,
                                                 int64_t n, int W, double* __restrict__ rows,
                                                 double* __restrict__ lw, MaxSlots ms)
@@ -118,17 +119,18 @@ __global__ __launch_bounds__(BLOCK) void k_init(ModelArgs a, uint64_t seed, uint
         double x[MAX_DIM];
         double ll;
         const double* const ob = obs_of<BLK>(a, i);
-        if constexpr (MODE == 1) ll = Mo::propose(a.P, true, nullptr, ob, seed, particle_gid(a, gid0, i), 0, epoch, TAG_INIT, x);
+        const double* const P = params_of<BP>(a, i);
+        if constexpr (MODE == 1) ll = Mo::propose(P, true, nullptr, ob, seed, particle_gid(a, gid0, i), 0, epoch, TAG_INIT, x);
         else if constexpr (MODE == 2) {
             const double v = a.strata[stratum_of<Mo, BLK>(a, seed, epoch, gid0, i, n, TAG_INIT)];
-            const double lp = Mo::sample_stratum(a.P, true, nullptr, ob, v, seed, particle_gid(a, gid0, i), 0, epoch, TAG_INIT, x);
-            ll = (lp + Mo::loglik(a.P, x, ob)) + a.logK;                      // initialize.jl:103-104
+            const double lp = Mo::sample_stratum(P, true, nullptr, ob, v, seed, particle_gid(a, gid0, i), 0, epoch, TAG_INIT, x);
+            ll = (lp + Mo::loglik(P, x, ob)) + a.logK;                      // initialize.jl:103-104
         } else if constexpr (MODE == 3) {                                        // strata + native proposal, initialize.jl:122-126
             const double v = a.strata[stratum_of<Mo, BLK>(a, seed, epoch, gid0, i, n, TAG_INIT)];
-            ll = Mo::propose_stratum(a.P, ob, v, x) + a.logK;
+            ll = Mo::propose_stratum(P, ob, v, x) + a.logK;
         } else {
-            Mo::sample(a.P, true, nullptr, ob, seed, particle_gid(a, gid0, i), 0, epoch, TAG_INIT, x);
-            ll = Mo::loglik(a.P, x, ob);
+            Mo::sample(P, true, nullptr, ob, seed, particle_gid(a, gid0, i), 0, epoch, TAG_INIT, x);
+            ll = Mo::loglik(P, x, ob);
         }
         double* r = rows + i * W;
 #pragma unroll
@@ -171,7 +173,7 @@ struct PackedCommit {
 #define GPF_STEP_WAVES_WIDE 4
 #endif
 template <int W> constexpr int step_min_waves() { return W >= 8 ? GPF_STEP_WAVES_WIDE : 4; }
-template <int M, int W, bool KEEP_PREV, bool GATHER, int MODE = 0, bool PACKED = false, bool BLK = false>
+template <int M, int W, bool KEEP_PREV, bool GATHER, int MODE = 0, bool PACKED = false, bool BLK = false, bool BP = false>
 __global__ __launch_bounds__(BLOCK, step_min_waves<W>()) void k_step(ModelArgs a, uint64_t seed, uint32_t epoch, int64_t gid0,
                                                 int64_t n, const int32_t* __restrict__ anc,
                                                 const double* __restrict__ rows_in,
@@ -252,20 +254,21 @@ __global__ __launch_bounds__(BLOCK, step_min_waves<W>()) void k_step(ModelArgs a
         double xn[MAX_DIM];
         double ll;
         const double* const ob = obs_of<BLK>(a, i);
-        if constexpr (MODE == 1) ll = Mo::propose(a.P, false, r, ob, seed, particle_gid(a, gid0, i), 0, epoch, TAG_UPDATE, xn);
+        const double* const P = params_of<BP>(a, i);
+        if constexpr (MODE == 1) ll = Mo::propose(P, false, r, ob, seed, particle_gid(a, gid0, i), 0, epoch, TAG_UPDATE, xn);
         else if constexpr (MODE == 4) {
             // block-wise update with a proposal PER BLOCK (the per-view updates of test/update.jl:179-189 in one launch): the block's flag
             // selects update.jl:79-96 (native proposal) or update.jl:12-25 (default) for its particles -- the same counters either way
-            if (a.blk_prop[(uint32_t)i / (uint32_t)a.blk_size]) ll = Mo::propose(a.P, false, r, ob, seed, particle_gid(a, gid0, i), 0, epoch, TAG_UPDATE, xn);
-            else { Mo::sample(a.P, false, r, ob, seed, particle_gid(a, gid0, i), 0, epoch, TAG_UPDATE, xn); ll = Mo::loglik(a.P, xn, ob); }
+            if (a.blk_prop[(uint32_t)i / (uint32_t)a.blk_size]) ll = Mo::propose(P, false, r, ob, seed, particle_gid(a, gid0, i), 0, epoch, TAG_UPDATE, xn);
+            else { Mo::sample(P, false, r, ob, seed, particle_gid(a, gid0, i), 0, epoch, TAG_UPDATE, xn); ll = Mo::loglik(P, xn, ob); }
         }
         else if constexpr (MODE == 2) {
             const double v = a.strata[stratum_of<Mo, BLK>(a, seed, epoch, gid0, i, n, TAG_UPDATE)];
-            const double lp = Mo::sample_stratum(a.P, false, r, ob, v, seed, particle_gid(a, gid0, i), 0, epoch, TAG_UPDATE, xn);
-            ll = (lp + Mo::loglik(a.P, xn, ob)) + a.logK;                     // update.jl:201-206
+            const double lp = Mo::sample_stratum(P, false, r, ob, v, seed, particle_gid(a, gid0, i), 0, epoch, TAG_UPDATE, xn);
+            ll = (lp + Mo::loglik(P, xn, ob)) + a.logK;                     // update.jl:201-206
         } else {
-            Mo::sample(a.P, false, r, ob, seed, particle_gid(a, gid0, i), 0, epoch, TAG_UPDATE, xn);
-            ll = Mo::loglik(a.P, xn, ob);
+            Mo::sample(P, false, r, ob, seed, particle_gid(a, gid0, i), 0, epoch, TAG_UPDATE, xn);
+            ll = Mo::loglik(P, xn, ob);
         }
         double o[W];
 #pragma unroll
@@ -311,7 +314,8 @@ static __global__ void k_sum_accepts(const unsigned long long* __restrict__ part
 // relative weight; without: Gen.mh(trace, proposal, proposal_args) under pf_move_accept! (rejuvenate.jl:40-53) -- accept iff log(rand()) <
 // alpha, the weights stay (the uniform: block NBLK behind the proposal's, tag MOVE, as in the selection variant).
 // BLK: block-wise (ModelArgs::blk_*): the observation of the particle's block; blocks whose mask bit is clear keep their particles
-template <int M, int W, bool REWEIGHT, bool GATHER = false, bool PROP = false, bool BLK = false>
+// BP (gpf_set_block_params, BLK only): the parameter row of the particle's block instead of a.P
+template <int M, int W, bool REWEIGHT, bool GATHER = false, bool PROP = false, bool BLK = false, bool BP = false>
 __global__ __launch_bounds__(BLOCK) void k_move(ModelArgs a, uint64_t seed, uint32_t epoch, int64_t gid0,
                                                 int64_t n, int has_prev, int n_iters, const int32_t* __restrict__ anc,
                                                 const double* __restrict__ rows_in,
@@ -346,22 +350,23 @@ __global__ __launch_bounds__(BLOCK) void k_move(ModelArgs a, uint64_t seed, uint
         for (int k = 0; k < D; ++k) x[k] = r[k];
         const double* xp = r + D;                    // x_{t-1} (valid when has_prev)
         const double* const ob = obs_of<BLK>(a, i);
+        const double* const P = params_of<BP>(a, i);
         const bool live = alive && !(BLK && a.blk_mask && !(a.blk_mask[(uint32_t)i / (uint32_t)a.blk_size] & 1));
         const int iters = live ? n_iters : 0;
-        double llx = Mo::loglik(a.P, x, ob);
+        double llx = Mo::loglik(P, x, ob);
         double wsum = 0.0;
         const uint32_t gid = particle_gid(a, gid0, i);
         for (int it = 0; it < iters; ++it) {
             if constexpr (PROP) {
                 if constexpr (Mo::HAS_MOVE_PROPOSAL && REWEIGHT) {
-                    const double rw = Mo::move_propose(a.P, a.q, !has_prev, xp, x, ob, seed, gid, (uint32_t)(it * NB), epoch, TAG_REWEIGHT, xs);
+                    const double rw = Mo::move_propose(P, a.q, !has_prev, xp, x, ob, seed, gid, (uint32_t)(it * NB), epoch, TAG_REWEIGHT, xs);
                     wsum = wsum + rw;                                          // rejuvenate.jl:86
 #pragma unroll
                     for (int k = 0; k < D; ++k) x[k] = xs[k];
                     ++acc;
                 } else if constexpr (Mo::HAS_MOVE_PROPOSAL) {
                     const uint32_t blk0 = (uint32_t)(it * (NB + 1));
-                    const double alpha = Mo::move_propose(a.P, a.q, !has_prev, xp, x, ob, seed, gid, blk0, epoch, TAG_MOVE, xs);
+                    const double alpha = Mo::move_propose(P, a.q, !has_prev, xp, x, ob, seed, gid, blk0, epoch, TAG_MOVE, xs);
                     const Philox b = rng(seed, gid, blk0 + NB, epoch, TAG_MOVE);
                     if (log_(u52(b.w0, b.w1)) < alpha) {                       // Gen.mh: accept iff log(rand()) < weight - fwd_score + bwd_score
 #pragma unroll
@@ -370,8 +375,8 @@ __global__ __launch_bounds__(BLOCK) void k_move(ModelArgs a, uint64_t seed, uint
                     }
                 }
             } else if (REWEIGHT) {
-                Mo::sample(a.P, !has_prev, xp, ob, seed, gid, (uint32_t)(it * NB), epoch, TAG_REWEIGHT, xs);
-                const double lls = Mo::loglik(a.P, xs, ob);
+                Mo::sample(P, !has_prev, xp, ob, seed, gid, (uint32_t)(it * NB), epoch, TAG_REWEIGHT, xs);
+                const double lls = Mo::loglik(P, xs, ob);
                 wsum = wsum + (lls - llx);
 #pragma unroll
                 for (int k = 0; k < D; ++k) x[k] = xs[k];
@@ -379,8 +384,8 @@ __global__ __launch_bounds__(BLOCK) void k_move(ModelArgs a, uint64_t seed, uint
                 ++acc;
             } else {
                 const uint32_t blk0 = (uint32_t)(it * (NB + 1));
-                Mo::sample(a.P, !has_prev, xp, ob, seed, gid, blk0, epoch, TAG_MOVE, xs);
-                const double lls = Mo::loglik(a.P, xs, ob);
+                Mo::sample(P, !has_prev, xp, ob, seed, gid, blk0, epoch, TAG_MOVE, xs);
+                const double lls = Mo::loglik(P, xs, ob);
                 const Philox b = rng(seed, gid, blk0 + NB, epoch, TAG_MOVE);
                 const double lu = log_(u52(b.w0, b.w1));
                 if (lu < lls - llx) {

@@ -37,6 +37,10 @@ struct ModelArgs {          // passed by value in the kernarg segment: no device
     // block-wise operations (many small filters in one state, gpf_update_blocks & co.): particle i belongs to block i / blk_size and
     // sees that block's observation blk_obs[block][MAX_OBS]; blk_mask (rejuvenation): bit 0 of word [block] = the block takes part
     const double* blk_obs; const int32_t* blk_mask; int32_t blk_size, pad2_;
+    // gpf_set_block_params: the model parameters of every block, [block][MAX_PARAMS] (zero-padded, device); read only by the BP instantiations
+    // of the block kernels (params_of) -- every other kernel reads P from the kernarg segment.  (Here, not behind blk_prop: the fields read with
+    // dynamic indices keep their offsets and blk_prop stays next to the kernel argument that follows ModelArgs.)
+    const double* blk_params;
     // gpf_update_blocks_proposal: word [block] != 0 = the block's particles are extended with the model's native proposal (MODE 4 of k_step)
     const int32_t* blk_prop;
 };
@@ -46,6 +50,14 @@ __device__ __forceinline__ const double* obs_of(const ModelArgs& a, int64_t i)
 {
     if constexpr (BLK) return a.blk_obs + (size_t)((uint32_t)i / (uint32_t)a.blk_size) * MAX_OBS;
     else return a.obs;
+}
+
+// the parameter vector particle i's model uses: block i / blk_size's row (BP), else the filter's P
+template <bool BP>
+__device__ __forceinline__ const double* params_of(const ModelArgs& a, int64_t i)
+{
+    if constexpr (BP) return a.blk_params + (size_t)((uint32_t)i / (uint32_t)a.blk_size) * MAX_PARAMS;
+    else return a.P;
 }
 
 // the RNG counter of local particle i: its id in the whole filter

@@ -9,47 +9,48 @@ using namespace gpfh;
 namespace gpfh {
 
 // block-wise propagate / move (ModelArgs::blk_*): the default proposal only, no fused gather (a block resample gathers eagerly)
-template <int M>
+// BP: per-block parameters are set (gpf_set_block_params) -- the kernels read block b's row of ModelArgs::blk_params instead of P
+template <int M, bool BP>
 void launch_init_blk(gpf_filter* h, int grid)
 {
-    GPF_LAUNCH((k_init<M, 0, true>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
+    GPF_LAUNCH((k_init<M, 0, true, BP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
                        h->cfg.gid0, h->n, h->W, h->rows[h->cur], h->lw, next_slots(h));
 }
-template <int M, bool KEEP>
+template <int M, bool KEEP, bool BP>
 void launch_step_blk(gpf_filter* h, int grid)
 {
     constexpr int Wc = row_width(Model<M>::D, KEEP);
-    GPF_LAUNCH((k_step<M, Wc, KEEP, false, 0, false, true>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
+    GPF_LAUNCH((k_step<M, Wc, KEEP, false, 0, false, true, BP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
                        h->cfg.gid0, h->n, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, next_slots(h), PackedCommit{});
 }
-template <int M>
+template <int M, bool BP>
 void launch_init_blk_strata(gpf_filter* h, int grid)
 {
     if constexpr (!Model<M>::HAS_STRATA) { (void)h; (void)grid; return; }
-    else GPF_LAUNCH((k_init<M, 2, true>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
+    else GPF_LAUNCH((k_init<M, 2, true, BP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
                     h->cfg.gid0, h->n, h->W, h->rows[h->cur], h->lw, next_slots(h));
 }
-template <int M, bool KEEP>
+template <int M, bool KEEP, bool BP>
 void launch_step_blk_strata(gpf_filter* h, int grid)
 {
     constexpr int Wc = row_width(Model<M>::D, KEEP);
     if constexpr (!Model<M>::HAS_STRATA) { (void)h; (void)grid; return; }
-    else GPF_LAUNCH((k_step<M, Wc, KEEP, false, 2, false, true>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
+    else GPF_LAUNCH((k_step<M, Wc, KEEP, false, 2, false, true, BP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
                     h->cfg.gid0, h->n, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, next_slots(h), PackedCommit{});
 }
-template <int M, bool KEEP>
+template <int M, bool KEEP, bool BP>
 void launch_step_blk_prop(gpf_filter* h, int grid)
 {
     constexpr int Wc = row_width(Model<M>::D, KEEP);
     if constexpr (!Model<M>::HAS_PROPOSAL) { (void)h; (void)grid; return; }
-    else GPF_LAUNCH((k_step<M, Wc, KEEP, false, 4, false, true>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
+    else GPF_LAUNCH((k_step<M, Wc, KEEP, false, 4, false, true, BP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
                     h->cfg.gid0, h->n, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, next_slots(h), PackedCommit{});
 }
-template <int M, bool RW>
+template <int M, bool RW, bool BP>
 void launch_move_blk(gpf_filter* h, int grid, int n_iters)
 {
     constexpr int Wc = row_width(Model<M>::D, true);
-    GPF_LAUNCH((k_move<M, Wc, RW, false, false, true>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
+    GPF_LAUNCH((k_move<M, Wc, RW, false, false, true, BP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
                        h->cfg.gid0, h->n, (int)h->has_prev, n_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw,
                        h->acc_part, RW ? next_slots(h) : MaxSlots{nullptr, nullptr});
 }
@@ -315,6 +316,9 @@ static gpf_status block_step_checks(gpf_handle h, int64_t& block_size, const cha
     if (h->hist_on) return fail(h, GPF_ERR_STATE, std::string(who) + " on a filter with a trajectory store");
     if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");      // (the per-block steps index observations by i / block_size: any size)
     block_size = std::min<int64_t>(block_size, std::max<int64_t>(h->n, 1));
+    if (h->bp_size > 0 && block_size != h->bp_size)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": block_size " + std::to_string(block_size) + " differs from the " +
+                    std::to_string(h->bp_size) + " of the per-block parameters (gpf_set_block_params)");
     // (callers that change the handle's arguments before set_block_obs -- the strata -- validate the observations first, so that a bad call changes nothing)
     if (with_obs && (!obs || n_obs != model_obs_dim(h->cfg.model)))
         return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model takes " + std::to_string(model_obs_dim(h->cfg.model)) + " observation values per step and block");
@@ -328,7 +332,11 @@ gpf_status gpf_initialize_blocks(gpf_handle h, const double* obs, int32_t n_obs,
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     if ((s = set_block_obs(h, obs, n_obs, block_size))) return s;
     const int grid = step_grid(h);
-    s = timed(h, GPF_K_STEP, [&] { DISPATCH_MODEL(h, (launch_init_blk<MM>(h, grid))); });
+    const bool bp = h->bp_size > 0;
+    s = timed(h, GPF_K_STEP, [&] {
+        if (bp) { DISPATCH_MODEL(h, (launch_init_blk<MM, true>(h, grid))); }
+        else    { DISPATCH_MODEL(h, (launch_init_blk<MM, false>(h, grid))); }
+    });
     if (s) return s;
     h->pending_gather = false; h->pending_fill = false; h->pending_packed = false; h->pending_search = false; h->pending_move = false;
     h->max_valid = true;
@@ -350,9 +358,12 @@ gpf_status gpf_update_blocks(gpf_handle h, const double* obs, int32_t n_obs, int
     if ((s = set_block_obs(h, obs, n_obs, block_size))) return s;
     const int grid = step_grid(h);
     const bool keep = h->cfg.keep_prev != 0;
+    const bool bp = h->bp_size > 0;
     s = timed(h, GPF_K_STEP, [&] {
-        if (keep) { DISPATCH_MODEL(h, (launch_step_blk<MM, true>(h, grid))); }
-        else      { DISPATCH_MODEL(h, (launch_step_blk<MM, false>(h, grid))); }
+        if (keep && bp) { DISPATCH_MODEL(h, (launch_step_blk<MM, true, true>(h, grid))); }
+        else if (keep)  { DISPATCH_MODEL(h, (launch_step_blk<MM, true, false>(h, grid))); }
+        else if (bp)    { DISPATCH_MODEL(h, (launch_step_blk<MM, false, true>(h, grid))); }
+        else            { DISPATCH_MODEL(h, (launch_step_blk<MM, false, false>(h, grid))); }
     });
     if (s) return s;
     HIP_TRY(h, hipGetLastError());
@@ -379,7 +390,11 @@ gpf_status gpf_initialize_blocks_strata(gpf_handle h, const double* obs, int32_t
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     if ((s = set_block_obs(h, obs, n_obs, block_size))) return s;
     const int grid = step_grid(h);
-    s = timed(h, GPF_K_STEP, [&] { DISPATCH_MODEL(h, (launch_init_blk_strata<MM>(h, grid))); });
+    const bool bp = h->bp_size > 0;
+    s = timed(h, GPF_K_STEP, [&] {
+        if (bp) { DISPATCH_MODEL(h, (launch_init_blk_strata<MM, true>(h, grid))); }
+        else    { DISPATCH_MODEL(h, (launch_init_blk_strata<MM, false>(h, grid))); }
+    });
     if (s) return s;
     h->pending_gather = false; h->pending_fill = false; h->pending_packed = false; h->pending_search = false; h->pending_move = false;
     h->max_valid = true;
@@ -403,9 +418,12 @@ gpf_status gpf_update_blocks_strata(gpf_handle h, const double* obs, int32_t n_o
     if ((s = set_block_obs(h, obs, n_obs, block_size))) return s;
     const int grid = step_grid(h);
     const bool keep = h->cfg.keep_prev != 0;
+    const bool bp = h->bp_size > 0;
     s = timed(h, GPF_K_STEP, [&] {
-        if (keep) { DISPATCH_MODEL(h, (launch_step_blk_strata<MM, true>(h, grid))); }
-        else      { DISPATCH_MODEL(h, (launch_step_blk_strata<MM, false>(h, grid))); }
+        if (keep && bp) { DISPATCH_MODEL(h, (launch_step_blk_strata<MM, true, true>(h, grid))); }
+        else if (keep)  { DISPATCH_MODEL(h, (launch_step_blk_strata<MM, true, false>(h, grid))); }
+        else if (bp)    { DISPATCH_MODEL(h, (launch_step_blk_strata<MM, false, true>(h, grid))); }
+        else            { DISPATCH_MODEL(h, (launch_step_blk_strata<MM, false, false>(h, grid))); }
     });
     if (s) return s;
     HIP_TRY(h, hipGetLastError());
@@ -440,9 +458,12 @@ gpf_status gpf_update_blocks_proposal(gpf_handle h, const double* obs, int32_t n
     h->args.blk_prop = h->blk_mask;
     const int grid = step_grid(h);
     const bool keep = h->cfg.keep_prev != 0;
+    const bool bp = h->bp_size > 0;
     s = timed(h, GPF_K_STEP, [&] {
-        if (keep) { DISPATCH_MODEL(h, (launch_step_blk_prop<MM, true>(h, grid))); }
-        else      { DISPATCH_MODEL(h, (launch_step_blk_prop<MM, false>(h, grid))); }
+        if (keep && bp) { DISPATCH_MODEL(h, (launch_step_blk_prop<MM, true, true>(h, grid))); }
+        else if (keep)  { DISPATCH_MODEL(h, (launch_step_blk_prop<MM, true, false>(h, grid))); }
+        else if (bp)    { DISPATCH_MODEL(h, (launch_step_blk_prop<MM, false, true>(h, grid))); }
+        else            { DISPATCH_MODEL(h, (launch_step_blk_prop<MM, false, false>(h, grid))); }
     });
     h->args.blk_prop = nullptr;
     if (s) return s;
@@ -472,9 +493,12 @@ gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, 
     if ((s = materialize(h))) return s;
     h->args.blk_mask = only_resampled ? h->blk_mask : nullptr;
     const int grid = move_grid(h);
+    const bool bp = h->bp_size > 0, rw = method == GPF_REJUVENATE_REWEIGHT;
     s = timed(h, GPF_K_MOVE, [&] {
-        if (method == GPF_REJUVENATE_REWEIGHT) { DISPATCH_MODEL(h, (launch_move_blk<MM, true>(h, grid, n_iters))); }
-        else                                   { DISPATCH_MODEL(h, (launch_move_blk<MM, false>(h, grid, n_iters))); }
+        if (rw && bp)  { DISPATCH_MODEL(h, (launch_move_blk<MM, true, true>(h, grid, n_iters))); }
+        else if (rw)   { DISPATCH_MODEL(h, (launch_move_blk<MM, true, false>(h, grid, n_iters))); }
+        else if (bp)   { DISPATCH_MODEL(h, (launch_move_blk<MM, false, true>(h, grid, n_iters))); }
+        else           { DISPATCH_MODEL(h, (launch_move_blk<MM, false, false>(h, grid, n_iters))); }
     });
     h->args.blk_mask = nullptr;
     if (s) return s;
@@ -505,6 +529,39 @@ gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, 
             *n_accepted = h->h_sc->n_accept;
         }
     }
+    return GPF_OK;
+}
+// for b in blocks: the model arguments of state[b] (src/update.jl:12-25 on a sub-state with new_args_b) -- gpf.h gpf_set_block_params.  The rows go
+// to the device once, zero-padded to MAX_PARAMS; the block-wise steps read them through ModelArgs::blk_params for as long as they are set
+gpf_status gpf_set_block_params(gpf_handle h, const double* params, int32_t n_params, int64_t block_size)
+{
+    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+    if (h->parent) return fail(h, GPF_ERR_STATE, "gpf_set_block_params on a sub-state view: call it on the filter");
+    if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, "gpf_set_block_params on a shard of a sharded filter");
+    if (h->hist_on) return fail(h, GPF_ERR_STATE, "gpf_set_block_params on a filter with a trajectory store");
+    if (!params) {                                               // clear: the filter's own parameter vector again (the buffer stays for reuse)
+        h->bp_size = 0; h->args.blk_params = nullptr;
+        return GPF_OK;
+    }
+    if (n_params < 1 || n_params > MAX_PARAMS) return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_set_block_params: need 1 <= n_params <= " + std::to_string(MAX_PARAMS));
+    if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");
+    block_size = std::min<int64_t>(block_size, std::max<int64_t>(h->n, 1));          // (as block_step_checks)
+    const int64_t nblocks = (h->n + block_size - 1) / block_size;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    std::vector<double> rows((size_t)nblocks * MAX_PARAMS, 0.0);
+    for (int64_t b = 0; b < nblocks; ++b)
+        for (int i = 0; i < n_params; ++i) rows[(size_t)b * MAX_PARAMS + i] = params[b * n_params + i];
+    // (kernels enqueued earlier may still read the old rows: the stream drains before the buffer is replaced or overwritten)
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->blk_params_cap < nblocks) {
+        if (h->blk_params) { (void)hipFree(h->blk_params); h->blk_params = nullptr; h->blk_params_cap = 0; h->bp_size = 0; h->args.blk_params = nullptr; }
+        HIP_TRY(h, hipMalloc(&h->blk_params, rows.size() * sizeof(double)));
+        h->blk_params_cap = nblocks;
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->blk_params, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                 // (the host rows go out of scope)
+    h->args.blk_params = h->blk_params;
+    h->bp_size = block_size;
     return GPF_OK;
 }
 
@@ -660,6 +717,7 @@ static gpf_status view_create_impl(gpf_handle parent, int64_t start, int64_t ste
 // bump = false (gpf_coalesce): the caller makes the views stale itself, once the call can no longer be refused
 static gpf_status resize_ready(gpf_handle h, bool bump = true)
 {
+    if (h && bp_refused(h, "resizing")) return GPF_ERR_STATE;   // (the rows are laid out by block: a new particle count breaks the layout)
     gpf_status s = check_ready(h);
     if (s) return s;
     if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, "resizing a sharded filter is not supported");
@@ -960,6 +1018,7 @@ gpf_status gpf_coalesce(gpf_handle h, uint64_t key_mask, int64_t* n_out)
 gpf_status gpf_introduce(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int64_t n_particles, int32_t proposal)
 {
     if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+    if (gpf_status b = bp_refused(h, "gpf_introduce")) return b;
     if (n_steps < 1 || !obs) return fail(h, GPF_ERR_INVALID_ARGUMENT, "introduce: need observations of at least one step");
     if (n_obs != model_obs_dim(h->cfg.model))
         return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model takes " + std::to_string(model_obs_dim(h->cfg.model)) + " observation values per step");

@@ -582,7 +582,7 @@ gpf_status gpf_destroy(gpf_handle h)
     for (void* q : {(void*)h->vrows[0], (void*)h->vrows[1], (void*)h->vlw, (void*)h->vanc, (void*)h->vidx, (void*)h->vgid}) if (q) (void)hipFree(q);
     { Bufs b = take_particle_buffers(h); free_bufs(b); }
     void* bufs[] = {h->mslots[0], h->mslots[1], h->blockQ, h->partial, h->dscal, h->sc, h->push_stage, h->shard_counts, h->shard_plan, h->tree_buf, h->acc_part,
-                    h->pull_req, h->pull_counts, h->pull_pc, h->pull_pc_all, h->blk_words, h->blk_mask, h->blk_stats, h->blk_obs};
+                    h->pull_req, h->pull_counts, h->pull_pc, h->pull_pc_all, h->blk_words, h->blk_mask, h->blk_stats, h->blk_obs, h->blk_params};
     for (void* b : bufs) if (b) hipFree(b);
     if (h->h_sc) hipHostFree(h->h_sc);
     if (h->h_sc_ticket) hipHostFree(h->h_sc_ticket);
@@ -631,6 +631,7 @@ static gpf_status initialize_impl(gpf_handle h, const double* obs, int32_t n_obs
     if (prop == 2 && !model_has_strata(h->cfg.model)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no discrete latent to stratify over");
     if (prop == 3 && h->cfg.model != MODEL_LINE) return fail(h, GPF_ERR_INVALID_ARGUMENT, "stratified initialisation with a native proposal: line_model only");
     if (h->parent) return fail(h, GPF_ERR_STATE, "gpf_initialize on a sub-state view");
+    if (gpf_status b = bp_refused(h, "gpf_initialize")) return b;
     h->generation += 1;
     gpf_status s = set_obs(h, obs, n_obs);
     if (s) return s;
@@ -676,6 +677,7 @@ gpf_status gpf_initialize_proposal(gpf_handle h, const double* obs, int32_t n_ob
 
 static gpf_status update_impl(gpf_handle h, const double* obs, int32_t n_obs, int prop)
 {
+    if (h && bp_refused(h, "gpf_update")) return GPF_ERR_STATE;
     gpf_status s = check_ready(h, prop == 0);                    // (the plain propagate carries a pending lazy move)
     if (s) return s;
     if (prop == 1 && !model_has_proposal(h->cfg.model)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no native proposal");
@@ -781,6 +783,7 @@ extern "C" {
 gpf_status gpf_step_ess(gpf_handle h, const double* obs, int32_t n_obs, double ess_frac, int32_t resample_method, int32_t sort_particles,
                         int32_t check, int32_t rejuvenate_method, int32_t n_iters, int32_t* resampled, int32_t* invalid, double* ess_out)
 {
+    if (h && bp_refused(h, "gpf_step_ess")) return GPF_ERR_STATE;
     gpf_status s = check_ready(h);
     if (s) return s;
     if (!(ess_frac == ess_frac) || ess_frac < 0.0) return fail(h, GPF_ERR_INVALID_ARGUMENT, "ess_frac must be >= 0");
@@ -859,6 +862,7 @@ gpf_status set_strata(gpf_handle h, const double* values, int32_t n_strata, int3
 extern "C" {
 gpf_status gpf_initialize_strata(gpf_handle h, const double* obs, int32_t n_obs, const double* values, int32_t n_strata, int32_t interleaved)
 {
+    if (h && bp_refused(h, "gpf_initialize_strata")) return GPF_ERR_STATE;   // (before set_strata changes the handle's arguments)
     gpf_status s = set_strata(h, values, n_strata, interleaved);
     return s ? s : initialize_impl(h, obs, n_obs, 2);
 }
@@ -866,11 +870,13 @@ gpf_status gpf_initialize_strata_proposal(gpf_handle h, const double* obs, int32
                                           int32_t proposal)
 {
     if (!proposal_matches(h, proposal) || proposal != GPF_PROPOSAL_LINE_FIXED) return fail(h, GPF_ERR_INVALID_ARGUMENT, "unknown proposal id for this model");
+    if (h && bp_refused(h, "gpf_initialize_strata_proposal")) return GPF_ERR_STATE;
     gpf_status s = set_strata(h, values, n_strata, interleaved);
     return s ? s : initialize_impl(h, obs, n_obs, 3);
 }
 gpf_status gpf_update_strata(gpf_handle h, const double* obs, int32_t n_obs, const double* values, int32_t n_strata, int32_t interleaved)
 {
+    if (h && bp_refused(h, "gpf_update_strata")) return GPF_ERR_STATE;
     gpf_status s = set_strata(h, values, n_strata, interleaved);
     return s ? s : update_impl(h, obs, n_obs, 2);
 }
@@ -891,11 +897,14 @@ gpf_status gpf_rejuvenate_with_proposal(gpf_handle h, int32_t method, int32_t pr
     const bool ok = (proposal == GPF_MOVE_PROPOSAL_LOCALLY_OPTIMAL && h->cfg.model == MODEL_LGSSM2 && n_params == 0) ||
                     (proposal == GPF_MOVE_PROPOSAL_LINE_OUTLIER && h->cfg.model == MODEL_LINE && n_params == 3);
     if (!ok || !model_has_move_proposal(h->cfg.model)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "unknown move proposal for this model (or wrong parameter count)");
+    if (gpf_status b = bp_refused(h, "gpf_rejuvenate_with_proposal")) return b;
     for (int i = 0; i < 4; ++i) h->args.q[i] = i < n_params ? params[i] : 0.0;
     return rejuvenate_impl(h, method, n_iters, n_accepted, true);
 }
 static gpf_status rejuvenate_impl(gpf_handle h, int32_t method, int32_t n_iters, uint64_t* n_accepted, bool with_proposal)
 {
+    // per-block parameters: only the delegation to gpf_rejuvenate_blocks below (a whole filter after a block-wise update) uses them
+    if (h && (h->parent || h->blk_obs_size <= 0) && bp_refused(h, "gpf_rejuvenate")) return GPF_ERR_STATE;
     gpf_status s = check_ready(h);
     if (s) return s;
     if (h->parent && h->parent->blk_obs_size != 0)

@@ -202,6 +202,27 @@ gpf_status gpf_update_blocks_proposal(gpf_handle h, const double* obs, int32_t n
 gpf_status gpf_initialize_blocks_strata(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, const double* values, int32_t n_strata, int32_t interleaved);
 gpf_status gpf_update_blocks_strata(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, const double* values, int32_t n_strata, int32_t interleaved);
 gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, int32_t only_resampled, uint64_t* n_accepted);
+/* for b in blocks: the model arguments of state[b] (src/update.jl:12-25 on a sub-state with new_args_b) -- many parameter values in one state,
+ * e.g. the likelihood p(y_1:T | theta_b) of every block from gpf_block_stats.
+ *   params: HOST [n_blocks][n_params] doubles, row b = block b's parameter vector in the layout of csrc/gpf_models.hpp (derived constants
+ *           included, exactly as gpf_config.params); 1 <= n_params <= 24; NULL clears them (n_params and block_size are then ignored).
+ *   block_size: as in the block-wise calls (clamped to the particle count); n_blocks = ceil(n / block_size).
+ * The rows are uploaded once and stay in force until they are cleared or the handle is destroyed.  While they are set:
+ *   - every block-wise step uses row b for block b: gpf_initialize_blocks, gpf_update_blocks, gpf_update_blocks_proposal,
+ *     gpf_{initialize,update}_blocks_strata and gpf_rejuvenate_blocks (move and reweight), and the whole-filter gpf_rejuvenate when it
+ *     delegates to gpf_rejuvenate_blocks after a block-wise update.  Block b's rows, weights, parents, accept counts and gpf_block_stats
+ *     entries are bit-identical to those of block b of the same calls on a filter created with params = row b (same seed, epochs and
+ *     particle ids: the RNG counters do not depend on the parameters);
+ *   - a block-wise step whose (clamped) block_size differs from the rows' returns GPF_ERR_INVALID_ARGUMENT and changes nothing;
+ *   - every call that would use gpf_config.params returns GPF_ERR_STATE and changes nothing: gpf_initialize*, gpf_update*, gpf_step_ess,
+ *     gpf_introduce, gpf_rejuvenate* other than the delegation above, any of these on a view of the filter, and the resize family
+ *     (gpf_resize, gpf_replicate, gpf_dereplicate, gpf_coalesce), which would break the block layout;
+ *   - model-independent calls work as before: gpf_resample*, gpf_resample_blocks, gpf_block_stats, the getters, views, checkpoints.
+ * Clearing the rows restores the behaviour without them exactly.  A checkpoint does not hold the rows (the blob layout is unchanged) and
+ * gpf_checkpoint_load neither sets nor clears them: restore, then call gpf_set_block_params again to continue bit for bit.
+ * Not on views, shards of a sharded filter or filters with a trajectory store (GPF_ERR_STATE); a NULL handle, n_params outside 1..24 or
+ * block_size < 1 return GPF_ERR_INVALID_ARGUMENT and change nothing. */
+gpf_status gpf_set_block_params(gpf_handle h, const double* params, int32_t n_params, int64_t block_size);
 
 /* same, with log_priorities = priority_fn.(log_weights) evaluated by the caller (any closure):
  * log_priorities is a HOST array of n_particles doubles. */

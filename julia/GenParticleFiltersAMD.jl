@@ -251,6 +251,22 @@ function pf_rejuvenate_blocks!(s::DeviceParticleFilterState, kern=nothing, kern_
     m = method == :move ? 0 : method == :reweight ? 1 : error("Method $method not recognized.")
     _status(s, ccall((:gpf_rejuvenate_blocks, libgpf), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{UInt64}), s.handle, m, n_iters, only_resampled ? 1 : 0, C_NULL)); s
 end
+# for b in blocks: the model arguments of state[b] (src/update.jl:12-25 on a sub-state with new_args_b) -- gpf.h gpf_set_block_params.  params: a
+# (n_params, n_blocks) Matrix, column b = block b's parameter vector in the layout of csrc/gpf_models.hpp (derived constants included), or a
+# Vector of NativeModel descriptors of the state's model; `nothing` clears them.  While set, the block-wise calls use column b for block b (this
+# block_size only) and every call that would use the state's own parameters fails.
+function set_block_params!(s::DeviceParticleFilterState, params::Matrix{Float64}, block_size::Int)
+    size(params, 2) == cld(s.n_particles, min(block_size, s.n_particles)) || error("one parameter column per block expected")
+    _status(s, ccall((:gpf_set_block_params, libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Int64), s.handle, params, size(params, 1), block_size)); s
+end
+function set_block_params!(s::DeviceParticleFilterState, models::Vector{NativeModel}, block_size::Int)
+    all(m -> m.id == s.model.id, models) || error("per-block parameters: descriptors of another model")
+    allequal(length.(getfield.(models, :params))) || error("per-block parameters: the descriptors' parameter vectors differ in length")
+    set_block_params!(s, reduce(hcat, getfield.(models, :params)), block_size)
+end
+function set_block_params!(s::DeviceParticleFilterState, ::Nothing, block_size::Int=0)
+    _status(s, ccall((:gpf_set_block_params, libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Int64), s.handle, C_NULL, 0, block_size)); s
+end
 "which blocks the last pf_resample_blocks! resampled"
 function block_resampled(s::DeviceParticleFilterState, block_size::Int)
     out = Vector{Cint}(undef, cld(s.n_particles, block_size))
