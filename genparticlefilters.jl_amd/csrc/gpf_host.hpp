@@ -16,6 +16,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace gpf;
@@ -418,6 +419,42 @@ inline int move_grid(const gpf_filter* h) { return std::min(grid_for(h, h->n, MO
         case MODEL_OBJECT_MOTION: { constexpr int MM = MODEL_OBJECT_MOTION; CALL; } break;       \
         case MODEL_LINE: { constexpr int MM = MODEL_LINE; CALL; } break;                         \
     }
+// the row width of the filter (2, 4 or 8 doubles) as constexpr int WW
+#define DISPATCH_W(h, CALL)                                                                      \
+    switch ((h)->W) {                                                                            \
+        case 2: { constexpr int WW = 2; CALL; } break;                                           \
+        case 4: { constexpr int WW = 4; CALL; } break;                                           \
+        case 8: { constexpr int WW = 8; CALL; } break;                                           \
+    }
+
+// f(std::bool_constant<a>{}[, std::bool_constant<b>{}]): runtime flags as template arguments, e.g. launch_x<MM, KEEP, BP> with KEEP, BP the arguments
+template <class F>
+inline void bool_dispatch(bool a, F&& f)
+{
+    if (a) f(std::true_type{}); else f(std::false_type{});
+}
+template <class F>
+inline void bool_dispatch(bool a, bool b, F&& f)
+{
+    bool_dispatch(a, [&](auto A) { bool_dispatch(b, [&](auto B) { f(A, B); }); });
+}
+
+// what the filter's model offers beyond its default sampler (gpf_models.hpp Model<M>::HAS_*)
+struct ModelCaps { bool proposal, strata, strata_proposal, move_proposal; };
+inline ModelCaps model_caps(const gpf_filter* h)
+{
+    ModelCaps c{};
+    DISPATCH_MODEL(h, (c = ModelCaps{Model<MM>::HAS_PROPOSAL, Model<MM>::HAS_STRATA, Model<MM>::HAS_STRATA_PROPOSAL, Model<MM>::HAS_MOVE_PROPOSAL}));
+    return c;
+}
+// does the native proposal id name this model's proposal: the locally optimal one (all models but line_model), the reference tests' fixed
+// proposals (line_model).  Whether the model has a native proposal at all is model_caps(h).proposal.
+inline bool proposal_valid(const gpf_filter* h, int32_t proposal)
+{
+    if (proposal == GPF_PROPOSAL_LOCALLY_OPTIMAL) return h->cfg.model != MODEL_LINE;
+    if (proposal == GPF_PROPOSAL_LINE_FIXED) return h->cfg.model == MODEL_LINE;
+    return false;
+}
 
 inline PrioView raw_view(const gpf_filter* h) { return PrioView{h->lw, nullptr, 0.0, 0}; }
 
@@ -451,6 +488,8 @@ gpf_status hist_snapshot(gpf_filter* h);
 gpf_status hist_on_resample(gpf_filter* h);
 gpf_status hist_begin_step(gpf_filter* h, bool first);
 void mutated(gpf_filter* h);
+gpf_status after_initialize(gpf_filter* h, int grid);
+void after_propagate(gpf_filter* h);
 gpf_status view_enter(gpf_filter* v);
 gpf_status view_exit(gpf_filter* v);
 gpf_status check_ready(gpf_handle h, bool keep_pending_move = false);

@@ -8,42 +8,22 @@ using namespace gpfh;
 
 namespace gpfh {
 
-// block-wise propagate / move (ModelArgs::blk_*): the default proposal only, no fused gather (a block resample gathers eagerly)
+// block-wise initialise / propagate / move (ModelArgs::blk_*): no fused gather (a block resample gathers eagerly).  MODE 0: the default proposal;
+// 2: stratified; 4 (propagate): per block the native proposal or the default one (ModelArgs::blk_prop).
 // BP: per-block parameters are set (gpf_set_block_params) -- the kernels read block b's row of ModelArgs::blk_params instead of P
-template <int M, bool BP>
+template <int M, int MODE, bool BP>
 void launch_init_blk(gpf_filter* h, int grid)
 {
-    GPF_LAUNCH((k_init<M, 0, true, BP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
-                       h->cfg.gid0, h->n, h->W, h->rows[h->cur], h->lw, next_slots(h));
+    if constexpr (MODE == 2 && !Model<M>::HAS_STRATA) { (void)h; (void)grid; return; }
+    else GPF_LAUNCH((k_init<M, MODE, true, BP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
+                    h->cfg.gid0, h->n, h->W, h->rows[h->cur], h->lw, next_slots(h));
 }
-template <int M, bool KEEP, bool BP>
+template <int M, int MODE, bool KEEP, bool BP>
 void launch_step_blk(gpf_filter* h, int grid)
 {
     constexpr int Wc = row_width(Model<M>::D, KEEP);
-    GPF_LAUNCH((k_step<M, Wc, KEEP, false, 0, false, true, BP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
-                       h->cfg.gid0, h->n, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, next_slots(h), PackedCommit{});
-}
-template <int M, bool BP>
-void launch_init_blk_strata(gpf_filter* h, int grid)
-{
-    if constexpr (!Model<M>::HAS_STRATA) { (void)h; (void)grid; return; }
-    else GPF_LAUNCH((k_init<M, 2, true, BP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
-                    h->cfg.gid0, h->n, h->W, h->rows[h->cur], h->lw, next_slots(h));
-}
-template <int M, bool KEEP, bool BP>
-void launch_step_blk_strata(gpf_filter* h, int grid)
-{
-    constexpr int Wc = row_width(Model<M>::D, KEEP);
-    if constexpr (!Model<M>::HAS_STRATA) { (void)h; (void)grid; return; }
-    else GPF_LAUNCH((k_step<M, Wc, KEEP, false, 2, false, true, BP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
-                    h->cfg.gid0, h->n, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, next_slots(h), PackedCommit{});
-}
-template <int M, bool KEEP, bool BP>
-void launch_step_blk_prop(gpf_filter* h, int grid)
-{
-    constexpr int Wc = row_width(Model<M>::D, KEEP);
-    if constexpr (!Model<M>::HAS_PROPOSAL) { (void)h; (void)grid; return; }
-    else GPF_LAUNCH((k_step<M, Wc, KEEP, false, 4, false, true, BP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
+    if constexpr ((MODE == 2 && !Model<M>::HAS_STRATA) || (MODE == 4 && !Model<M>::HAS_PROPOSAL)) { (void)h; (void)grid; return; }
+    else GPF_LAUNCH((k_step<M, Wc, KEEP, false, MODE, false, true, BP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
                     h->cfg.gid0, h->n, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, next_slots(h), PackedCommit{});
 }
 template <int M, bool RW, bool BP>
@@ -65,11 +45,7 @@ void launch_block_resample_w(gpf_filter* h, const BlockArgs& a)
 template <int METHOD>
 void launch_block_resample(gpf_filter* h, const BlockArgs& a, bool prio)
 {
-    switch (h->W) {
-        case 2: if (prio) launch_block_resample_w<METHOD, 2, true>(h, a); else launch_block_resample_w<METHOD, 2, false>(h, a); break;
-        case 4: if (prio) launch_block_resample_w<METHOD, 4, true>(h, a); else launch_block_resample_w<METHOD, 4, false>(h, a); break;
-        case 8: if (prio) launch_block_resample_w<METHOD, 8, true>(h, a); else launch_block_resample_w<METHOD, 8, false>(h, a); break;
-    }
+    bool_dispatch(prio, [&](auto PRIO) { DISPATCH_W(h, (launch_block_resample_w<METHOD, WW, PRIO>(h, a))); });
 }
 
 } // namespace gpfh
@@ -324,117 +300,81 @@ static gpf_status block_step_checks(gpf_handle h, int64_t& block_size, const cha
         return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model takes " + std::to_string(model_obs_dim(h->cfg.model)) + " observation values per step and block");
     return GPF_OK;
 }
+// The block-wise pf_initialize / pf_update! once the caller's checks have passed (a refused call changes nothing).  mode 0: the default proposal;
+// 2: stratified (the caller set the strata); 4 (update): block b is extended with the native proposal where use_proposal[b] != 0.
+static gpf_status block_initialize_impl(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, int mode)
+{
+    h->generation += 1;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    gpf_status s = set_block_obs(h, obs, n_obs, block_size);
+    if (s) return s;
+    const int grid = step_grid(h);
+    s = timed(h, GPF_K_STEP, [&] {
+        bool_dispatch(h->bp_size > 0, [&](auto BP) {
+            if (mode == 2) { DISPATCH_MODEL(h, (launch_init_blk<MM, 2, BP>(h, grid))); }
+            else           { DISPATCH_MODEL(h, (launch_init_blk<MM, 0, BP>(h, grid))); }
+        });
+    });
+    if (s || (s = after_initialize(h, grid))) return s;
+    h->blk_last = 0;                                             // only_resampled refers to a gpf_resample_blocks of the CURRENT step
+    return GPF_OK;
+}
+static gpf_status block_update_impl(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, int mode, const int32_t* use_proposal)
+{
+    gpf_status s = materialize(h);                               // (no fused gather in the block-wise step)
+    if (s || (s = set_block_obs(h, obs, n_obs, block_size))) return s;
+    if (mode == 4) {
+        const int64_t nblocks = (h->n + block_size - 1) / block_size;
+        if ((s = block_buffers(h, nblocks))) return s;           // (blk_mask doubles as the flag array: no block resample refers to it after this call)
+        HIP_TRY(h, hipMemcpyAsync(h->blk_mask, use_proposal, (size_t)nblocks * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));             // (the caller's array may go away)
+        h->args.blk_prop = h->blk_mask;
+    }
+    const int grid = step_grid(h);
+    s = timed(h, GPF_K_STEP, [&] {
+        bool_dispatch(h->cfg.keep_prev != 0, h->bp_size > 0, [&](auto KEEP, auto BP) {
+            if (mode == 4)      { DISPATCH_MODEL(h, (launch_step_blk<MM, 4, KEEP, BP>(h, grid))); }
+            else if (mode == 2) { DISPATCH_MODEL(h, (launch_step_blk<MM, 2, KEEP, BP>(h, grid))); }
+            else                { DISPATCH_MODEL(h, (launch_step_blk<MM, 0, KEEP, BP>(h, grid))); }
+        });
+    });
+    h->args.blk_prop = nullptr;
+    if (s) return s;
+    HIP_TRY(h, hipGetLastError());
+    after_propagate(h);
+    h->blk_last = 0;                                             // (as in block_initialize_impl)
+    return GPF_OK;
+}
 gpf_status gpf_initialize_blocks(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size)
 {
     gpf_status s = block_step_checks(h, block_size, "gpf_initialize_blocks");
-    if (s) return s;
-    h->generation += 1;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if ((s = set_block_obs(h, obs, n_obs, block_size))) return s;
-    const int grid = step_grid(h);
-    const bool bp = h->bp_size > 0;
-    s = timed(h, GPF_K_STEP, [&] {
-        if (bp) { DISPATCH_MODEL(h, (launch_init_blk<MM, true>(h, grid))); }
-        else    { DISPATCH_MODEL(h, (launch_init_blk<MM, false>(h, grid))); }
-    });
-    if (s) return s;
-    h->pending_gather = false; h->pending_fill = false; h->pending_packed = false; h->pending_search = false; h->pending_move = false;
-    h->max_valid = true;
-    GPF_LAUNCH(k_iota, dim3(grid), dim3(BLOCK), 0, h->stream, h->anc, h->n);            // parents = 1:N (initialize.jl:43)
-    HIP_TRY(h, hipMemsetAsync(&h->sc->lml_est, 0, sizeof(double), h->stream));
-    HIP_TRY(h, hipGetLastError());
-    h->epoch += 1;
-    h->initialized = true; h->has_prev = false; h->raw_valid = false; h->raw_sum_valid = false;
-    h->blk_last = 0;                                             // only_resampled refers to a gpf_resample_blocks of the CURRENT step
-    mutated(h);
-    return GPF_OK;
+    return s ? s : block_initialize_impl(h, obs, n_obs, block_size, 0);
 }
 gpf_status gpf_update_blocks(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size)
 {
     gpf_status s = block_step_checks(h, block_size, "gpf_update_blocks");
-    if (s) return s;
-    if ((s = check_ready(h))) return s;
-    if ((s = materialize(h))) return s;                          // (no fused gather in the block-wise step)
-    if ((s = set_block_obs(h, obs, n_obs, block_size))) return s;
-    const int grid = step_grid(h);
-    const bool keep = h->cfg.keep_prev != 0;
-    const bool bp = h->bp_size > 0;
-    s = timed(h, GPF_K_STEP, [&] {
-        if (keep && bp) { DISPATCH_MODEL(h, (launch_step_blk<MM, true, true>(h, grid))); }
-        else if (keep)  { DISPATCH_MODEL(h, (launch_step_blk<MM, true, false>(h, grid))); }
-        else if (bp)    { DISPATCH_MODEL(h, (launch_step_blk<MM, false, true>(h, grid))); }
-        else            { DISPATCH_MODEL(h, (launch_step_blk<MM, false, false>(h, grid))); }
-    });
-    if (s) return s;
-    HIP_TRY(h, hipGetLastError());
-    h->max_valid = true;
-    h->cur ^= 1;
-    h->epoch += 1;
-    h->has_prev = true;
-    h->raw_valid = false; h->raw_sum_valid = false;
-    h->blk_last = 0;                                             // (as in gpf_initialize_blocks)
-    mutated(h);
-    return GPF_OK;
+    if (s || (s = check_ready(h))) return s;
+    return block_update_impl(h, obs, n_obs, block_size, 0, nullptr);
 }
 // for b in blocks: pf_initialize(model, args, observations[b], strata, n_b) / pf_update!(state[b], ..., observations[b], strata) -- stratified
 // initialisation / update (src/initialize.jl:92-109, src/update.jl:193-210) of every block by itself, one launch: the stratum of a particle
 // follows from its index INSIDE its block and the block's own size (stratified_map!, src/utils.jl:29-55, on the sub-state), the same strata for all blocks
-static bool has_strata(gpf_filter* h) { bool v = false; DISPATCH_MODEL(h, (v = Model<MM>::HAS_STRATA)); return v; }
+static gpf_status block_strata(gpf_handle h, const double* values, int32_t n_strata, int32_t interleaved)
+{
+    if (!model_caps(h).strata) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no discrete latent to stratify over");
+    return set_strata(h, values, n_strata, interleaved);
+}
 gpf_status gpf_initialize_blocks_strata(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, const double* values, int32_t n_strata, int32_t interleaved)
 {
     gpf_status s = block_step_checks(h, block_size, "gpf_initialize_blocks_strata", obs, n_obs, true);
-    if (s) return s;
-    if (!has_strata(h)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no discrete latent to stratify over");
-    if ((s = set_strata(h, values, n_strata, interleaved))) return s;
-    h->generation += 1;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if ((s = set_block_obs(h, obs, n_obs, block_size))) return s;
-    const int grid = step_grid(h);
-    const bool bp = h->bp_size > 0;
-    s = timed(h, GPF_K_STEP, [&] {
-        if (bp) { DISPATCH_MODEL(h, (launch_init_blk_strata<MM, true>(h, grid))); }
-        else    { DISPATCH_MODEL(h, (launch_init_blk_strata<MM, false>(h, grid))); }
-    });
-    if (s) return s;
-    h->pending_gather = false; h->pending_fill = false; h->pending_packed = false; h->pending_search = false; h->pending_move = false;
-    h->max_valid = true;
-    GPF_LAUNCH(k_iota, dim3(grid), dim3(BLOCK), 0, h->stream, h->anc, h->n);            // parents = 1:N (initialize.jl:43)
-    HIP_TRY(h, hipMemsetAsync(&h->sc->lml_est, 0, sizeof(double), h->stream));
-    HIP_TRY(h, hipGetLastError());
-    h->epoch += 1;
-    h->initialized = true; h->has_prev = false; h->raw_valid = false; h->raw_sum_valid = false;
-    h->blk_last = 0;
-    mutated(h);
-    return GPF_OK;
+    if (s || (s = block_strata(h, values, n_strata, interleaved))) return s;
+    return block_initialize_impl(h, obs, n_obs, block_size, 2);
 }
 gpf_status gpf_update_blocks_strata(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, const double* values, int32_t n_strata, int32_t interleaved)
 {
     gpf_status s = block_step_checks(h, block_size, "gpf_update_blocks_strata", obs, n_obs, true);
-    if (s) return s;
-    if ((s = check_ready(h))) return s;
-    if (!has_strata(h)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no discrete latent to stratify over");
-    if ((s = set_strata(h, values, n_strata, interleaved))) return s;
-    if ((s = materialize(h))) return s;
-    if ((s = set_block_obs(h, obs, n_obs, block_size))) return s;
-    const int grid = step_grid(h);
-    const bool keep = h->cfg.keep_prev != 0;
-    const bool bp = h->bp_size > 0;
-    s = timed(h, GPF_K_STEP, [&] {
-        if (keep && bp) { DISPATCH_MODEL(h, (launch_step_blk_strata<MM, true, true>(h, grid))); }
-        else if (keep)  { DISPATCH_MODEL(h, (launch_step_blk_strata<MM, true, false>(h, grid))); }
-        else if (bp)    { DISPATCH_MODEL(h, (launch_step_blk_strata<MM, false, true>(h, grid))); }
-        else            { DISPATCH_MODEL(h, (launch_step_blk_strata<MM, false, false>(h, grid))); }
-    });
-    if (s) return s;
-    HIP_TRY(h, hipGetLastError());
-    h->max_valid = true;
-    h->cur ^= 1;
-    h->epoch += 1;
-    h->has_prev = true;
-    h->raw_valid = false; h->raw_sum_valid = false;
-    h->blk_last = 0;
-    mutated(h);
-    return GPF_OK;
+    if (s || (s = check_ready(h)) || (s = block_strata(h, values, n_strata, interleaved))) return s;
+    return block_update_impl(h, obs, n_obs, block_size, 2, nullptr);
 }
 // for b in blocks: pf_update!(state[b], new_args, argdiffs, observations[b][, proposal, proposal_args]) -- the per-view updates with DIFFERENT
 // proposals per view (test/update.jl:179-189) in one launch: use_proposal[b] != 0 -> block b is extended with the model's native proposal
@@ -442,40 +382,10 @@ gpf_status gpf_update_blocks_strata(gpf_handle h, const double* obs, int32_t n_o
 gpf_status gpf_update_blocks_proposal(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, const int32_t* use_proposal, int32_t proposal)
 {
     gpf_status s = block_step_checks(h, block_size, "gpf_update_blocks_proposal");
-    if (s) return s;
-    if ((s = check_ready(h))) return s;
+    if (s || (s = check_ready(h))) return s;
     if (!use_proposal) return fail(h, GPF_ERR_INVALID_ARGUMENT, "null use_proposal");
-    const bool ok = (proposal == GPF_PROPOSAL_LOCALLY_OPTIMAL && h->cfg.model != MODEL_LINE) || (proposal == GPF_PROPOSAL_LINE_FIXED && h->cfg.model == MODEL_LINE);
-    bool has = false;
-    DISPATCH_MODEL(h, (has = Model<MM>::HAS_PROPOSAL));
-    if (!ok || !has) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no such native proposal");
-    if ((s = materialize(h))) return s;                          // (no fused gather in the block-wise step)
-    if ((s = set_block_obs(h, obs, n_obs, block_size))) return s;
-    const int64_t nblocks = (h->n + block_size - 1) / block_size;
-    if ((s = block_buffers(h, nblocks))) return s;               // (blk_mask doubles as the flag array: no block resample refers to it after this call)
-    HIP_TRY(h, hipMemcpyAsync(h->blk_mask, use_proposal, (size_t)nblocks * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));                 // (the caller's array may go away)
-    h->args.blk_prop = h->blk_mask;
-    const int grid = step_grid(h);
-    const bool keep = h->cfg.keep_prev != 0;
-    const bool bp = h->bp_size > 0;
-    s = timed(h, GPF_K_STEP, [&] {
-        if (keep && bp) { DISPATCH_MODEL(h, (launch_step_blk_prop<MM, true, true>(h, grid))); }
-        else if (keep)  { DISPATCH_MODEL(h, (launch_step_blk_prop<MM, true, false>(h, grid))); }
-        else if (bp)    { DISPATCH_MODEL(h, (launch_step_blk_prop<MM, false, true>(h, grid))); }
-        else            { DISPATCH_MODEL(h, (launch_step_blk_prop<MM, false, false>(h, grid))); }
-    });
-    h->args.blk_prop = nullptr;
-    if (s) return s;
-    HIP_TRY(h, hipGetLastError());
-    h->max_valid = true;
-    h->cur ^= 1;
-    h->epoch += 1;
-    h->has_prev = true;
-    h->raw_valid = false; h->raw_sum_valid = false;
-    h->blk_last = 0;
-    mutated(h);
-    return GPF_OK;
+    if (!proposal_valid(h, proposal) || !model_caps(h).proposal) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no such native proposal");
+    return block_update_impl(h, obs, n_obs, block_size, 4, use_proposal);
 }
 gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, int32_t only_resampled, uint64_t* n_accepted)
 {
@@ -493,12 +403,10 @@ gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, 
     if ((s = materialize(h))) return s;
     h->args.blk_mask = only_resampled ? h->blk_mask : nullptr;
     const int grid = move_grid(h);
-    const bool bp = h->bp_size > 0, rw = method == GPF_REJUVENATE_REWEIGHT;
     s = timed(h, GPF_K_MOVE, [&] {
-        if (rw && bp)  { DISPATCH_MODEL(h, (launch_move_blk<MM, true, true>(h, grid, n_iters))); }
-        else if (rw)   { DISPATCH_MODEL(h, (launch_move_blk<MM, true, false>(h, grid, n_iters))); }
-        else if (bp)   { DISPATCH_MODEL(h, (launch_move_blk<MM, false, true>(h, grid, n_iters))); }
-        else           { DISPATCH_MODEL(h, (launch_move_blk<MM, false, false>(h, grid, n_iters))); }
+        bool_dispatch(method == GPF_REJUVENATE_REWEIGHT, h->bp_size > 0, [&](auto RW, auto BP) {
+            DISPATCH_MODEL(h, (launch_move_blk<MM, RW, BP>(h, grid, n_iters)));
+        });
     });
     h->args.blk_mask = nullptr;
     if (s) return s;
@@ -939,11 +847,7 @@ void launch_coal(gpf_filter* h, const CoalArgs& a, int stage, double log_ratio =
 }
 static void launch_coal_w(gpf_filter* h, const CoalArgs& a, int stage, double log_ratio = 0.0)
 {
-    switch (h->W) {
-        case 2: launch_coal<2>(h, a, stage, log_ratio); break;
-        case 4: launch_coal<4>(h, a, stage, log_ratio); break;
-        case 8: launch_coal<8>(h, a, stage, log_ratio); break;
-    }
+    DISPATCH_W(h, (launch_coal<WW>(h, a, stage, log_ratio)));
 }
 template <int M, bool KEEP, bool PROP>
 void launch_introduce(gpf_filter* h, uint64_t seed, const double* obs, int T, int64_t n_old, int64_t n_add)
@@ -953,14 +857,6 @@ void launch_introduce(gpf_filter* h, uint64_t seed, const double* obs, int T, in
     if constexpr (PROP && !Mo::HAS_PROPOSAL) { (void)h; (void)seed; (void)obs; (void)T; (void)n_old; (void)n_add; return; }
     else GPF_LAUNCH((k_introduce<M, Wc, KEEP, PROP>), dim3(grid_for(h, n_add, 8)), dim3(BLOCK), 0, h->stream, h->args, seed, obs, T, n_old, n_add,
                     h->rows[0], h->lw, h->anc);
-}
-static bool model_proposal_ok(const gpf_filter* h, int32_t proposal)
-{
-    bool has = false;
-    DISPATCH_MODEL(h, (has = Model<MM>::HAS_PROPOSAL));
-    if (proposal == GPF_PROPOSAL_LOCALLY_OPTIMAL) return has && h->cfg.model != MODEL_LINE;
-    if (proposal == GPF_PROPOSAL_LINE_FIXED) return h->cfg.model == MODEL_LINE;
-    return false;
 }
 } // namespace gpfh
 extern "C" {
@@ -1023,7 +919,7 @@ gpf_status gpf_introduce(gpf_handle h, const double* obs, int32_t n_obs, int32_t
     if (n_obs != model_obs_dim(h->cfg.model))
         return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model takes " + std::to_string(model_obs_dim(h->cfg.model)) + " observation values per step");
     if (n_particles < 1 || h->n + n_particles >= ((int64_t)1 << 31)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "introduce: bad n_particles");
-    if (proposal != 0 && !model_proposal_ok(h, proposal)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "unknown proposal id for this model");
+    if (proposal != 0 && !(proposal_valid(h, proposal) && model_caps(h).proposal)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "unknown proposal id for this model");
     gpf_status s = resize_ready(h);
     if (s) return s;
     const int64_t n_old = h->n;
@@ -1042,11 +938,9 @@ gpf_status gpf_introduce(gpf_handle h, const double* obs, int32_t n_obs, int32_t
     HIP_TRY(h, hipMemcpyAsync(h->anc, old.anc, (size_t)n_old * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
     GPF_LAUNCH(k_intro_old, dim3(grid_for(h, n_old, 8)), dim3(BLOCK), 0, h->stream, old.lw, h->sc, n_old, h->lw);
     HIP_TRY(h, hipMemsetAsync(reinterpret_cast<char*>(h->sc) + offsetof(Scalars, lml_est), 0, sizeof(double), h->stream));   // log_ml_est = 0
-    const bool keep = h->cfg.keep_prev != 0;
-    if (proposal) { if (keep) { DISPATCH_MODEL(h, (launch_introduce<MM, true, true>(h, seed, dobs, n_steps, n_old, n_particles))); }
-                    else      { DISPATCH_MODEL(h, (launch_introduce<MM, false, true>(h, seed, dobs, n_steps, n_old, n_particles))); } }
-    else          { if (keep) { DISPATCH_MODEL(h, (launch_introduce<MM, true, false>(h, seed, dobs, n_steps, n_old, n_particles))); }
-                    else      { DISPATCH_MODEL(h, (launch_introduce<MM, false, false>(h, seed, dobs, n_steps, n_old, n_particles))); } }
+    bool_dispatch(h->cfg.keep_prev != 0, proposal != 0, [&](auto KEEP, auto PROP) {
+        DISPATCH_MODEL(h, (launch_introduce<MM, KEEP, PROP>(h, seed, dobs, n_steps, n_old, n_particles)));
+    });
     HIP_TRY(h, hipStreamSynchronize(h->stream));                 // (the old buffers and the host copy of the history are read above)
     free_bufs(old);
     HIP_TRY(h, hipGetLastError());

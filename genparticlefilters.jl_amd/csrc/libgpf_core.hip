@@ -65,60 +65,62 @@ gpf_status alloc_particle_buffers(gpf_filter* h)
 }
 
 
+// A sharded commit is pending (gpf_shard_commit) and rides in the propagate.  Own-direct (pend_own): the first launch gathers the shard's own hits
+// through the ancestor array (it reads anc[j] >= 0 / -1) -- after a window exchange also the other slots, out of this rank's receive window -- and
+// updates the log-ML; the second one, behind it, commits the pend_m received packed entries (overwriting the -1).  Else one launch commits the packed entries.
+struct CommitArgs { PackedCommit first, second; };
+static CommitArgs pending_commit(const gpf_filter* h)
+{
+    const PackedCommit packed{h->pend_packed, h->anc, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, nullptr, nullptr, (int)h->pend_mailbox, 0, 0, nullptr};
+    if (!h->pend_own) {
+        PackedCommit only = packed;
+        only.sc = h->sc;
+        return {only, PackedCommit{}};
+    }
+    PackedCommit own{nullptr, h->anc, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, h->sc, nullptr, (int)h->pend_mailbox, h->pend_own_range ? 2 : 1, h->cfg.gid0,
+                     h->pend_own_range ? h->shard_plan->own_range : nullptr};
+    if (h->pend_ring) own.ring = RingIn{h->ring + (int64_t)(h->pend_ring_seq & (RING_PARITIES - 1)) * h->ring_parity_words, h->pend_ring_seq, h->h_timeout};
+    return {own, packed};
+}
+
 // PROP 0: the model's own sampler; 1: native custom proposal; 2: stratified
 template <int M, bool KEEP, int PROP = 0>
 void launch_step_t(gpf_filter* h, int grid, const GateIn* gate = nullptr)
 {
     constexpr int Wc = row_width(Model<M>::D, KEEP);
     if constexpr ((PROP == 1 && !Model<M>::HAS_PROPOSAL) || (PROP == 2 && !Model<M>::HAS_STRATA)) { (void)h; (void)grid; return; }
-    else if (h->pending_packed && h->pend_own) {
-        // own-direct commit: the shard's own hits through the ancestor array FIRST (it reads anc[j] >= 0 / -1; the packed entries'
-        // launch behind it overwrites the -1 with the received ancestors), then the received entries; one weight vector, one slot array
-        const MaxSlots ms = next_slots(h);
-        PackedCommit pg{nullptr, h->anc, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, h->sc, nullptr, (int)h->pend_mailbox, h->pend_own_range ? 2 : 1, h->cfg.gid0,
-                        h->pend_own_range ? h->shard_plan->own_range : nullptr};
-        // (a window exchange: the slots outside the own range are read from this rank's receive window in the same launch -- no packed entries)
-        if (h->pend_ring) pg.ring = RingIn{h->ring + (int64_t)(h->pend_ring_seq & (RING_PARITIES - 1)) * h->ring_parity_words, h->pend_ring_seq, h->h_timeout};
-        GPF_LAUNCH((k_step<M, Wc, KEEP, true, PROP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
-                           h->cfg.gid0, h->n, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, ms, pg);
-        if (h->pend_m > 0) {
-            const PackedCommit pc{h->pend_packed, h->anc, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, nullptr, nullptr, (int)h->pend_mailbox, 0, 0, nullptr};
-            g_ev_start = g_ev_stop = nullptr;                    // (timed(): the event pair belongs to the first launch)
-            GPF_LAUNCH((k_step<M, Wc, KEEP, false, PROP, true>), dim3(grid_for(h, h->pend_m, STEP_BLOCKS_PER_CU)), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
-                               h->cfg.gid0, h->pend_m, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, ms, pc);
-        }
-    }
     else if (h->pending_packed) {
         const MaxSlots ms = next_slots(h);
-        const PackedCommit pc{h->pend_packed, h->anc, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, h->sc, nullptr, (int)h->pend_mailbox, 0, 0, nullptr};
-        GPF_LAUNCH((k_step<M, Wc, KEEP, false, PROP, true>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
-                           h->cfg.gid0, h->n, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, ms, pc);
+        const CommitArgs c = pending_commit(h);
+        if (h->pend_own) {
+            GPF_LAUNCH((k_step<M, Wc, KEEP, true, PROP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
+                       h->cfg.gid0, h->n, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, ms, c.first);
+            if (h->pend_m > 0) {
+                g_ev_start = g_ev_stop = nullptr;                // (timed(): the event pair belongs to the first launch)
+                GPF_LAUNCH((k_step<M, Wc, KEEP, false, PROP, true>), dim3(grid_for(h, h->pend_m, STEP_BLOCKS_PER_CU)), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
+                           h->cfg.gid0, h->pend_m, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, ms, c.second);
+            }
+        } else
+            GPF_LAUNCH((k_step<M, Wc, KEEP, false, PROP, true>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
+                       h->cfg.gid0, h->n, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, ms, c.first);
     } else if (h->pending_gather && h->pending_search && PROP == 0) {
         // the pending multinomial search rides in the propagate (gpf_k_fused.hpp): one 1024-thread workgroup per CU like k_search_multi
         const MaxSlots ms = next_slots(h);
         const SearchArgs& sa = h->pend_sa;
         const int gsr = (int)std::max<int64_t>(1, std::min<int64_t>((sa.n + FCH - 1) / FCH, (int64_t)h->n_cu));
         const size_t tbytes = (multi_lds_bytes(sa.ntiles, sa.w.logg) + 15) & ~(size_t)15;
-        if (sa.w.logg == 0)
-            GPF_LAUNCH((k_step_search<M, Wc, KEEP, 0>), dim3(gsr), dim3(SBLOCK), tbytes + FUSED_LDS_EXTRA, h->stream, h->args, h->cfg.seed, h->epoch, sa,
+        bool_dispatch(sa.w.logg != 0, [&](auto LOGG) {           // (k_step_search<LOGG>: 0 or 1)
+            GPF_LAUNCH((k_step_search<M, Wc, KEEP, LOGG>), dim3(gsr), dim3(SBLOCK), tbytes + FUSED_LDS_EXTRA, h->stream, h->args, h->cfg.seed, h->epoch, sa,
                        h->rows[h->cur], h->rows[1 - h->cur], h->lw, ms, (uint32_t)(tbytes / 4));
-        else
-            GPF_LAUNCH((k_step_search<M, Wc, KEEP, 1>), dim3(gsr), dim3(SBLOCK), tbytes + FUSED_LDS_EXTRA, h->stream, h->args, h->cfg.seed, h->epoch, sa,
-                       h->rows[h->cur], h->rows[1 - h->cur], h->lw, ms, (uint32_t)(tbytes / 4));
+        });
         h->pending_search = false;
-    } else if (h->pending_gather) {
-        const MaxSlots ms = next_slots(h);
+    } else bool_dispatch(h->pending_gather, [&](auto GATHER) {
         PackedCommit pc{};
-        pc.lw_fill = h->pending_fill ? &h->sc->lw_fill : nullptr;
-        GPF_LAUNCH((k_step<M, Wc, KEEP, true, PROP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
-                           h->cfg.gid0, h->n, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, ms, pc);
-    }
-    else {
-        PackedCommit pc{};
-        if (gate) pc.gate = *gate;                                   // (gpf_step_ess: a speculative propagate behind the ESS reduction)
-        GPF_LAUNCH((k_step<M, Wc, KEEP, false, PROP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
-                           h->cfg.gid0, h->n, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, next_slots(h), pc);
-    }
+        if (GATHER) pc.lw_fill = h->pending_fill ? &h->sc->lw_fill : nullptr;
+        else if (gate) pc.gate = *gate;                          // (gpf_step_ess: a speculative propagate behind the ESS reduction)
+        GPF_LAUNCH((k_step<M, Wc, KEEP, GATHER, PROP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
+                   h->cfg.gid0, h->n, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, next_slots(h), pc);
+    });
 }
 template <int M, int PROP = 0>
 void launch_init_t(gpf_filter* h, int grid)
@@ -128,65 +130,18 @@ void launch_init_t(gpf_filter* h, int grid)
         GPF_LAUNCH((k_init<M, PROP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
                            h->cfg.gid0, h->n, h->W, h->rows[h->cur], h->lw, next_slots(h));
 }
-bool model_has_proposal(int model)
-{
-    switch (model) {
-        case MODEL_LGSSM2: return Model<MODEL_LGSSM2>::HAS_PROPOSAL;
-        case MODEL_BEARINGS4: return Model<MODEL_BEARINGS4>::HAS_PROPOSAL;
-        case MODEL_SV1: return Model<MODEL_SV1>::HAS_PROPOSAL;
-        case MODEL_OBJECT_MOTION: return Model<MODEL_OBJECT_MOTION>::HAS_PROPOSAL;
-        case MODEL_LINE: return Model<MODEL_LINE>::HAS_PROPOSAL;
-    }
-    return false;
-}
-bool model_has_strata(int model)
-{
-    switch (model) {
-        case MODEL_LGSSM2: return Model<MODEL_LGSSM2>::HAS_STRATA;
-        case MODEL_BEARINGS4: return Model<MODEL_BEARINGS4>::HAS_STRATA;
-        case MODEL_SV1: return Model<MODEL_SV1>::HAS_STRATA;
-        case MODEL_OBJECT_MOTION: return Model<MODEL_OBJECT_MOTION>::HAS_STRATA;
-        case MODEL_LINE: return Model<MODEL_LINE>::HAS_STRATA;
-    }
-    return false;
-}
-template <int M, bool RW>
-void launch_move_prop_t(gpf_filter* h, int grid, int n_iters)
-{
-    constexpr int Wc = row_width(Model<M>::D, true);
-    if constexpr (!Model<M>::HAS_MOVE_PROPOSAL) { (void)h; (void)grid; (void)n_iters; return; }
-    else if (h->pending_gather)
-        GPF_LAUNCH((k_move<M, Wc, RW, true, true>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
-                           h->cfg.gid0, h->n, (int)h->has_prev, n_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw,
-                           h->acc_part, RW ? next_slots(h) : MaxSlots{nullptr, nullptr});
-    else
-        GPF_LAUNCH((k_move<M, Wc, RW, false, true>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
-                           h->cfg.gid0, h->n, (int)h->has_prev, n_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw,
-                           h->acc_part, RW ? next_slots(h) : MaxSlots{nullptr, nullptr});
-}
-bool model_has_move_proposal(int model)
-{
-    switch (model) {
-        case MODEL_LGSSM2: return Model<MODEL_LGSSM2>::HAS_MOVE_PROPOSAL;
-        case MODEL_BEARINGS4: return Model<MODEL_BEARINGS4>::HAS_MOVE_PROPOSAL;
-        case MODEL_SV1: return Model<MODEL_SV1>::HAS_MOVE_PROPOSAL;
-        case MODEL_OBJECT_MOTION: return Model<MODEL_OBJECT_MOTION>::HAS_MOVE_PROPOSAL;
-        case MODEL_LINE: return Model<MODEL_LINE>::HAS_MOVE_PROPOSAL;
-    }
-    return false;
-}
-template <int M, bool RW>
+// PROP: the model's native move proposal (gpf_rejuvenate_with_proposal); a pending resample gather rides on the move (rows read through anc,
+// incoming weights 0)
+template <int M, bool RW, bool PROP = false>
 void launch_move_t(gpf_filter* h, int grid, int n_iters, const ModelArgs& args, uint32_t epoch)
 {
     constexpr int Wc = row_width(Model<M>::D, true);
-    if (h->pending_gather)           // the resample gather rides on the move (rows read through anc, incoming weights 0)
-        GPF_LAUNCH((k_move<M, Wc, RW, true>), dim3(grid), dim3(BLOCK), 0, h->stream, args, h->cfg.seed, epoch,
-                           h->cfg.gid0, h->n, (int)h->has_prev, n_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw,
-                           h->acc_part, RW ? next_slots(h) : MaxSlots{nullptr, nullptr});
-    else
-        GPF_LAUNCH((k_move<M, Wc, RW, false>), dim3(grid), dim3(BLOCK), 0, h->stream, args, h->cfg.seed, epoch,
-                           h->cfg.gid0, h->n, (int)h->has_prev, n_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw,
-                           h->acc_part, RW ? next_slots(h) : MaxSlots{nullptr, nullptr});
+    if constexpr (PROP && !Model<M>::HAS_MOVE_PROPOSAL) { (void)h; (void)grid; (void)n_iters; (void)args; (void)epoch; return; }
+    else bool_dispatch(h->pending_gather, [&](auto GATHER) {
+        GPF_LAUNCH((k_move<M, Wc, RW, GATHER, PROP>), dim3(grid), dim3(BLOCK), 0, h->stream, args, h->cfg.seed, epoch,
+                   h->cfg.gid0, h->n, (int)h->has_prev, n_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw,
+                   h->acc_part, RW ? next_slots(h) : MaxSlots{nullptr, nullptr});
+    });
 }
 // the pending move inside the propagate (k_move_step): old observation + the move's epoch, new observation (h->args) + the update's epoch
 template <int M, bool RW>
@@ -196,40 +151,29 @@ void launch_move_step_t(gpf_filter* h, int grid)
     ObsVec om;
     for (int i = 0; i < MAX_OBS; ++i) om.v[i] = h->pm_args.obs[i];
     const MaxSlots ms = next_slots(h);
-    if (h->pending_packed && h->pend_own) {
-        // a sharded commit is pending (gpf_shard_commit, own-direct): the shard's own hits through the ancestor array -- and, after a window exchange, the
-        // other slots out of the receive window -- in the first launch, the received packed entries in a second one (as launch_step_t)
-        PackedCommit pg{nullptr, h->anc, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, h->sc, nullptr, (int)h->pend_mailbox, h->pend_own_range ? 2 : 1, h->cfg.gid0,
-                        h->pend_own_range ? h->shard_plan->own_range : nullptr};
-        if (h->pend_ring) pg.ring = RingIn{h->ring + (int64_t)(h->pend_ring_seq & (RING_PARITIES - 1)) * h->ring_parity_words, h->pend_ring_seq, h->h_timeout};
-        GPF_LAUNCH((k_move_step<M, Wc, RW, true>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, om, h->cfg.seed, h->pm_epoch, h->epoch,
-                   h->cfg.gid0, h->n, (int)h->has_prev, h->pm_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, ms, pg);
-        if (h->pend_m > 0) {
-            const PackedCommit pc{h->pend_packed, h->anc, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, nullptr, nullptr, (int)h->pend_mailbox, 0, 0, nullptr};
-            g_ev_start = g_ev_stop = nullptr;                    // (timed(): the event pair belongs to the first launch)
-            GPF_LAUNCH((k_move_step<M, Wc, RW, false, true>), dim3(grid_for(h, h->pend_m, MOVE_BLOCKS_PER_CU)), dim3(BLOCK), 0, h->stream, h->args, om, h->cfg.seed, h->pm_epoch, h->epoch,
-                       h->cfg.gid0, h->pend_m, (int)h->has_prev, h->pm_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, ms, pc);
-        }
-    } else if (h->pending_packed) {
-        const PackedCommit pc{h->pend_packed, h->anc, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, h->sc, nullptr, (int)h->pend_mailbox, 0, 0, nullptr};
-        GPF_LAUNCH((k_move_step<M, Wc, RW, false, true>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, om, h->cfg.seed, h->pm_epoch, h->epoch,
-                   h->cfg.gid0, h->n, (int)h->has_prev, h->pm_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, ms, pc);
-    } else if (h->pending_gather)
-        GPF_LAUNCH((k_move_step<M, Wc, RW, true>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, om, h->cfg.seed, h->pm_epoch, h->epoch,
+    if (h->pending_packed) {                                     // (as launch_step_t)
+        const CommitArgs c = pending_commit(h);
+        if (h->pend_own) {
+            GPF_LAUNCH((k_move_step<M, Wc, RW, true>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, om, h->cfg.seed, h->pm_epoch, h->epoch,
+                       h->cfg.gid0, h->n, (int)h->has_prev, h->pm_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, ms, c.first);
+            if (h->pend_m > 0) {
+                g_ev_start = g_ev_stop = nullptr;                // (timed(): the event pair belongs to the first launch)
+                GPF_LAUNCH((k_move_step<M, Wc, RW, false, true>), dim3(grid_for(h, h->pend_m, MOVE_BLOCKS_PER_CU)), dim3(BLOCK), 0, h->stream, h->args, om, h->cfg.seed, h->pm_epoch, h->epoch,
+                           h->cfg.gid0, h->pend_m, (int)h->has_prev, h->pm_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, ms, c.second);
+            }
+        } else
+            GPF_LAUNCH((k_move_step<M, Wc, RW, false, true>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, om, h->cfg.seed, h->pm_epoch, h->epoch,
+                       h->cfg.gid0, h->n, (int)h->has_prev, h->pm_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, ms, c.first);
+    } else bool_dispatch(h->pending_gather, [&](auto GATHER) {
+        GPF_LAUNCH((k_move_step<M, Wc, RW, GATHER>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, om, h->cfg.seed, h->pm_epoch, h->epoch,
                    h->cfg.gid0, h->n, (int)h->has_prev, h->pm_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, ms, PackedCommit{});
-    else
-        GPF_LAUNCH((k_move_step<M, Wc, RW, false>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, om, h->cfg.seed, h->pm_epoch, h->epoch,
-                   h->cfg.gid0, h->n, (int)h->has_prev, h->pm_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw, ms, PackedCommit{});
+    });
 }
 
 void launch_gather_ex(gpf_filter* h, const int32_t* anc, const double* in, double* out, const PrioView& pv, double* lw_out, int64_t n)
 {
     const int grid = grid_for(h, n * (h->W / 2), 8);
-    switch (h->W) {
-        case 2: GPF_LAUNCH((k_gather<2>), dim3(grid), dim3(BLOCK), 0, h->stream, anc, in, out, pv, lw_out, n); break;
-        case 4: GPF_LAUNCH((k_gather<4>), dim3(grid), dim3(BLOCK), 0, h->stream, anc, in, out, pv, lw_out, n); break;
-        case 8: GPF_LAUNCH((k_gather<8>), dim3(grid), dim3(BLOCK), 0, h->stream, anc, in, out, pv, lw_out, n); break;
-    }
+    DISPATCH_W(h, GPF_LAUNCH((k_gather<WW>), dim3(grid), dim3(BLOCK), 0, h->stream, anc, in, out, pv, lw_out, n));
 }
 void launch_gather(gpf_filter* h, const PrioView& pv, double* lw_out)
 {
@@ -239,11 +183,7 @@ void launch_gather_rows_lw(gpf_filter* h, const int32_t* anc, const double* rows
                            double* lw_out, int64_t n)
 {
     const int grid = grid_for(h, n * (h->W / 2), 8);
-    switch (h->W) {
-        case 2: GPF_LAUNCH((k_gather_rows_lw<2>), dim3(grid), dim3(BLOCK), 0, h->stream, anc, rows_in, lw_in, rows_out, lw_out, n); break;
-        case 4: GPF_LAUNCH((k_gather_rows_lw<4>), dim3(grid), dim3(BLOCK), 0, h->stream, anc, rows_in, lw_in, rows_out, lw_out, n); break;
-        case 8: GPF_LAUNCH((k_gather_rows_lw<8>), dim3(grid), dim3(BLOCK), 0, h->stream, anc, rows_in, lw_in, rows_out, lw_out, n); break;
-    }
+    DISPATCH_W(h, GPF_LAUNCH((k_gather_rows_lw<WW>), dim3(grid), dim3(BLOCK), 0, h->stream, anc, rows_in, lw_in, rows_out, lw_out, n));
 }
 
 // a pending resample gather is executed now: rows[1-cur][j] = rows[cur][anc[j]], lw = 0
@@ -255,11 +195,7 @@ gpf_status materialize(gpf_filter* h)
         if (h->pend_own) {                                       // the shard's own hits first (anc[j] >= 0; the scatter below overwrites the -1 of the others)
             const int go = grid_for(h, h->n * (h->W / 2), 8);
             const int64_t* own_rng = h->pend_own_range ? h->shard_plan->own_range : nullptr;
-            switch (h->W) {
-                case 2: GPF_LAUNCH((k_gather_own<2>), dim3(go), dim3(BLOCK), 0, h->stream, h->anc, h->cfg.gid0, h->rows[h->cur], out, h->lw, h->n, own_rng); break;
-                case 4: GPF_LAUNCH((k_gather_own<4>), dim3(go), dim3(BLOCK), 0, h->stream, h->anc, h->cfg.gid0, h->rows[h->cur], out, h->lw, h->n, own_rng); break;
-                case 8: GPF_LAUNCH((k_gather_own<8>), dim3(go), dim3(BLOCK), 0, h->stream, h->anc, h->cfg.gid0, h->rows[h->cur], out, h->lw, h->n, own_rng); break;
-            }
+            DISPATCH_W(h, GPF_LAUNCH((k_gather_own<WW>), dim3(go), dim3(BLOCK), 0, h->stream, h->anc, h->cfg.gid0, h->rows[h->cur], out, h->lw, h->n, own_rng));
         }
         const int grid = grid_for(h, std::max<int64_t>(m, 1), 8);
         if (h->pend_ring) {                                      // a window exchange: the other slots' entries out of the receive window (+ log-ML update)
@@ -267,16 +203,9 @@ gpf_status materialize(gpf_filter* h)
             // (ascending targets: few slots outside the own range -- a small grid; i.i.d. targets: (G-1)/G of all slots sit in the window)
             const int gr = h->pend_own_range ? grid_for(h, std::min<int64_t>(h->n, (int64_t)1 << 16), 8) : grid_for(h, h->n, 8);
             const int64_t* own_rng_ring = h->pend_own_range ? h->shard_plan->own_range : nullptr;
-            switch (h->W) {
-                case 2: GPF_LAUNCH((k_commit_ring<2>), dim3(gr), dim3(BLOCK), 0, h->stream, rin, h->n, own_rng_ring, out, h->anc, h->lw, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, h->sc, (int)h->pend_mailbox); break;
-                case 4: GPF_LAUNCH((k_commit_ring<4>), dim3(gr), dim3(BLOCK), 0, h->stream, rin, h->n, own_rng_ring, out, h->anc, h->lw, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, h->sc, (int)h->pend_mailbox); break;
-                case 8: GPF_LAUNCH((k_commit_ring<8>), dim3(gr), dim3(BLOCK), 0, h->stream, rin, h->n, own_rng_ring, out, h->anc, h->lw, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, h->sc, (int)h->pend_mailbox); break;
-            }
-        } else
-        switch (h->W) {
-            case 2: GPF_LAUNCH((k_commit_packed<2>), dim3(grid), dim3(BLOCK), 0, h->stream, h->pend_packed, m, out, h->anc, h->lw, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, h->sc, (int)h->pend_mailbox); break;
-            case 4: GPF_LAUNCH((k_commit_packed<4>), dim3(grid), dim3(BLOCK), 0, h->stream, h->pend_packed, m, out, h->anc, h->lw, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, h->sc, (int)h->pend_mailbox); break;
-            case 8: GPF_LAUNCH((k_commit_packed<8>), dim3(grid), dim3(BLOCK), 0, h->stream, h->pend_packed, m, out, h->anc, h->lw, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, h->sc, (int)h->pend_mailbox); break;
+            DISPATCH_W(h, GPF_LAUNCH((k_commit_ring<WW>), dim3(gr), dim3(BLOCK), 0, h->stream, rin, h->n, own_rng_ring, out, h->anc, h->lw, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, h->sc, (int)h->pend_mailbox));
+        } else {
+            DISPATCH_W(h, GPF_LAUNCH((k_commit_packed<WW>), dim3(grid), dim3(BLOCK), 0, h->stream, h->pend_packed, m, out, h->anc, h->lw, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, h->sc, (int)h->pend_mailbox));
         }
         HIP_TRY(h, hipGetLastError());
         h->cur ^= 1;
@@ -347,6 +276,30 @@ void mutated(gpf_filter* h)
     gpf_filter* root = h->parent ? h->parent : h;
     root->mutations += 1;
     if (h->parent) h->seen_mutations = root->mutations;          // its own change: this view's bookkeeping is already current
+}
+
+// the bookkeeping behind an initialise's k_init launch (whole filter or block-wise): parents = 1:N (initialize.jl:43), log_ml_est = 0, nothing pending
+gpf_status after_initialize(gpf_filter* h, int grid)
+{
+    h->pending_gather = false; h->pending_fill = false; h->pending_packed = false; h->pending_search = false; h->pending_move = false;
+    h->max_valid = true;
+    GPF_LAUNCH(k_iota, dim3(grid), dim3(BLOCK), 0, h->stream, h->anc, h->n);
+    HIP_TRY(h, hipMemsetAsync(&h->sc->lml_est, 0, sizeof(double), h->stream));
+    HIP_TRY(h, hipGetLastError());
+    h->epoch += 1;
+    h->initialized = true; h->has_prev = false; h->raw_valid = false; h->raw_sum_valid = false;
+    mutated(h);
+    return GPF_OK;
+}
+// ... and behind a propagate that wrote rows[1 - cur] and the log-weights with their maximum (update_refs!, utils.jl:10-15)
+void after_propagate(gpf_filter* h)
+{
+    h->max_valid = true;
+    h->cur ^= 1;
+    h->epoch += 1;
+    h->has_prev = true;
+    h->raw_valid = false; h->raw_sum_valid = false;
+    mutated(h);
 }
 
 // A view re-derives its aliased pointers from the parent on every call (the parent may have swapped its row buffers),
@@ -442,8 +395,7 @@ gpf_status finish_move(gpf_filter* h)
     const int grid = move_grid(h);
     const int n_iters = h->pm_iters;
     gpf_status s = timed(h, GPF_K_MOVE, [&] {
-        if (h->pm_method == GPF_REJUVENATE_REWEIGHT) { DISPATCH_MODEL(h, (launch_move_t<MM, true>(h, grid, n_iters, h->pm_args, h->pm_epoch))); }
-        else                                         { DISPATCH_MODEL(h, (launch_move_t<MM, false>(h, grid, n_iters, h->pm_args, h->pm_epoch))); }
+        bool_dispatch(h->pm_method == GPF_REJUVENATE_REWEIGHT, [&](auto RW) { DISPATCH_MODEL(h, (launch_move_t<MM, RW>(h, grid, n_iters, h->pm_args, h->pm_epoch))); });
     });
     if (s) return s;
     HIP_TRY(h, hipGetLastError());
@@ -627,9 +579,10 @@ gpf_status gpf_synchronize(gpf_handle h)
 static gpf_status initialize_impl(gpf_handle h, const double* obs, int32_t n_obs, int prop)
 {
     if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
-    if (prop == 1 && !model_has_proposal(h->cfg.model)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no native proposal");
-    if (prop == 2 && !model_has_strata(h->cfg.model)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no discrete latent to stratify over");
-    if (prop == 3 && h->cfg.model != MODEL_LINE) return fail(h, GPF_ERR_INVALID_ARGUMENT, "stratified initialisation with a native proposal: line_model only");
+    const ModelCaps caps = model_caps(h);
+    if (prop == 1 && !caps.proposal) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no native proposal");
+    if (prop == 2 && !caps.strata) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no discrete latent to stratify over");
+    if (prop == 3 && !caps.strata_proposal) return fail(h, GPF_ERR_INVALID_ARGUMENT, "stratified initialisation with a native proposal: line_model only");
     if (h->parent) return fail(h, GPF_ERR_STATE, "gpf_initialize on a sub-state view");
     if (gpf_status b = bp_refused(h, "gpf_initialize")) return b;
     h->generation += 1;
@@ -645,33 +598,14 @@ static gpf_status initialize_impl(gpf_handle h, const double* obs, int32_t n_obs
         else if (prop == 3) { DISPATCH_MODEL(h, (launch_init_t<MM, 3>(h, grid))); }
         else                { DISPATCH_MODEL(h, (launch_init_t<MM, 0>(h, grid))); }
     });
-    if (s) return s;
-    h->pending_gather = false; h->pending_fill = false; h->pending_search = false; h->pending_move = false;
-    h->pending_packed = false;
-    h->max_valid = true;
-    GPF_LAUNCH(k_iota, dim3(grid), dim3(BLOCK), 0, h->stream, h->anc, h->n);            // parents = 1:N (initialize.jl:43)
-    HIP_TRY(h, hipMemsetAsync(&h->sc->lml_est, 0, sizeof(double), h->stream));                   // log_ml_est = 0.
-    HIP_TRY(h, hipGetLastError());
-    h->epoch += 1;
-    h->initialized = true;
-    h->has_prev = false;
-    h->raw_valid = false; h->raw_sum_valid = false;
-    mutated(h);
-    return GPF_OK;
+    return s ? s : after_initialize(h, grid);
 }
 
 gpf_status gpf_initialize(gpf_handle h, const double* obs, int32_t n_obs) { return initialize_impl(h, obs, n_obs, 0); }
-// the native proposal a model has: the locally optimal one (lgssm2), the reference tests' fixed proposals (line_model)
-static bool proposal_matches(gpf_handle h, int32_t proposal)
-{
-    if (!h) return true;                                          // reported by the callee
-    if (proposal == GPF_PROPOSAL_LOCALLY_OPTIMAL) return h->cfg.model != MODEL_LINE;
-    if (proposal == GPF_PROPOSAL_LINE_FIXED) return h->cfg.model == MODEL_LINE;
-    return false;
-}
+// (a null handle is reported by the callee)
 gpf_status gpf_initialize_proposal(gpf_handle h, const double* obs, int32_t n_obs, int32_t proposal)
 {
-    if (!proposal_matches(h, proposal)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "unknown proposal id for this model");
+    if (h && !proposal_valid(h, proposal)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "unknown proposal id for this model");
     return initialize_impl(h, obs, n_obs, 1);
 }
 
@@ -680,65 +614,37 @@ static gpf_status update_impl(gpf_handle h, const double* obs, int32_t n_obs, in
     if (h && bp_refused(h, "gpf_update")) return GPF_ERR_STATE;
     gpf_status s = check_ready(h, prop == 0);                    // (the plain propagate carries a pending lazy move)
     if (s) return s;
-    if (prop == 1 && !model_has_proposal(h->cfg.model)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no native proposal");
-    if (prop == 2 && !model_has_strata(h->cfg.model)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no discrete latent to stratify over");
+    const ModelCaps caps = model_caps(h);
+    if (prop == 1 && !caps.proposal) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no native proposal");
+    if (prop == 2 && !caps.strata) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no discrete latent to stratify over");
     if ((s = set_obs(h, obs, n_obs))) return s;
     h->blk_obs_size = 0;                                         // one observation for all particles again
     if ((s = hist_begin_step(h, false))) return s;
     if (prop != 0 && (s = finish_search(h))) return s;           // (only the plain propagate carries a pending search)
     const int grid = step_grid(h);
     const bool keep = h->cfg.keep_prev != 0;
-    if (h->pending_move) {
-        // gather (if pending) -> move -> propagate in one launch (k_move_step): the old observation and epoch travel with the move
-        const bool rw = h->pm_method == GPF_REJUVENATE_REWEIGHT;
-        s = timed(h, GPF_K_STEP, [&] {
-            if (rw) { DISPATCH_MODEL(h, (launch_move_step_t<MM, true>(h, grid))); }
-            else    { DISPATCH_MODEL(h, (launch_move_step_t<MM, false>(h, grid))); }
-        });
-        if (s) return s;
-        HIP_TRY(h, hipGetLastError());
-        phase_mark(h, GPF_PHASE_COMMIT);
-        h->pending_move = false;
-        h->pending_gather = false; h->pending_fill = false;
-        h->pending_packed = false; h->pend_own = false; h->pend_ring = false;   // (a sharded commit rode in the launch)
-        h->max_valid = true;
-        h->cur ^= 1;                // (read rows[cur], wrote the other buffer once: the move's and the update's swaps cancel to one)
-        h->epoch += 1;
-        h->has_prev = true;
-        h->raw_valid = false; h->raw_sum_valid = false;
-        mutated(h);
-        return GPF_OK;
-    }
+    // a pending move (plain propagates only, never on a view): gather (if pending) -> move -> propagate in one launch (k_move_step), the old
+    // observation and epoch travel with the move.  It reads rows[cur] and writes the other buffer once: the move's and the update's swaps cancel to one.
     s = timed(h, GPF_K_STEP, [&] {
-        if (prop == 1) {
-            if (keep) { DISPATCH_MODEL(h, (launch_step_t<MM, true, 1>(h, grid))); }
-            else      { DISPATCH_MODEL(h, (launch_step_t<MM, false, 1>(h, grid))); }
-        } else if (prop == 2) {
-            if (keep) { DISPATCH_MODEL(h, (launch_step_t<MM, true, 2>(h, grid))); }
-            else      { DISPATCH_MODEL(h, (launch_step_t<MM, false, 2>(h, grid))); }
-        } else {
-            if (keep) { DISPATCH_MODEL(h, (launch_step_t<MM, true>(h, grid))); }
-            else      { DISPATCH_MODEL(h, (launch_step_t<MM, false>(h, grid))); }
-        }
+        if (h->pending_move) bool_dispatch(h->pm_method == GPF_REJUVENATE_REWEIGHT, [&](auto RW) { DISPATCH_MODEL(h, (launch_move_step_t<MM, RW>(h, grid))); });
+        else if (prop == 1)  bool_dispatch(keep, [&](auto KEEP) { DISPATCH_MODEL(h, (launch_step_t<MM, KEEP, 1>(h, grid))); });
+        else if (prop == 2)  bool_dispatch(keep, [&](auto KEEP) { DISPATCH_MODEL(h, (launch_step_t<MM, KEEP, 2>(h, grid))); });
+        else                 bool_dispatch(keep, [&](auto KEEP) { DISPATCH_MODEL(h, (launch_step_t<MM, KEEP>(h, grid))); });
     });
     if (s) return s;
     HIP_TRY(h, hipGetLastError());
     phase_mark(h, GPF_PHASE_COMMIT);                         // (gpf_phase_timing: the propagate that committed a sharded resample)
+    h->pending_move = false;
     h->pending_gather = false; h->pending_fill = false;      // a pending resample gather was fused into this step
     h->pending_packed = false; h->pend_own = false; h->pend_ring = false;     // ... or a pending sharded commit
-    h->max_valid = true;
-    h->cur ^= 1;                    // update_refs! (utils.jl:10-15)
-    h->epoch += 1;
-    h->has_prev = true;
-    h->raw_valid = false; h->raw_sum_valid = false;
-    mutated(h);
+    after_propagate(h);
     return view_exit(h);            // sub-state: copy back (utils.jl:17-20)
 }
 
 gpf_status gpf_update(gpf_handle h, const double* obs, int32_t n_obs) { return update_impl(h, obs, n_obs, 0); }
 gpf_status gpf_update_proposal(gpf_handle h, const double* obs, int32_t n_obs, int32_t proposal)
 {
-    if (!proposal_matches(h, proposal)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "unknown proposal id for this model");
+    if (h && !proposal_valid(h, proposal)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "unknown proposal id for this model");
     return update_impl(h, obs, n_obs, 1);
 }
 
@@ -749,10 +655,8 @@ namespace gpfh {
 gpf_status speculative_step(gpf_filter* h, const GateIn& gate)
 {
     const int grid = step_grid(h);
-    const bool keep = h->cfg.keep_prev != 0;
     gpf_status s = timed(h, GPF_K_STEP, [&] {
-        if (keep) { DISPATCH_MODEL(h, (launch_step_t<MM, true>(h, grid, &gate))); }
-        else      { DISPATCH_MODEL(h, (launch_step_t<MM, false>(h, grid, &gate))); }
+        bool_dispatch(h->cfg.keep_prev != 0, [&](auto KEEP) { DISPATCH_MODEL(h, (launch_step_t<MM, KEEP>(h, grid, &gate))); });
     });
     if (s) return s;
     HIP_TRY(h, hipGetLastError());
@@ -762,12 +666,7 @@ gpf_status speculative_step(gpf_filter* h, const GateIn& gate)
 void speculative_step_done(gpf_filter* h, bool ran)
 {
     if (!ran) { h->mcur ^= 1; return; }
-    h->max_valid = true;
-    h->cur ^= 1;                        // update_refs! (utils.jl:10-15)
-    h->epoch += 1;
-    h->has_prev = true;
-    h->raw_valid = false; h->raw_sum_valid = false;
-    mutated(h);
+    after_propagate(h);
 }
 } // namespace gpfh
 extern "C" {
@@ -869,7 +768,7 @@ gpf_status gpf_initialize_strata(gpf_handle h, const double* obs, int32_t n_obs,
 gpf_status gpf_initialize_strata_proposal(gpf_handle h, const double* obs, int32_t n_obs, const double* values, int32_t n_strata, int32_t interleaved,
                                           int32_t proposal)
 {
-    if (!proposal_matches(h, proposal) || proposal != GPF_PROPOSAL_LINE_FIXED) return fail(h, GPF_ERR_INVALID_ARGUMENT, "unknown proposal id for this model");
+    if ((h && !proposal_valid(h, proposal)) || proposal != GPF_PROPOSAL_LINE_FIXED) return fail(h, GPF_ERR_INVALID_ARGUMENT, "unknown proposal id for this model");
     if (h && bp_refused(h, "gpf_initialize_strata_proposal")) return GPF_ERR_STATE;
     gpf_status s = set_strata(h, values, n_strata, interleaved);
     return s ? s : initialize_impl(h, obs, n_obs, 3);
@@ -896,7 +795,7 @@ gpf_status gpf_rejuvenate_with_proposal(gpf_handle h, int32_t method, int32_t pr
     if (n_params < 0 || n_params > 4 || (n_params > 0 && !params)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad proposal parameters");
     const bool ok = (proposal == GPF_MOVE_PROPOSAL_LOCALLY_OPTIMAL && h->cfg.model == MODEL_LGSSM2 && n_params == 0) ||
                     (proposal == GPF_MOVE_PROPOSAL_LINE_OUTLIER && h->cfg.model == MODEL_LINE && n_params == 3);
-    if (!ok || !model_has_move_proposal(h->cfg.model)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "unknown move proposal for this model (or wrong parameter count)");
+    if (!ok || !model_caps(h).move_proposal) return fail(h, GPF_ERR_INVALID_ARGUMENT, "unknown move proposal for this model (or wrong parameter count)");
     if (gpf_status b = bp_refused(h, "gpf_rejuvenate_with_proposal")) return b;
     for (int i = 0; i < 4; ++i) h->args.q[i] = i < n_params ? params[i] : 0.0;
     return rejuvenate_impl(h, method, n_iters, n_accepted, true);
@@ -934,10 +833,9 @@ static gpf_status rejuvenate_impl(gpf_handle h, int32_t method, int32_t n_iters,
     const bool fused_gather = h->pending_gather;                 // a pending resample gather rides on the move kernel
     const int grid = move_grid(h);
     s = timed(h, GPF_K_MOVE, [&] {
-        if (with_proposal && method == GPF_REJUVENATE_REWEIGHT) { DISPATCH_MODEL(h, (launch_move_prop_t<MM, true>(h, grid, n_iters))); }
-        else if (with_proposal)                     { DISPATCH_MODEL(h, (launch_move_prop_t<MM, false>(h, grid, n_iters))); }
-        else if (method == GPF_REJUVENATE_REWEIGHT) { DISPATCH_MODEL(h, (launch_move_t<MM, true>(h, grid, n_iters, h->args, h->epoch))); }
-        else                                        { DISPATCH_MODEL(h, (launch_move_t<MM, false>(h, grid, n_iters, h->args, h->epoch))); }
+        bool_dispatch(method == GPF_REJUVENATE_REWEIGHT, with_proposal, [&](auto RW, auto PROP) {
+            DISPATCH_MODEL(h, (launch_move_t<MM, RW, PROP>(h, grid, n_iters, h->args, h->epoch)));
+        });
     });
     if (s) return s;
     HIP_TRY(h, hipGetLastError());

@@ -9,19 +9,15 @@ using namespace gpfh;
 template <int METHOD>
 static void launch_push(gpf_filter* h, const PushArgs& a, int grid, size_t lds, const CdfLevels& lw_, const CdfLevels& lc_, int64_t capacity, double* out)
 {
-    switch (h->W) {
-        case 2: GPF_LAUNCH((k_push<METHOD, 2>), dim3(grid), dim3(SBLOCK), lds, h->stream, a, lw_, lc_, h->n, h->ntiles, h->cfg.gid0, h->rows[h->cur], capacity, out); break;
-        case 4: GPF_LAUNCH((k_push<METHOD, 4>), dim3(grid), dim3(SBLOCK), lds, h->stream, a, lw_, lc_, h->n, h->ntiles, h->cfg.gid0, h->rows[h->cur], capacity, out); break;
-        case 8: GPF_LAUNCH((k_push<METHOD, 8>), dim3(grid), dim3(SBLOCK), lds, h->stream, a, lw_, lc_, h->n, h->ntiles, h->cfg.gid0, h->rows[h->cur], capacity, out); break;
-    }
+    DISPATCH_W(h, GPF_LAUNCH((k_push<METHOD, WW>), dim3(grid), dim3(SBLOCK), lds, h->stream, a, lw_, lc_, h->n, h->ntiles, h->cfg.gid0, h->rows[h->cur], capacity, out));
 }
 
 static void launch_push_multi(gpf_filter* h, const PushArgs& a, int grid, const CdfLevels& lw_, int64_t capacity, double* out)
 {
-#define GPF_PN(LG, WW) GPF_LAUNCH((k_push_multi<LG, WW>), dim3(grid), dim3(SBLOCK), multi_lds_bytes(h->ntiles, LG), h->stream, a, lw_, h->n, h->ntiles, h->cfg.gid0, h->rows[h->cur], capacity, out)
-    if (lw_.logg == 0) { switch (h->W) { case 2: GPF_PN(0, 2); break; case 4: GPF_PN(0, 4); break; case 8: GPF_PN(0, 8); break; } }
-    else               { switch (h->W) { case 2: GPF_PN(1, 2); break; case 4: GPF_PN(1, 4); break; case 8: GPF_PN(1, 8); break; } }
-#undef GPF_PN
+    bool_dispatch(lw_.logg != 0, [&](auto LG) {                 // (k_push_multi<LOGG>: 0 or 1)
+        DISPATCH_W(h, GPF_LAUNCH((k_push_multi<LG, WW>), dim3(grid), dim3(SBLOCK), multi_lds_bytes(h->ntiles, LG), h->stream, a, lw_, h->n, h->ntiles, h->cfg.gid0,
+                                 h->rows[h->cur], capacity, out));
+    });
 }
 
 
@@ -1147,11 +1143,7 @@ static gpf_status shard_sorted_push(gpf_filter* h, int G, int me, bool own, int6
     const AncPlan ap = anc_plan(h, G, me);
     const double* rows = h->rows[h->cur];
     gpf_status s = timed(h, GPF_K_GATHER, [&] {
-        switch (h->W) {
-            case 2: GPF_LAUNCH((k_anc_pack<2>), dim3(grid), dim3(ANC_BLOCK), 0, h->stream, ap, own ? 1 : 0, rows, h->shard_counts, h->anc_cursors, capacity, packed_out); break;
-            case 4: GPF_LAUNCH((k_anc_pack<4>), dim3(grid), dim3(ANC_BLOCK), 0, h->stream, ap, own ? 1 : 0, rows, h->shard_counts, h->anc_cursors, capacity, packed_out); break;
-            case 8: GPF_LAUNCH((k_anc_pack<8>), dim3(grid), dim3(ANC_BLOCK), 0, h->stream, ap, own ? 1 : 0, rows, h->shard_counts, h->anc_cursors, capacity, packed_out); break;
-        }
+        DISPATCH_W(h, GPF_LAUNCH((k_anc_pack<WW>), dim3(grid), dim3(ANC_BLOCK), 0, h->stream, ap, own ? 1 : 0, rows, h->shard_counts, h->anc_cursors, capacity, packed_out));
     });
     if (s) return s;
     HIP_TRY(h, hipGetLastError());
@@ -1401,11 +1393,7 @@ static gpf_status shard_resample_impl(gpf_handle h, int32_t method, double prior
         const int grid = grid_for(h, n, 8);
         double* out = h->rows[1 - h->cur];
         const int mbx = (int)h->mb_active;
-        switch (h->W) {
-            case 2: GPF_LAUNCH((k_commit_packed_ws<2>), dim3(grid), dim3(BLOCK), 0, h->stream, commit_from, n, out, h->anc, h->lws, raw_mf, raw_tot, G, h->K, h->logN, h->sc, mbx); break;
-            case 4: GPF_LAUNCH((k_commit_packed_ws<4>), dim3(grid), dim3(BLOCK), 0, h->stream, commit_from, n, out, h->anc, h->lws, raw_mf, raw_tot, G, h->K, h->logN, h->sc, mbx); break;
-            case 8: GPF_LAUNCH((k_commit_packed_ws<8>), dim3(grid), dim3(BLOCK), 0, h->stream, commit_from, n, out, h->anc, h->lws, raw_mf, raw_tot, G, h->K, h->logN, h->sc, mbx); break;
-        }
+        DISPATCH_W(h, GPF_LAUNCH((k_commit_packed_ws<WW>), dim3(grid), dim3(BLOCK), 0, h->stream, commit_from, n, out, h->anc, h->lws, raw_mf, raw_tot, G, h->K, h->logN, h->sc, mbx));
         HIP_TRY(h, hipGetLastError());
         h->cur ^= 1;
     }
