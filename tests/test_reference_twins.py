@@ -40,6 +40,21 @@ def test_twin_inputs_are_the_oracles(g, o):
         assert oracle_loglik(g, o, name, obs, prev, cur) == ll
 
 
+def test_twin_inputs_agree_with_the_mpmath_reference(g):
+    """the fixture's one independent witness while Gen's answers are absent: every log p(y_t | x_t) a Julia box would score equals the density of
+    the model DEFINITION in mpmath (tests/hp_reference.py, natural parameters only), within the bound derived for that value"""
+    import hp_reference as hp
+    rows = read_inputs()
+    refs = {name: hp.Ref(g.models.by_name(name)) for name in {r[0] for r in rows}}
+    tols = []
+    for name, t, obs, prev, cur, ll in rows:
+        want = refs[name].loglik(list(cur), list(obs))
+        d, tol = hp.differs(ll, want)
+        assert d <= tol, (name, t, ll, want)
+        tols.append(hp.rel_tol(want))
+    assert np.median(tols) < 1e-12
+
+
 def test_twins_script_names_every_model():
     src = open(os.path.join(os.path.dirname(HERE), "julia", "reference_twins.jl")).read()
     for fn in ("lgssm2_step", "bearings4_step", "sv1_step", "object_motion_step", "line_step_twin", "project(trace, ysel)", "pf_resample!"):
