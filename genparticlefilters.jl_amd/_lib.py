@@ -48,6 +48,8 @@ SYMBOLS = [
     ("gpf_resample_blocks", C.c_int, [_H, C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_double, C.c_int32, _pi32, C.POINTER(C.c_int64)]),
     ("gpf_block_resampled", C.c_int, [_H, _pi32]),
     ("gpf_block_stats", C.c_int, [_H, C.c_int64, _pd, _pd]),
+    ("gpf_block_moments", C.c_int, [_H, C.c_int64, _pd, _pd]),
+    ("gpf_block_proportion", C.c_int, [_H, C.c_int64, C.c_int32, _pd, C.c_int32, _pd]),
     ("gpf_initialize_blocks", C.c_int, [_H, _pd, C.c_int32, C.c_int64]),
     ("gpf_update_blocks", C.c_int, [_H, _pd, C.c_int32, C.c_int64]),
     ("gpf_initialize_blocks_strata", C.c_int, [_H, _pd, C.c_int32, C.c_int64, _pd, C.c_int32, C.c_int32]),

@@ -611,6 +611,68 @@ def block_stats(state, block_size: int):
     return ess, lml
 
 
+def _block_column(addr, who: str):
+    if isinstance(addr, tuple):
+        raise ErrorException(f"{who}: a past-step address (t, column) needs a trajectory store, which block-wise states do not have")
+    return None if addr is None else int(addr)
+
+
+def _block_moments(state, block_size: int, want_mean: bool, want_var: bool):
+    nb = (state.n_particles + int(block_size) - 1) // int(block_size)
+    mu = np.empty((nb, state.row_width)) if want_mean else None
+    s2 = np.empty((nb, state.row_width)) if want_var else None
+    state._check(state._L.gpf_block_moments(state._h, int(block_size), _pd(mu) if want_mean else None, _pd(s2) if want_var else None))
+    return mu, s2
+
+
+def _block_pick(state, a: np.ndarray, col):
+    if col is None:
+        return a
+    if not 0 <= col < state.row_width:
+        raise ErrorException("bad column")
+    return np.ascontiguousarray(a[:, col])
+
+
+def block_moments(state, block_size: int):
+    """([mean(state[b], c) for c in columns], [var(state[b], c) ...]) of every block, src/statistics.jl:13-14,48-50 on sub-states:
+    two [n_blocks, row_width] arrays from one launch, bit-identical to the loop over views.  A block with NaN / +Inf weights is NaN."""
+    return _block_moments(state, block_size, True, True)
+
+
+def block_mean(state, block_size: int, addr=None) -> np.ndarray:
+    """mean(state[b], addr) of every block in one launch: [n_blocks] for a column, [n_blocks, row_width] for addr=None"""
+    col = _block_column(addr, "block_mean")
+    return _block_pick(state, _block_moments(state, block_size, True, False)[0], col)
+
+
+def block_var(state, block_size: int, addr=None) -> np.ndarray:
+    """var(state[b], addr) (population form) of every block in one launch: [n_blocks] for a column, [n_blocks, row_width] for addr=None"""
+    col = _block_column(addr, "block_var")
+    return _block_pick(state, _block_moments(state, block_size, False, True)[1], col)
+
+
+def block_proportionmap(state, block_size: int, addr, max_values: int = 256):
+    """proportionmap(state[b], addr) of every block, src/statistics.jl:91-101 on sub-states: (values, proportions[n_blocks, n_values]).
+    The distinct values are read from the column over all blocks (a value a block does not hold has proportion 0.0 there); each
+    launch answers 16 values for all blocks."""
+    col = _block_column(addr, "block_proportionmap")
+    if col is None:
+        raise ErrorException("block_proportionmap: give a column")
+    nb = (state.n_particles + int(block_size) - 1) // int(block_size)
+    if not 0 <= col < state.row_width:
+        raise ErrorException("bad column")
+    vals = np.unique(state.column(col))
+    if vals.size > max_values:
+        raise ErrorException(f"proportionmap: {vals.size} distinct values; the column does not look discrete")
+    out = np.empty((nb, vals.size))
+    for k0 in range(0, vals.size, 16):
+        chunk = np.ascontiguousarray(vals[k0:k0 + 16], np.float64)
+        part = np.empty((nb, chunk.size))
+        state._check(state._L.gpf_block_proportion(state._h, int(block_size), col, _pd(chunk), int(chunk.size), _pd(part)))
+        out[:, k0:k0 + chunk.size] = part
+    return vals, out
+
+
 def _rejuvenate(state, method_id: int, n_iters: int, want_count: bool):
     acc = C.c_uint64(0)
     st = state._L.gpf_rejuvenate(state._h, method_id, int(n_iters), C.byref(acc) if want_count else None)

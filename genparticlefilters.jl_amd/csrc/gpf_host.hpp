@@ -193,6 +193,7 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     int64_t* h_qpub = nullptr; int64_t q_ticket = 0;   // the ESS getter's scan publishes {flags, S, limbs of sum q^2} itself (ScanExtras::q_host)
     bool q_published = false;                          // ... and the scan of THIS call did
     int32_t* blk_words = nullptr; int32_t* blk_mask = nullptr; double* blk_stats = nullptr; int64_t blk_cap = 0, blk_last = 0;
+    double* blk_est = nullptr; int64_t blk_est_cap = 0;         // per-block estimates (gpf_block_moments / gpf_block_proportion): blk_est_cap doubles
     // blocks of more than BLK_MAX particles: gpf_resample_blocks / gpf_block_stats run the loop over sub-states themselves, through view
     // handles kept on the filter (one per block; rebuilt when the block size or the particle buffers change)
     std::vector<gpf_filter*> blk_views; int64_t blk_views_size = 0; uint64_t blk_views_gen = 0;

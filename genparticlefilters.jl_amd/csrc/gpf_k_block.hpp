@@ -343,6 +343,164 @@ __global__ __launch_bounds__(BLOCK) void k_block_stats(const double* __restrict_
     }
 }
 
+// ----------------------------------------------------------------------------- per-block estimates: mean / var / proportionmap of every sub-state
+// for b in blocks; mean(state[b], addr); var(state[b], addr); proportionmap(state[b], addr); end (statistics.jl:13-14, 48-50, 91-101 on
+// ParticleFilterSubStates, view.jl:35-48) in ONE launch for all blocks and all columns, bit-identical to gpf_mean / gpf_var / gpf_proportion on a view
+// of the block.  The order of the sum is the spec's (k_wsum_tree): a block of <= 2048 particles is ONE chunk of the binary tree over
+// the block-local index.  A lane holds ITEMS consecutive terms and sums them as their own subtree, the xor butterfly m = 1, 2, ..., 32 joins the 64
+// lanes, the workgroup team joins its four waves as (s0 + s1) + (s2 + s3); the levels a narrower team does not have only ever add +0.0.
+// Teams as in k_block_stats.  The normalised weights stay in registers; the rows are read as 16-byte column pairs (a lane's rows are one
+// contiguous run -- at W = 8 the four passes over it hit in L2, a block is at most 128 KB).
+template <int ITEMS>
+__device__ __forceinline__ double lane_tree(const double (&t)[ITEMS])
+{
+    static_assert(ITEMS == 2 || ITEMS == 8, "a lane's subtree");
+    if constexpr (ITEMS == 2) return t[0] + t[1];
+    else return tree8(t);
+}
+// the tree over the team of two values at once (every thread gets the results); s_t: [NWAVES][2] words of LDS (TEAM = BLOCK only)
+template <int TEAM>
+__device__ __forceinline__ void team_tree2(double (&v)[2], double (*s_t)[2])
+{
+#pragma unroll
+    for (int m = 1; m < WAVE; m <<= 1) {                             // neighbours first
+        v[0] += u2d(shfl_xor_u64(d2u(v[0]), m));
+        v[1] += u2d(shfl_xor_u64(d2u(v[1]), m));
+    }
+    if (TEAM == BLOCK) {
+        static_assert(NWAVES == 4, "two more levels");
+        __syncthreads();                                           // (s_t may still be read from a previous call)
+        if (lane_id() == 0) { s_t[wave_id()][0] = v[0]; s_t[wave_id()][1] = v[1]; }
+        __syncthreads();
+        v[0] = (s_t[0][0] + s_t[1][0]) + (s_t[2][0] + s_t[3][0]);
+        v[1] = (s_t[0][1] + s_t[1][1]) + (s_t[2][1] + s_t[3][1]);
+    }
+}
+// the block's normalised weights w_i = q_i / S of the lane's ITEMS particles (0 beyond the block), as a view of the block has them: K from the
+// block's particle count, maximum and flags of the block (safe_softmax, utils.jl:119-126), q = 1 for an all -Inf block.  Returns the flags.
+template <int TEAM, int ITEMS>
+__device__ __forceinline__ int block_norm_weights(const double* __restrict__ lw, int64_t b0, int cnt, int tl, double* s_m, int* s_f, uint64_t (*s_x)[4],
+                                                  double (&w)[ITEMS])
+{
+    const int K = fix_K(cnt);
+    double lwv[ITEMS];
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) { const int i = ITEMS * tl + k; lwv[k] = i < cnt ? lw[b0 + i] : -__builtin_huge_val(); }
+    double m; int f;
+    team_max_flags<TEAM, ITEMS>(lwv, tl, cnt, s_m, s_f, m, f);
+    uint64_t q[ITEMS], S = 0;
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) { q[k] = ITEMS * tl + k < cnt ? ((f & FLAG_ALL_NEGINF) ? 1ull : exp_fix(lwv[k] - m, K)) : 0ull; S += q[k]; }
+    S = wave_sum_u64(S);
+    if (TEAM == BLOCK) {
+        __syncthreads();
+        if (lane_id() == 0) s_x[wave_id()][0] = S;
+        __syncthreads();
+        S = 0;
+#pragma unroll
+        for (int wv = 0; wv < NWAVES; ++wv) S += s_x[wv][0];
+    }
+    const double Sd = (double)S;
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) w[k] = (double)q[k] / Sd;
+    return f;
+}
+// mean_out / var_out: [nblocks][W]; a block with NaN / +Inf weights gets NaN everywhere.  want_var = 0: var_out is not touched
+template <int W, int TEAM, int ITEMS>
+__global__ __launch_bounds__(BLOCK) void k_block_moments(const double* __restrict__ rows, const double* __restrict__ lw, int64_t n, int64_t nb, int64_t nblocks,
+                                                         int want_var, double* __restrict__ mean_out, double* __restrict__ var_out)
+{
+    constexpr int TEAMS = BLOCK / TEAM;
+    static_assert(TEAM == WAVE || TEAM == BLOCK, "a wave or the workgroup");
+    static_assert(W % 2 == 0, "rows are read as 16-byte column pairs");
+    __shared__ double s_m[NWAVES];
+    __shared__ int s_f[NWAVES];
+    __shared__ uint64_t s_x[NWAVES][4];
+    __shared__ double s_t[NWAVES][2];
+    const int tm = (int)threadIdx.x / TEAM, tl = (int)threadIdx.x % TEAM;
+    const int64_t blk = (int64_t)blockIdx.x * TEAMS + tm;
+    if (TEAM != BLOCK && blk >= nblocks) return;                   // (an idle wave: the wave-team path has no workgroup barrier)
+    const int64_t b0 = blk * nb;
+    const int cnt = (int)(n - b0 < nb ? n - b0 : nb);
+    double w[ITEMS];
+    const int f = block_norm_weights<TEAM, ITEMS>(lw, b0, cnt, tl, s_m, s_f, s_x, w);
+    if (f & (FLAG_NAN | FLAG_POSINF)) {                            // (team-uniform)
+        for (int c = tl; c < W; c += TEAM) { mean_out[blk * W + c] = __builtin_nan(""); if (want_var) var_out[blk * W + c] = __builtin_nan(""); }
+        return;
+    }
+#pragma unroll 1
+    for (int c2 = 0; c2 < W / 2; ++c2) {
+        double2 v[ITEMS];
+        double t0[ITEMS], t1[ITEMS];
+#pragma unroll
+        for (int k = 0; k < ITEMS; ++k) {
+            const int i = ITEMS * tl + k;
+            const bool in = i < cnt;
+            v[k] = in ? reinterpret_cast<const double2*>(rows + (b0 + i) * W)[c2] : double2{0.0, 0.0};
+            t0[k] = in ? w[k] * v[k].x : 0.0;
+            t1[k] = in ? w[k] * v[k].y : 0.0;
+        }
+        double mu[2] = {lane_tree<ITEMS>(t0), lane_tree<ITEMS>(t1)};
+        team_tree2<TEAM>(mu, s_t);
+        if (tl == 0) { mean_out[blk * W + 2 * c2] = mu[0]; mean_out[blk * W + 2 * c2 + 1] = mu[1]; }
+        if (want_var) {                                            // (grid-uniform)
+#pragma unroll
+            for (int k = 0; k < ITEMS; ++k) {
+                const bool in = ITEMS * tl + k < cnt;
+                double d0 = v[k].x - mu[0], d1 = v[k].y - mu[1];
+                d0 = d0 * d0; d1 = d1 * d1;
+                t0[k] = in ? w[k] * d0 : 0.0;
+                t1[k] = in ? w[k] * d1 : 0.0;
+            }
+            double s2[2] = {lane_tree<ITEMS>(t0), lane_tree<ITEMS>(t1)};
+            team_tree2<TEAM>(s2, s_t);
+            if (tl == 0) { var_out[blk * W + 2 * c2] = s2[0]; var_out[blk * W + 2 * c2 + 1] = s2[1]; }
+        }
+    }
+}
+// proportionmap: out[blk][j] = sum of the normalised weights of block blk's particles whose `col` equals v[j], j < n  (statistics.jl:91-101)
+constexpr int BLK_MATCH_MAX = 16;
+struct BlockMatch { double v[BLK_MATCH_MAX]; int n; };
+template <int TEAM, int ITEMS>
+__global__ __launch_bounds__(BLOCK) void k_block_proportion(const double* __restrict__ rows, int W, int col, const double* __restrict__ lw, int64_t n, int64_t nb,
+                                                            int64_t nblocks, BlockMatch mv, double* __restrict__ out)
+{
+    constexpr int TEAMS = BLOCK / TEAM;
+    static_assert(TEAM == WAVE || TEAM == BLOCK, "a wave or the workgroup");
+    __shared__ double s_m[NWAVES];
+    __shared__ int s_f[NWAVES];
+    __shared__ uint64_t s_x[NWAVES][4];
+    __shared__ double s_t[NWAVES][2];
+    const int tm = (int)threadIdx.x / TEAM, tl = (int)threadIdx.x % TEAM;
+    const int64_t blk = (int64_t)blockIdx.x * TEAMS + tm;
+    if (TEAM != BLOCK && blk >= nblocks) return;
+    const int64_t b0 = blk * nb;
+    const int cnt = (int)(n - b0 < nb ? n - b0 : nb);
+    double w[ITEMS];
+    const int f = block_norm_weights<TEAM, ITEMS>(lw, b0, cnt, tl, s_m, s_f, s_x, w);
+    if (f & (FLAG_NAN | FLAG_POSINF)) {
+        for (int j = tl; j < mv.n; j += TEAM) out[blk * mv.n + j] = __builtin_nan("");
+        return;
+    }
+    double x[ITEMS];
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) { const int i = ITEMS * tl + k; x[k] = i < cnt ? rows[(b0 + i) * W + col] : 0.0; }
+#pragma unroll 1
+    for (int j = 0; j < mv.n; j += 2) {                            // two match values per pass (mv.v is padded to an even count)
+        const double a0 = mv.v[j], a1 = mv.v[j + 1];
+        double t0[ITEMS], t1[ITEMS];
+#pragma unroll
+        for (int k = 0; k < ITEMS; ++k) {
+            const bool in = ITEMS * tl + k < cnt;
+            t0[k] = in ? w[k] * (x[k] == a0 ? 1.0 : 0.0) : 0.0;
+            t1[k] = in ? w[k] * (x[k] == a1 ? 1.0 : 0.0) : 0.0;
+        }
+        double p[2] = {lane_tree<ITEMS>(t0), lane_tree<ITEMS>(t1)};
+        team_tree2<TEAM>(p, s_t);
+        if (tl == 0) { out[blk * mv.n + j] = p[0]; if (j + 1 < mv.n) out[blk * mv.n + j + 1] = p[1]; }
+    }
+}
+
 // the blocks' observation vectors from a pinned host buffer into device memory, by a KERNEL (coalesced reads over PCIe) rather than a
 // hipMemcpyAsync: the copy stays on the compute queue (an SDMA copy costs a cross-queue dependency of ~10-20 us in front of the step
 // kernel that reads it).  The last workgroup publishes `ticket` to pinned memory: the host may then refill that staging buffer.

@@ -234,6 +234,127 @@ gpf_status gpf_block_stats(gpf_handle h, int64_t block_size, double* ess_out, do
     return GPF_OK;
 }
 
+} // extern "C"
+
+namespace gpfh {
+template <int Wc>
+void launch_block_moments_w(gpf_filter* h, int64_t nb, int64_t nblocks, int want_var, double* mean, double* var)
+{
+    if (nb <= 2 * WAVE)      GPF_LAUNCH((k_block_moments<Wc, WAVE, 2>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->rows[h->cur], h->lw, h->n, nb, nblocks, want_var, mean, var);
+    else if (nb <= 8 * WAVE) GPF_LAUNCH((k_block_moments<Wc, WAVE, 8>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->rows[h->cur], h->lw, h->n, nb, nblocks, want_var, mean, var);
+    else                     GPF_LAUNCH((k_block_moments<Wc, BLOCK, 8>), dim3((unsigned)nblocks), dim3(BLOCK), 0, h->stream, h->rows[h->cur], h->lw, h->n, nb, nblocks, want_var, mean, var);
+}
+// the device buffer of the per-block estimates: at least `need` doubles
+static gpf_status block_est_buffer(gpf_filter* h, int64_t need)
+{
+    if (h->blk_est_cap >= need) return GPF_OK;
+    if (h->blk_est) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->blk_est); h->blk_est = nullptr; h->blk_est_cap = 0; }
+    HIP_TRY(h, hipMalloc(&h->blk_est, (size_t)need * sizeof(double)));
+    h->blk_est_cap = need;
+    return GPF_OK;
+}
+// what the per-block estimates ask beyond block_checks: a filter that can have sub-state views, rows of column pairs
+static gpf_status block_est_checks(gpf_handle h, int64_t block_size, const char* who)
+{
+    // (what can be refused without touching the handle comes first: block_checks brings a lazy move or a view up to date)
+    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+    if (h->parent) return fail(h, GPF_ERR_STATE, std::string(who) + " on a sub-state view: call it on the filter");
+    if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, std::string(who) + " on a shard of a sharded filter");
+    if (h->hist_on) return fail(h, GPF_ERR_STATE, std::string(who) + " on a filter with a trajectory store (it has no sub-state views)");
+    if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");
+    gpf_status s = block_checks(h, block_size, who);
+    if (s) return s;
+    if (h->W != 2 && h->W != 4 && h->W != 8) return fail(h, GPF_ERR_STATE, "row width");
+    return GPF_OK;
+}
+// the view of one big block (big_block_views) brought up to date, its weight summary on the host: *bad = NaN / +Inf weights
+static gpf_status big_block_flags(gpf_filter* h, gpf_filter* v, bool* bad)
+{
+    gpf_status s = check_ready(v);
+    if (s || (s = ensure_raw(v)) || (s = fetch_scalars(v))) { h->err = v->err; return s; }
+    *bad = (v->h_sc->raw.flags & (FLAG_NAN | FLAG_POSINF)) != 0;
+    return GPF_OK;
+}
+} // namespace gpfh
+
+extern "C" {
+
+// for b in blocks: [mean(state[b], c) for c in columns], [var(state[b], c) ...] (src/statistics.jl:13-14, 48-50 on sub-states) -- gpf.h
+gpf_status gpf_block_moments(gpf_handle h, int64_t block_size, double* mean_out, double* var_out)
+{
+    if (h && !mean_out && !var_out) return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_block_moments: both outputs are NULL");
+    gpf_status s = block_est_checks(h, block_size, "gpf_block_moments");
+    if (s) return s;
+    if ((s = materialize(h))) return s;
+    const int64_t nblocks = (h->n + block_size - 1) / block_size;
+    const int W = h->W;
+    if (block_size > BLK_MAX) {                                  // the loop over sub-states (big_block_views)
+        if ((s = big_block_views(h, block_size))) return s;
+        for (int64_t b = 0; b < nblocks; ++b) {
+            gpf_filter* v = h->blk_views[(size_t)b];
+            bool bad = false;
+            if ((s = big_block_flags(h, v, &bad))) return s;
+            for (int c = 0; c < W; ++c) {
+                double* mo = mean_out ? mean_out + b * W + c : nullptr;
+                double* vo = var_out ? var_out + b * W + c : nullptr;
+                if (bad) { if (mo) *mo = __builtin_nan(""); if (vo) *vo = __builtin_nan(""); continue; }
+                if (mo && (s = gpf_mean(v, c, mo))) { h->err = v->err; return s; }
+                if (vo && (s = gpf_var(v, c, vo))) { h->err = v->err; return s; }
+            }
+        }
+        return GPF_OK;
+    }
+    const size_t cells = (size_t)nblocks * (size_t)W;
+    if ((s = block_est_buffer(h, (int64_t)(2 * cells)))) return s;
+    double* const mean = h->blk_est; double* const var = h->blk_est + cells;
+    DISPATCH_W(h, (launch_block_moments_w<WW>(h, block_size, nblocks, var_out ? 1 : 0, mean, var)));
+    HIP_TRY(h, hipGetLastError());
+    if (mean_out) HIP_TRY(h, hipMemcpyAsync(mean_out, mean, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (var_out) HIP_TRY(h, hipMemcpyAsync(var_out, var, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GPF_OK;
+}
+// for b in blocks: proportionmap(state[b], column)[values[k]] (src/statistics.jl:91-101 on sub-states) -- gpf.h
+gpf_status gpf_block_proportion(gpf_handle h, int64_t block_size, int32_t column, const double* values, int32_t n_values, double* out)
+{
+    if (h) {                                                     // (the arguments first: a refused call has not touched the handle)
+        if (!values || !out) return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_block_proportion: null values / output");
+        if (column < 0 || column >= h->W) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad column");
+        if (n_values < 1 || n_values > BLK_MATCH_MAX) return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_block_proportion: need 1 <= n_values <= " + std::to_string(BLK_MATCH_MAX));
+    }
+    gpf_status s = block_est_checks(h, block_size, "gpf_block_proportion");
+    if (s) return s;
+    if ((s = materialize(h))) return s;
+    const int64_t nblocks = (h->n + block_size - 1) / block_size;
+    if (block_size > BLK_MAX) {                                  // the loop over sub-states (big_block_views)
+        if ((s = big_block_views(h, block_size))) return s;
+        for (int64_t b = 0; b < nblocks; ++b) {
+            gpf_filter* v = h->blk_views[(size_t)b];
+            bool bad = false;
+            if ((s = big_block_flags(h, v, &bad))) return s;
+            for (int k = 0; k < n_values; ++k) {
+                double* o = out + b * n_values + k;
+                if (bad) { *o = __builtin_nan(""); continue; }
+                if ((s = gpf_proportion(v, 0, column, values[k], o))) { h->err = v->err; return s; }
+            }
+        }
+        return GPF_OK;
+    }
+    const size_t cells = (size_t)nblocks * (size_t)n_values;
+    if ((s = block_est_buffer(h, (int64_t)cells))) return s;
+    BlockMatch mv{};
+    for (int k = 0; k < BLK_MATCH_MAX; ++k) mv.v[k] = k < n_values ? values[k] : values[n_values - 1];
+    mv.n = n_values;
+    const double* rows = h->rows[h->cur];
+    if (block_size <= 2 * WAVE)      GPF_LAUNCH((k_block_proportion<WAVE, 2>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, rows, h->W, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
+    else if (block_size <= 8 * WAVE) GPF_LAUNCH((k_block_proportion<WAVE, 8>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, rows, h->W, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
+    else                             GPF_LAUNCH((k_block_proportion<BLOCK, 8>), dim3((unsigned)nblocks), dim3(BLOCK), 0, h->stream, rows, h->W, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out, h->blk_est, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GPF_OK;
+}
+
 // the blocks' observation vectors -> device ([n_blocks][MAX_OBS], zero-padded), ModelArgs::blk_* set
 static gpf_status set_block_obs(gpf_filter* h, const double* obs, int32_t n_obs, int64_t block_size)
 {

@@ -179,6 +179,27 @@ gpf_status gpf_block_resampled(gpf_handle h, int32_t* out);
 /* effective_sample_size(state[b]) and log_ml_estimate(state[b]) = log_ml_est + logsumexp(block weights) - log(block size) of every block
  * (src/utils.jl:163-178); host arrays of ceil(n / block_size) doubles, either may be NULL */
 gpf_status gpf_block_stats(gpf_handle h, int64_t block_size, double* ess_out, double* lml_out);
+/* The state estimates of every block -- the batched form of
+ *     for b in blocks; mean(state[b], addr); var(state[b], addr); proportionmap(state[b], addr); end
+ * (src/statistics.jl:13-14, 48-50, 91-101 on ParticleFilterSubStates, src/view.jl:35-48).  Blocks as in gpf_resample_blocks, n_blocks =
+ * ceil(n / block_size), the last block may be shorter.  Up to 2048 particles per block ONE launch answers all blocks and all columns; block b's
+ * values are bit-identical to gpf_mean / gpf_var / gpf_proportion on gpf_view_create(h, b * block_size, count_b): weights normalised over the
+ * block in fixed point (K from the block's particle count; 1 each if all its log-weights are -Inf), the terms summed by the binary tree of
+ * DESIGN.md 3.5 over the block-local index -- a block is one 2048-term chunk of it.  Larger blocks run the loop over view handles inside
+ * the library (as gpf_block_stats does): the same results, a few launches per block and column.
+ * DEVIATION from the per-view calls: a block whose log-weights hold a NaN or +Inf gets NaN in all its outputs (as its ESS from
+ * gpf_block_stats) and the call succeeds; the other blocks are unaffected.
+ * The calls read the state and change nothing: no epoch advance, no RNG draw.  They do not read model parameters, so they work unchanged
+ * with gpf_set_block_params.  Not on views, shards of a sharded filter or filters with a trajectory store (GPF_ERR_STATE); bad arguments
+ * return GPF_ERR_INVALID_ARGUMENT.  Both synchronise the stream.
+ *
+ * for b in blocks: [mean(state[b], c) for c in columns], [var(state[b], c) ...]   (src/statistics.jl:13-14, 48-50 on sub-states)
+ * mean_out, var_out: [n_blocks][row_width] row-major, host; either may be NULL, not both.  row_width as gpf_state_dim reports it (the
+ * x_{t-1} columns of keep_prev included, like gpf_mean). */
+gpf_status gpf_block_moments(gpf_handle h, int64_t block_size, double* mean_out, double* var_out);
+/* for b in blocks: sum of the normalised weights of block b's particles whose `column` equals values[k]   (src/statistics.jl:91-101)
+ * out: [n_blocks][n_values] row-major, host; 1 <= n_values <= 16.  A value no particle of the block holds gives 0.0. */
+gpf_status gpf_block_proportion(gpf_handle h, int64_t block_size, int32_t column, const double* values, int32_t n_values, double* out);
 
 /* The other steps of the loop over sub-states, block by block in one launch each (blocks as in gpf_resample_blocks):
  *   gpf_initialize_blocks / gpf_update_blocks: block b is initialised / extended with ITS OWN observation vector

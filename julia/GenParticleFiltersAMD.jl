@@ -215,6 +215,50 @@ function block_stats(s::DeviceParticleFilterState, block_size::Int)
     _status(s, ccall((:gpf_block_stats, libgpf), Cint, (Ptr{Cvoid}, Int64, Ptr{Cdouble}, Ptr{Cdouble}), s.handle, block_size, ess, lml))
     return ess, lml
 end
+# The state estimates of every block: for b in blocks; mean(state[b], addr); var(state[b], addr); proportionmap(state[b], addr); end
+# (src/statistics.jl:13-14, 48-50, 91-101 on sub-states) in one launch, bit-identical to the loop over views (gpf.h gpf_block_moments,
+# gpf_block_proportion).  Matrices are (row_width, n_blocks) / (n_values, n_blocks): column b for block b.  addr = 0-based column.
+function _row_width(s::DeviceParticleFilterState)
+    dim = Ref{Cint}(0); w = Ref{Cint}(0)
+    _status(s, ccall((:gpf_state_dim, libgpf), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cint}), s.handle, dim, w))
+    return Int(w[])
+end
+function block_moments(s::DeviceParticleFilterState, block_size::Int)
+    nb = cld(s.n_particles, block_size); W = _row_width(s)
+    mu = Matrix{Float64}(undef, W, nb); s2 = Matrix{Float64}(undef, W, nb)
+    _status(s, ccall((:gpf_block_moments, libgpf), Cint, (Ptr{Cvoid}, Int64, Ptr{Cdouble}, Ptr{Cdouble}), s.handle, block_size, mu, s2))
+    return mu, s2
+end
+function block_mean(s::DeviceParticleFilterState, block_size::Int, addr::Union{Nothing,Integer}=nothing)
+    nb = cld(s.n_particles, block_size); W = _row_width(s)
+    mu = Matrix{Float64}(undef, W, nb)
+    _status(s, ccall((:gpf_block_moments, libgpf), Cint, (Ptr{Cvoid}, Int64, Ptr{Cdouble}, Ptr{Cdouble}), s.handle, block_size, mu, C_NULL))
+    return addr === nothing ? mu : mu[addr + 1, :]
+end
+function block_var(s::DeviceParticleFilterState, block_size::Int, addr::Union{Nothing,Integer}=nothing)
+    nb = cld(s.n_particles, block_size); W = _row_width(s)
+    s2 = Matrix{Float64}(undef, W, nb)
+    _status(s, ccall((:gpf_block_moments, libgpf), Cint, (Ptr{Cvoid}, Int64, Ptr{Cdouble}, Ptr{Cdouble}), s.handle, block_size, C_NULL, s2))
+    return addr === nothing ? s2 : s2[addr + 1, :]
+end
+block_mean(s::DeviceParticleFilterState, block_size::Int, addr::Pair) = error("block_mean: a past-step address needs a trajectory store, which block-wise states do not have")
+block_var(s::DeviceParticleFilterState, block_size::Int, addr::Pair) = error("block_var: a past-step address needs a trajectory store, which block-wise states do not have")
+# returns (values, proportions): the distinct values of the column over all blocks, and a (n_values, n_blocks) Matrix; 16 values per launch
+function block_proportionmap(s::DeviceParticleFilterState, block_size::Int, addr::Integer; max_values::Int=256)
+    col = Vector{Float64}(undef, s.n_particles)
+    _status(s, ccall((:gpf_get_column, libgpf), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Int64), s.handle, addr, col, length(col)))
+    vals = sort(unique(col))
+    length(vals) > max_values && error("proportionmap: $(length(vals)) distinct values; the column does not look discrete")
+    nb = cld(s.n_particles, block_size)
+    out = Matrix{Float64}(undef, length(vals), nb)
+    for k0 in 1:16:length(vals)
+        chunk = vals[k0:min(k0 + 15, length(vals))]
+        part = Matrix{Float64}(undef, length(chunk), nb)
+        _status(s, ccall((:gpf_block_proportion, libgpf), Cint, (Ptr{Cvoid}, Int64, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}), s.handle, block_size, addr, chunk, length(chunk), part))
+        out[k0:k0 + length(chunk) - 1, :] = part
+    end
+    return vals, out
+end
 # Every block a filter on ITS OWN data: per-block initialisation / update / rejuvenation, one launch each (gpf.h gpf_initialize_blocks,
 # gpf_update_blocks, gpf_rejuvenate_blocks).  observations: a (n_obs, n_blocks) Matrix -- column b for block b.
 function pf_initialize_blocks(model::NativeModel, model_args::Tuple, observations::Matrix{Float64}, n_particles::Int, block_size::Int; kw...)
