@@ -4,10 +4,22 @@ an adapter, and after every operation compare every particle's row and log-weigh
 import numpy as np
 
 import hp_reference as hp
+import hp_weights as hw
 from hp_reference import E
 
 MEDIAN_REL_TOL = 1e-12        # the bound may not go vacuous: median over a case's particles, relative to max(1, |value|)
-MAX_UNDECIDABLE = 2           # MH: particles whose |log u - alpha| is below alpha's bound
+MAX_TOL = {}                  # largest derived bound per weight-side quantity over the cases run so far: the table of DESIGN.md 3.3,
+                              # printed by `python tests/test_hp_weights.py`
+
+
+def sum_guard(sm):
+    """What the bound of a sum over a weight vector (ESS, log-ML, mean, var, a proportion) may not exceed, relative to max(1, |value|).
+    Every particle is off by up to half a count and the largest weight alone is 2^K counts, so S and a weighted numerator are each off by up
+    to N / 2^(K+1) relative: N 2^-K for the two.  A second moment amplifies a weight's error by (x - mu)^2 / var, taken as at most 64 (8
+    standard deviations).  Never below the guard of the per-particle values."""
+    return max(MEDIAN_REL_TOL, 64.0 * sm.n * 2.0 ** -sm.K)
+MAX_UNDECIDABLE = 2           # MH: particles whose |log u - alpha| is below alpha's bound; resampling: slots whose target is within the
+                              # quantisation bound of a CDF boundary (multinomial, stratified; the residual resampler: none at all)
 
 
 # ------------------------------------------------------------------------------------------- adapters
@@ -17,16 +29,78 @@ class OracleAdapter:
 
     rows = property(lambda s: s.f.rows.copy())
     lw = property(lambda s: s.f.lw.copy())
+    parents = property(lambda s: s.f.parents.copy())
+    history = False
 
     def initialize(self, obs, proposal=False, strata=None, layout="contiguous"):
-        self.f = self.o.OracleFilter(self.model.model_id, self.model.params, self.n, self.seed, keep_prev=True)      # a new filter: epoch 0
+        self.f = self.o.OracleFilter(self.model.model_id, self.model.params, self.n, self.seed, keep_prev=True, history=self.history)      # a new filter: epoch 0
         self.f.initialize(obs, proposal=proposal, strata=strata, layout=layout)
 
     def update(self, obs, proposal=False, strata=None, layout="interleaved"):
         self.f.update(obs, proposal=proposal, strata=strata, layout=layout)
 
-    def resample(self, method):
-        self.f.resample(method, check=False)
+    def resample(self, method, alpha=None, sort_particles=True):
+        return bool(self.f.resample(method, priority_alpha=alpha, sort_particles=sort_particles, check=False))
+
+    def resize(self, n_new, method, alpha=None):
+        return bool(self.f.resize(n_new, method, priority_alpha=alpha, check=False))
+
+    def sample_unweighted(self, k):
+        return self.f.sample_unweighted(k)[1] - 1
+
+    def set_lw(self, lw):
+        self.f.lw = np.array(lw, np.float64)
+
+    def set_rows(self, rows):
+        self.f.rows = np.array(rows, np.float64)
+
+    # the getters and statistics (utils.jl:148-178, statistics.jl:13-14, 48-50, 91-101); addr: a column, or (step, column) for a past choice
+    def ess(self):
+        return self.f.effective_sample_size()
+
+    def lml_estimate(self):
+        return self.f.log_ml_estimate()
+
+    def log_norm_weights(self):
+        return self.f.log_norm_weights()
+
+    def norm_weights(self):
+        return self.f.norm_weights()
+
+    def column(self, addr):
+        return self.f.history_column(*addr) if isinstance(addr, tuple) else self.f.column(addr)
+
+    # proportionmap and the block-wise estimates have no function of their own in oracle.py: what is under test here is the composition the
+    # GPU parity tests use as the oracle (tests/test_gpu_block_estimates.py): WeightSummary of the (block's) weights + o_wsum over its rows
+    def _wsum(self, lw, x, pw, c=0.0):
+        s = self.o.WeightSummary(np.ascontiguousarray(lw), len(lw))
+        return self.o.lib().o_wsum(s.q, s.S, np.ascontiguousarray(x, np.float64).reshape(-1, 1), 1, 0, len(lw), pw, float(c))
+
+    def mean(self, addr):
+        return self.f.history_mean(*addr) if isinstance(addr, tuple) else self.f.mean(addr)
+
+    def var(self, addr):
+        return self.f.history_var(*addr) if isinstance(addr, tuple) else self.f.var(addr)
+
+    def proportionmap(self, addr):
+        x = self.column(addr)
+        return {float(v): self._wsum(self.f.lw, x, 3, v) for v in np.unique(x)}
+
+    def block_stats(self, nb):
+        vs = [self.f[a:b] for a, b in self.o.blocks_of(self.f, nb)]
+        return np.array([v.effective_sample_size() for v in vs]), np.array([v.log_ml_estimate() for v in vs])
+
+    def block_moments(self, nb, col):
+        mu, s2 = [], []
+        for a, b in self.o.blocks_of(self.f, nb):
+            lw, x = self.f.lw[a:b], self.f.rows[a:b, col]
+            mu.append(self._wsum(lw, x, 1))
+            s2.append(self._wsum(lw, x, 2, mu[-1]))
+        return np.array(mu), np.array(s2)
+
+    def block_proportionmap(self, nb, col):
+        vals = np.unique(self.f.rows[:, col])
+        return vals, np.array([[self._wsum(self.f.lw[a:b], self.f.rows[a:b, col], 3, v) for v in vals] for a, b in self.o.blocks_of(self.f, nb)])
 
     def rejuvenate(self, method, n_iters, q=None):
         self.f.rejuvenate(method, n_iters, proposal=q)
@@ -49,6 +123,8 @@ class DeviceAdapter:
 
     rows = property(lambda s: s.st.traces)
     lw = property(lambda s: s.st.log_weights)
+    parents = property(lambda s: s.st.parents)
+    history = False
 
     def _prop(self):
         return self.g.locally_optimal if self.model.name == "lgssm2" else self.g.line_fixed
@@ -59,7 +135,8 @@ class DeviceAdapter:
             rest.append(list(strata))
         if proposal:
             rest += [self._prop(), ()]
-        self.st = g.pf_initialize(self.model, (), obs, *rest, self.n, seed=self.seed, keep_prev=True, layout=layout)
+        kw = {"history": 8} if self.history else {}
+        self.st = g.pf_initialize(self.model, (), obs, *rest, self.n, seed=self.seed, keep_prev=True, layout=layout, **kw)
 
     def update(self, obs, proposal=False, strata=None, layout="interleaved"):
         if strata is not None:
@@ -69,8 +146,71 @@ class DeviceAdapter:
         else:
             self.g.pf_update(self.st, (), (), obs)
 
-    def resample(self, method):
-        self.g.pf_resample(self.st, method, check=False)
+    def _prio(self, alpha):
+        return None if alpha is None else self.g.Tempering(alpha)
+
+    def resample(self, method, alpha=None, sort_particles=True):
+        kw = {"sort_particles": sort_particles} if method == "stratified" else {}
+        return self._invalid(lambda check: self.g.pf_resample(self.st, method, priority_fn=self._prio(alpha), check=check, **kw))
+
+    check = False
+
+    def _invalid(self, call):
+        """check=False is the fully asynchronous path and reports nothing: the verdict is None (unknown).  With `self.check = "warn"` (the
+        synchronising path) the library's own verdict comes back"""
+        import warnings
+        if self.check is False:
+            call(False)
+            return None
+        with warnings.catch_warnings(record=True) as w:
+            warnings.simplefilter("always")
+            call(self.check)
+        return any("Invalid weights" in str(x.message) for x in w)
+
+    def resize(self, n_new, method, alpha=None):
+        return self._invalid(lambda check: self.g.pf_resize(self.st, n_new, method, priority_fn=self._prio(alpha), check=check))
+
+    def sample_unweighted(self, k):
+        return self.g.sample_unweighted_traces(self.st, k, return_indices=True)[1] - 1
+
+    def set_lw(self, lw):
+        self.st.log_weights = np.array(lw, np.float64)
+
+    def set_rows(self, rows):
+        self.st.traces = np.array(rows, np.float64)
+
+    def ess(self):
+        return self.g.effective_sample_size(self.st)
+
+    def lml_estimate(self):
+        return self.g.log_ml_estimate(self.st)
+
+    def log_norm_weights(self):
+        return self.g.get_log_norm_weights(self.st)
+
+    def norm_weights(self):
+        return self.g.get_norm_weights(self.st)
+
+    def column(self, addr):
+        return self.st.history_column(*addr) if isinstance(addr, tuple) else self.st.column(addr)
+
+    def mean(self, addr):
+        return self.g.mean(self.st, addr)
+
+    def var(self, addr):
+        return self.g.var(self.st, addr)
+
+    def proportionmap(self, addr):
+        return self.g.proportionmap(self.st, addr)
+
+    def block_stats(self, nb):
+        return self.g.block_stats(self.st, nb)
+
+    def block_moments(self, nb, col):
+        return self.g.block_mean(self.st, nb, col), self.g.block_var(self.st, nb, col)
+
+    def block_proportionmap(self, nb, col):
+        return self.g.block_proportionmap(self.st, nb, col)
 
     def _move_proposal(self, q):
         return self.g.locally_optimal_move if self.model.name == "lgssm2" else self.g.outlier_propose(q[0])
@@ -91,11 +231,18 @@ class DeviceAdapter:
 # ------------------------------------------------------------------------------------------- the checked run
 class Violations:
     def __init__(self):
-        self.bad, self.tols = [], []
+        self.bad, self.tols, self.by, self.vacuous = [], [], {}, []
 
-    def value(self, what, i, got, want: E):
+    def value(self, what, i, got, want: E, guard=None):
+        """`guard`: a sum over many particles is not pooled into the median of the per-particle bounds (thousands of them would hide it): its
+        own bound must stay below `guard` (sum_guard)"""
         d, t = hp.differs(got, want)
-        self.tols.append(hp.rel_tol(want))
+        r = hp.rel_tol(want)
+        if guard is None:
+            self.tols.append(r)
+        elif not r < guard:
+            self.vacuous.append((what, i, r, guard))
+        self.by[what] = max(self.by.get(what, 0.0), r)
         if not d <= t:
             self.bad.append((what, i, float(got), hp.M.nstr(want.v, 20), d, t))
 
@@ -105,6 +252,7 @@ class Violations:
 
     def finish(self, label):
         assert not self.bad, f"{label}: {len(self.bad)} values off the reference, first {self.bad[:3]}"
+        assert not self.vacuous, f"{label}: derived bounds of sums above their guard, (what, index, bound, guard) {self.vacuous[:3]}"
         if self.tols:
             med = float(np.median(self.tols))
             assert med < MEDIAN_REL_TOL, f"{label}: median derived tolerance {med:.3g} is not below {MEDIAN_REL_TOL}"
@@ -120,6 +268,7 @@ class Run:
         self.ref = ref or hp.Ref(model)
         self.d, self.epoch, self.has_prev, self.obs = model.dim, 0, False, None
         self.disc = hp.DISCRETE[model.name]
+        self.lml = E(0.0)                  # the running log-ML estimate (resample.jl:178-182), carried with its bound
 
     def _row(self, v, what, i, got, want, prev=None):
         for k in range(self.d):
@@ -133,10 +282,14 @@ class Run:
             for k in range(self.d):
                 v.exact(f"{what} x_prev[{k}]", i, got[self.d + k], prev[k])
 
-    def initialize(self, obs, proposal=False, strata=None, layout="contiguous"):
+    def initialize(self, obs, proposal=False, strata=None, layout="contiguous", check=True):
+        """check=False: the rows and weights are some filter's state for the weight-side checks; what they are is the other tests' business"""
         obs = np.ascontiguousarray(obs, np.float64)
         self.epoch = 0
         self.a.initialize(obs, proposal=proposal, strata=strata, layout=layout)
+        if not check:
+            self.epoch, self.has_prev, self.obs, self.lml = 1, False, obs, E(0.0)
+            return 0.0
         rows, lw, v = self.a.rows, self.a.lw, Violations()
         for i in range(self.n):
             if strata is not None:
@@ -147,13 +300,16 @@ class Run:
                 x, wf = hp.initialize(self.ref, self.seed, self.epoch, i, obs)
             self._row(v, "initialize", i, rows[i], x)
             v.value("initialize lw", i, lw[i], wf(list(rows[i, :self.d])))
-        self.epoch, self.has_prev, self.obs = 1, False, obs
+        self.epoch, self.has_prev, self.obs, self.lml = 1, False, obs, E(0.0)
         return v.finish(f"{self.model.name} initialize")
 
-    def update(self, obs, proposal=False, strata=None, layout="interleaved"):
+    def update(self, obs, proposal=False, strata=None, layout="interleaved", check=True):
         obs = np.ascontiguousarray(obs, np.float64)
         rows0, lw0 = self.a.rows, self.a.lw
         self.a.update(obs, proposal=proposal, strata=strata, layout=layout)
+        if not check:
+            self.epoch, self.has_prev, self.obs = self.epoch + 1, True, obs
+            return 0.0
         rows, lw, v = self.a.rows, self.a.lw, Violations()
         for i in range(self.n):
             xp = list(rows0[i, :self.d])
@@ -169,9 +325,128 @@ class Run:
         self.has_prev, self.obs = True, obs
         return v.finish(f"{self.model.name} update")
 
-    def resample(self, method="multinomial"):
-        self.a.resample(method)
+    def _note(self, what, v):
+        v.finish(f"{self.model.name} {what}")
+        for k, t in v.by.items():
+            k = k.split(" (")[0]
+            MAX_TOL[k] = max(MAX_TOL.get(k, 0.0), t)
+
+    def _lml_estimate(self, v, what, sm):
+        if self.lml.v == -hp.M.inf:                       # a resample of all -Inf weights: logsumexp = -Inf, for good
+            assert self.a.lml_estimate() == -np.inf, what
+        else:
+            v.value(what, 0, self.a.lml_estimate(), hw.lml_estimate_from(self.lml, sm), guard=sum_guard(sm))
+
+    def _check_resampled(self, label, method, alpha, sort_particles, rows0, lw0, n_new, invalid, K=None):
+        """after a resample / resize under epoch self.epoch: ancestors against the reference's (tests/hp_weights.py), the gathered rows bit for
+        bit, the new log-weights and the log-ML estimate.  Returns the number of undecidable slots (residual: asserted 0)."""
+        a, n_old = self.a, len(lw0)
+        parents0 = np.asarray(a.parents) - 1
+        lp = lw0 if alpha is None else np.float64(alpha) * lw0                   # priority_fn.(log_weights), Float64 like the reference
+        sm, ref, bad = hw.reference_ancestors(lp, method, self.seed, self.epoch, n_new, sort_particles, K)
+        assert invalid is None or invalid == sm.invalid, (label, invalid)      # None: a check=False call on the device reports no verdict
+        left_out = hw.check_ancestors(ref, parents0, sm, label)
+        if method == "residual":
+            assert not bad and left_out == 0, f"{label}: residual resampling with undecidable copy counts {bad[:4]} / tail slots {ref.undecidable[:4]}"
+        else:
+            assert left_out <= MAX_UNDECIDABLE, (label, ref.undecidable)
+        rows, lw = a.rows, a.lw
+        assert rows.shape[0] == n_new and np.array_equal(np.ascontiguousarray(rows).view(np.uint64), np.ascontiguousarray(rows0[parents0]).view(np.uint64)), f"{label}: gathered rows"
+        v = Violations()
+        if alpha is None:
+            assert (lw == 0.0).all(), f"{label}: weights after the resample are not 0"
+        else:
+            want = hw.weights_after(lw0, lp, parents0, n_new)
+            for j in range(n_new):
+                v.value("lw after a resample under a priority", j, lw[j], want[j])
+        # the log-ML estimate: the running sum grows by logsumexp(RAW lw) - log N_old; the getter adds logsumexp(new lw) - log N_new
+        if np.all(lw0 == -np.inf):
+            self.lml = E(-hp.M.inf)
+        else:
+            self.lml = self.lml + (hw.Softmax(lw0, K).lse() - hw.log_n(n_old))
+        self._lml_estimate(v, "log_ml_estimate", hw.Softmax(lw))
+        self._note(label, v)
+        return left_out
+
+    def resample(self, method="multinomial", alpha=None, sort_particles=True):
+        rows0, lw0 = self.a.rows, self.a.lw
+        invalid = self.a.resample(method, alpha, sort_particles)
+        left_out = self._check_resampled(f"resample {method}", method, alpha, sort_particles, rows0, lw0, self.n, invalid)
         self.epoch += 1
+        return left_out
+
+    def resize(self, n_new, method="multinomial", alpha=None):
+        """pf_resize (resize.jl:46-124): n_new slots over the old weights; K is sized for the larger of the two counts"""
+        rows0, lw0 = self.a.rows, self.a.lw
+        invalid = self.a.resize(n_new, method, alpha)
+        left_out = self._check_resampled(f"resize {method}", method, alpha, True, rows0, lw0, n_new, invalid, K=hw.fix_K(max(self.n, n_new)))
+        self.n = self.a.n = n_new
+        self.epoch += 1
+        return left_out
+
+    def sample_unweighted(self, k):
+        """Gen.sample_unweighted_traces: k categorical draws, slot j of an epoch of its own; the filter is left as it was"""
+        rows0, lw0 = self.a.rows, self.a.lw
+        idx = self.a.sample_unweighted(k)
+        sm = hw.Softmax(lw0)
+        left_out = hw.check_ancestors(hw.multinomial(sm, self.seed, self.epoch, k), idx, sm, "sample_unweighted")
+        assert np.array_equal(self.a.rows, rows0) and np.array_equal(self.a.lw, lw0)
+        assert left_out <= MAX_UNDECIDABLE
+        self.epoch += 1
+        return left_out
+
+    # ---- getters and statistics against the definitions
+    def check_summaries(self, addrs=(), discrete=()):
+        """effective_sample_size, log_ml_estimate, get_log_norm_weights, get_norm_weights, and mean / var (addrs) / proportionmap (discrete)
+        of columns of the current step or (step, column) addresses of a past one"""
+        a, lw, v = self.a, self.a.lw, Violations()
+        sm = hw.Softmax(lw)
+        if sm.invalid:                                                       # utils.jl:100-107: lognorm / softmax of all -Inf are NaN
+            assert np.isnan(a.ess()) and np.isnan(a.norm_weights()).all() and np.isnan(a.log_norm_weights()).all()
+        else:
+            v.value("ess", 0, a.ess(), sm.ess(), guard=sum_guard(sm))
+            self._lml_estimate(v, "log_ml_estimate", sm)
+            got_l, got_w = a.log_norm_weights(), a.norm_weights()
+            for i, (wl, ww) in enumerate(zip(hw.log_norm_weights(sm), hw.norm_weights(sm))):
+                if lw[i] == -np.inf:
+                    assert got_l[i] == -np.inf and got_w[i] == 0.0, i
+                    continue
+                v.value("log_norm_weights", i, got_l[i], wl)
+                v.value("norm_weights", i, got_w[i], ww)
+        for addr in addrs:
+            x = a.column(addr)
+            v.value(f"mean ({addr})", 0, a.mean(addr), hw.mean(sm, x), guard=sum_guard(sm))
+            v.value(f"var ({addr})", 0, a.var(addr), hw.var(sm, x), guard=sum_guard(sm))
+        for addr in discrete:
+            x, pm = a.column(addr), a.proportionmap(addr)
+            assert sorted(pm) == sorted(float(t) for t in np.unique(x)), addr
+            for val, got in pm.items():
+                v.value(f"proportion ({addr} = {val})", 0, got, hw.proportion(sm, x, val), guard=sum_guard(sm))
+        self._note("getters and statistics", v)               # one case: the median bound is over all its values
+
+    def check_blocks(self, nb, col, discrete_col=None):
+        """block_stats, block_mean / block_var and block_proportionmap: block b is the sub-state of its particles (view.jl:16-48)"""
+        a, lw, rows, v = self.a, self.a.lw, self.a.rows, Violations()
+        ess, lml = a.block_stats(nb)
+        mu, s2 = a.block_moments(nb, col)
+        if discrete_col is not None:
+            vals, pr = a.block_proportionmap(nb, discrete_col)
+            assert np.array_equal(vals, np.unique(rows[:, discrete_col]))
+        for b, i0 in enumerate(range(0, self.n, nb)):
+            sm = hw.Softmax(lw[i0:i0 + nb])
+            x = rows[i0:i0 + nb, col]
+            if sm.invalid:                                                   # the uniform fallback answers mean / var / proportions
+                assert np.isnan(ess[b]) and lml[b] == -np.inf, b
+            else:
+                v.value("block ess", b, ess[b], sm.ess(), guard=sum_guard(sm))
+                v.value("block log_ml_estimate", b, lml[b], hw.lml_estimate_from(self.lml, sm), guard=sum_guard(sm))
+            v.value("block mean", b, mu[b], hw.mean(sm, x), guard=sum_guard(sm))
+            v.value("block var", b, s2[b], hw.var(sm, x), guard=sum_guard(sm))
+            if discrete_col is not None:
+                xd = rows[i0:i0 + nb, discrete_col]
+                for k, val in enumerate(vals):
+                    v.value(f"block proportion ({val})", b, pr[b, k], hw.proportion(sm, xd, val), guard=sum_guard(sm))
+        self._note(f"blocks of {nb}", v)
 
     def check_conjugacy(self, rows0, lw0, first):
         """lgssm2 with the locally optimal proposal: the increment is log N(y; A x', (sq^2 + sr^2) I) whatever x was drawn"""
@@ -255,14 +530,27 @@ class Run:
         v.finish(f"{self.model.name} move fused into update")
         return len(undecidable)
 
-    def step_ess(self, obs, ess_threshold=0.5):
+    def step_ess(self, obs, ess_threshold=0.5, must_decide=False):
         """pf_step_ess: (resample if ESS < threshold N), update, in one call.  The resampled x_{t-1} is what the new row keeps in its second
         half: an old row, from which the update is predicted; the weights restart from 0 after a multinomial resample."""
         obs = np.ascontiguousarray(obs, np.float64)
         rows0, lw0 = self.a.rows, self.a.lw
         resampled = self.a.step_ess(obs, ess_threshold)
         rows, lw, v, d = self.a.rows, self.a.lw, Violations(), self.d
+        # the verdict ESS < threshold N is the reference's wherever the reference can tell
+        sm0 = hw.Softmax(lw0)
+        ess, cut = sm0.ess(), E(ess_threshold) * float(self.n)
+        decidable = abs(float(ess.v - cut.v)) > ess.e + cut.e
+        assert decidable or not must_decide, f"step_ess: ESS {ess} against {cut} is not decidable: choose another threshold"
+        if decidable:
+            assert resampled == bool(ess.v < cut.v), (resampled, ess, cut)
         if resampled:
+            # the resample of the call, seen through the update that followed it: ancestors, the gathered x_{t-1}, the log-ML estimate
+            parents0 = np.asarray(self.a.parents) - 1
+            ref = hw.multinomial(sm0, self.seed, self.epoch)
+            assert hw.check_ancestors(ref, parents0, sm0, "step_ess resample") <= MAX_UNDECIDABLE
+            assert np.array_equal(np.ascontiguousarray(rows[:, d:2 * d]).view(np.uint64), np.ascontiguousarray(rows0[parents0][:, :d]).view(np.uint64))
+            self.lml = self.lml + (sm0.lse() - hw.log_n(self.n))
             self.epoch += 1
             old = {tuple(r[:d].view(np.uint64)) for r in np.ascontiguousarray(rows0)}
         for i in range(self.n):
@@ -277,6 +565,7 @@ class Run:
             v.value("step_ess lw", i, lw[i], E(0.0 if resampled else lw0[i]) + wf(list(rows[i, :d])))
         self.epoch += 1
         self.has_prev, self.obs = True, obs
+        self._lml_estimate(v, "log_ml_estimate", hw.Softmax(lw))
         v.finish(f"{self.model.name} step_ess")
         return resampled
 
