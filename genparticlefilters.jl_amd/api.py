@@ -534,12 +534,62 @@ def set_block_params(state, params, block_size: int | None = None):
     call that would use the state's one parameter vector (pf_update, pf_initialize, the resize family, ...) raises.  Uploaded once."""
     if params is None:
         state._check(state._L.gpf_set_block_params(state._h, None, 0, 0))
+        state._n_param_blocks = 0
         return state
     if block_size is None:
         raise ErrorException("set_block_params needs the block_size of the block-wise calls")
     rows = block_params_rows(state.model, params, state.n_particles, block_size)
     state._check(state._L.gpf_set_block_params(state._h, _pd(rows), rows.shape[1], int(block_size)))
+    state._n_param_blocks = rows.shape[0]
     return state
+
+
+def get_block_params(state) -> np.ndarray:
+    """the per-block parameter rows as they stand, (n_blocks, n_params) (gpf.h gpf_get_block_params): after pf_resample_across_blocks the rows
+    set_block_params uploaded, permuted by its block ancestors.  A checkpoint does not hold them: `set_block_params(state, get_block_params(state),
+    block_size)` after `restore` continues bit for bit.  Raises when none are set."""
+    nb = getattr(state, "_n_param_blocks", 0)
+    if nb < 1:
+        raise ErrorException("get_block_params: no per-block parameters are set (set_block_params)")
+    out = np.empty((nb, int(np.asarray(state.model.params).size)))
+    state._check(state._L.gpf_get_block_params(state._h, _pd(out), out.shape[1], nb))
+    return out
+
+
+def pf_resample_across_blocks(state, block_size: int, method: str = "multinomial", *, ess_frac=None, sort_particles: bool = True, check="warn"):
+    """Resampling ACROSS blocks -- the outer level of SMC^2 / a nested or island filter (gpf.h gpf_resample_across_blocks): every block of
+    block_size particles is one super-particle with the log-weight log_ml_estimate(state[b]) (`block_stats`); the blocks are resampled by the
+    reference's resampler (src/resample.jl:19-175) on those B = n / block_size weights -- the ancestors of a filter of B particles with this state's
+    seed at this state's RNG epoch -- and whole filters are copied: rows, parents, per-block parameters and observations, and the log-weights plus
+    M - L[a], so that every block then carries the average mass M and the weights inside a block are kept.  ess_frac: resample only if the ESS of
+    the block weights is below ess_frac * B.  Returns the 1-based block ancestors (int64, theta = theta[A - 1]), or None when the gate did not fire."""
+    if method not in ("multinomial", "residual", "stratified"):
+        raise ErrorException(f"Resampling method {method} not recognized.")
+    if check not in (True, False, "warn"):
+        raise ValueError("check must be True, 'warn' or False")
+    if isinstance(state, DeviceParticleFilterSubState):
+        raise ErrorException("pf_resample_across_blocks works on the whole filter")
+    check_id = 2 if check is True else (1 if check == "warn" else 0)
+    inv, res, ess = C.c_int32(0), C.c_int32(0), C.c_double(0.0)
+    st = state._L.gpf_resample_across_blocks(state._h, RESAMPLE_METHODS[method], int(block_size), int(sort_particles),
+                                             float("nan") if ess_frac is None else float(ess_frac), check_id, C.byref(inv), C.byref(res), C.byref(ess))
+    if st != _lib.OK:
+        raise ErrorException(state._L.gpf_last_error(state._h).decode())
+    state._across_ess = ess.value
+    if check == "warn" and inv.value:
+        warnings.warn("Invalid block weights (all -Inf): blocks resampled with uniform weights.")
+    if not res.value:
+        return None
+    state._n_blocks_last = 0                                     # (the mask of pf_resample_blocks no longer describes the blocks)
+    state._n_across_blocks = state.n_particles // int(block_size)
+    return block_ancestors(state)
+
+
+def block_ancestors(state) -> np.ndarray:
+    """the 1-based block ancestors of the last pf_resample_across_blocks that fired (gpf.h gpf_block_ancestors)"""
+    out = np.zeros(max(getattr(state, "_n_across_blocks", 0), 1), np.int64)
+    state._check(state._L.gpf_block_ancestors(state._h, out.ctypes.data_as(C.POINTER(C.c_int64))))
+    return out[:getattr(state, "_n_across_blocks", 0)]
 
 
 def pf_initialize_blocks(model: NativeModel, model_args: tuple, observations, n_particles: int, block_size: int, *, seed: int = 1,

@@ -207,6 +207,13 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     // bp_size > 0: the rows are in force for blocks of this (clamped) size -- the block-wise steps run their BP kernels, everything that would
     // read cfg.params is refused (bp_refused)
     double* blk_params = nullptr; int64_t blk_params_cap = 0, bp_size = 0;
+    // gpf_resample_across_blocks: the planner filter of n_blocks particles whose log-weights are the blocks' log-ML estimates (its ancestors name the
+    // source block of every block; it runs on this filter's stream), the second buffers the per-block rows are gathered into (swapped with
+    // blk_params / blk_obs), and the 1-based block ancestors of the last call that fired with the buffers they refer to (gpf_block_ancestors)
+    gpf_filter* xb_planner = nullptr;
+    double* blk_params_alt = nullptr; int64_t blk_params_alt_cap = 0;
+    double* blk_obs_alt = nullptr; int64_t blk_obs_alt_cap = 0;
+    std::vector<int64_t> xb_anc; uint64_t xb_anc_gen = 0; int64_t xb_anc_n = 0;
     // the pull plan (gpf_comm_set_plan): request lists [G][n], their counters, the dense / gathered request matrix and its pinned mirror
     int shard_plan_kind = 0;
     ulonglong2* pull_req = nullptr; int64_t pull_req_cap = 0;

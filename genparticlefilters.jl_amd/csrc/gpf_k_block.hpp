@@ -501,6 +501,96 @@ __global__ __launch_bounds__(BLOCK) void k_block_proportion(const double* __rest
     }
 }
 
+// ----------------------------------------------------------------------------- resampling ACROSS blocks: the block-granular gather
+// gpf_resample_across_blocks (gpf.h): every block is one "super-particle" with the log-weight L[b] = log_ml_estimate(state[b]); a planner filter
+// of nblocks particles resampled them (the reference's resampler, src/resample.jl:19-175, one level up) and left the source block A[b] of every
+// destination block on the device.  This kernel copies whole filters: destination particle p = b nb + i takes the row, the log-weight and the
+// per-block rows of particle A[b] nb + i,
+//     lw'[p] = lw[A[b] nb + i] + delta_a,  delta_a = M - L[a]  (0 where L[a] = -Inf),  parents'[p] = A[b] nb + i + 1,
+// so the weights INSIDE a block are kept (its inner filter carries on) and only its total mass becomes the average mass M.
+// A block's rows are one contiguous, 16-byte aligned run of nb W doubles: the copy is a stream of 16-byte pieces with a block-granular source
+// offset.  The grid is sized by BYTES, not by blocks -- one workgroup per chunk of BG_PIECES pieces of the destination (16 KB of rows, and
+// the log-weights and parents of the same particles), grid-striding beyond the launch's workgroups -- so 10^4 blocks of 100 particles and 8
+// blocks of 10^5 fill the machine alike, and there is no LDS limit on nb.  A lane issues all its loads before its stores.  The per-block
+// parameter and observation rows (a few hundred bytes per block) ride in the same launch.  Traffic: 2 (8 W + 16) n bytes incl. the ancestor words.
+constexpr int BG_PIECES = 1024;                    // 16-byte pieces of rows per chunk
+struct BlockGatherArgs {
+    const double* rows_in; double* rows_out;       // the ping-pong row buffers
+    const double* lw_in; double* lw_out;           // log-weights: read at the source, written to a second array (the host swaps them)
+    int32_t* anc_out;                              // state.parents (0-based here)
+    const int32_t* A;                              // [nblocks] source block of every destination block (the planner's ancestors)
+    const double* L;                               // [nblocks] block log-weights
+    double M;                                      // log_ml_estimate(planner) = logsumexp(L) - log(nblocks)
+    const double* par_in; double* par_out;         // [nblocks][MAX_PARAMS] or null
+    const double* obs_in; double* obs_out;         // [nblocks][MAX_OBS] or null
+    int64_t n; int32_t nb, nblocks;
+};
+template <int W>
+__global__ __launch_bounds__(BLOCK) void k_block_gather(BlockGatherArgs a)
+{
+    constexpr int PW = W / 2;                      // pieces per row
+    constexpr int CP = BG_PIECES / PW;             // particles per chunk
+    constexpr int PER = BG_PIECES / BLOCK;         // pieces per lane and chunk
+    constexpr int PPER = CP / BLOCK;               // particles per lane and chunk
+    static_assert(CP % BLOCK == 0 && PPER >= 1, "a chunk is a whole number of particles per lane");
+    const uint32_t nb = (uint32_t)a.nb;
+    const int32_t last = a.nblocks - 1;
+    // (the planner's search clamps its ancestors to [0, nblocks); the clamp here costs nothing and keeps every read inside the buffers)
+    auto src_block = [&](uint32_t b) { const int32_t s = a.A[b]; return (uint32_t)(s < 0 ? 0 : (s > last ? last : s)); };
+    const int64_t gt = (int64_t)blockIdx.x * BLOCK + threadIdx.x, gs = (int64_t)gridDim.x * BLOCK;
+    if (a.par_in)
+        for (int64_t i = gt; i < (int64_t)a.nblocks * MAX_PARAMS; i += gs) {
+            const uint32_t b = (uint32_t)i / (uint32_t)MAX_PARAMS, k = (uint32_t)i - b * MAX_PARAMS;
+            a.par_out[i] = a.par_in[(size_t)src_block(b) * MAX_PARAMS + k];
+        }
+    if (a.obs_in)
+        for (int64_t i = gt; i < (int64_t)a.nblocks * MAX_OBS; i += gs) {
+            const uint32_t b = (uint32_t)i / (uint32_t)MAX_OBS, k = (uint32_t)i - b * MAX_OBS;
+            a.obs_out[i] = a.obs_in[(size_t)src_block(b) * MAX_OBS + k];
+        }
+    typedef double piece_t __attribute__((ext_vector_type(2)));      // (a native vector: an array of them stays in registers)
+    const piece_t* __restrict__ in2 = reinterpret_cast<const piece_t*>(a.rows_in);
+    piece_t* __restrict__ out2 = reinterpret_cast<piece_t*>(a.rows_out);
+    const int64_t nchunks = (a.n + CP - 1) / CP;
+    for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int64_t p0 = c * CP;
+        piece_t v[PER];
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const uint32_t e = (uint32_t)(k * BLOCK) + threadIdx.x;
+            const int64_t p = p0 + e / PW;
+            v[k] = piece_t{0.0, 0.0};
+            if (p < a.n) {
+                const uint32_t b = (uint32_t)p / nb, i = (uint32_t)p - b * nb;
+                v[k] = in2[((size_t)src_block(b) * nb + i) * PW + e % PW];
+            }
+        }
+        double w[PPER]; int32_t s[PPER];
+#pragma unroll
+        for (int k = 0; k < PPER; ++k) {
+            const int64_t p = p0 + k * BLOCK + threadIdx.x;
+            w[k] = 0.0; s[k] = 0;
+            if (p < a.n) {
+                const uint32_t b = (uint32_t)p / nb, i = (uint32_t)p - b * nb, sb = src_block(b);
+                const double Ls = a.L[sb];
+                const double delta = Ls == -__builtin_huge_val() ? 0.0 : a.M - Ls;
+                s[k] = (int32_t)(sb * nb + i);
+                w[k] = a.lw_in[s[k]] + delta;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const uint32_t e = (uint32_t)(k * BLOCK) + threadIdx.x;
+            if (p0 + e / PW < a.n) out2[(size_t)p0 * PW + e] = v[k];
+        }
+#pragma unroll
+        for (int k = 0; k < PPER; ++k) {
+            const int64_t p = p0 + k * BLOCK + threadIdx.x;
+            if (p < a.n) { a.lw_out[p] = w[k]; a.anc_out[p] = s[k]; }
+        }
+    }
+}
+
 // the blocks' observation vectors from a pinned host buffer into device memory, by a KERNEL (coalesced reads over PCIe) rather than a
 // hipMemcpyAsync: the copy stays on the compute queue (an SDMA copy costs a cross-queue dependency of ~10-20 us in front of the step
 // kernel that reads it).  The last workgroup publishes `ticket` to pinned memory: the host may then refill that staging buffer.

@@ -208,6 +208,17 @@ gpf_status gpf_block_resampled(gpf_handle h, int32_t* out)
     for (int64_t i = 0; i < h->blk_last; ++i) out[i] &= 1;       // (the words also carry the blocks' validity flags)
     return GPF_OK;
 }
+// the ESS and the log-ML estimate of every block of <= BLK_MAX particles into blk_stats = [ess | lml] (device)
+static gpf_status launch_block_stats(gpf_filter* h, int64_t block_size, int64_t nblocks)
+{
+    gpf_status s = block_buffers(h, nblocks);
+    if (s) return s;
+    if (block_size <= 2 * WAVE)      GPF_LAUNCH((k_block_stats<WAVE, 2>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->lw, h->n, block_size, nblocks, &h->sc->lml_est, h->blk_stats, h->blk_stats + nblocks);
+    else if (block_size <= 8 * WAVE) GPF_LAUNCH((k_block_stats<WAVE, 8>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->lw, h->n, block_size, nblocks, &h->sc->lml_est, h->blk_stats, h->blk_stats + nblocks);
+    else                             GPF_LAUNCH((k_block_stats<BLOCK, 8>), dim3((unsigned)nblocks), dim3(BLOCK), 0, h->stream, h->lw, h->n, block_size, nblocks, &h->sc->lml_est, h->blk_stats, h->blk_stats + nblocks);
+    HIP_TRY(h, hipGetLastError());
+    return GPF_OK;
+}
 gpf_status gpf_block_stats(gpf_handle h, int64_t block_size, double* ess_out, double* lml_out)
 {
     gpf_status s = block_checks(h, block_size, "gpf_block_stats");
@@ -223,11 +234,7 @@ gpf_status gpf_block_stats(gpf_handle h, int64_t block_size, double* ess_out, do
         }
         return GPF_OK;
     }
-    if ((s = block_buffers(h, nblocks))) return s;
-    if (block_size <= 2 * WAVE)      GPF_LAUNCH((k_block_stats<WAVE, 2>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->lw, h->n, block_size, nblocks, &h->sc->lml_est, h->blk_stats, h->blk_stats + nblocks);
-    else if (block_size <= 8 * WAVE) GPF_LAUNCH((k_block_stats<WAVE, 8>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->lw, h->n, block_size, nblocks, &h->sc->lml_est, h->blk_stats, h->blk_stats + nblocks);
-    else                             GPF_LAUNCH((k_block_stats<BLOCK, 8>), dim3((unsigned)nblocks), dim3(BLOCK), 0, h->stream, h->lw, h->n, block_size, nblocks, &h->sc->lml_est, h->blk_stats, h->blk_stats + nblocks);
-    HIP_TRY(h, hipGetLastError());
+    if ((s = launch_block_stats(h, block_size, nblocks))) return s;
     if (ess_out) HIP_TRY(h, hipMemcpyAsync(ess_out, h->blk_stats, (size_t)nblocks * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (lml_out) HIP_TRY(h, hipMemcpyAsync(lml_out, h->blk_stats + nblocks, (size_t)nblocks * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -591,6 +598,155 @@ gpf_status gpf_set_block_params(gpf_handle h, const double* params, int32_t n_pa
     HIP_TRY(h, hipStreamSynchronize(h->stream));                 // (the host rows go out of scope)
     h->args.blk_params = h->blk_params;
     h->bp_size = block_size;
+    return GPF_OK;
+}
+// the per-block parameter rows as they stand (after gpf_resample_across_blocks: permuted by its block ancestors) -- gpf.h
+gpf_status gpf_get_block_params(gpf_handle h, double* out, int32_t n_params, int64_t n_blocks)
+{
+    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+    if (h->parent) return fail(h, GPF_ERR_STATE, "gpf_get_block_params on a sub-state view: call it on the filter");
+    if (h->bp_size < 1 || !h->blk_params) return fail(h, GPF_ERR_STATE, "gpf_get_block_params: no per-block parameters are set (gpf_set_block_params)");
+    const int64_t nblocks = (h->n + h->bp_size - 1) / h->bp_size;
+    if (!out || n_params < 1 || n_params > MAX_PARAMS || n_blocks != nblocks)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_get_block_params: need an output of [" + std::to_string(nblocks) + "][1 <= n_params <= " + std::to_string(MAX_PARAMS) + "] doubles");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    std::vector<double> rows((size_t)nblocks * MAX_PARAMS);
+    HIP_TRY(h, hipMemcpyAsync(rows.data(), h->blk_params, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int64_t b = 0; b < nblocks; ++b)
+        for (int i = 0; i < n_params; ++i) out[b * n_params + i] = rows[(size_t)b * MAX_PARAMS + i];
+    return GPF_OK;
+}
+
+// ------------------------------------------------------------------ resampling ACROSS blocks: the outer level of a nested filter (gpf.h)
+// the planner: a filter of n_blocks particles on this filter's stream -- same seed, gid0 = 0 -- that only ever sees log-weights
+static gpf_status across_planner(gpf_filter* h, int64_t nblocks)
+{
+    if (h->xb_planner && h->xb_planner->n == nblocks) return GPF_OK;
+    if (h->xb_planner) { gpf_destroy(h->xb_planner); h->xb_planner = nullptr; }
+    gpf_config c = h->cfg;
+    c.n_particles = nblocks; c.n_global = nblocks; c.gid0 = 0; c.keep_prev = 0; c.stream = (void*)h->stream; c.params = h->args.P;
+    gpf_handle p = nullptr;
+    gpf_status s = gpf_create(&c, &p);
+    if (s) return fail(h, s, std::string("planner of gpf_resample_across_blocks: ") + gpf_last_error(nullptr));
+    h->xb_planner = p;
+    if (p->chain_counted && p->cfg.device < 16) {                // the planner runs on its owner's stream, never beside it (as the planner of the
+        std::lock_guard<std::mutex> lk(g_chain[p->cfg.device].mu);   // sorted sharded resample): not one more filter for the gate of chained kernels
+        g_chain[p->cfg.device].live -= 1; p->chain_counted = false;
+    }
+    return GPF_OK;
+}
+// the second buffer of a per-block row array, at least as large as the first
+static gpf_status across_alt(gpf_filter* h, double*& alt, int64_t& alt_cap, int64_t cap, int width)
+{
+    if (alt_cap >= cap) return GPF_OK;
+    if (alt) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(alt); alt = nullptr; alt_cap = 0; }
+    HIP_TRY(h, hipMalloc(&alt, (size_t)cap * width * sizeof(double)));
+    alt_cap = cap;
+    return GPF_OK;
+}
+gpf_status gpf_resample_across_blocks(gpf_handle h, int32_t method, int64_t block_size, int32_t sort_particles, double ess_frac, int32_t check,
+                                      int32_t* invalid, int32_t* resampled, double* ess_out)
+{
+    // (what can be refused without touching the handle comes first)
+    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+    if (h->parent) return fail(h, GPF_ERR_STATE, "gpf_resample_across_blocks on a sub-state view: call it on the filter");
+    if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, "gpf_resample_across_blocks on a shard of a sharded filter");
+    if (h->hist_on) return fail(h, GPF_ERR_STATE, "gpf_resample_across_blocks on a filter with a trajectory store");
+    if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");
+    if (h->n % block_size != 0)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_resample_across_blocks: " + std::to_string(h->n) + " particles are no whole number of blocks of " +
+                    std::to_string(block_size) + " (blocks are copied whole: they must be congruent)");
+    if (h->bp_size > 0 && block_size != h->bp_size)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_resample_across_blocks: block_size " + std::to_string(block_size) + " differs from the " +
+                    std::to_string(h->bp_size) + " of the per-block parameters (gpf_set_block_params)");
+    if (h->blk_obs_size > 0 && block_size != h->blk_obs_size)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_resample_across_blocks: block_size " + std::to_string(block_size) + " differs from the " +
+                    std::to_string(h->blk_obs_size) + " of the per-block observations (gpf_update_blocks)");
+    if (method != GPF_RESAMPLE_MULTINOMIAL && method != GPF_RESAMPLE_RESIDUAL && method != GPF_RESAMPLE_STRATIFIED)
+        return fail(h, GPF_ERR_UNKNOWN_METHOD, "Resampling method not recognized.");          // resample.jl:28
+    if (h->W != 2 && h->W != 4 && h->W != 8) return fail(h, GPF_ERR_STATE, "row width");
+    gpf_status s = check_ready(h);
+    if (s || (s = materialize(h))) return s;
+    const int64_t nblocks = h->n / block_size;
+    // 1. L[b] = log_ml_estimate(state[b]): the double gpf_block_stats reports
+    std::vector<double> L((size_t)nblocks);
+    if (block_size > BLK_MAX) {
+        if ((s = gpf_block_stats(h, block_size, nullptr, L.data()))) return s;
+    } else {
+        if ((s = launch_block_stats(h, block_size, nblocks))) return s;
+        HIP_TRY(h, hipMemcpyAsync(L.data(), h->blk_stats + nblocks, (size_t)nblocks * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    if ((s = across_planner(h, nblocks))) return s;
+    gpf_filter* p = h->xb_planner;
+    if (block_size > BLK_MAX) HIP_TRY(h, hipMemcpyAsync(p->lw, L.data(), (size_t)nblocks * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    else HIP_TRY(h, hipMemcpyAsync(p->lw, h->blk_stats + nblocks, (size_t)nblocks * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(&p->sc->lml_est, 0, sizeof(double), h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    // 6. invalid weights: a NaN / +Inf estimate = a block with NaN / +Inf weights (refused whatever `check` says); all -Inf
+    bool bad = false, all_neginf = true;
+    for (double v : L) { if (v != v || v == __builtin_huge_val()) bad = true; if (v != -__builtin_huge_val()) all_neginf = false; }
+    if (invalid) *invalid = (bad || all_neginf) ? 1 : 0;
+    if (bad) return fail(h, GPF_ERR_INVALID_WEIGHTS, "Invalid weights (NaN).");
+    if (all_neginf && check == GPF_CHECK_TRUE) return fail(h, GPF_ERR_INVALID_WEIGHTS, "Invalid weights.");   // resample.jl:55
+    // 2. the planner at the call's epoch: ESS, M = logsumexp(L) - log(n_blocks)
+    const uint32_t E = h->epoch;
+    p->epoch = E; p->initialized = true;
+    p->pending_gather = false; p->pending_fill = false; p->pending_search = false;
+    p->max_valid = false; p->raw_valid = false; p->raw_sum_valid = false; p->raw_has_q = false; p->raw_q_folded = false;
+    mutated(p);
+    double ess = 0.0, M = 0.0;
+    if ((s = gpf_effective_sample_size(p, &ess)) || (s = gpf_log_ml_estimate(p, &M))) return fail(h, s, "planner: " + p->err);
+    if (ess_out) *ess_out = ess;
+    // 3. the gate (NaN ESS of all -Inf estimates: `<` is false, like the reference's)
+    const bool gated = ess_frac == ess_frac && ess_frac >= 0.0;
+    const bool go = !gated || ess < ess_frac * (double)nblocks;
+    if (resampled) *resampled = go ? 1 : 0;
+    if (go) {
+        s = gpf_resample(p, method, __builtin_nan(""), sort_particles, GPF_CHECK_FALSE, nullptr);   // (validity was decided above)
+        if (!s) s = finish_search(p);
+        p->pending_gather = false; p->pending_fill = false;      // (its ancestors are all this call wants: the planner has no rows worth gathering)
+        if (s) return fail(h, s, "planner: " + p->err);
+        const bool with_par = h->bp_size > 0, with_obs = h->blk_obs_size > 0;
+        if (with_par && (s = across_alt(h, h->blk_params_alt, h->blk_params_alt_cap, h->blk_params_cap, MAX_PARAMS))) return s;
+        if (with_obs && (s = across_alt(h, h->blk_obs_alt, h->blk_obs_alt_cap, h->blk_obs_cap, MAX_OBS))) return s;
+        // 4. whole blocks: rows, log-weights + (M - L[a]), parents, per-block rows -- one launch
+        BlockGatherArgs a{};
+        a.rows_in = h->rows[h->cur]; a.rows_out = h->rows[1 - h->cur]; a.lw_in = h->lw; a.lw_out = h->lws; a.anc_out = h->anc;
+        a.A = p->anc; a.L = p->lw; a.M = M;                      // (the planner's weights are untouched by its resample: its gather stays undone)
+        a.par_in = with_par ? h->blk_params : nullptr; a.par_out = with_par ? h->blk_params_alt : nullptr;
+        a.obs_in = with_obs ? h->blk_obs : nullptr; a.obs_out = with_obs ? h->blk_obs_alt : nullptr;
+        a.n = h->n; a.nb = (int32_t)block_size; a.nblocks = (int32_t)nblocks;
+        const int64_t chunks = (h->n * (h->W / 2) + BG_PIECES - 1) / BG_PIECES;
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(chunks, MAX_PARTIALS));
+        s = timed(h, GPF_K_GATHER, [&] { DISPATCH_W(h, GPF_LAUNCH((k_block_gather<WW>), dim3(grid), dim3(BLOCK), 0, h->stream, a)); });
+        if (s) return s;
+        HIP_TRY(h, hipGetLastError());
+        std::vector<int32_t> A((size_t)nblocks);
+        HIP_TRY(h, hipMemcpyAsync(A.data(), p->anc, (size_t)nblocks * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        h->xb_anc.resize((size_t)nblocks);
+        for (int64_t b = 0; b < nblocks; ++b) h->xb_anc[(size_t)b] = (int64_t)A[(size_t)b] + 1;
+        h->xb_anc_gen = h->generation; h->xb_anc_n = h->n;
+        h->cur ^= 1;                                             // update_refs! (utils.jl:10-15)
+        std::swap(h->lw, h->lws);
+        if (with_par) { std::swap(h->blk_params, h->blk_params_alt); std::swap(h->blk_params_cap, h->blk_params_alt_cap); h->args.blk_params = h->blk_params; }
+        if (with_obs) { std::swap(h->blk_obs, h->blk_obs_alt); std::swap(h->blk_obs_cap, h->blk_obs_alt_cap); h->args.blk_obs = h->blk_obs; }
+        h->raw_valid = false; h->raw_sum_valid = false; h->raw_has_q = false; h->raw_q_folded = false; h->max_valid = false;
+        h->blk_last = 0;                                         // only_resampled refers to a gpf_resample_blocks of the CURRENT block layout
+        mutated(h);
+    }
+    // 5. one epoch per accepted call, fired or not (as gpf_resample_blocks)
+    h->epoch = E + 1;
+    return GPF_OK;
+}
+gpf_status gpf_block_ancestors(gpf_handle h, int64_t* out)
+{
+    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+    if (!out) return fail(h, GPF_ERR_INVALID_ARGUMENT, "null out");
+    if (h->xb_anc.empty() || h->xb_anc_gen != h->generation || h->xb_anc_n != h->n)
+        return fail(h, GPF_ERR_STATE, "gpf_block_ancestors needs a gpf_resample_across_blocks that resampled first (and no resize since)");
+    std::copy(h->xb_anc.begin(), h->xb_anc.end(), out);
     return GPF_OK;
 }
 

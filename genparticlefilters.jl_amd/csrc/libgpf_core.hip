@@ -521,6 +521,8 @@ gpf_status gpf_destroy(gpf_handle h)
     }
     h->pending_packed = false;                                   // the filter goes away: nothing to scatter a deferred commit into
     if (h->planner) { gpf_destroy(h->planner); h->planner = nullptr; }
+    if (h->xb_planner) { gpf_destroy(h->xb_planner); h->xb_planner = nullptr; }
+    for (void* q : {(void*)h->blk_params_alt, (void*)h->blk_obs_alt}) if (q) (void)hipFree(q);
     for (void* q : {(void*)h->sorted_src, (void*)h->sorted_gath, (void*)h->anc_cursors}) if (q) (void)hipFree(q);
     { const std::vector<gpf_filter*> own = h->blk_views; h->blk_views.clear(); for (gpf_filter* v : own) gpf_destroy(v); }
     // view handles the host still holds outlive this filter as orphans: every later call on them fails ("stale view"), their own gpf_destroy frees

@@ -244,6 +244,45 @@ gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, 
  * Not on views, shards of a sharded filter or filters with a trajectory store (GPF_ERR_STATE); a NULL handle, n_params outside 1..24 or
  * block_size < 1 return GPF_ERR_INVALID_ARGUMENT and change nothing. */
 gpf_status gpf_set_block_params(gpf_handle h, const double* params, int32_t n_params, int64_t block_size);
+/* the per-block parameter rows as they stand: out = HOST [n_blocks][n_params] doubles, the first n_params entries of every row (n_blocks must be
+ * the rows' block count).  After gpf_resample_across_blocks the rows are permuted by its block ancestors; a checkpoint does not hold them, so
+ * this getter (or gpf_block_ancestors) is how a caller keeps track of them.  GPF_ERR_STATE when none are set. */
+gpf_status gpf_get_block_params(gpf_handle h, double* out, int32_t n_params, int64_t n_blocks);
+
+/* Resampling ACROSS blocks -- the outer level of SMC^2, a nested or an island particle filter: every block is one "super-particle" whose weight is
+ * its likelihood estimate, blocks are resampled and whole filters are copied.  It is the reference's resampler (src/resample.jl:19-175) applied one
+ * level up, to B = n / block_size consecutive, congruent blocks:
+ *   1. L[b] = log_ml_estimate(state[b]) = log_ml_est + logsumexp(block b) - log(block_size): exactly the double gpf_block_stats reports.
+ *   2. the planner: a filter of B particles with the handle's seed, gid0 = 0, log_ml_est = 0, log-weights L and the handle's RNG epoch E at the call.
+ *        ess = effective_sample_size(planner)   (-> *ess_out),      M = log_ml_estimate(planner) = logsumexp(L) - log B,
+ *        A[0..B) = the ancestors gpf_resample(planner, method, NaN, sort_particles) yields: bit-identical to a stand-alone filter of B particles.
+ *      method: GPF_RESAMPLE_MULTINOMIAL | _RESIDUAL | _STRATIFIED (else GPF_ERR_UNKNOWN_METHOD).
+ *   3. ess_frac >= 0: resample only if ess < ess_frac x B (decided on the host: the caller needs the verdict to jitter its parameters);
+ *      ess_frac < 0 or NaN: always.  *resampled = 1 / 0.  A call whose gate does not fire changes nothing but the epoch.
+ *   4. when it fires, the new block b is a complete copy of the old block a = A[b], for i < block_size:
+ *        rows'[b bs + i] = rows[a bs + i] (the full row, keep_prev columns included),       parents'[b bs + i] = a bs + i + 1,
+ *        lw'[b bs + i]   = lw[a bs + i] + delta_a,   delta_a = M - L[a] in double (0 where L[a] = -Inf),
+ *      the per-block parameter rows (gpf_set_block_params) and, after a block-wise update, the per-block observations: row b' = old row A[b].
+ *      Every block's gpf_block_stats estimate then equals M up to rounding; log_ml_est is untouched (the sub-state rule, src/resample.jl:185-187,
+ *      205-218, one level up).
+ *      DEVIATION from pf_resample! on a sub-state: the weights INSIDE a block are not reset -- its inner filter carries on, only its total
+ *      mass becomes the average mass.
+ *   5. the RNG epoch advances once per accepted call, fired or not (as gpf_resample_blocks).  A call that fired invalidates the "resampled last"
+ *      mask of gpf_resample_blocks (gpf_rejuvenate_blocks(only_resampled) then fails) and the cached weight summaries, also those of views.  A
+ *      deferred gather or lazy move is materialised first.
+ *   6. a NaN or +Inf L[b] (a block with NaN / +Inf weights): GPF_ERR_INVALID_WEIGHTS, state and epoch untouched, *invalid = 1, whatever `check`
+ *      says.  All L = -Inf: with GPF_CHECK_TRUE the same refusal; else safe_softmax's uniform fallback as in gpf_resample (ancestors from
+ *      uniform block weights, every delta = 0, *invalid = 1; its ESS is NaN, so a gated call does not fire).
+ * Refused without changing anything: n not a multiple of block_size, block_size < 1, a block_size other than that of the per-block parameters or
+ * of the per-block observations (GPF_ERR_INVALID_ARGUMENT); views, shards of a sharded filter, filters with a trajectory store (GPF_ERR_STATE).
+ * B = 1 is legal: A = [0], delta = 0, the state comes back bit for bit.  Blocks of any size (no LDS limit); beyond 2048 particles per block L comes
+ * from gpf_block_stats's loop over view handles.  Not here: priorities / tempering at block level, sharded filters, parameter jitter (host:
+ * theta = theta[A], perturb, gpf_set_block_params).  invalid / resampled / ess_out may be NULL. */
+gpf_status gpf_resample_across_blocks(gpf_handle h, int32_t method, int64_t block_size, int32_t sort_particles, double ess_frac, int32_t check,
+                                      int32_t* invalid, int32_t* resampled, double* ess_out);
+/* the 1-based block ancestors A of the last gpf_resample_across_blocks that fired: out = HOST int64[B].  GPF_ERR_STATE before any such call and
+ * after a resize or a re-initialisation. */
+gpf_status gpf_block_ancestors(gpf_handle h, int64_t* out);
 
 /* same, with log_priorities = priority_fn.(log_weights) evaluated by the caller (any closure):
  * log_priorities is a HOST array of n_particles doubles. */

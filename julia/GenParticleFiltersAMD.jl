@@ -311,6 +311,33 @@ end
 function set_block_params!(s::DeviceParticleFilterState, ::Nothing, block_size::Int=0)
     _status(s, ccall((:gpf_set_block_params, libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Int64), s.handle, C_NULL, 0, block_size)); s
 end
+"the per-block parameters as they stand, a (n_params, n_blocks) Matrix (gpf.h gpf_get_block_params): after pf_resample_across_blocks! permuted by its ancestors"
+function get_block_params(s::DeviceParticleFilterState, block_size::Int)
+    out = Matrix{Float64}(undef, length(s.model.params), cld(s.n_particles, min(block_size, s.n_particles)))
+    _status(s, ccall((:gpf_get_block_params, libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Int64), s.handle, out, size(out, 1), size(out, 2)))
+    return out
+end
+# Resampling ACROSS blocks -- the outer level of SMC^2, a nested or an island filter (gpf.h gpf_resample_across_blocks): every block is one
+# super-particle with the log-weight log_ml_estimate(state[b]); the blocks are resampled by the reference's resampler (src/resample.jl:19-175) on
+# those weights and whole filters are copied -- rows, parents, per-block parameters and observations, log-weights + (M - L[a]).  Returns the
+# 1-based block ancestors A (theta = theta[A]), or nothing when the ESS gate did not fire.
+function pf_resample_across_blocks!(s::DeviceParticleFilterState, block_size::Int, method::Symbol=:multinomial;
+                                    ess_frac=nothing, sort_particles::Bool=true, check=:warn)
+    m = method == :multinomial ? 0 : method == :residual ? 1 : method == :stratified ? 2 : error("Resampling method $method not recognized.")
+    chk = check === true ? 2 : (check === :warn ? 1 : 0)
+    invalid = Ref{Cint}(0); resampled = Ref{Cint}(0); ess = Ref{Cdouble}(0.0)
+    st = ccall((:gpf_resample_across_blocks, libgpf), Cint, (Ptr{Cvoid}, Cint, Int64, Cint, Cdouble, Cint, Ptr{Cint}, Ptr{Cint}, Ptr{Cdouble}),
+               s.handle, m, block_size, sort_particles ? 1 : 0, ess_frac === nothing ? NaN : Float64(ess_frac), chk, invalid, resampled, ess)
+    _status(s, st)
+    check === :warn && invalid[] != 0 && @warn("Invalid block weights (all -Inf): blocks resampled with uniform weights.")
+    return resampled[] != 0 ? block_ancestors(s, block_size) : nothing
+end
+"the 1-based block ancestors of the last pf_resample_across_blocks! that fired"
+function block_ancestors(s::DeviceParticleFilterState, block_size::Int)
+    out = Vector{Int64}(undef, cld(s.n_particles, block_size))
+    _status(s, ccall((:gpf_block_ancestors, libgpf), Cint, (Ptr{Cvoid}, Ptr{Int64}), s.handle, out))
+    return out
+end
 "which blocks the last pf_resample_blocks! resampled"
 function block_resampled(s::DeviceParticleFilterState, block_size::Int)
     out = Vector{Cint}(undef, cld(s.n_particles, block_size))
