@@ -81,7 +81,7 @@ class DeviceParticleFilterState:
 
     def __init__(self, model: NativeModel, n_particles: int, seed: int = 1, keep_prev: bool = False,
                  device: int = 0, n_global: int | None = None, gid0: int = 0, stream: int | None = None,
-                 history: int = 0):
+                 history: int = 0, history_blocks: bool = False):
         self._L = _lib.load()
         self.model, self.n_particles, self.seed = model, int(n_particles), int(seed)
         self.keep_prev = bool(keep_prev)
@@ -101,8 +101,10 @@ class DeviceParticleFilterState:
         d, w = C.c_int32(), C.c_int32()
         self._L.gpf_state_dim(self._h, C.byref(d), C.byref(w))
         self.dim, self.row_width = d.value, w.value
-        if history:                      # trajectory store for `history` time steps (persistent-trace queries)
-            self._check(self._L.gpf_history_enable(self._h, int(history)))
+        self.history_blocks = bool(history and history_blocks)
+        if history:                      # trajectory store for `history` time steps (persistent-trace queries); history_blocks: the block-wise
+            enable = self._L.gpf_history_enable_blocks if history_blocks else self._L.gpf_history_enable   # calls feed it too (gpf.h)
+            self._check(enable(self._h, int(history)))
 
     # -- state[idxs] / view(state, idxs): a sub-state over a range start:step:stop or over ANY vector of distinct indices
     #    (src/view.jl:35-48 takes `idxs::AbstractVector`; the reference's tests use contiguous and strided ranges, state[1:50],
@@ -593,12 +595,14 @@ def block_ancestors(state) -> np.ndarray:
 
 
 def pf_initialize_blocks(model: NativeModel, model_args: tuple, observations, n_particles: int, block_size: int, *, seed: int = 1,
-                         keep_prev: bool = False, device: int = 0, strata=None, layout: str = "contiguous", params=None):
+                         keep_prev: bool = False, device: int = 0, strata=None, layout: str = "contiguous", params=None, history: int = 0):
     """many small filters in one state, each with its own data: block b (block_size consecutive particles) is initialised with
     observations[b] -- the batched form of per-view initialisation (gpf.h gpf_initialize_blocks).  strata: every block is initialised
     stratified by itself (src/initialize.jl:92-109 per sub-state, gpf.h gpf_initialize_blocks_strata), the same strata for all blocks.
-    params: per-block model parameters (set_block_params) in force from this call on; `model` gives the model kind and the rows' length"""
-    state = DeviceParticleFilterState(model, n_particles, seed=seed, keep_prev=keep_prev, device=device)
+    params: per-block model parameters (set_block_params) in force from this call on; `model` gives the model kind and the rows' length.
+    history = T: the block-wise trajectory store for T time steps (gpf.h gpf_history_enable_blocks) -- past-step addresses (t, column) in
+    block_mean / block_var / block_proportionmap, block_moments(..., step=t), and everything the whole-filter store answers"""
+    state = DeviceParticleFilterState(model, n_particles, seed=seed, keep_prev=keep_prev, device=device, history=history, history_blocks=bool(history))
     obs = _block_obs(state, observations, block_size)
     if params is not None:
         set_block_params(state, params, block_size)
@@ -661,64 +665,84 @@ def block_stats(state, block_size: int):
     return ess, lml
 
 
-def _block_column(addr, who: str):
+def _block_column(state, addr, who: str):
+    """addr -> (step, column): step 0 = the current step; (t, column) = the past choice t => column, which needs the block-wise trajectory store"""
     if isinstance(addr, tuple):
-        raise ErrorException(f"{who}: a past-step address (t, column) needs a trajectory store, which block-wise states do not have")
-    return None if addr is None else int(addr)
+        if not getattr(state, "history_blocks", False):
+            raise ErrorException(f"{who}: a past-step address (t, column) needs a block-wise trajectory store (pf_initialize_blocks(..., history=T)), "
+                                 "which this state does not have")
+        if int(addr[0]) < 1:
+            raise ErrorException(f"{who}: the step of a past-step address is 1-based (step 1 = the initialisation); use a plain column for the current step")
+        return int(addr[0]), int(addr[1])
+    return 0, (None if addr is None else int(addr))
 
 
-def _block_moments(state, block_size: int, want_mean: bool, want_var: bool):
+def _block_moments(state, block_size: int, want_mean: bool, want_var: bool, step: int = 0):
     nb = (state.n_particles + int(block_size) - 1) // int(block_size)
-    mu = np.empty((nb, state.row_width)) if want_mean else None
-    s2 = np.empty((nb, state.row_width)) if want_var else None
-    state._check(state._L.gpf_block_moments(state._h, int(block_size), _pd(mu) if want_mean else None, _pd(s2) if want_var else None))
+    width = state.dim if step else state.row_width                 # (the store keeps the latent columns, not the row width)
+    mu = np.empty((nb, width)) if want_mean else None
+    s2 = np.empty((nb, width)) if want_var else None
+    if step:
+        state._check(state._L.gpf_block_history_moments(state._h, int(step), int(block_size), _pd(mu) if want_mean else None, _pd(s2) if want_var else None))
+    else:
+        state._check(state._L.gpf_block_moments(state._h, int(block_size), _pd(mu) if want_mean else None, _pd(s2) if want_var else None))
     return mu, s2
 
 
 def _block_pick(state, a: np.ndarray, col):
     if col is None:
         return a
-    if not 0 <= col < state.row_width:
+    if not 0 <= col < a.shape[1]:
         raise ErrorException("bad column")
     return np.ascontiguousarray(a[:, col])
 
 
-def block_moments(state, block_size: int):
+def block_moments(state, block_size: int, step: int | None = None):
     """([mean(state[b], c) for c in columns], [var(state[b], c) ...]) of every block, src/statistics.jl:13-14,48-50 on sub-states:
-    two [n_blocks, row_width] arrays from one launch, bit-identical to the loop over views.  A block with NaN / +Inf weights is NaN."""
+    two [n_blocks, row_width] arrays from one launch, bit-identical to the loop over views.  A block with NaN / +Inf weights is NaN.
+    step=t (1-based, step 1 = the initialisation): the past choices t => c of the block-wise trajectory store instead (gpf.h
+    gpf_block_history_moments): two [n_blocks, dim] arrays.  step=None is the current step; step < 1 raises."""
+    if step is not None:
+        _block_column(state, (step, 0), "block_moments")
+        return _block_moments(state, block_size, True, True, int(step))
     return _block_moments(state, block_size, True, True)
 
 
 def block_mean(state, block_size: int, addr=None) -> np.ndarray:
-    """mean(state[b], addr) of every block in one launch: [n_blocks] for a column, [n_blocks, row_width] for addr=None"""
-    col = _block_column(addr, "block_mean")
-    return _block_pick(state, _block_moments(state, block_size, True, False)[0], col)
+    """mean(state[b], addr) of every block in one launch: [n_blocks] for a column or a past-step address (t, column), [n_blocks, row_width]
+    for addr=None"""
+    step, col = _block_column(state, addr, "block_mean")
+    return _block_pick(state, _block_moments(state, block_size, True, False, step)[0], col)
 
 
 def block_var(state, block_size: int, addr=None) -> np.ndarray:
-    """var(state[b], addr) (population form) of every block in one launch: [n_blocks] for a column, [n_blocks, row_width] for addr=None"""
-    col = _block_column(addr, "block_var")
-    return _block_pick(state, _block_moments(state, block_size, False, True)[1], col)
+    """var(state[b], addr) (population form) of every block in one launch: [n_blocks] for a column or a past-step address (t, column),
+    [n_blocks, row_width] for addr=None"""
+    step, col = _block_column(state, addr, "block_var")
+    return _block_pick(state, _block_moments(state, block_size, False, True, step)[1], col)
 
 
 def block_proportionmap(state, block_size: int, addr, max_values: int = 256):
     """proportionmap(state[b], addr) of every block, src/statistics.jl:91-101 on sub-states: (values, proportions[n_blocks, n_values]).
     The distinct values are read from the column over all blocks (a value a block does not hold has proportion 0.0 there); each
-    launch answers 16 values for all blocks."""
-    col = _block_column(addr, "block_proportionmap")
+    launch answers 16 values for all blocks.  addr = (t, column): the past choice t => column (block-wise trajectory store)."""
+    step, col = _block_column(state, addr, "block_proportionmap")
     if col is None:
         raise ErrorException("block_proportionmap: give a column")
     nb = (state.n_particles + int(block_size) - 1) // int(block_size)
-    if not 0 <= col < state.row_width:
+    if not 0 <= col < (state.dim if step else state.row_width):
         raise ErrorException("bad column")
-    vals = np.unique(state.column(col))
+    vals = np.unique(state.history_column(step, col) if step else state.column(col))
     if vals.size > max_values:
         raise ErrorException(f"proportionmap: {vals.size} distinct values; the column does not look discrete")
     out = np.empty((nb, vals.size))
     for k0 in range(0, vals.size, 16):
         chunk = np.ascontiguousarray(vals[k0:k0 + 16], np.float64)
         part = np.empty((nb, chunk.size))
-        state._check(state._L.gpf_block_proportion(state._h, int(block_size), col, _pd(chunk), int(chunk.size), _pd(part)))
+        if step:
+            state._check(state._L.gpf_block_history_proportion(state._h, step, int(block_size), col, _pd(chunk), int(chunk.size), _pd(part)))
+        else:
+            state._check(state._L.gpf_block_proportion(state._h, int(block_size), col, _pd(chunk), int(chunk.size), _pd(part)))
         out[:, k0:k0 + chunk.size] = part
     return vals, out
 

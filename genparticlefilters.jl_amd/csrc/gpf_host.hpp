@@ -129,6 +129,7 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     // trajectory store (gpf_history_enable): per recorded step the d latent columns in the step's final particle
     // order, and the composed ancestor map of the resamples that happened during that step (nullptr = identity)
     bool hist_on = false;
+    bool hist_blocks = false;            // gpf_history_enable_blocks: the block-wise calls feed the store too (the plain store refuses them)
     int hist_cap = 0;
     std::vector<double*> hist_x;         // [step] n*d doubles (nullptr until snapshotted)
     std::vector<int32_t*> hist_map;      // [step] n int32 or nullptr
@@ -493,7 +494,7 @@ gpf_status materialize(gpf_filter* h);
 gpf_status finish_move(gpf_filter* h);
 void hist_clear(gpf_filter* h);
 gpf_status hist_snapshot(gpf_filter* h);
-gpf_status hist_on_resample(gpf_filter* h);
+gpf_status hist_on_resample(gpf_filter* h, int64_t block_size = 0);
 gpf_status hist_begin_step(gpf_filter* h, bool first);
 void mutated(gpf_filter* h);
 gpf_status after_initialize(gpf_filter* h, int grid);

@@ -501,6 +501,127 @@ __global__ __launch_bounds__(BLOCK) void k_block_proportion(const double* __rest
     }
 }
 
+// ----------------------------------------------------------------------------- per-block estimates of a PAST choice: the trajectory store, block by block
+// for b in blocks; mean(state[b], t => addr); var(state[b], t => addr); proportionmap(state[b], t => addr); end -- a Gen trace is persistent and a
+// sub-state is a slice of the traces (statistics.jl:13-14, 48-50, 91-101 with a past address on ParticleFilterSubStates, view.jl:35-48).  ONE launch
+// for all blocks and all d latent columns of the store (gpf_history_enable_blocks).  A lane first resolves, for each of its ITEMS particles, the
+// particle of step t it descends from: the composed ancestor maps of the steps T, T-1, ..., t+1 in that order (k_hist_column; maps = nullptr entries
+// are steps without a resample, n_maps = 0 reads the step's own snapshot), then reads that particle's columns of the step's snapshot hx = [n][D].
+// The ancestor may sit in any block (gpf_resample_across_blocks copies whole blocks).  Weights, order of the sums and the NaN rule are those of
+// k_block_moments / k_block_proportion -- the same device functions -- so a block's values are bit-identical to those calls on a filter whose rows
+// hold the past values.  D may be 1: the snapshot is read by single words.
+template <int ITEMS>
+__device__ __forceinline__ void block_hist_index(const int32_t* const* __restrict__ maps, int n_maps, int64_t b0, int cnt, int tl, int64_t (&idx)[ITEMS])
+{
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) idx[k] = b0 + (ITEMS * tl + k < cnt ? ITEMS * tl + k : 0);        // (beyond the block: the block's first particle, never read)
+    for (int s = 0; s < n_maps; ++s) {
+        const int32_t* __restrict__ m = maps[s];
+        if (!m) continue;                                          // (kernel-uniform)
+#pragma unroll
+        for (int k = 0; k < ITEMS; ++k) idx[k] = m[idx[k]];
+    }
+}
+// mean_out / var_out: [nblocks][D]; a block with NaN / +Inf weights gets NaN everywhere.  want_var = 0: var_out is not touched
+template <int D, int TEAM, int ITEMS>
+__global__ __launch_bounds__(BLOCK) void k_block_hist_moments(const int32_t* const* __restrict__ maps, int n_maps, const double* __restrict__ hx,
+                                                              const double* __restrict__ lw, int64_t n, int64_t nb, int64_t nblocks, int want_var,
+                                                              double* __restrict__ mean_out, double* __restrict__ var_out)
+{
+    constexpr int TEAMS = BLOCK / TEAM;
+    static_assert(TEAM == WAVE || TEAM == BLOCK, "a wave or the workgroup");
+    static_assert(D == 1 || D % 2 == 0, "the latent columns go through the tree two at a time");
+    __shared__ double s_m[NWAVES];
+    __shared__ int s_f[NWAVES];
+    __shared__ uint64_t s_x[NWAVES][4];
+    __shared__ double s_t[NWAVES][2];
+    const int tm = (int)threadIdx.x / TEAM, tl = (int)threadIdx.x % TEAM;
+    const int64_t blk = (int64_t)blockIdx.x * TEAMS + tm;
+    if (TEAM != BLOCK && blk >= nblocks) return;                   // (an idle wave: the wave-team path has no workgroup barrier)
+    const int64_t b0 = blk * nb;
+    const int cnt = (int)(n - b0 < nb ? n - b0 : nb);
+    double w[ITEMS];
+    const int f = block_norm_weights<TEAM, ITEMS>(lw, b0, cnt, tl, s_m, s_f, s_x, w);
+    if (f & (FLAG_NAN | FLAG_POSINF)) {                            // (team-uniform)
+        for (int c = tl; c < D; c += TEAM) { mean_out[blk * D + c] = __builtin_nan(""); if (want_var) var_out[blk * D + c] = __builtin_nan(""); }
+        return;
+    }
+    int64_t idx[ITEMS];
+    block_hist_index<ITEMS>(maps, n_maps, b0, cnt, tl, idx);
+    constexpr bool PAIR = D > 1;                                   // (D = 1: the tree's second value only ever adds +0.0)
+#pragma unroll 1
+    for (int c = 0; c < D; c += 2) {
+        double x0[ITEMS], x1[ITEMS], t0[ITEMS], t1[ITEMS];
+#pragma unroll
+        for (int k = 0; k < ITEMS; ++k) {
+            const bool in = ITEMS * tl + k < cnt;
+            x0[k] = in ? hx[idx[k] * D + c] : 0.0;
+            x1[k] = in && PAIR ? hx[idx[k] * D + c + (PAIR ? 1 : 0)] : 0.0;
+            t0[k] = in ? w[k] * x0[k] : 0.0;
+            t1[k] = in ? w[k] * x1[k] : 0.0;
+        }
+        double mu[2] = {lane_tree<ITEMS>(t0), lane_tree<ITEMS>(t1)};
+        team_tree2<TEAM>(mu, s_t);
+        if (tl == 0) { mean_out[blk * D + c] = mu[0]; if (PAIR) mean_out[blk * D + c + 1] = mu[1]; }
+        if (want_var) {                                            // (grid-uniform)
+#pragma unroll
+            for (int k = 0; k < ITEMS; ++k) {
+                const bool in = ITEMS * tl + k < cnt;
+                double d0 = x0[k] - mu[0], d1 = x1[k] - mu[1];
+                d0 = d0 * d0; d1 = d1 * d1;
+                t0[k] = in ? w[k] * d0 : 0.0;
+                t1[k] = in ? w[k] * d1 : 0.0;
+            }
+            double s2[2] = {lane_tree<ITEMS>(t0), lane_tree<ITEMS>(t1)};
+            team_tree2<TEAM>(s2, s_t);
+            if (tl == 0) { var_out[blk * D + c] = s2[0]; if (PAIR) var_out[blk * D + c + 1] = s2[1]; }
+        }
+    }
+}
+// out[blk][j] = sum of the normalised weights of block blk's particles whose past choice (column col of the snapshot hx = [n][d]) equals v[j]
+template <int TEAM, int ITEMS>
+__global__ __launch_bounds__(BLOCK) void k_block_hist_proportion(const int32_t* const* __restrict__ maps, int n_maps, const double* __restrict__ hx, int d, int col,
+                                                                 const double* __restrict__ lw, int64_t n, int64_t nb, int64_t nblocks, BlockMatch mv,
+                                                                 double* __restrict__ out)
+{
+    constexpr int TEAMS = BLOCK / TEAM;
+    static_assert(TEAM == WAVE || TEAM == BLOCK, "a wave or the workgroup");
+    __shared__ double s_m[NWAVES];
+    __shared__ int s_f[NWAVES];
+    __shared__ uint64_t s_x[NWAVES][4];
+    __shared__ double s_t[NWAVES][2];
+    const int tm = (int)threadIdx.x / TEAM, tl = (int)threadIdx.x % TEAM;
+    const int64_t blk = (int64_t)blockIdx.x * TEAMS + tm;
+    if (TEAM != BLOCK && blk >= nblocks) return;
+    const int64_t b0 = blk * nb;
+    const int cnt = (int)(n - b0 < nb ? n - b0 : nb);
+    double w[ITEMS];
+    const int f = block_norm_weights<TEAM, ITEMS>(lw, b0, cnt, tl, s_m, s_f, s_x, w);
+    if (f & (FLAG_NAN | FLAG_POSINF)) {
+        for (int j = tl; j < mv.n; j += TEAM) out[blk * mv.n + j] = __builtin_nan("");
+        return;
+    }
+    int64_t idx[ITEMS];
+    block_hist_index<ITEMS>(maps, n_maps, b0, cnt, tl, idx);
+    double x[ITEMS];
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) x[k] = ITEMS * tl + k < cnt ? hx[idx[k] * d + col] : 0.0;
+#pragma unroll 1
+    for (int j = 0; j < mv.n; j += 2) {                            // two match values per pass (mv.v is padded to an even count)
+        const double a0 = mv.v[j], a1 = mv.v[j + 1];
+        double t0[ITEMS], t1[ITEMS];
+#pragma unroll
+        for (int k = 0; k < ITEMS; ++k) {
+            const bool in = ITEMS * tl + k < cnt;
+            t0[k] = in ? w[k] * (x[k] == a0 ? 1.0 : 0.0) : 0.0;
+            t1[k] = in ? w[k] * (x[k] == a1 ? 1.0 : 0.0) : 0.0;
+        }
+        double p[2] = {lane_tree<ITEMS>(t0), lane_tree<ITEMS>(t1)};
+        team_tree2<TEAM>(p, s_t);
+        if (tl == 0) { out[blk * mv.n + j] = p[0]; if (j + 1 < mv.n) out[blk * mv.n + j + 1] = p[1]; }
+    }
+}
+
 // ----------------------------------------------------------------------------- resampling ACROSS blocks: the block-granular gather
 // gpf_resample_across_blocks (gpf.h): every block is one "super-particle" with the log-weight L[b] = log_ml_estimate(state[b]); a planner filter
 // of nblocks particles resampled them (the reference's resampler, src/resample.jl:19-175, one level up) and left the source block A[b] of every

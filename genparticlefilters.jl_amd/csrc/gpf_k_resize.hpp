@@ -121,6 +121,21 @@ static __global__ void k_hist_compose(const int32_t* __restrict__ anc, const int
     for (int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x; j < n; j += (int64_t)gridDim.x * BLOCK)
         b_new[j] = b_old ? b_old[anc[j]] : anc[j];
 }
+// the same after gpf_resample_blocks (k_block_resample): in a block that resampled -- bit 0 of its mask word; bits 8.. carry validity flags -- anc is
+// LOCAL to the block (0-based); in a block that did not, the kernel returned early and anc is whatever an earlier call left: that block's
+// particles stayed where they were.  g[j] = resampled ? block start + anc[j] : j, then as k_hist_compose.  (The clamp keeps a read through b_old
+// inside the block whatever anc holds.)
+static __global__ void k_hist_compose_blocks(const int32_t* __restrict__ anc, const int32_t* __restrict__ mask, int64_t nb, const int32_t* __restrict__ b_old,
+                                             int64_t n, int32_t* __restrict__ b_new)
+{
+    for (int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x; j < n; j += (int64_t)gridDim.x * BLOCK) {
+        const int64_t blk = j / nb, b0 = blk * nb;
+        const int64_t cnt = n - b0 < nb ? n - b0 : nb;
+        int64_t g = j;
+        if (mask[blk] & 1) { const int64_t a = anc[j]; g = b0 + (a < 0 ? 0 : (a >= cnt ? cnt - 1 : a)); }
+        b_new[j] = b_old ? b_old[g] : (int32_t)g;
+    }
+}
 // value of column `col` of step `t` along the ancestry of every current particle: follow B_T, B_{T-1}, ..., B_{t+1}
 static __global__ void k_hist_column(const int32_t* const* __restrict__ maps, int n_maps, const double* __restrict__ hx, int d, int col,
                               int64_t n, double* __restrict__ out)

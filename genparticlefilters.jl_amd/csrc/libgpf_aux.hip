@@ -74,6 +74,17 @@ static gpf_status block_checks(gpf_handle h, int64_t block_size, const char* who
     if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");
     return GPF_OK;
 }
+// A filter with a trajectory store has no sub-state views, and blocks of more than BLK_MAX particles are the work of view handles (below): on a
+// filter with the block-wise store (gpf_history_enable_blocks) such a call is refused.  block_size comes back clamped to the particle count
+// ("one block" asked for as any size >= n is one block of n particles).
+static gpf_status block_store_size(gpf_filter* h, int64_t& block_size, const char* who)
+{
+    if (!h->hist_blocks) return GPF_OK;
+    block_size = std::min<int64_t>(block_size, std::max<int64_t>(h->n, 1));
+    if (block_size > BLK_MAX)
+        return fail(h, GPF_ERR_STATE, std::string(who) + ": blocks of more than " + std::to_string(BLK_MAX) + " particles on a filter with a trajectory store (they would need sub-state views)");
+    return GPF_OK;
+}
 // Blocks of more than BLK_MAX = 2048 particles do not fit the one-workgroup-per-block kernels (gpf_k_block.hpp keeps a block's weights, CDF
 // and order in LDS).  Their loop over sub-states (for b in blocks; pf_resample!(state[b], ...); end -- test/resample.jl:130-162 has no
 // size limit) runs on the host over view handles of the blocks, with the full-size kernels: the same results as the views give, the
@@ -156,7 +167,8 @@ gpf_status gpf_resample_blocks(gpf_handle h, int32_t method, int64_t block_size,
     if (s) return s;
     if (method != GPF_RESAMPLE_MULTINOMIAL && method != GPF_RESAMPLE_RESIDUAL && method != GPF_RESAMPLE_STRATIFIED)
         return fail(h, GPF_ERR_UNKNOWN_METHOD, "Resampling method not recognized.");          // resample.jl:28
-    if (h->hist_on) return fail(h, GPF_ERR_STATE, "gpf_resample_blocks on a filter with a trajectory store");
+    if (h->hist_on && !h->hist_blocks) return fail(h, GPF_ERR_STATE, "gpf_resample_blocks on a filter with a trajectory store");
+    if ((s = block_store_size(h, block_size, "gpf_resample_blocks"))) return s;
     if (h->W != 2 && h->W != 4 && h->W != 8) return fail(h, GPF_ERR_STATE, "row width");
     if ((s = materialize(h))) return s;
     if (block_size > BLK_MAX) return resample_big_blocks(h, method, block_size, priority_alpha, sort_particles, ess_frac, check, invalid, n_resampled);
@@ -184,6 +196,8 @@ gpf_status gpf_resample_blocks(gpf_handle h, int32_t method, int64_t block_size,
     h->raw_valid = false; h->raw_sum_valid = false; h->raw_has_q = false; h->raw_q_folded = false; h->max_valid = false;
     h->epoch += 1;
     mutated(h);
+    // (the block-wise store: this call's parents into the step's ancestor map -- behind the bookkeeping, so that a failure here leaves a consistent filter)
+    if ((s = hist_on_resample(h, block_size))) return s;
     if (check != GPF_CHECK_FALSE || invalid || n_resampled) {
         int32_t words[2] = {0, 0};
         GPF_LAUNCH(k_block_summary, dim3(1), dim3(BLOCK), 0, h->stream, h->blk_mask, nblocks, h->blk_words);
@@ -222,7 +236,7 @@ static gpf_status launch_block_stats(gpf_filter* h, int64_t block_size, int64_t 
 gpf_status gpf_block_stats(gpf_handle h, int64_t block_size, double* ess_out, double* lml_out)
 {
     gpf_status s = block_checks(h, block_size, "gpf_block_stats");
-    if (s) return s;
+    if (s || (s = block_store_size(h, block_size, "gpf_block_stats"))) return s;
     if ((s = materialize(h))) return s;
     const int64_t nblocks = (h->n + block_size - 1) / block_size;
     if (block_size > BLK_MAX) {                                  // the loop over sub-states (big_block_views)
@@ -261,16 +275,16 @@ static gpf_status block_est_buffer(gpf_filter* h, int64_t need)
     return GPF_OK;
 }
 // what the per-block estimates ask beyond block_checks: a filter that can have sub-state views, rows of column pairs
-static gpf_status block_est_checks(gpf_handle h, int64_t block_size, const char* who)
+static gpf_status block_est_checks(gpf_handle h, int64_t& block_size, const char* who)
 {
     // (what can be refused without touching the handle comes first: block_checks brings a lazy move or a view up to date)
     if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
     if (h->parent) return fail(h, GPF_ERR_STATE, std::string(who) + " on a sub-state view: call it on the filter");
     if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, std::string(who) + " on a shard of a sharded filter");
-    if (h->hist_on) return fail(h, GPF_ERR_STATE, std::string(who) + " on a filter with a trajectory store (it has no sub-state views)");
+    if (h->hist_on && !h->hist_blocks) return fail(h, GPF_ERR_STATE, std::string(who) + " on a filter with a trajectory store (it has no sub-state views)");
     if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");
-    gpf_status s = block_checks(h, block_size, who);
-    if (s) return s;
+    gpf_status s = block_store_size(h, block_size, who);
+    if (s || (s = block_checks(h, block_size, who))) return s;
     if (h->W != 2 && h->W != 4 && h->W != 8) return fail(h, GPF_ERR_STATE, "row width");
     return GPF_OK;
 }
@@ -417,7 +431,7 @@ static gpf_status block_step_checks(gpf_handle h, int64_t& block_size, const cha
     if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
     if (h->parent) return fail(h, GPF_ERR_STATE, std::string(who) + " on a sub-state view: call it on the filter");
     if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, std::string(who) + " on a shard of a sharded filter");
-    if (h->hist_on) return fail(h, GPF_ERR_STATE, std::string(who) + " on a filter with a trajectory store");
+    if (h->hist_on && !h->hist_blocks) return fail(h, GPF_ERR_STATE, std::string(who) + " on a filter with a trajectory store");
     if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");      // (the per-block steps index observations by i / block_size: any size)
     block_size = std::min<int64_t>(block_size, std::max<int64_t>(h->n, 1));
     if (h->bp_size > 0 && block_size != h->bp_size)
@@ -428,14 +442,21 @@ static gpf_status block_step_checks(gpf_handle h, int64_t& block_size, const cha
         return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model takes " + std::to_string(model_obs_dim(h->cfg.model)) + " observation values per step and block");
     return GPF_OK;
 }
-// The block-wise pf_initialize / pf_update! once the caller's checks have passed (a refused call changes nothing).  mode 0: the default proposal;
+// a block-wise update begins a step of the trajectory store: a full store refuses here, before strata, observations, rows or epoch change
+static gpf_status block_store_room(gpf_filter* h)
+{
+    if (h->hist_on && (int)h->hist_x.size() >= h->hist_cap)
+        return fail(h, GPF_ERR_STATE, "trajectory store full: raise max_steps of gpf_history_enable");
+    return GPF_OK;
+}
+// The block-wise pf_initialize / pf_update! once the caller's checks (the observations among them: hist_begin_step comes before set_block_obs) have passed (a refused call changes nothing).  mode 0: the default proposal;
 // 2: stratified (the caller set the strata); 4 (update): block b is extended with the native proposal where use_proposal[b] != 0.
 static gpf_status block_initialize_impl(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, int mode)
 {
     h->generation += 1;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    gpf_status s = set_block_obs(h, obs, n_obs, block_size);
-    if (s) return s;
+    gpf_status s = hist_begin_step(h, true);                     // (the block-wise store: step 1)
+    if (s || (s = set_block_obs(h, obs, n_obs, block_size))) return s;
     const int grid = step_grid(h);
     s = timed(h, GPF_K_STEP, [&] {
         bool_dispatch(h->bp_size > 0, [&](auto BP) {
@@ -450,7 +471,8 @@ static gpf_status block_initialize_impl(gpf_handle h, const double* obs, int32_t
 static gpf_status block_update_impl(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, int mode, const int32_t* use_proposal)
 {
     gpf_status s = materialize(h);                               // (no fused gather in the block-wise step)
-    if (s || (s = set_block_obs(h, obs, n_obs, block_size))) return s;
+    // (the block-wise store: the step that ends is snapshotted and the next one begins; the entry points have checked the observations and the store's room)
+    if (s || (s = hist_begin_step(h, false)) || (s = set_block_obs(h, obs, n_obs, block_size))) return s;
     if (mode == 4) {
         const int64_t nblocks = (h->n + block_size - 1) / block_size;
         if ((s = block_buffers(h, nblocks))) return s;           // (blk_mask doubles as the flag array: no block resample refers to it after this call)
@@ -475,13 +497,13 @@ static gpf_status block_update_impl(gpf_handle h, const double* obs, int32_t n_o
 }
 gpf_status gpf_initialize_blocks(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size)
 {
-    gpf_status s = block_step_checks(h, block_size, "gpf_initialize_blocks");
+    gpf_status s = block_step_checks(h, block_size, "gpf_initialize_blocks", obs, n_obs, true);   // (a refused call leaves the trajectory store alone too)
     return s ? s : block_initialize_impl(h, obs, n_obs, block_size, 0);
 }
 gpf_status gpf_update_blocks(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size)
 {
-    gpf_status s = block_step_checks(h, block_size, "gpf_update_blocks");
-    if (s || (s = check_ready(h))) return s;
+    gpf_status s = block_step_checks(h, block_size, "gpf_update_blocks", obs, n_obs, true);
+    if (s || (s = check_ready(h)) || (s = block_store_room(h))) return s;
     return block_update_impl(h, obs, n_obs, block_size, 0, nullptr);
 }
 // for b in blocks: pf_initialize(model, args, observations[b], strata, n_b) / pf_update!(state[b], ..., observations[b], strata) -- stratified
@@ -501,7 +523,7 @@ gpf_status gpf_initialize_blocks_strata(gpf_handle h, const double* obs, int32_t
 gpf_status gpf_update_blocks_strata(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, const double* values, int32_t n_strata, int32_t interleaved)
 {
     gpf_status s = block_step_checks(h, block_size, "gpf_update_blocks_strata", obs, n_obs, true);
-    if (s || (s = check_ready(h)) || (s = block_strata(h, values, n_strata, interleaved))) return s;
+    if (s || (s = check_ready(h)) || (s = block_store_room(h)) || (s = block_strata(h, values, n_strata, interleaved))) return s;
     return block_update_impl(h, obs, n_obs, block_size, 2, nullptr);
 }
 // for b in blocks: pf_update!(state[b], new_args, argdiffs, observations[b][, proposal, proposal_args]) -- the per-view updates with DIFFERENT
@@ -509,8 +531,8 @@ gpf_status gpf_update_blocks_strata(gpf_handle h, const double* obs, int32_t n_o
 // (src/update.jl:79-96), else with the default one (src/update.jl:12-25).  One epoch for all blocks, like gpf_update_blocks.
 gpf_status gpf_update_blocks_proposal(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, const int32_t* use_proposal, int32_t proposal)
 {
-    gpf_status s = block_step_checks(h, block_size, "gpf_update_blocks_proposal");
-    if (s || (s = check_ready(h))) return s;
+    gpf_status s = block_step_checks(h, block_size, "gpf_update_blocks_proposal", obs, n_obs, true);
+    if (s || (s = check_ready(h)) || (s = block_store_room(h))) return s;
     if (!use_proposal) return fail(h, GPF_ERR_INVALID_ARGUMENT, "null use_proposal");
     if (!proposal_valid(h, proposal) || !model_caps(h).proposal) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no such native proposal");
     return block_update_impl(h, obs, n_obs, block_size, 4, use_proposal);
@@ -574,7 +596,7 @@ gpf_status gpf_set_block_params(gpf_handle h, const double* params, int32_t n_pa
     if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
     if (h->parent) return fail(h, GPF_ERR_STATE, "gpf_set_block_params on a sub-state view: call it on the filter");
     if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, "gpf_set_block_params on a shard of a sharded filter");
-    if (h->hist_on) return fail(h, GPF_ERR_STATE, "gpf_set_block_params on a filter with a trajectory store");
+    if (h->hist_on && !h->hist_blocks) return fail(h, GPF_ERR_STATE, "gpf_set_block_params on a filter with a trajectory store");
     if (!params) {                                               // clear: the filter's own parameter vector again (the buffer stays for reuse)
         h->bp_size = 0; h->args.blk_params = nullptr;
         return GPF_OK;
@@ -652,8 +674,9 @@ gpf_status gpf_resample_across_blocks(gpf_handle h, int32_t method, int64_t bloc
     if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
     if (h->parent) return fail(h, GPF_ERR_STATE, "gpf_resample_across_blocks on a sub-state view: call it on the filter");
     if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, "gpf_resample_across_blocks on a shard of a sharded filter");
-    if (h->hist_on) return fail(h, GPF_ERR_STATE, "gpf_resample_across_blocks on a filter with a trajectory store");
+    if (h->hist_on && !h->hist_blocks) return fail(h, GPF_ERR_STATE, "gpf_resample_across_blocks on a filter with a trajectory store");
     if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");
+    { int64_t clamped = block_size; if (gpf_status bs = block_store_size(h, clamped, "gpf_resample_across_blocks")) return bs; }
     if (h->n % block_size != 0)
         return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_resample_across_blocks: " + std::to_string(h->n) + " particles are no whole number of blocks of " +
                     std::to_string(block_size) + " (blocks are copied whole: they must be congruent)");
@@ -738,7 +761,8 @@ gpf_status gpf_resample_across_blocks(gpf_handle h, int32_t method, int64_t bloc
     }
     // 5. one epoch per accepted call, fired or not (as gpf_resample_blocks)
     h->epoch = E + 1;
-    return GPF_OK;
+    // (the block-wise store: h->anc holds global ancestors after a call that fired, as after gpf_resample; one that did not composes nothing)
+    return go ? hist_on_resample(h) : GPF_OK;
 }
 gpf_status gpf_block_ancestors(gpf_handle h, int64_t* out)
 {
@@ -1232,9 +1256,18 @@ gpf_status gpf_history_enable(gpf_handle h, int32_t max_steps)
     if (max_steps < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "max_steps < 1");
     if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, "the trajectory store is not available for sharded filters");
     if (h->initialized) return fail(h, GPF_ERR_STATE, "enable the trajectory store before gpf_initialize");
-    h->hist_on = true; h->hist_cap = max_steps;
+    h->hist_on = true; h->hist_blocks = false; h->hist_cap = max_steps;
     if (h->hist_dev_maps) (void)hipFree(h->hist_dev_maps);
     HIP_TRY(h, hipMalloc(&h->hist_dev_maps, (size_t)max_steps * sizeof(int32_t*)));
+    return GPF_OK;
+}
+
+// the block-wise store: the same store, fed by the block-wise calls as well (gpf.h)
+gpf_status gpf_history_enable_blocks(gpf_handle h, int32_t max_steps)
+{
+    gpf_status s = gpf_history_enable(h, max_steps);
+    if (s) return s;
+    h->hist_blocks = true;
     return GPF_OK;
 }
 
@@ -1304,6 +1337,91 @@ gpf_status gpf_proportion(gpf_handle h, int32_t step, int32_t column, double val
     if ((s = ensure_raw(h))) return s;
     if ((s = weighted_tree_sum(h, h->dtmp, 1, 0, 3, nullptr, value, h->dscal))) return s;
     return copy_out(h, h->dscal, out, sizeof(double));
+}
+
+// ---- past choices per block (gpf.h gpf_block_history_moments / _proportion): the block-wise store queried block by block, one launch
+} // extern "C"
+namespace gpfh {
+// what both queries check once their own arguments have passed; block_size comes back clamped.  Then the current step is snapshotted and the maps of
+// the steps T, T-1, ..., step+1 go to h->hist_dev_maps (as history_values): *n_maps of them
+static gpf_status block_hist_prepare(gpf_handle h, int32_t step, int64_t& block_size, const char* who, int* n_maps)
+{
+    if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");
+    if (!h->hist_on || !h->hist_blocks)
+        return fail(h, GPF_ERR_STATE, std::string(who) + " needs the block-wise trajectory store (gpf_history_enable_blocks before gpf_initialize_blocks)");
+    gpf_status s = check_ready(h);
+    if (s) return s;
+    const int T = (int)h->hist_x.size();
+    if (step < 1 || step > T) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad step");
+    if ((s = block_store_size(h, block_size, who))) return s;
+    if (h->d != 1 && h->d != 2 && h->d != 4) return fail(h, GPF_ERR_STATE, "latent dimension");
+    if ((s = hist_snapshot(h))) return s;                         // the current step, in its current order
+    std::vector<const int32_t*> maps;
+    for (int q = T - 1; q >= step; --q) maps.push_back(h->hist_map[q]);
+    if (!maps.empty())
+        HIP_TRY(h, hipMemcpyAsync(h->hist_dev_maps, maps.data(), maps.size() * sizeof(int32_t*), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                   // `maps` is a host temporary
+    *n_maps = (int)maps.size();
+    return GPF_OK;
+}
+template <int D>
+void launch_block_hist_moments(gpf_filter* h, int n_maps, const double* hx, int64_t nb, int64_t nblocks, int want_var, double* mean, double* var)
+{
+    if (nb <= 2 * WAVE)      GPF_LAUNCH((k_block_hist_moments<D, WAVE, 2>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->hist_dev_maps, n_maps, hx, h->lw, h->n, nb, nblocks, want_var, mean, var);
+    else if (nb <= 8 * WAVE) GPF_LAUNCH((k_block_hist_moments<D, WAVE, 8>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->hist_dev_maps, n_maps, hx, h->lw, h->n, nb, nblocks, want_var, mean, var);
+    else                     GPF_LAUNCH((k_block_hist_moments<D, BLOCK, 8>), dim3((unsigned)nblocks), dim3(BLOCK), 0, h->stream, h->hist_dev_maps, n_maps, hx, h->lw, h->n, nb, nblocks, want_var, mean, var);
+}
+} // namespace gpfh
+extern "C" {
+// for b in blocks: [mean(state[b], step => c) for c in latent columns], [var(state[b], step => c) ...]
+// (src/statistics.jl:13-14, 48-50 with a past address on sub-states, src/view.jl:35-48) -- gpf.h
+gpf_status gpf_block_history_moments(gpf_handle h, int32_t step, int64_t block_size, double* mean_out, double* var_out)
+{
+    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+    if (!mean_out && !var_out) return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_block_history_moments: both outputs are NULL");
+    int n_maps = 0;
+    gpf_status s = block_hist_prepare(h, step, block_size, "gpf_block_history_moments", &n_maps);
+    if (s) return s;
+    const int64_t nblocks = (h->n + block_size - 1) / block_size;
+    const size_t cells = (size_t)nblocks * (size_t)h->d;
+    if ((s = block_est_buffer(h, (int64_t)(2 * cells)))) return s;
+    double* const mean = h->blk_est; double* const var = h->blk_est + cells;
+    const double* hx = h->hist_x[step - 1];
+    switch (h->d) {
+        case 1: launch_block_hist_moments<1>(h, n_maps, hx, block_size, nblocks, var_out ? 1 : 0, mean, var); break;
+        case 2: launch_block_hist_moments<2>(h, n_maps, hx, block_size, nblocks, var_out ? 1 : 0, mean, var); break;
+        default: launch_block_hist_moments<4>(h, n_maps, hx, block_size, nblocks, var_out ? 1 : 0, mean, var); break;
+    }
+    HIP_TRY(h, hipGetLastError());
+    if (mean_out) HIP_TRY(h, hipMemcpyAsync(mean_out, mean, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (var_out) HIP_TRY(h, hipMemcpyAsync(var_out, var, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GPF_OK;
+}
+// for b in blocks: proportionmap(state[b], step => column)[values[k]] (src/statistics.jl:91-101 with a past address on sub-states) -- gpf.h
+gpf_status gpf_block_history_proportion(gpf_handle h, int32_t step, int64_t block_size, int32_t column, const double* values, int32_t n_values, double* out)
+{
+    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+    if (!values || !out) return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_block_history_proportion: null values / output");
+    if (column < 0 || column >= h->d) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad column");
+    if (n_values < 1 || n_values > BLK_MATCH_MAX) return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_block_history_proportion: need 1 <= n_values <= " + std::to_string(BLK_MATCH_MAX));
+    int n_maps = 0;
+    gpf_status s = block_hist_prepare(h, step, block_size, "gpf_block_history_proportion", &n_maps);
+    if (s) return s;
+    const int64_t nblocks = (h->n + block_size - 1) / block_size;
+    const size_t cells = (size_t)nblocks * (size_t)n_values;
+    if ((s = block_est_buffer(h, (int64_t)cells))) return s;
+    BlockMatch mv{};
+    for (int k = 0; k < BLK_MATCH_MAX; ++k) mv.v[k] = k < n_values ? values[k] : values[n_values - 1];
+    mv.n = n_values;
+    const double* hx = h->hist_x[step - 1];
+    if (block_size <= 2 * WAVE)      GPF_LAUNCH((k_block_hist_proportion<WAVE, 2>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->hist_dev_maps, n_maps, hx, h->d, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
+    else if (block_size <= 8 * WAVE) GPF_LAUNCH((k_block_hist_proportion<WAVE, 8>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->hist_dev_maps, n_maps, hx, h->d, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
+    else                             GPF_LAUNCH((k_block_hist_proportion<BLOCK, 8>), dim3((unsigned)nblocks), dim3(BLOCK), 0, h->stream, h->hist_dev_maps, n_maps, hx, h->d, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out, h->blk_est, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GPF_OK;
 }
 // ---- checkpoint / resume: everything a filter needs to continue bit for bit -- the population, its log-weights and parents, the log-ML
 // estimate, the RNG epoch, the latest observation and strata -- as ONE host blob; loads into a handle created with the same gpf_config

@@ -244,14 +244,16 @@ gpf_status hist_snapshot(gpf_filter* h)
     HIP_TRY(h, hipGetLastError());
     return GPF_OK;
 }
-// a resample happened during the current step: compose its ancestors into the step's map
-gpf_status hist_on_resample(gpf_filter* h)
+// a resample happened during the current step: compose its ancestors into the step's map.  block_size > 0: it was a gpf_resample_blocks -- h->anc is
+// local to the blocks that resampled and stale in the others, h->blk_mask says which (k_hist_compose_blocks)
+gpf_status hist_on_resample(gpf_filter* h, int64_t block_size)
 {
     if (!h->hist_on || h->hist_step < 0) return GPF_OK;
     int32_t* old = h->hist_map[h->hist_step];
     int32_t* neu = nullptr;
     HIP_TRY(h, hipMalloc(&neu, (size_t)h->n * sizeof(int32_t)));
-    GPF_LAUNCH(k_hist_compose, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->anc, old, h->n, neu);
+    if (block_size > 0) GPF_LAUNCH(k_hist_compose_blocks, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->anc, h->blk_mask, block_size, old, h->n, neu);
+    else GPF_LAUNCH(k_hist_compose, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->anc, old, h->n, neu);
     HIP_TRY(h, hipGetLastError());
     if (old) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(old); }
     h->hist_map[h->hist_step] = neu;

@@ -171,7 +171,7 @@ gpf_status gpf_resample_local(gpf_handle h, int32_t method, int32_t sort_particl
  *   n_resampled: if non-NULL receives the number of blocks that resampled (synchronises).
  * Blocks of more than 2048 particles (no size limit in the reference's loop, test/resample.jl:130-162) are resampled one after the other with the
  * full-size kernels through view handles the filter keeps -- the same results, the same single epoch, one set of launches per block.
- * Not on sharded filters, views or filters with a trajectory store (GPF_ERR_STATE). */
+ * Not on sharded filters, views or filters with a whole-filter trajectory store (GPF_ERR_STATE). */
 gpf_status gpf_resample_blocks(gpf_handle h, int32_t method, int64_t block_size, double priority_alpha, int32_t sort_particles,
                                double ess_frac, int32_t check, int32_t* invalid, int64_t* n_resampled);
 /* which blocks the last gpf_resample_blocks resampled: out[ceil(n / block_size)] (host), 1 / 0 */
@@ -190,7 +190,7 @@ gpf_status gpf_block_stats(gpf_handle h, int64_t block_size, double* ess_out, do
  * DEVIATION from the per-view calls: a block whose log-weights hold a NaN or +Inf gets NaN in all its outputs (as its ESS from
  * gpf_block_stats) and the call succeeds; the other blocks are unaffected.
  * The calls read the state and change nothing: no epoch advance, no RNG draw.  They do not read model parameters, so they work unchanged
- * with gpf_set_block_params.  Not on views, shards of a sharded filter or filters with a trajectory store (GPF_ERR_STATE); bad arguments
+ * with gpf_set_block_params.  Not on views, shards of a sharded filter or filters with a whole-filter trajectory store (GPF_ERR_STATE); bad arguments
  * return GPF_ERR_INVALID_ARGUMENT.  Both synchronise the stream.
  *
  * for b in blocks: [mean(state[b], c) for c in columns], [var(state[b], c) ...]   (src/statistics.jl:13-14, 48-50 on sub-states)
@@ -210,7 +210,7 @@ gpf_status gpf_block_proportion(gpf_handle h, int64_t block_size, int32_t column
  *     n_accepted as in gpf_rejuvenate (over the blocks that took part).
  * After gpf_update_blocks the whole-filter gpf_rejuvenate also uses the per-block observations; gpf_update / gpf_initialize go back
  * to one observation for all particles.  Each call advances the epoch once; block b's result is bit-identical to the same call on a
- * view of the block.  Not on sharded filters, views or filters with a trajectory store. */
+ * view of the block.  Not on sharded filters, views or filters with a whole-filter trajectory store. */
 gpf_status gpf_initialize_blocks(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size);
 gpf_status gpf_update_blocks(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size);
 /* the same with a proposal PER BLOCK -- "Update with different proposals per view", test/update.jl:179-189, in one launch:
@@ -241,7 +241,7 @@ gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, 
  *   - model-independent calls work as before: gpf_resample*, gpf_resample_blocks, gpf_block_stats, the getters, views, checkpoints.
  * Clearing the rows restores the behaviour without them exactly.  A checkpoint does not hold the rows (the blob layout is unchanged) and
  * gpf_checkpoint_load neither sets nor clears them: restore, then call gpf_set_block_params again to continue bit for bit.
- * Not on views, shards of a sharded filter or filters with a trajectory store (GPF_ERR_STATE); a NULL handle, n_params outside 1..24 or
+ * Not on views, shards of a sharded filter or filters with a whole-filter trajectory store (GPF_ERR_STATE); a NULL handle, n_params outside 1..24 or
  * block_size < 1 return GPF_ERR_INVALID_ARGUMENT and change nothing. */
 gpf_status gpf_set_block_params(gpf_handle h, const double* params, int32_t n_params, int64_t block_size);
 /* the per-block parameter rows as they stand: out = HOST [n_blocks][n_params] doubles, the first n_params entries of every row (n_blocks must be
@@ -274,7 +274,7 @@ gpf_status gpf_get_block_params(gpf_handle h, double* out, int32_t n_params, int
  *      says.  All L = -Inf: with GPF_CHECK_TRUE the same refusal; else safe_softmax's uniform fallback as in gpf_resample (ancestors from
  *      uniform block weights, every delta = 0, *invalid = 1; its ESS is NaN, so a gated call does not fire).
  * Refused without changing anything: n not a multiple of block_size, block_size < 1, a block_size other than that of the per-block parameters or
- * of the per-block observations (GPF_ERR_INVALID_ARGUMENT); views, shards of a sharded filter, filters with a trajectory store (GPF_ERR_STATE).
+ * of the per-block observations (GPF_ERR_INVALID_ARGUMENT); views, shards of a sharded filter, filters with a whole-filter trajectory store (GPF_ERR_STATE).
  * B = 1 is legal: A = [0], delta = 0, the state comes back bit for bit.  Blocks of any size (no LDS limit); beyond 2048 particles per block L comes
  * from gpf_block_stats's loop over view handles.  Not here: priorities / tempering at block level, sharded filters, parameter jitter (host:
  * theta = theta[A], perturb, gpf_set_block_params).  invalid / resampled / ess_out may be NULL. */
@@ -459,6 +459,40 @@ gpf_status gpf_history_var(gpf_handle h, int32_t step, int32_t column, double* o
 /* proportionmap(state, addr)[value]  (src/statistics.jl:91-101): normalised weight of the particles whose column == value;
  * step = 0 -> current step's column, step >= 1 -> past choice (trajectory store) */
 gpf_status gpf_proportion(gpf_handle h, int32_t step, int32_t column, double value, double* out);
+
+/* ---- the block-wise trajectory store: past choices per block ------------------------------------------------
+ * A sub-state is a slice of persistent traces (src/view.jl:35-48), so the reference answers mean(state[b], 5 => :moving) for any block of
+ * "many small filters in one state".  gpf_history_enable_blocks is gpf_history_enable -- same preconditions (before initialisation, unsharded,
+ * max_steps >= 1), same store, same whole-filter calls and queries (gpf_update, gpf_resample, gpf_rejuvenate, gpf_history_*, gpf_proportion) --
+ * and declares that the block-wise calls feed the store too; a store enabled with gpf_history_enable keeps refusing them (GPF_ERR_STATE).
+ *   recording: gpf_initialize_blocks* begins step 1, gpf_update_blocks* begins the next step (a full store returns GPF_ERR_STATE and leaves rows,
+ *     weights, per-block observations and the epoch untouched; so does a call refused for its observations: it begins no step and an
+ *     initialisation so refused clears nothing); gpf_rejuvenate_blocks is seen when the step ends or at query time;
+ *     gpf_resample_blocks composes, for the blocks that resampled, their block-local parents into the step's ancestor map (the particles of the
+ *     other blocks stay where they are); gpf_resample_across_blocks composes its global parents when it fires, nothing when it does not.
+ *     Several resamples of one step compose in call order (a nested filter: gpf_resample_blocks, then gpf_resample_across_blocks).
+ *   blocks of more than 2048 particles are the work of view handles inside the library and a filter with a store has no views: with a (clamped)
+ *     block_size > 2048, gpf_resample_blocks, gpf_block_stats, gpf_block_moments, gpf_block_proportion, gpf_resample_across_blocks and the two
+ *     queries below return GPF_ERR_STATE and change nothing.  gpf_initialize_blocks*, gpf_update_blocks* and gpf_rejuvenate_blocks take any size.
+ *   still refused on either store: views, gpf_resize / gpf_coalesce / gpf_introduce, gpf_checkpoint_load.
+ *
+ * The queries -- the batched form of
+ *     for b in blocks; mean(state[b], step => addr); var(state[b], step => addr); proportionmap(state[b], step => addr); end
+ * (src/statistics.jl:13-14, 48-50, 91-101 on ParticleFilterSubStates, src/view.jl:35-48) -- answer all blocks and all latent columns in ONE launch.
+ * step is 1-based, 1 <= step <= gpf_history_steps; blocks as in gpf_block_moments (n_blocks = ceil(n / block_size), the last may be shorter).
+ * Every particle's value is trace[step => column] along its ancestry (what gpf_history_column returns); the weights are the block's CURRENT
+ * log-weights, normalised and summed exactly as gpf_block_moments / gpf_block_proportion do (the tree of DESIGN.md 3.5 over the block-local index):
+ * the results are bit-identical to those calls on a filter of the same log-weights whose rows hold the past values.
+ * DEVIATION, as in gpf_block_moments: a block whose log-weights hold a NaN or +Inf reads NaN and the call succeeds; the other blocks are unaffected.
+ * The queries read the state and change nothing (no epoch advance, no RNG draw) and synchronise the stream.  Without a block-wise store:
+ * GPF_ERR_STATE; bad step / column / n_values / NULL arguments: GPF_ERR_INVALID_ARGUMENT, nothing is written.
+ *
+ * mean_out, var_out: [n_blocks][dim] row-major, host, dim as gpf_state_dim reports it (the store keeps the latent columns, not the row width);
+ * either may be NULL, not both. */
+gpf_status gpf_history_enable_blocks(gpf_handle h, int32_t max_steps);   /* before gpf_initialize_blocks / gpf_initialize */
+gpf_status gpf_block_history_moments(gpf_handle h, int32_t step, int64_t block_size, double* mean_out, double* var_out);
+/* out: [n_blocks][n_values] row-major, host; 1 <= n_values <= 16, 0 <= column < dim.  A value no particle of the block held gives 0.0. */
+gpf_status gpf_block_history_proportion(gpf_handle h, int32_t step, int64_t block_size, int32_t column, const double* values, int32_t n_values, double* out);
 
 /* ---- shard-level building blocks (multi-GPU) ------------------------------------------------------
  * A filter sharded over G GPUs is G handles created with the same seed / n_global and contiguous

@@ -39,7 +39,10 @@ mutable struct DeviceParticleFilterState
     handle::Ptr{Cvoid}
     model::NativeModel
     n_particles::Int
-    function DeviceParticleFilterState(model::NativeModel, n::Int; seed::Integer=1, keep_prev::Bool=false, device::Integer=0)
+    # history = T: the trajectory store for T time steps (gpf.h gpf_history_enable); history_blocks: the block-wise store, which the block-wise
+    # calls feed too (gpf_history_enable_blocks)
+    function DeviceParticleFilterState(model::NativeModel, n::Int; seed::Integer=1, keep_prev::Bool=false, device::Integer=0, history::Integer=0,
+                                       history_blocks::Bool=false)
         h = Ref{Ptr{Cvoid}}(C_NULL)
         GC.@preserve model begin
             cfg = Ref(GpfConfig(GPF_ABI_VERSION, model.id, length(model.params), keep_prev, pointer(model.params),
@@ -49,6 +52,11 @@ mutable struct DeviceParticleFilterState
         st == 0 || error(unsafe_string(ccall((:gpf_last_error, libgpf), Cstring, (Ptr{Cvoid},), C_NULL)))
         state = new(h[], model, n)
         finalizer(s -> ccall((:gpf_destroy, libgpf), Cint, (Ptr{Cvoid},), getfield(s, :handle)), state)
+        if history > 0
+            st = history_blocks ? ccall((:gpf_history_enable_blocks, libgpf), Cint, (Ptr{Cvoid}, Cint), h[], history) :
+                                  ccall((:gpf_history_enable, libgpf), Cint, (Ptr{Cvoid}, Cint), h[], history)
+            st == 0 || error(unsafe_string(ccall((:gpf_last_error, libgpf), Cstring, (Ptr{Cvoid},), h[])))
+        end
         return state
     end
     # wrap an existing handle (a sub-state view created by gpf_view_create)
@@ -241,8 +249,48 @@ function block_var(s::DeviceParticleFilterState, block_size::Int, addr::Union{No
     _status(s, ccall((:gpf_block_moments, libgpf), Cint, (Ptr{Cvoid}, Int64, Ptr{Cdouble}, Ptr{Cdouble}), s.handle, block_size, C_NULL, s2))
     return addr === nothing ? s2 : s2[addr + 1, :]
 end
-block_mean(s::DeviceParticleFilterState, block_size::Int, addr::Pair) = error("block_mean: a past-step address needs a trajectory store, which block-wise states do not have")
-block_var(s::DeviceParticleFilterState, block_size::Int, addr::Pair) = error("block_var: a past-step address needs a trajectory store, which block-wise states do not have")
+# A PAST choice per block: for b in blocks; mean(state[b], t => addr); ...; end (a sub-state is a slice of persistent traces, src/view.jl:35-48) from the
+# block-wise trajectory store (pf_initialize_blocks(...; history=T); gpf.h gpf_block_history_moments, gpf_block_history_proportion).  Matrices are
+# (dim, n_blocks): the store keeps the latent columns.  Without the store the library refuses (ErrorException naming the trajectory store).
+function _latent_dim(s::DeviceParticleFilterState)
+    dim = Ref{Cint}(0); w = Ref{Cint}(0)
+    _status(s, ccall((:gpf_state_dim, libgpf), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cint}), s.handle, dim, w))
+    return Int(dim[])
+end
+function block_moments(s::DeviceParticleFilterState, block_size::Int, step::Integer)
+    nb = cld(s.n_particles, block_size); d = _latent_dim(s)
+    mu = Matrix{Float64}(undef, d, nb); s2 = Matrix{Float64}(undef, d, nb)
+    _status(s, ccall((:gpf_block_history_moments, libgpf), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Cdouble}, Ptr{Cdouble}), s.handle, step, block_size, mu, s2))
+    return mu, s2
+end
+function block_mean(s::DeviceParticleFilterState, block_size::Int, addr::Pair{<:Integer,<:Integer})
+    nb = cld(s.n_particles, block_size); d = _latent_dim(s)
+    mu = Matrix{Float64}(undef, d, nb)
+    _status(s, ccall((:gpf_block_history_moments, libgpf), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Cdouble}, Ptr{Cdouble}), s.handle, addr.first, block_size, mu, C_NULL))
+    return mu[addr.second + 1, :]
+end
+function block_var(s::DeviceParticleFilterState, block_size::Int, addr::Pair{<:Integer,<:Integer})
+    nb = cld(s.n_particles, block_size); d = _latent_dim(s)
+    s2 = Matrix{Float64}(undef, d, nb)
+    _status(s, ccall((:gpf_block_history_moments, libgpf), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Cdouble}, Ptr{Cdouble}), s.handle, addr.first, block_size, C_NULL, s2))
+    return s2[addr.second + 1, :]
+end
+function block_proportionmap(s::DeviceParticleFilterState, block_size::Int, addr::Pair{<:Integer,<:Integer}; max_values::Int=256)
+    col = Vector{Float64}(undef, s.n_particles)
+    _status(s, ccall((:gpf_history_column, libgpf), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Int64), s.handle, addr.first, addr.second, col, length(col)))
+    vals = sort(unique(col))
+    length(vals) > max_values && error("proportionmap: $(length(vals)) distinct values; the column does not look discrete")
+    nb = cld(s.n_particles, block_size)
+    out = Matrix{Float64}(undef, length(vals), nb)
+    for k0 in 1:16:length(vals)
+        chunk = vals[k0:min(k0 + 15, length(vals))]
+        part = Matrix{Float64}(undef, length(chunk), nb)
+        _status(s, ccall((:gpf_block_history_proportion, libgpf), Cint, (Ptr{Cvoid}, Cint, Int64, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}),
+                         s.handle, addr.first, block_size, addr.second, chunk, length(chunk), part))
+        out[k0:k0 + length(chunk) - 1, :] = part
+    end
+    return vals, out
+end
 # returns (values, proportions): the distinct values of the column over all blocks, and a (n_values, n_blocks) Matrix; 16 values per launch
 function block_proportionmap(s::DeviceParticleFilterState, block_size::Int, addr::Integer; max_values::Int=256)
     col = Vector{Float64}(undef, s.n_particles)
@@ -261,8 +309,8 @@ function block_proportionmap(s::DeviceParticleFilterState, block_size::Int, addr
 end
 # Every block a filter on ITS OWN data: per-block initialisation / update / rejuvenation, one launch each (gpf.h gpf_initialize_blocks,
 # gpf_update_blocks, gpf_rejuvenate_blocks).  observations: a (n_obs, n_blocks) Matrix -- column b for block b.
-function pf_initialize_blocks(model::NativeModel, model_args::Tuple, observations::Matrix{Float64}, n_particles::Int, block_size::Int; kw...)
-    state = DeviceParticleFilterState(model, n_particles; kw...)
+function pf_initialize_blocks(model::NativeModel, model_args::Tuple, observations::Matrix{Float64}, n_particles::Int, block_size::Int; history::Integer=0, kw...)
+    state = DeviceParticleFilterState(model, n_particles; history=history, history_blocks=history > 0, kw...)    # (history = T: the block-wise store)
     size(observations, 2) == cld(n_particles, block_size) || error("one observation column per block expected")
     _status(state, ccall((:gpf_initialize_blocks, libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Int64), state.handle, observations, size(observations, 1), block_size))
     return state
