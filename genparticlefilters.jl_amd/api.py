@@ -1007,6 +1007,36 @@ def sample_unweighted_traces(state, n_samples: int, return_indices: bool = False
     return (rows, idx) if return_indices else rows
 
 
+def block_sample_trajectories(state, block_size: int, n_samples: int = 1, steps=None, return_indices: bool = False):
+    """for b in blocks; sample_unweighted_traces(state[b], n_samples); end (src/utils.jl:7,189-194 on sub-states, src/view.jl:35-48): the reference's
+    traces are persistent, so every draw is a whole path of block b.  One launch for all blocks (gpf.h gpf_block_sample_trajectories); needs the
+    block-wise trajectory store (pf_initialize_blocks(..., history=T)).  Returns [n_blocks, n_samples, n_steps, dim]: the latent columns of the drawn
+    particle's ancestors, and with return_indices=True also the [n_blocks, n_samples] int64 indices (1-based, inside the block) of the drawn
+    current particles.  steps=None: all recorded steps; steps=t: that step; steps=(lo, hi): a range, 1-based and inclusive (step 1 = the
+    initialisation).  A block with NaN / +Inf weights gets index 0 and NaN paths.  Advances the RNG epoch once; the filter is left untouched."""
+    if not getattr(state, "history_blocks", False):
+        raise ErrorException("block_sample_trajectories needs a block-wise trajectory store (pf_initialize_blocks(..., history=T)), which this state does not have")
+    if steps is None:
+        k = C.c_int32(0)
+        state._check(state._L.gpf_history_steps(state._h, C.byref(k)))
+        lo, hi = 1, int(k.value)
+    elif isinstance(steps, (tuple, list)):
+        lo, hi = int(steps[0]), int(steps[1])
+    else:
+        lo = hi = int(steps)
+    if lo < 1 or hi < 1:
+        raise ErrorException("block_sample_trajectories: steps are 1-based (step 1 = the initialisation)")
+    if hi < lo or int(n_samples) < 1 or int(block_size) < 1:
+        raise ErrorException("block_sample_trajectories: need lo <= hi, n_samples >= 1 and block_size >= 1")
+    bs = min(int(block_size), max(state.n_particles, 1))
+    nb = (state.n_particles + bs - 1) // bs
+    traj = np.empty((nb, int(n_samples), hi - lo + 1, state.dim))
+    idx = np.empty((nb, int(n_samples)), np.int64) if return_indices else None
+    state._check(state._L.gpf_block_sample_trajectories(state._h, int(block_size), int(n_samples), lo, hi, _pd(traj),
+                                                        idx.ctypes.data_as(C.POINTER(C.c_int64)) if return_indices else None))
+    return (traj, idx) if return_indices else traj
+
+
 # ----------------------------------------------------------------------------- statistics (src/statistics.jl)
 def _addr_values(state, addr) -> np.ndarray:
     """the values at one address over all particles: a column of the current step, or (t, column) for a past choice"""

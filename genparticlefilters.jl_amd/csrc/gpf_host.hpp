@@ -135,6 +135,7 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     std::vector<int32_t*> hist_map;      // [step] n int32 or nullptr
     int hist_step = -1;                  // index of the current step (0 = after gpf_initialize)
     const int32_t** hist_dev_maps = nullptr;
+    const double** hist_dev_x = nullptr;   // device table of the snapshots hist_x[s], hist_cap entries (gpf_block_sample_trajectories walks all steps in one launch)
     // sub-state view (src/view.jl:16-48): this handle aliases particles [view_start, view_start + n) of `parent`
     gpf_filter* parent = nullptr;
     std::vector<gpf_filter*> views;      // the live view handles of THIS filter: gpf_destroy orphans them (a view used after its filter is gone fails loudly)

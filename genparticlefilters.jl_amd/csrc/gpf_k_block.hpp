@@ -622,6 +622,82 @@ __global__ __launch_bounds__(BLOCK) void k_block_hist_proportion(const int32_t* 
     }
 }
 
+// ----------------------------------------------------------------------------- whole trajectories per block: the ancestral paths of the store
+// for b in blocks; sample_unweighted_traces(state[b], n_samples); end -- a draw from a sub-state is a persistent trace, i.e. a whole path x_1:T of
+// the block (src/utils.jl:7,189-194 on a ParticleFilterSubState, src/view.jl:35-48).  ONE launch for all blocks (gpf.h gpf_block_sample_trajectories):
+//   weights   the block's fixed-point weights and their inclusive CDF in LDS, exactly as k_block_resample builds them (K from the block's particle
+//             count, safe_softmax's maximum and flags, q = 1 for an all -Inf block);
+//   draws     draw j of block b reads resample slot b n_samples + j of the call's epoch: a = upper_bound(cdf, mulhi64(U, S)); the draws are dealt to the
+//             team's lanes as j = tl, tl + TEAM, ..., so n_samples may exceed the team;
+//   walk      every lane follows ITS draw back through the composed ancestor maps: maps[q] (q the 0-based step, nullptr = no resample in that step:
+//             kernel-uniform) leads from the final order of step q to that of step q - 1.  On the way down it reads, at every step q in [lo0, hi0],
+//             the D latent columns of snapshot hx[q] at the particle it stands on.  A chain of T dependent 4-byte loads per draw: the launch is fast
+//             when many draws are in flight, not through anything a lane does.
+//   output    traj = [nblocks][n_samples][hi0 - lo0 + 1][D], the layout the caller receives: a lane fills the contiguous run of its own draw, one
+//             16-byte piece (D = 1: one word) per step and pair of columns, from the last step down -- every 128-byte line is written by one lane in
+//             consecutive iterations and merges in L2; the reads of the walk are one line per lane and step whatever the layout.  idx = [nblocks]
+//             [n_samples], 1-based inside the block.  Either may be null.
+// A block with NaN / +Inf log-weights: idx 0, NaN paths.  Teams as in k_block_hist_moments.
+template <int D, int TEAM, int ITEMS>
+__global__ __launch_bounds__(BLOCK) void k_block_sample_traj(const int32_t* const* __restrict__ maps, const double* const* __restrict__ hx, int T, int lo0, int hi0,
+                                                             const double* __restrict__ lw, int64_t n, int64_t nb, int64_t nblocks, int n_samples,
+                                                             uint64_t seed, uint32_t epoch, double* __restrict__ traj, int64_t* __restrict__ idx_out)
+{
+    constexpr int TEAMS = BLOCK / TEAM, CAP = TEAM * ITEMS;
+    static_assert(TEAM == WAVE || TEAM == BLOCK, "a wave or the workgroup");
+    static_assert(D == 1 || D == 2 || D == 4, "the latent columns are moved as words or 16-byte pairs");
+    __shared__ uint64_t s_cdf_[BLOCK * ITEMS];
+    __shared__ uint64_t s_x[NWAVES][4];
+    __shared__ double s_m[NWAVES];
+    __shared__ int s_f[NWAVES];
+    const int tm = (int)threadIdx.x / TEAM, tl = (int)threadIdx.x % TEAM;
+    const int64_t blk = (int64_t)blockIdx.x * TEAMS + tm;
+    if (TEAM != BLOCK && blk >= nblocks) return;                   // (an idle wave: the wave-team path has no workgroup barrier)
+    uint64_t* const s_cdf = s_cdf_ + tm * CAP;
+    const int64_t b0 = blk * nb;
+    const int cnt = (int)(n - b0 < nb ? n - b0 : nb);
+    const int K = fix_K(cnt);
+    const int n_steps = hi0 - lo0 + 1;
+    double lwv[ITEMS];
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) { const int i = ITEMS * tl + k; lwv[k] = i < cnt ? lw[b0 + i] : -__builtin_huge_val(); }
+    double m; int f;
+    team_max_flags<TEAM, ITEMS>(lwv, tl, cnt, s_m, s_f, m, f);
+    uint64_t q[ITEMS];
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) q[k] = ITEMS * tl + k < cnt ? ((f & FLAG_ALL_NEGINF) ? 1ull : exp_fix(lwv[k] - m, K)) : 0ull;
+    const uint64_t S = team_scan_incl<TEAM, ITEMS>(q, s_x);
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) s_cdf[ITEMS * tl + k] = q[k];
+    team_sync<TEAM>();
+    const bool bad = (f & (FLAG_NAN | FLAG_POSINF)) != 0;          // (team-uniform)
+    for (int j = tl; j < n_samples; j += TEAM) {
+        const int64_t draw = blk * n_samples + j;                  // < 2^31 (checked by the host): the draw's resample slot
+        int a = -1;
+        if (!bad) a = lds_upper_bound(s_cdf, cnt, mulhi64(resample_u64(seed, (uint32_t)draw, epoch), S));
+        if (idx_out) idx_out[draw] = (int64_t)a + 1;
+        if (!traj) continue;
+        double* const out = traj + draw * n_steps * D;
+        if (bad) {
+            for (int t = 0; t < n_steps * D; ++t) out[t] = __builtin_nan("");
+            continue;
+        }
+        int64_t p = b0 + a;
+        for (int s = T - 1; s >= lo0; --s) {
+            if (s <= hi0) {
+                const double* __restrict__ x = hx[s] + p * D;
+                double* const o = out + (s - lo0) * D;
+                if constexpr (D == 1) o[0] = x[0];
+                else {
+#pragma unroll
+                    for (int c = 0; c < D / 2; ++c) reinterpret_cast<double2*>(o)[c] = reinterpret_cast<const double2*>(x)[c];
+                }
+            }
+            if (s > lo0) { const int32_t* __restrict__ g = maps[s]; if (g) p = g[p]; }      // (kernel-uniform)
+        }
+    }
+}
+
 // ----------------------------------------------------------------------------- resampling ACROSS blocks: the block-granular gather
 // gpf_resample_across_blocks (gpf.h): every block is one "super-particle" with the log-weight L[b] = log_ml_estimate(state[b]); a planner filter
 // of nblocks particles resampled them (the reference's resampler, src/resample.jl:19-175, one level up) and left the source block A[b] of every

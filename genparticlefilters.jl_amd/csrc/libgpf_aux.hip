@@ -1259,6 +1259,8 @@ gpf_status gpf_history_enable(gpf_handle h, int32_t max_steps)
     h->hist_on = true; h->hist_blocks = false; h->hist_cap = max_steps;
     if (h->hist_dev_maps) (void)hipFree(h->hist_dev_maps);
     HIP_TRY(h, hipMalloc(&h->hist_dev_maps, (size_t)max_steps * sizeof(int32_t*)));
+    if (h->hist_dev_x) { (void)hipFree(h->hist_dev_x); h->hist_dev_x = nullptr; }
+    HIP_TRY(h, hipMalloc(&h->hist_dev_x, (size_t)max_steps * sizeof(double*)));
     return GPF_OK;
 }
 
@@ -1421,6 +1423,69 @@ gpf_status gpf_block_history_proportion(gpf_handle h, int32_t step, int64_t bloc
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(out, h->blk_est, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GPF_OK;
+}
+// ---- whole trajectories per block (gpf.h gpf_block_sample_trajectories): weights, draws, genealogy walk and gather of all blocks in one launch
+} // extern "C"
+namespace gpfh {
+struct TrajLaunch { int T, lo0, hi0; int64_t nb, nblocks; int n_samples; double* traj; int64_t* idx; };
+template <int D>
+void launch_block_sample_traj(gpf_filter* h, const TrajLaunch& a)
+{
+#define GPF_TRAJ_ARGS h->hist_dev_maps, h->hist_dev_x, a.T, a.lo0, a.hi0, h->lw, h->n, a.nb, a.nblocks, a.n_samples, h->cfg.seed, h->epoch, a.traj, a.idx
+    if (a.nb <= 2 * WAVE)      GPF_LAUNCH((k_block_sample_traj<D, WAVE, 2>), dim3((unsigned)((a.nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, GPF_TRAJ_ARGS);
+    else if (a.nb <= 8 * WAVE) GPF_LAUNCH((k_block_sample_traj<D, WAVE, 8>), dim3((unsigned)((a.nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, GPF_TRAJ_ARGS);
+    else                       GPF_LAUNCH((k_block_sample_traj<D, BLOCK, 8>), dim3((unsigned)a.nblocks), dim3(BLOCK), 0, h->stream, GPF_TRAJ_ARGS);
+#undef GPF_TRAJ_ARGS
+}
+} // namespace gpfh
+extern "C" {
+// for b in blocks; sample_unweighted_traces(state[b], n_samples); end (src/utils.jl:7,189-194 on sub-states, src/view.jl:35-48) -- gpf.h
+gpf_status gpf_block_sample_trajectories(gpf_handle h, int64_t block_size, int32_t n_samples, int32_t step_lo, int32_t step_hi,
+                                         double* traj_out, int64_t* idx_out)
+{
+    const char* who = "gpf_block_sample_trajectories";
+    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+    if (!traj_out && !idx_out) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": both outputs are NULL");
+    if (n_samples < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": n_samples < 1");
+    if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");
+    if (!h->hist_on || !h->hist_blocks)
+        return fail(h, GPF_ERR_STATE, std::string(who) + " needs the block-wise trajectory store (gpf_history_enable_blocks before gpf_initialize_blocks)");
+    gpf_status s = check_ready(h);
+    if (s) return s;
+    const int T = (int)h->hist_x.size();
+    if (step_lo < 1 || step_hi < step_lo || step_hi > T) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": need 1 <= step_lo <= step_hi <= gpf_history_steps");
+    if ((s = block_store_size(h, block_size, who))) return s;
+    if (h->d != 1 && h->d != 2 && h->d != 4) return fail(h, GPF_ERR_STATE, "latent dimension");
+    const int64_t nblocks = (h->n + block_size - 1) / block_size, n_steps = step_hi - step_lo + 1;
+    const int64_t lim = (int64_t)1 << 31;
+    // (nblocks <= n < 2^31, n_samples < 2^31, n_steps d < 2^31: no product below overflows 64 bits before it is compared)
+    const int64_t draws = nblocks * n_samples;
+    if (draws >= lim || n_steps * h->d >= lim || draws >= (lim + n_steps * h->d - 1) / (n_steps * h->d))
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": n_blocks * n_samples and n_blocks * n_samples * n_steps * dim must stay below 2^31");
+    const size_t cells = (size_t)draws * (size_t)n_steps * (size_t)h->d;
+    if ((s = hist_snapshot(h))) return s;                         // whatever is deferred becomes state; the current step, in its current order
+    // the device tables, indexed by the 0-based step: the snapshots and the composed ancestor maps (nullptr: a step without a resample)
+    std::vector<const int32_t*> maps(h->hist_map.begin(), h->hist_map.end());
+    std::vector<const double*> xs(h->hist_x.begin(), h->hist_x.end());
+    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_maps, maps.data(), maps.size() * sizeof(int32_t*), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_x, xs.data(), xs.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                   // the two vectors are host temporaries
+    // scratch of this call: freed before it returns (up to 16 GB of trajectories are nothing to keep on a handle)
+    CallScratch d_traj, d_idx;
+    if (traj_out) HIP_TRY(h, hipMalloc(&d_traj.p, cells * sizeof(double)));
+    if (idx_out) HIP_TRY(h, hipMalloc(&d_idx.p, (size_t)draws * sizeof(int64_t)));
+    const TrajLaunch a{T, step_lo - 1, step_hi - 1, block_size, nblocks, (int)n_samples, static_cast<double*>(d_traj.p), static_cast<int64_t*>(d_idx.p)};
+    switch (h->d) {
+        case 1: launch_block_sample_traj<1>(h, a); break;
+        case 2: launch_block_sample_traj<2>(h, a); break;
+        default: launch_block_sample_traj<4>(h, a); break;
+    }
+    HIP_TRY(h, hipGetLastError());
+    if (traj_out) HIP_TRY(h, hipMemcpyAsync(traj_out, d_traj.p, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (idx_out) HIP_TRY(h, hipMemcpyAsync(idx_out, d_idx.p, (size_t)draws * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->epoch += 1;                                                // as gpf_sample_unweighted: the draws' slots are not read again
     return GPF_OK;
 }
 // ---- checkpoint / resume: everything a filter needs to continue bit for bit -- the population, its log-weights and parents, the log-ML

@@ -493,6 +493,39 @@ gpf_status gpf_history_enable_blocks(gpf_handle h, int32_t max_steps);   /* befo
 gpf_status gpf_block_history_moments(gpf_handle h, int32_t step, int64_t block_size, double* mean_out, double* var_out);
 /* out: [n_blocks][n_values] row-major, host; 1 <= n_values <= 16, 0 <= column < dim.  A value no particle of the block held gives 0.0. */
 gpf_status gpf_block_history_proportion(gpf_handle h, int32_t step, int64_t block_size, int32_t column, const double* values, int32_t n_values, double* out);
+/* Whole trajectories per block: the batched form of
+ *     for b in blocks; sample_unweighted_traces(state[b], n_samples); end
+ * (Gen.sample_unweighted_traces, src/utils.jl:7,189-194 on a ParticleFilterSubState, src/view.jl:35-48).  The reference's traces are persistent, so
+ * every draw is a whole path x_1:T of block b: what SMC^2 / particle marginal MH keep per theta, what particle Gibbs conditions its next sweep
+ * on, what a nested filter reports per island.  ONE launch does the weights, the draws, the genealogy walk and the gather of all blocks.
+ *   blocks    as in gpf_block_moments: block_size is clamped to the particle count, n_blocks = ceil(n / block_size), the last block may be shorter.
+ *             Needs the block-wise store (without it: GPF_ERR_STATE naming the trajectory store); a clamped block_size > 2048 is refused with
+ *             GPF_ERR_STATE like the other block queries on a store (it would need sub-state views, which a filter with a store does not have).
+ *   steps     step_lo, step_hi: 1-based and inclusive, 1 <= step_lo <= step_hi <= gpf_history_steps; n_steps = step_hi - step_lo + 1.
+ *   traj_out  HOST [n_blocks][n_samples][n_steps][dim] row-major, dim as gpf_state_dim reports it; idx_out: HOST int64 [n_blocks][n_samples], the
+ *             1-based index INSIDE the block of the drawn current particle.  Either may be NULL, not both.
+ *   refused   with GPF_ERR_INVALID_ARGUMENT, nothing written: n_samples < 1, n_blocks * n_samples >= 2^31, n_blocks * n_samples * n_steps * dim
+ *             >= 2^31, bad steps, both outputs NULL, block_size < 1, a NULL handle.
+ * The draw: for block b of cnt particles K = fix_K(cnt); maximum and flags as in safe_softmax (src/utils.jl:117-140);
+ * q_i = exp_fix(lw_i - m, K), every q_i = 1 if all log-weights of the block are -Inf (the uniform fallback, as in gpf_sample_unweighted); cdf = the
+ * inclusive integer CDF of q, S its total -- what gpf_resample_blocks and gpf_block_moments compute for the block.  Draw j reads resample slot
+ * b * n_samples + j of the call's epoch E:
+ *     U = resample_u64(seed, b * n_samples + j, E);  target = mulhi64(U, S);  a = the first index with cdf[a] > target, clamped to cnt - 1;
+ *     idx_out[b][j] = a + 1.
+ * The slots are numbered by draw, not by particle, so the draws of different blocks never share a uniform whatever n_samples is; for ONE block
+ * (block_size >= n, n <= 2048) draw j reads slot j, the numbering of gpf_sample_unweighted: the indices equal that call's bit for bit.
+ * The path: traj_out[b][j][s - step_lo][c] = trace[s => c] of particle b * block_size + a -- the value gpf_history_column(s, c) holds at that
+ * particle -- found by following the composed ancestor maps of the steps T, T-1, ..., s+1.  The ancestor may sit in another block (after
+ * gpf_resample_across_blocks or a whole-filter resample).  This is the ancestral path only, no backward simulation.
+ * DEVIATION, as in gpf_block_moments: a block whose log-weights hold a NaN or +Inf gets idx_out = 0 and NaN trajectories; the call succeeds and the
+ * other blocks are unaffected (gpf_sample_unweighted on such a sub-state fails).
+ * An accepted call advances the RNG epoch once, as gpf_sample_unweighted does, and changes nothing else: rows, weights, parents, log-ML estimate,
+ * the "resampled last" mask and the store's records stay.  A refused call changes nothing, the epoch included.  Like the store's other queries
+ * the call first materialises anything deferred and snapshots the current step; it synchronises the stream.  The per-block parameter rows are
+ * not read (works with gpf_set_block_params).  The device scratch of the results (8 bytes per trajectory cell and per index) is allocated by the
+ * call and freed before it returns; the two pointer tables of the walk belong to the store and go with gpf_destroy. */
+gpf_status gpf_block_sample_trajectories(gpf_handle h, int64_t block_size, int32_t n_samples, int32_t step_lo, int32_t step_hi,
+                                         double* traj_out, int64_t* idx_out);
 
 /* ---- shard-level building blocks (multi-GPU) ------------------------------------------------------
  * A filter sharded over G GPUs is G handles created with the same seed / n_global and contiguous

@@ -557,6 +557,23 @@ function sample_unweighted_traces(s::DeviceParticleFilterState, n::Int)
     permutedims(rows)[:, 1:dim[]], idx
 end
 
+# Whole trajectories per block: for b in blocks; sample_unweighted_traces(state[b], n); end (src/utils.jl:7,189-194 on sub-states, src/view.jl:35-48) in one
+# launch from the block-wise trajectory store (gpf.h gpf_block_sample_trajectories).  steps = lo:hi, 1-based (default: every recorded step).  Returns the
+# paths as a (dim, n_steps, n, n_blocks) array -- [c, s - lo + 1, j, b] = trace[s => c] of draw j of block b -- and the (n, n_blocks) indices of the
+# drawn particles inside their blocks (0 for a block with NaN weights, whose paths are NaN).  Advances the RNG epoch once.
+function block_sample_trajectories(s::DeviceParticleFilterState, block_size::Int, n::Int=1; steps::Union{Nothing,UnitRange{Int}}=nothing)
+    if steps === nothing
+        k = Ref{Cint}(0)
+        _status(s, ccall((:gpf_history_steps, libgpf), Cint, (Ptr{Cvoid}, Ref{Cint}), s.handle, k))
+        steps = 1:Int(k[])
+    end
+    nb = cld(s.n_particles, min(block_size, s.n_particles)); d = _latent_dim(s)
+    traj = Array{Float64}(undef, d, length(steps), n, nb); idx = Matrix{Int64}(undef, n, nb)
+    _status(s, ccall((:gpf_block_sample_trajectories, libgpf), Cint, (Ptr{Cvoid}, Int64, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Int64}),
+                     s.handle, block_size, n, first(steps), last(steps), traj, idx))
+    return traj, idx
+end
+
 # ---------------------------------------------------------------- multi-GPU: one process per GPU, the exchange inside libgpf
 # A shard of a filter of `n_global` particles: rank r of `world` holds the contiguous global range that starts at gid0 (the
 # first n_global % world ranks hold one particle more).  The communicator is libgpf's own (RCCL); the host only carries the
