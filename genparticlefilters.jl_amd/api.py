@@ -461,7 +461,8 @@ def pf_resample(state, method: str = "multinomial", **kwargs):
     raise ErrorException(f"Resampling method {method} not recognized.")
 
 
-def pf_resample_blocks(state, block_size: int, method: str = "multinomial", *, priority_fn=None, ess_frac=None, sort_particles: bool = True, check="warn"):
+def pf_resample_blocks(state, block_size: int, method: str = "multinomial", *, priority_fn=None, ess_frac=None, sort_particles: bool = True, check="warn",
+                       conditional: bool = False):
     """Many small filters in one state: the batched form of
 
         for b in blocks:                                   # consecutive blocks of block_size particles
@@ -470,9 +471,17 @@ def pf_resample_blocks(state, block_size: int, method: str = "multinomial", *, p
 
     (sub-states: src/view.jl:16-48, src/resample.jl:185-187,205-218; the README loop README.md:60-79 per block) in ONE kernel
     launch (gpf.h gpf_resample_blocks): one workgroup per block, everything out of LDS, the ESS test on the device.  Every block's
-    result is bit-identical to the loop above run through views.  Returns the number of blocks that resampled."""
+    result is bit-identical to the loop above run through views.  Returns the number of blocks that resampled.
+
+    conditional=True: the conditional multinomial step of conditional SMC (Andrieu, Doucet & Holenstein 2010; gpf.h
+    gpf_resample_blocks_conditional): in every block that resamples, slot 0 -- the retained particle -- keeps itself (parent 0), the other slots
+    draw exactly as in the plain call.  Multinomial only, no priority_fn, blocks of at most 2048 particles."""
     if method not in RESAMPLE_METHODS:
         raise ErrorException(f"Resampling method {method} not recognized.")
+    if conditional and method != "multinomial":
+        raise ValueError(f"conditional=True is multinomial only: forcing one slot is not a valid conditional scheme for {method} resampling")
+    if conditional and priority_fn is not None:
+        raise ValueError("conditional=True takes no priority_fn")
     if check not in (True, False, "warn"):
         raise ValueError("check must be True, 'warn' or False")
     if isinstance(state, DeviceParticleFilterSubState):
@@ -481,9 +490,15 @@ def pf_resample_blocks(state, block_size: int, method: str = "multinomial", *, p
         raise ErrorException("block-wise resampling takes priority_fn = None or Tempering(alpha) (w -> alpha w)")
     check_id = 2 if check is True else (1 if check == "warn" else 0)
     inv, cnt = C.c_int32(0), C.c_int64(0)
-    st = state._L.gpf_resample_blocks(state._h, RESAMPLE_METHODS[method], int(block_size),
-                                      float("nan") if priority_fn is None else float(priority_fn.alpha), int(sort_particles),
-                                      float("nan") if ess_frac is None else float(ess_frac), check_id, C.byref(inv), C.byref(cnt))
+    if conditional:
+        st = state._L.gpf_resample_blocks_conditional(state._h, RESAMPLE_METHODS[method], int(block_size),
+                                                      float("nan") if ess_frac is None else float(ess_frac), check_id, C.byref(inv), C.byref(cnt))
+        if st != _lib.OK:                                        # (a refused call: the state, its epoch and the mask of the last call are untouched)
+            raise ErrorException(state._L.gpf_last_error(state._h).decode())
+    else:
+        st = state._L.gpf_resample_blocks(state._h, RESAMPLE_METHODS[method], int(block_size),
+                                          float("nan") if priority_fn is None else float(priority_fn.alpha), int(sort_particles),
+                                          float("nan") if ess_frac is None else float(ess_frac), check_id, C.byref(inv), C.byref(cnt))
     state._n_blocks_last = (state.n_particles + int(block_size) - 1) // int(block_size) if int(block_size) > 0 else 0
     if st != _lib.OK:
         raise ErrorException(state._L.gpf_last_error(state._h).decode())
@@ -500,6 +515,14 @@ def _block_obs(state, observations, block_size: int) -> np.ndarray:
     if obs.ndim != 2 or obs.shape[0] != nb:
         raise ErrorException(f"one observation vector per block expected: {nb} rows, got an array of shape {obs.shape}")
     return obs
+
+
+def _block_reference(state, reference, n_blocks: int) -> np.ndarray:
+    """the reference rows of a pinned step as a contiguous (n_blocks, k) array; k is checked against the model by the library"""
+    ref = np.ascontiguousarray(reference, np.float64)
+    if ref.ndim != 2 or ref.shape[0] != n_blocks:
+        raise ErrorException(f"one reference row per block expected: shape ({n_blocks}, {state.model.dim}), got an array of shape {ref.shape}")
+    return ref
 
 
 def block_params_rows(model: NativeModel, params, n_particles: int, block_size: int) -> np.ndarray:
@@ -595,13 +618,19 @@ def block_ancestors(state) -> np.ndarray:
 
 
 def pf_initialize_blocks(model: NativeModel, model_args: tuple, observations, n_particles: int, block_size: int, *, seed: int = 1,
-                         keep_prev: bool = False, device: int = 0, strata=None, layout: str = "contiguous", params=None, history: int = 0):
+                         keep_prev: bool = False, device: int = 0, strata=None, layout: str = "contiguous", params=None, history: int = 0,
+                         reference=None):
     """many small filters in one state, each with its own data: block b (block_size consecutive particles) is initialised with
     observations[b] -- the batched form of per-view initialisation (gpf.h gpf_initialize_blocks).  strata: every block is initialised
     stratified by itself (src/initialize.jl:92-109 per sub-state, gpf.h gpf_initialize_blocks_strata), the same strata for all blocks.
     params: per-block model parameters (set_block_params) in force from this call on; `model` gives the model kind and the rows' length.
     history = T: the block-wise trajectory store for T time steps (gpf.h gpf_history_enable_blocks) -- past-step addresses (t, column) in
-    block_mean / block_var / block_proportionmap, block_moments(..., step=t), and everything the whole-filter store answers"""
+    block_mean / block_var / block_proportionmap, block_moments(..., step=t), and everything the whole-filter store answers.
+    reference: conditional SMC (gpf.h gpf_initialize_blocks_ref) -- an (n_blocks, dim) array; slot 0 of block b (particle b * block_size) is
+    pinned to reference[b] and weighted by log p(y_b | reference[b]); every other particle is what the call without a reference gives.  A
+    per-call input (nothing is kept), default proposal only, all values finite; the values of discrete latents are the caller's business."""
+    if reference is not None and strata is not None:
+        raise ValueError("a reference is offered with the default proposal only, not with strata")
     state = DeviceParticleFilterState(model, n_particles, seed=seed, keep_prev=keep_prev, device=device, history=history, history_blocks=bool(history))
     obs = _block_obs(state, observations, block_size)
     if params is not None:
@@ -610,15 +639,30 @@ def pf_initialize_blocks(model: NativeModel, model_args: tuple, observations, n_
         v = _strata_values(model, strata, "initialize")
         state._check(state._L.gpf_initialize_blocks_strata(state._h, _pd(obs), obs.shape[1], int(block_size), _pd(v), v.size, int(_layout_id(layout))))
         return state
+    if reference is not None:
+        ref = _block_reference(state, reference, obs.shape[0])
+        state._check(state._L.gpf_initialize_blocks_ref(state._h, _pd(obs), obs.shape[1], int(block_size), _pd(ref), ref.shape[1]))
+        return state
     state._check(state._L.gpf_initialize_blocks(state._h, _pd(obs), obs.shape[1], int(block_size)))
     return state
 
 
-def pf_update_blocks(state, new_args: tuple, argdiffs: tuple, observations, block_size: int, proposals=None, *, strata=None, layout: str = "interleaved"):
+def pf_update_blocks(state, new_args: tuple, argdiffs: tuple, observations, block_size: int, proposals=None, *, strata=None, layout: str = "interleaved",
+                     reference=None):
     """for b in blocks: pf_update!(state[b], new_args, argdiffs, observations[b]) (per-view updates, test/update.jl:179-189) in one launch.
     proposals: one entry per block, None (default proposal, update.jl:12-25) or the model's native proposal (update.jl:79-96) -- "Update with
-    different proposals per view" in one launch (gpf.h gpf_update_blocks_proposal)"""
+    different proposals per view" in one launch (gpf.h gpf_update_blocks_proposal).
+    reference: conditional SMC (gpf.h gpf_update_blocks_ref) -- an (n_blocks, dim) array; slot 0 of block b is pinned to reference[b], its
+    log-weight becomes lw + log p(y_b | reference[b]), its x_{t-1} columns (keep_prev) are its incoming latent; every other particle is what the
+    call without a reference gives.  A per-call input, default proposal only (ValueError with proposals= or strata=), all values finite.  A
+    rejuvenation move on slot 0 changes the retained value at the current step."""
+    if reference is not None and (proposals is not None or strata is not None):
+        raise ValueError("a reference is offered with the default proposal only, not with proposals= or strata=")
     obs = _block_obs(state, observations, block_size)
+    if reference is not None:
+        ref = _block_reference(state, reference, obs.shape[0])
+        state._check(state._L.gpf_update_blocks_ref(state._h, _pd(obs), obs.shape[1], int(block_size), _pd(ref), ref.shape[1]))
+        return state
     if strata is not None:                                       # every block stratified by itself (src/update.jl:193-210 per sub-state)
         if proposals is not None:
             raise ErrorException("block-wise updates take strata or per-block proposals, not both")

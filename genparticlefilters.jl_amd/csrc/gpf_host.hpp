@@ -205,6 +205,10 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     int64_t blk_stage_next = 0;                                                        // staging copies issued so far (ticket of the next one - 1)
     int64_t* h_blk_done = nullptr; unsigned int* blk_stage_counter = nullptr;          // pinned: ticket of the last finished staging copy; device: its workgroup counter
     int64_t blk_obs_size = 0;                                                          // > 0: the latest observations are per block, blocks of this size
+    // conditional SMC (gpf_initialize_blocks_ref / gpf_update_blocks_ref): the reference rows of the CURRENT call, [n_blocks][MAX_DIM] on the device
+    // (ModelArgs::blk_ref for the one launch).  They are staged behind the observations in the same pinned buffer (h_blk_obs holds MAX_OBS + MAX_DIM
+    // words per block) and copied by the same launch; nothing of them is kept between calls
+    double* blk_ref = nullptr; int64_t blk_ref_cap = 0;
     // gpf_set_block_params: every block's own model parameters, [n_blocks][MAX_PARAMS] on the device (ModelArgs::blk_params), uploaded once;
     // bp_size > 0: the rows are in force for blocks of this (clamped) size -- the block-wise steps run their BP kernels, everything that would
     // read cfg.params is refused (bp_refused)

@@ -119,9 +119,17 @@ __device__ __forceinline__ void team_max_flags(const double (&v)[ITEMS], int tl,
 
 // PRIO: priority_fn = w -> alpha w (resample.jl:51-52): ancestors from the priorities' CDF, the ESS gate on the raw weights, new weights
 // log_ws + (logsumexp(block weights) - logsumexp(log_ws)) with log_ws = lw[a] - lp[a] (the sub-state form, resample.jl:213-216)
-template <int METHOD, int W, int TEAM, int ITEMS, bool PRIO = false>     // METHOD 0 multinomial, 1 residual, 2 stratified
+// METHOD_COND (conditional SMC, gpf_resample_blocks_conditional; Andrieu, Doucet & Holenstein 2010, the conditional multinomial step): METHOD 0 in
+// which slot 0 of every block that resamples keeps local ancestor 0 -- its own row -- while the slots j >= 1 draw exactly as in METHOD 0 (same
+// counters, same CDF) and every particle gets the same new weight.  A value of METHOD rather than one more template parameter: the names of the
+// instantiations that existed before stay as they are.
+constexpr int METHOD_COND = 3;
+template <int METHOD_, int W, int TEAM, int ITEMS, bool PRIO = false>    // METHOD 0 multinomial, 1 residual, 2 stratified
 __global__ __launch_bounds__(BLOCK) void k_block_resample(BlockArgs a)
 {
+    constexpr bool COND = METHOD_ == METHOD_COND;
+    constexpr int METHOD = COND ? 0 : METHOD_;
+    static_assert(!COND || !PRIO, "the conditional step is multinomial on the raw weights");
     constexpr int TEAMS = BLOCK / TEAM, CAP = TEAM * ITEMS;        // blocks per workgroup, particles a team holds
     static_assert(TEAM == WAVE || TEAM == BLOCK, "a wave or the workgroup");
     __shared__ uint64_t s_cdf_[BLOCK * ITEMS];                     // the CDF that is sampled (weights; residual: residual weights)
@@ -267,6 +275,7 @@ __global__ __launch_bounds__(BLOCK) void k_block_resample(BlockArgs a)
             anc = lds_upper_bound(s_cdf, cnt, L0 + mulhi64(resample_u64(a.seed, slot, a.epoch), L1 - L0));        // :162-166
             if (a.sorted) anc = (int)s_idx[anc];                                                           // :168
         }
+        if (COND && j == 0) anc = 0;                                                                       // the retained path survives
         const double2* src = reinterpret_cast<const double2*>(a.rows_in + (b0 + anc) * W);
         double2* dst = reinterpret_cast<double2*>(a.rows_out + (b0 + j) * W);
 #pragma unroll
@@ -799,6 +808,25 @@ static __global__ __launch_bounds__(BLOCK) void k_stage_obs(const double* __rest
     // (the ticket says "the staging buffer has been READ": every load of this workgroup has returned -- its value went into a store that has
     //  been issued -- before the barrier; nothing the host reads is published, so no fence: an agent / system release is an L2 write-back)
     if (threadIdx.x == 0) {
+        if (__hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
+            __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(host_done, ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+// k_stage_obs with the reference rows of a pinned step behind the observations in the SAME staging buffer: src_host = [n_obs_words | n_ref_words],
+// the first part to dst_obs, the second to dst_ref -- one launch, one ticket
+static __global__ __launch_bounds__(BLOCK) void k_stage_obs_ref(const double* __restrict__ src_host, double* __restrict__ dst_obs, int64_t n_obs_words,
+                                                         double* __restrict__ dst_ref, int64_t n_ref_words,
+                                                         unsigned int* counter, int64_t* host_done, int64_t ticket)
+{
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n_obs_words + n_ref_words; i += (int64_t)gridDim.x * BLOCK) {
+        const double v = src_host[i];
+        if (i < n_obs_words) dst_obs[i] = v; else dst_ref[i - n_obs_words] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {                                        // (the ticket: as k_stage_obs)
         if (__hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
             __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(host_done, ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

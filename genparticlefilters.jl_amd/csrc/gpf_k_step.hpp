@@ -108,12 +108,43 @@ __device__ __forceinline__ void wave_rows_store(double* __restrict__ rows_out, i
 // MODE 0: the model's own sampler; 1: native custom proposal; 2: stratified (the discrete latent constrained per stratum);
 // 3 (k_init only): stratified with a native proposal for the other choice
 // BP (gpf_set_block_params, BLK only): every block's particles use the block's own parameter row (params_of) instead of a.P
-template <int M, int MODE = 0, bool BLK = false, bool BP = false>
+// MODE_REF (BLK only; conditional SMC, gpf_initialize_blocks_ref / gpf_update_blocks_ref): MODE 0 with slot 0 of every block -- the lane with
+// i % blk_size == 0 -- pinned to its block's row of ModelArgs::blk_ref: its latent is that row instead of Model::sample's draw, its weight increment
+// Model::loglik of the row (the bootstrap weight).  Every lane draws as in MODE 0 (counter-based RNG: the pinned lane's draw disturbs nobody, and the
+// wave stays uniform -- the STAGE path of k_step relies on that); the pinned lane then overwrites the draw.  A value of MODE rather than one more
+// template parameter: the names of the instantiations that existed before stay as they are.
+constexpr int MODE_REF = 5;
+// the reference row of particle i's block for the lane that is the block's slot 0 (pin), loaded BEFORE the draw so that its latency hides behind
+// the sampler's arithmetic; pin_reference then selects (no branch around the likelihood)
+template <int D>
+__device__ __forceinline__ bool load_reference(const ModelArgs& a, int64_t i, double (&rv)[D])
+{
+    const uint32_t b = (uint32_t)i / (uint32_t)a.blk_size;            // (the division obs_of / params_of already make)
+    const bool pin = (uint32_t)i - b * (uint32_t)a.blk_size == 0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) rv[k] = 0.0;
+    if (pin) {
+        const double* const ref = a.blk_ref + (size_t)b * MAX_DIM;
+#pragma unroll
+        for (int k = 0; k < D; ++k) rv[k] = ref[k];
+    }
+    return pin;
+}
+template <int D>
+__device__ __forceinline__ void pin_reference(bool pin, const double (&rv)[D], double* x)
+{
+#pragma unroll
+    for (int k = 0; k < D; ++k) x[k] = pin ? rv[k] : x[k];
+}
+template <int M, int MODE_ = 0, bool BLK = false, bool BP = false>
 __global__ __launch_bounds__(BLOCK) void k_init(ModelArgs a, uint64_t seed, uint32_t epoch, int64_t gid0,
                                                 int64_t n, int W, double* __restrict__ rows,
                                                 double* __restrict__ lw, MaxSlots ms)
 {
     using Mo = Model<M>;
+    constexpr bool REF = MODE_ == MODE_REF;
+    constexpr int MODE = REF ? 0 : MODE_;
+    static_assert(!REF || BLK, "a pinned reference is per block");
     double bm = -__builtin_huge_val(); int bf = 0;
     for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
         double x[MAX_DIM];
@@ -129,7 +160,11 @@ __global__ __launch_bounds__(BLOCK) void k_init(ModelArgs a, uint64_t seed, uint
             const double v = a.strata[stratum_of<Mo, BLK>(a, seed, epoch, gid0, i, n, TAG_INIT)];
             ll = Mo::propose_stratum(P, ob, v, x) + a.logK;
         } else {
+            double rv[REF ? Mo::D : 1];
+            bool pin = false;
+            if constexpr (REF) pin = load_reference<Mo::D>(a, i, rv);
             Mo::sample(P, true, nullptr, ob, seed, particle_gid(a, gid0, i), 0, epoch, TAG_INIT, x);
+            if constexpr (REF) pin_reference<Mo::D>(pin, rv, x);
             ll = Mo::loglik(P, x, ob);
         }
         double* r = rows + i * W;
@@ -173,7 +208,7 @@ struct PackedCommit {
 #define GPF_STEP_WAVES_WIDE 4
 #endif
 template <int W> constexpr int step_min_waves() { return W >= 8 ? GPF_STEP_WAVES_WIDE : 4; }
-template <int M, int W, bool KEEP_PREV, bool GATHER, int MODE = 0, bool PACKED = false, bool BLK = false, bool BP = false>
+template <int M, int W, bool KEEP_PREV, bool GATHER, int MODE_ = 0, bool PACKED = false, bool BLK = false, bool BP = false>
 __global__ __launch_bounds__(BLOCK, step_min_waves<W>()) void k_step(ModelArgs a, uint64_t seed, uint32_t epoch, int64_t gid0,
                                                 int64_t n, const int32_t* __restrict__ anc,
                                                 const double* __restrict__ rows_in,
@@ -182,6 +217,9 @@ __global__ __launch_bounds__(BLOCK, step_min_waves<W>()) void k_step(ModelArgs a
 {
     using Mo = Model<M>;
     constexpr int D = Mo::D;
+    constexpr bool REF = MODE_ == MODE_REF;                               // slot 0 of every block pinned to ModelArgs::blk_ref (k_init)
+    constexpr int MODE = REF ? 0 : MODE_;
+    static_assert(!REF || (BLK && !GATHER && !PACKED), "a pinned reference is per block; the block-wise step has no fused gather");
     // a speculative propagate behind the ESS reduction (gpf_step_ess): every wave forms the verdict from the reduction's accumulators and
     // returns before its first store if the filter resamples first (kernel-uniform)
 #ifndef GPF_NO_GATE
@@ -267,7 +305,14 @@ __global__ __launch_bounds__(BLOCK, step_min_waves<W>()) void k_step(ModelArgs a
             const double lp = Mo::sample_stratum(P, false, r, ob, v, seed, particle_gid(a, gid0, i), 0, epoch, TAG_UPDATE, xn);
             ll = (lp + Mo::loglik(P, xn, ob)) + a.logK;                     // update.jl:201-206
         } else {
+            // (wide rows sit at the 128-VGPR cap: a reference row held across the sampler would spill, so there the load comes behind it)
+            constexpr bool REF_EARLY = W < 8;
+            double rv[REF ? D : 1];
+            bool pin = false;
+            if constexpr (REF && REF_EARLY) pin = load_reference<D>(a, i, rv);
             Mo::sample(P, false, r, ob, seed, particle_gid(a, gid0, i), 0, epoch, TAG_UPDATE, xn);
+            if constexpr (REF && !REF_EARLY) pin = load_reference<D>(a, i, rv);
+            if constexpr (REF) pin_reference<D>(pin, rv, xn);           // (lane-local: the STAGE path's wave-uniform conditions are untouched)
             ll = Mo::loglik(P, xn, ob);
         }
         double o[W];

@@ -42,7 +42,10 @@ struct ModelArgs {          // passed by value in the kernarg segment: no device
     // dynamic indices keep their offsets and blk_prop stays next to the kernel argument that follows ModelArgs.)
     const double* blk_params;
     // gpf_update_blocks_proposal: word [block] != 0 = the block's particles are extended with the model's native proposal (MODE 4 of k_step)
-    const int32_t* blk_prop;
+    // gpf_initialize_blocks_ref / gpf_update_blocks_ref: slot 0 of block b is pinned to row b of blk_ref, [block][MAX_DIM] (MODE_REF of k_init / k_step).
+    // The two modes exclude each other (a reference is refused together with a proposal), so the pointers share the slot: ModelArgs keeps its
+    // size and every field its offset, and the kernels that existed before this pointer are unchanged instruction for instruction.
+    union { const int32_t* blk_prop; const double* blk_ref; };
 };
 // the observation particle i conditions on
 template <bool BLK>

@@ -11,6 +11,7 @@ namespace gpfh {
 // block-wise initialise / propagate / move (ModelArgs::blk_*): no fused gather (a block resample gathers eagerly).  MODE 0: the default proposal;
 // 2: stratified; 4 (propagate): per block the native proposal or the default one (ModelArgs::blk_prop).
 // BP: per-block parameters are set (gpf_set_block_params) -- the kernels read block b's row of ModelArgs::blk_params instead of P
+// MODE_REF: MODE 0 with slot 0 of every block pinned to its reference row (ModelArgs::blk_ref, conditional SMC)
 template <int M, int MODE, bool BP>
 void launch_init_blk(gpf_filter* h, int grid)
 {
@@ -35,6 +36,7 @@ void launch_move_blk(gpf_filter* h, int grid, int n_iters)
                        h->acc_part, RW ? next_slots(h) : MaxSlots{nullptr, nullptr});
 }
 // a block of <= 128 / <= 512 particles is the work of one wave (2 / 8 particles per lane, four blocks per workgroup), a larger one of a workgroup
+// METHOD_COND: the conditional multinomial step (slot 0 of every resampling block keeps itself), PRIO = false only
 template <int METHOD, int Wc, bool PRIO>
 void launch_block_resample_w(gpf_filter* h, const BlockArgs& a)
 {
@@ -45,7 +47,8 @@ void launch_block_resample_w(gpf_filter* h, const BlockArgs& a)
 template <int METHOD>
 void launch_block_resample(gpf_filter* h, const BlockArgs& a, bool prio)
 {
-    bool_dispatch(prio, [&](auto PRIO) { DISPATCH_W(h, (launch_block_resample_w<METHOD, WW, PRIO>(h, a))); });
+    if constexpr (METHOD == METHOD_COND) { (void)prio; DISPATCH_W(h, (launch_block_resample_w<METHOD, WW, false>(h, a))); }
+    else bool_dispatch(prio, [&](auto PRIO) { DISPATCH_W(h, (launch_block_resample_w<METHOD, WW, PRIO>(h, a))); });
 }
 
 } // namespace gpfh
@@ -160,17 +163,32 @@ static gpf_status resample_big_blocks(gpf_handle h, int32_t method, int64_t bloc
     }
     return GPF_OK;
 }
-gpf_status gpf_resample_blocks(gpf_handle h, int32_t method, int64_t block_size, double priority_alpha, int32_t sort_particles,
-                               double ess_frac, int32_t check, int32_t* invalid, int64_t* n_resampled)
+static gpf_status resample_blocks_impl(gpf_handle h, int32_t method, int64_t block_size, double priority_alpha, int32_t sort_particles,
+                                       double ess_frac, int32_t check, int32_t* invalid, int64_t* n_resampled, bool conditional)
 {
-    gpf_status s = block_checks(h, block_size, "gpf_resample_blocks");
+    const char* const who = conditional ? "gpf_resample_blocks_conditional" : "gpf_resample_blocks";
+    if (conditional) {                                           // (what can be refused without touching the handle comes first: block_checks brings a lazy move up to date)
+        if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+        if (h->parent) return fail(h, GPF_ERR_STATE, std::string(who) + " on a sub-state view: call it on the filter");
+        if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, std::string(who) + " on a shard of a sharded filter");
+        if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");
+        if (method == GPF_RESAMPLE_RESIDUAL || method == GPF_RESAMPLE_STRATIFIED)
+            return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": multinomial only -- forcing one slot to keep its particle is not a valid conditional scheme "
+                        "for residual or stratified resampling (their slots are not exchangeable)");
+        if (method != GPF_RESAMPLE_MULTINOMIAL) return fail(h, GPF_ERR_UNKNOWN_METHOD, "Resampling method not recognized.");   // resample.jl:28
+        if (h->hist_on && !h->hist_blocks) return fail(h, GPF_ERR_STATE, std::string(who) + " on a filter with a trajectory store");
+        if (std::min<int64_t>(block_size, std::max<int64_t>(h->n, 1)) > BLK_MAX)
+            return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": blocks of more than " + std::to_string(BLK_MAX) + " particles resample through sub-state views, which have no conditional form");
+    }
+    gpf_status s = block_checks(h, block_size, who);
     if (s) return s;
     if (method != GPF_RESAMPLE_MULTINOMIAL && method != GPF_RESAMPLE_RESIDUAL && method != GPF_RESAMPLE_STRATIFIED)
         return fail(h, GPF_ERR_UNKNOWN_METHOD, "Resampling method not recognized.");          // resample.jl:28
-    if (h->hist_on && !h->hist_blocks) return fail(h, GPF_ERR_STATE, "gpf_resample_blocks on a filter with a trajectory store");
-    if ((s = block_store_size(h, block_size, "gpf_resample_blocks"))) return s;
+    if (h->hist_on && !h->hist_blocks) return fail(h, GPF_ERR_STATE, std::string(who) + " on a filter with a trajectory store");
+    if ((s = block_store_size(h, block_size, who))) return s;
     if (h->W != 2 && h->W != 4 && h->W != 8) return fail(h, GPF_ERR_STATE, "row width");
     if ((s = materialize(h))) return s;
+    if (conditional) block_size = std::min<int64_t>(block_size, std::max<int64_t>(h->n, 1));   // ("one block" asked for as any size >= n)
     if (block_size > BLK_MAX) return resample_big_blocks(h, method, block_size, priority_alpha, sort_particles, ess_frac, check, invalid, n_resampled);
     const int64_t nblocks = (h->n + block_size - 1) / block_size;
     if ((s = block_buffers(h, nblocks))) return s;
@@ -184,7 +202,8 @@ gpf_status gpf_resample_blocks(gpf_handle h, int32_t method, int64_t block_size,
     a.check_true = check == GPF_CHECK_TRUE ? 1 : 0;
     a.resampled = h->blk_mask;
     s = timed(h, GPF_K_SEARCH, [&] {
-        if (method == GPF_RESAMPLE_MULTINOMIAL)   launch_block_resample<0>(h, a, prio);
+        if (conditional)                          launch_block_resample<METHOD_COND>(h, a, false);
+        else if (method == GPF_RESAMPLE_MULTINOMIAL) launch_block_resample<0>(h, a, prio);
         else if (method == GPF_RESAMPLE_RESIDUAL) launch_block_resample<1>(h, a, prio);
         else                                      launch_block_resample<2>(h, a, prio);
     });
@@ -210,6 +229,17 @@ gpf_status gpf_resample_blocks(gpf_handle h, int32_t method, int64_t block_size,
         if (check == GPF_CHECK_TRUE && words[0]) return fail(h, GPF_ERR_INVALID_WEIGHTS, "Invalid weights.");   // resample.jl:55
     }
     return GPF_OK;
+}
+gpf_status gpf_resample_blocks(gpf_handle h, int32_t method, int64_t block_size, double priority_alpha, int32_t sort_particles,
+                               double ess_frac, int32_t check, int32_t* invalid, int64_t* n_resampled)
+{
+    return resample_blocks_impl(h, method, block_size, priority_alpha, sort_particles, ess_frac, check, invalid, n_resampled, false);
+}
+// the conditional multinomial step of conditional SMC (Andrieu, Doucet & Holenstein 2010) for every block -- gpf.h
+gpf_status gpf_resample_blocks_conditional(gpf_handle h, int32_t method, int64_t block_size, double ess_frac, int32_t check,
+                                           int32_t* invalid, int64_t* n_resampled)
+{
+    return resample_blocks_impl(h, method, block_size, __builtin_nan(""), 0, ess_frac, check, invalid, n_resampled, true);
 }
 gpf_status gpf_block_resampled(gpf_handle h, int32_t* out)
 {
@@ -377,7 +407,9 @@ gpf_status gpf_block_proportion(gpf_handle h, int64_t block_size, int32_t column
 }
 
 // the blocks' observation vectors -> device ([n_blocks][MAX_OBS], zero-padded), ModelArgs::blk_* set
-static gpf_status set_block_obs(gpf_filter* h, const double* obs, int32_t n_obs, int64_t block_size)
+// ref (a pinned step, [n_blocks][dim], validated by the caller): the reference rows travel behind the observations in the same staging buffer and the
+// same launch into blk_ref ([n_blocks][MAX_DIM], zero-padded)
+static gpf_status set_block_obs(gpf_filter* h, const double* obs, int32_t n_obs, int64_t block_size, const double* ref = nullptr)
 {
     if (!obs || n_obs != model_obs_dim(h->cfg.model))
         return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model takes " + std::to_string(model_obs_dim(h->cfg.model)) + " observation values per step and block");
@@ -389,13 +421,20 @@ static gpf_status set_block_obs(gpf_filter* h, const double* obs, int32_t n_obs,
             for (int k = 0; k < gpf_filter::BLK_STAGE; ++k) { (void)hipHostFree(h->h_blk_obs[k]); h->h_blk_obs[k] = nullptr; }
         }
         HIP_TRY(h, hipMalloc(&h->blk_obs, (size_t)nblocks * MAX_OBS * sizeof(double)));
-        for (int k = 0; k < gpf_filter::BLK_STAGE; ++k) HIP_TRY(h, hipHostMalloc(&h->h_blk_obs[k], (size_t)nblocks * MAX_OBS * sizeof(double)));
+        // (MAX_DIM more words per block: the reference rows of a pinned step.  blk_obs_cap is also the capacity of these buffers: they are only ever
+        //  reallocated here, together with blk_obs, and gpf_resample_across_blocks swaps in a second buffer of at least this capacity)
+        for (int k = 0; k < gpf_filter::BLK_STAGE; ++k) HIP_TRY(h, hipHostMalloc(&h->h_blk_obs[k], (size_t)nblocks * (MAX_OBS + MAX_DIM) * sizeof(double)));
         if (!h->h_blk_done) {
             HIP_TRY(h, hipHostMalloc(&h->h_blk_done, sizeof(int64_t))); *h->h_blk_done = 0;
             HIP_TRY(h, hipMalloc(&h->blk_stage_counter, sizeof(unsigned int)));
             HIP_TRY(h, hipMemsetAsync(h->blk_stage_counter, 0, sizeof(unsigned int), h->stream));
         }
         h->blk_obs_cap = nblocks;
+    }
+    if (ref && h->blk_ref_cap < nblocks) {
+        if (h->blk_ref) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->blk_ref); h->blk_ref = nullptr; h->blk_ref_cap = 0; }
+        HIP_TRY(h, hipMalloc(&h->blk_ref, (size_t)nblocks * MAX_DIM * sizeof(double)));
+        h->blk_ref_cap = nblocks;
     }
     // the staging buffers are used in turn: wait only until the copy that last read THIS buffer (four calls ago) has finished -- its
     // kernel publishes a ticket to pinned memory -- not for the stream
@@ -417,6 +456,18 @@ static gpf_status set_block_obs(gpf_filter* h, const double* obs, int32_t n_obs,
     for (int64_t b = 0; b < nblocks; ++b)
         for (int i = 0; i < MAX_OBS; ++i) stage[b * MAX_OBS + i] = i < n_obs ? obs[b * n_obs + i] : 0.0;
     const int64_t n_words = nblocks * MAX_OBS;
+    if (ref) {
+        const int dim = model_dim(h->cfg.model);
+        double* const rs = stage + n_words;
+        static_assert(MAX_DIM == 4, "the four columns of a staged reference row");
+        for (int64_t b = 0; b < nblocks; ++b) {
+            double* const d = rs + b * MAX_DIM; const double* const r = ref + b * dim;
+            d[0] = r[0]; d[1] = dim > 1 ? r[1] : 0.0; d[2] = dim > 2 ? r[2] : 0.0; d[3] = dim > 3 ? r[3] : 0.0;
+        }
+        const int64_t n_ref_words = nblocks * MAX_DIM;
+        GPF_LAUNCH(k_stage_obs_ref, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(64, (n_words + n_ref_words + BLOCK - 1) / BLOCK))), dim3(BLOCK), 0, h->stream,
+                   stage, h->blk_obs, n_words, h->blk_ref, n_ref_words, h->blk_stage_counter, h->h_blk_done, h->blk_stage_next);
+    } else
     GPF_LAUNCH(k_stage_obs, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(64, (n_words + BLOCK - 1) / BLOCK))), dim3(BLOCK), 0, h->stream,
                stage, h->blk_obs, n_words, h->blk_stage_counter, h->h_blk_done, h->blk_stage_next);
     HIP_TRY(h, hipGetLastError());
@@ -451,28 +502,34 @@ static gpf_status block_store_room(gpf_filter* h)
 }
 // The block-wise pf_initialize / pf_update! once the caller's checks (the observations among them: hist_begin_step comes before set_block_obs) have passed (a refused call changes nothing).  mode 0: the default proposal;
 // 2: stratified (the caller set the strata); 4 (update): block b is extended with the native proposal where use_proposal[b] != 0.
-static gpf_status block_initialize_impl(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, int mode)
+// ref != nullptr (mode 0 only): slot 0 of every block is pinned to its row of ref (MODE_REF of the kernels).
+static gpf_status block_initialize_impl(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, int mode, const double* ref = nullptr)
 {
     h->generation += 1;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     gpf_status s = hist_begin_step(h, true);                     // (the block-wise store: step 1)
-    if (s || (s = set_block_obs(h, obs, n_obs, block_size))) return s;
+    if (s || (s = set_block_obs(h, obs, n_obs, block_size, ref))) return s;
+    if (ref) h->args.blk_ref = h->blk_ref;
     const int grid = step_grid(h);
     s = timed(h, GPF_K_STEP, [&] {
         bool_dispatch(h->bp_size > 0, [&](auto BP) {
-            if (mode == 2) { DISPATCH_MODEL(h, (launch_init_blk<MM, 2, BP>(h, grid))); }
-            else           { DISPATCH_MODEL(h, (launch_init_blk<MM, 0, BP>(h, grid))); }
+            if (ref)            { DISPATCH_MODEL(h, (launch_init_blk<MM, MODE_REF, BP>(h, grid))); }
+            else if (mode == 2) { DISPATCH_MODEL(h, (launch_init_blk<MM, 2, BP>(h, grid))); }
+            else                { DISPATCH_MODEL(h, (launch_init_blk<MM, 0, BP>(h, grid))); }
         });
     });
+    h->args.blk_ref = nullptr;                                   // (the reference is this call's input: nothing of it stays)
     if (s || (s = after_initialize(h, grid))) return s;
     h->blk_last = 0;                                             // only_resampled refers to a gpf_resample_blocks of the CURRENT step
     return GPF_OK;
 }
-static gpf_status block_update_impl(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, int mode, const int32_t* use_proposal)
+static gpf_status block_update_impl(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, int mode, const int32_t* use_proposal,
+                                    const double* ref = nullptr)
 {
     gpf_status s = materialize(h);                               // (no fused gather in the block-wise step)
     // (the block-wise store: the step that ends is snapshotted and the next one begins; the entry points have checked the observations and the store's room)
-    if (s || (s = hist_begin_step(h, false)) || (s = set_block_obs(h, obs, n_obs, block_size))) return s;
+    if (s || (s = hist_begin_step(h, false)) || (s = set_block_obs(h, obs, n_obs, block_size, ref))) return s;
+    if (ref) h->args.blk_ref = h->blk_ref;                       // (shares its slot with blk_prop: mode 4 and a reference exclude each other)
     if (mode == 4) {
         const int64_t nblocks = (h->n + block_size - 1) / block_size;
         if ((s = block_buffers(h, nblocks))) return s;           // (blk_mask doubles as the flag array: no block resample refers to it after this call)
@@ -483,7 +540,8 @@ static gpf_status block_update_impl(gpf_handle h, const double* obs, int32_t n_o
     const int grid = step_grid(h);
     s = timed(h, GPF_K_STEP, [&] {
         bool_dispatch(h->cfg.keep_prev != 0, h->bp_size > 0, [&](auto KEEP, auto BP) {
-            if (mode == 4)      { DISPATCH_MODEL(h, (launch_step_blk<MM, 4, KEEP, BP>(h, grid))); }
+            if (ref)            { DISPATCH_MODEL(h, (launch_step_blk<MM, MODE_REF, KEEP, BP>(h, grid))); }
+            else if (mode == 4) { DISPATCH_MODEL(h, (launch_step_blk<MM, 4, KEEP, BP>(h, grid))); }
             else if (mode == 2) { DISPATCH_MODEL(h, (launch_step_blk<MM, 2, KEEP, BP>(h, grid))); }
             else                { DISPATCH_MODEL(h, (launch_step_blk<MM, 0, KEEP, BP>(h, grid))); }
         });
@@ -505,6 +563,35 @@ gpf_status gpf_update_blocks(gpf_handle h, const double* obs, int32_t n_obs, int
     gpf_status s = block_step_checks(h, block_size, "gpf_update_blocks", obs, n_obs, true);
     if (s || (s = check_ready(h)) || (s = block_store_room(h))) return s;
     return block_update_impl(h, obs, n_obs, block_size, 0, nullptr);
+}
+// the reference rows of a pinned step, checked on the host before anything changes: [n_blocks][n_ref] with n_ref = the model's dimension, all finite
+static gpf_status block_ref_checks(gpf_filter* h, int64_t block_size, const double* ref, int32_t n_ref, const char* who)
+{
+    const int dim = model_dim(h->cfg.model);
+    if (!ref || n_ref != dim)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": the reference has " + std::to_string(dim) + " values per block (the model's latent columns)");
+    const int64_t nblocks = (h->n + block_size - 1) / block_size;
+    // (one branch-free pass over the exponent fields -- all ones = NaN or +-Inf --, so that the check of 10^4 blocks costs a few microseconds; the
+    //  offender is looked for only when there is one)
+    uint64_t bad = 0;
+    for (int64_t k = 0; k < nblocks * dim; ++k) { uint64_t u; memcpy(&u, ref + k, sizeof(u)); bad |= (uint64_t)(((u >> 52) & 0x7ffu) == 0x7ffu); }
+    if (bad)
+        for (int64_t k = 0; k < nblocks * dim; ++k)
+            if (!(ref[k] - ref[k] == 0.0)) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": the reference of block " + std::to_string(k / dim) + " is not finite");
+    return GPF_OK;
+}
+// conditional SMC: the block-wise pf_initialize / pf_update! with slot 0 of every block pinned to a reference row -- gpf.h
+gpf_status gpf_initialize_blocks_ref(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, const double* ref, int32_t n_ref)
+{
+    gpf_status s = block_step_checks(h, block_size, "gpf_initialize_blocks_ref", obs, n_obs, true);
+    if (s || (s = block_ref_checks(h, block_size, ref, n_ref, "gpf_initialize_blocks_ref"))) return s;
+    return block_initialize_impl(h, obs, n_obs, block_size, 0, ref);
+}
+gpf_status gpf_update_blocks_ref(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, const double* ref, int32_t n_ref)
+{
+    gpf_status s = block_step_checks(h, block_size, "gpf_update_blocks_ref", obs, n_obs, true);
+    if (s || (s = block_ref_checks(h, block_size, ref, n_ref, "gpf_update_blocks_ref")) || (s = check_ready(h)) || (s = block_store_room(h))) return s;
+    return block_update_impl(h, obs, n_obs, block_size, 0, nullptr, ref);
 }
 // for b in blocks: pf_initialize(model, args, observations[b], strata, n_b) / pf_update!(state[b], ..., observations[b], strata) -- stratified
 // initialisation / update (src/initialize.jl:92-109, src/update.jl:193-210) of every block by itself, one launch: the stratum of a particle

@@ -174,6 +174,26 @@ gpf_status gpf_resample_local(gpf_handle h, int32_t method, int32_t sort_particl
  * Not on sharded filters, views or filters with a whole-filter trajectory store (GPF_ERR_STATE). */
 gpf_status gpf_resample_blocks(gpf_handle h, int32_t method, int64_t block_size, double priority_alpha, int32_t sort_particles,
                                double ess_frac, int32_t check, int32_t* invalid, int64_t* n_resampled);
+/* Conditional SMC, the resampling half: gpf_resample_blocks(method = multinomial, priority_fn nothing) in which the RETAINED particle of every
+ * block -- slot 0, particle b * block_size -- survives.  This is the conditional multinomial step of Andrieu, Doucet & Holenstein (2010), "Particle
+ * Markov chain Monte Carlo methods", JRSS B 72(3), section 4.3 (conditional SMC update, step (b): "sample A_{n-1}^{-B} ~ r(. | W_{n-1}, B)"); the
+ * reference package has no counterpart (src/resample.jl:19-175 resamples every slot).  In every block that resamples:
+ *   - slot 0's ancestor is local index 0: its row is copied from the block's own slot 0, and gpf_parents / the trajectory store record parent 0;
+ *   - the slots j >= 1 get exactly the ancestors of the unconditional call: the same counters (slot b * block_size + j, the call's epoch), the
+ *     same CDF over ALL particles of the block, slot 0 included;
+ *   - the new weights are gpf_resample_blocks's: every particle of the block carries logsumexp(block weights) - log(block size).
+ * ess_frac, check, invalid, n_resampled, the validity flags, gpf_block_resampled and the epoch advance are those of gpf_resample_blocks; the
+ * block-wise trajectory store composes the recorded parents as it does there.  With gpf_{initialize,update}_blocks_ref below this is the
+ * conditional filter particle Gibbs and the cSMC rejuvenation of SMC^2 run per block.
+ * Refused with the state untouched, epoch included:
+ *   - method GPF_RESAMPLE_RESIDUAL or _STRATIFIED (GPF_ERR_INVALID_ARGUMENT): forcing one slot is not a valid conditional scheme for them --
+ *     their slots are not exchangeable, the conditional law of the other ancestors given the retained one is not their unconditional law;
+ *   - there is no priority_fn argument: priorities are not offered;
+ *   - blocks of more than 2048 particles (GPF_ERR_INVALID_ARGUMENT): they resample through the loop over view handles, which has no conditional form;
+ *   - everything gpf_resample_blocks refuses: views, shards of a sharded filter, filters with a whole-filter trajectory store (GPF_ERR_STATE),
+ *     block_size < 1, an unknown method. */
+gpf_status gpf_resample_blocks_conditional(gpf_handle h, int32_t method, int64_t block_size, double ess_frac, int32_t check,
+                                           int32_t* invalid, int64_t* n_resampled);
 /* which blocks the last gpf_resample_blocks resampled: out[ceil(n / block_size)] (host), 1 / 0 */
 gpf_status gpf_block_resampled(gpf_handle h, int32_t* out);
 /* effective_sample_size(state[b]) and log_ml_estimate(state[b]) = log_ml_est + logsumexp(block weights) - log(block size) of every block
@@ -223,6 +243,27 @@ gpf_status gpf_update_blocks_proposal(gpf_handle h, const double* obs, int32_t n
 gpf_status gpf_initialize_blocks_strata(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, const double* values, int32_t n_strata, int32_t interleaved);
 gpf_status gpf_update_blocks_strata(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, const double* values, int32_t n_strata, int32_t interleaved);
 gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, int32_t only_resampled, uint64_t* n_accepted);
+/* Conditional SMC, the propagation half: gpf_initialize_blocks / gpf_update_blocks with ONE PARTICLE PER BLOCK PINNED to a given value -- the
+ * conditional filter of Andrieu, Doucet & Holenstein (2010), section 4.3 (step (a) / (b): "set X_n^{B_n} = the retained path, sample the other
+ * N - 1 particles"), on the reference's per-view loop
+ *     for b in blocks; pf_update!(state[b], new_args, argdiffs, observations[b]); end      (test/update.jl:179-189; src/update.jl:12-25)
+ * of which the reference itself has no conditional form.
+ *   ref: HOST [n_blocks][n_ref] doubles, row b for block b, n_ref = the model's dimension (its latent columns); a per-call input: the library
+ *        keeps no "conditional mode" and no copy of the reference between calls.
+ * Slot 0 of block b is particle b * block_size.  Its latent columns become ref[b] instead of the model's draw; its weight increment is
+ * log p(y_b | ref[b]) under the block's parameters -- the bootstrap weight, no transition density is needed; on an update lw' = lw + that
+ * increment with the incoming lw, and with keep_prev the x_{t-1} columns are the incoming row's latent columns, as for any particle; every other
+ * column is 0.  Every other particle is bit-identical to the same call without a reference on the same incoming state (counter-based RNG: slot
+ * 0's unused counters disturb nobody).  Epoch advance, per-block observations, the tracked maximum and flags and the trajectory store's snapshot
+ * behave as in the plain call; the store records the pinned value.  Works with and without gpf_set_block_params and keep_prev, for any block size.
+ * The values of DISCRETE latents in ref (the moving / slope / outlier indicators of the models that have one) are the caller's business: they are
+ * stored as given.  Rejuvenation is not restricted: a move on slot 0 changes the retained value at the current step.
+ * Refused with nothing changed (no store, launch, epoch advance or trajectory-store step), GPF_ERR_INVALID_ARGUMENT:
+ *   - ref NULL, n_ref other than the model's dimension, any value of ref not finite (NaN, +-Inf);
+ *   - everything the plain calls refuse (their status codes).
+ * Pinning is offered with the default proposal only: the strata, per-block-proposal and native-proposal forms take no reference. */
+gpf_status gpf_initialize_blocks_ref(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, const double* ref, int32_t n_ref);
+gpf_status gpf_update_blocks_ref(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, const double* ref, int32_t n_ref);
 /* for b in blocks: the model arguments of state[b] (src/update.jl:12-25 on a sub-state with new_args_b) -- many parameter values in one state,
  * e.g. the likelihood p(y_1:T | theta_b) of every block from gpf_block_stats.
  *   params: HOST [n_blocks][n_params] doubles, row b = block b's parameter vector in the layout of csrc/gpf_models.hpp (derived constants

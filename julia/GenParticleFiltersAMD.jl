@@ -216,6 +216,17 @@ function pf_resample_blocks!(s::DeviceParticleFilterState, block_size::Int, meth
     check === :warn && invalid[] != 0 && @warn("Invalid weights in some block: resampled with uniform weights.")
     return Int(count[])
 end
+# Conditional SMC, the resampling half (gpf.h gpf_resample_blocks_conditional; Andrieu, Doucet & Holenstein 2010): multinomial block-wise resampling in
+# which slot 0 of every block that resamples keeps itself (parent 0); the other slots draw as in pf_resample_blocks!.  Blocks of <= 2048 particles.
+function pf_resample_blocks_conditional!(s::DeviceParticleFilterState, block_size::Int; ess_frac=nothing, check=:warn)
+    chk = check === true ? 2 : (check === :warn ? 1 : 0)
+    invalid = Ref{Cint}(0); count = Ref{Int64}(0)
+    st = ccall((:gpf_resample_blocks_conditional, libgpf), Cint, (Ptr{Cvoid}, Cint, Int64, Cdouble, Cint, Ptr{Cint}, Ptr{Int64}),
+               s.handle, 0, block_size, ess_frac === nothing ? NaN : Float64(ess_frac), chk, invalid, count)
+    _status(s, st)
+    check === :warn && invalid[] != 0 && @warn("Invalid weights in some block: resampled with uniform weights.")
+    return Int(count[])
+end
 "(effective_sample_size(state[b]), log_ml_estimate(state[b])) of every block of block_size particles (src/utils.jl:163-178), one launch"
 function block_stats(s::DeviceParticleFilterState, block_size::Int)
     nb = cld(s.n_particles, block_size)
@@ -318,6 +329,20 @@ end
 function pf_update_blocks!(s::DeviceParticleFilterState, new_args::Tuple, argdiffs::Tuple, observations::Matrix{Float64}, block_size::Int)
     size(observations, 2) == cld(s.n_particles, block_size) || error("one observation column per block expected")
     _status(s, ccall((:gpf_update_blocks, libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Int64), s.handle, observations, size(observations, 1), block_size)); s
+end
+# Conditional SMC, the propagation half (gpf.h gpf_initialize_blocks_ref / gpf_update_blocks_ref): slot 0 of block b is pinned to reference[:, b] (a
+# (dim, n_blocks) Matrix -- column b for block b) and weighted by log p(y_b | reference[:, b]); every other particle as without a reference.
+function pf_initialize_blocks_ref(model::NativeModel, model_args::Tuple, observations::Matrix{Float64}, reference::Matrix{Float64}, n_particles::Int, block_size::Int; history::Integer=0, kw...)
+    state = DeviceParticleFilterState(model, n_particles; history=history, history_blocks=history > 0, kw...)
+    size(observations, 2) == size(reference, 2) == cld(n_particles, block_size) || error("one observation column and one reference column per block expected")
+    _status(state, ccall((:gpf_initialize_blocks_ref, libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Int64, Ptr{Cdouble}, Cint),
+                         state.handle, observations, size(observations, 1), block_size, reference, size(reference, 1)))
+    return state
+end
+function pf_update_blocks_ref!(s::DeviceParticleFilterState, new_args::Tuple, argdiffs::Tuple, observations::Matrix{Float64}, reference::Matrix{Float64}, block_size::Int)
+    size(observations, 2) == size(reference, 2) == cld(s.n_particles, block_size) || error("one observation column and one reference column per block expected")
+    _status(s, ccall((:gpf_update_blocks_ref, libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Int64, Ptr{Cdouble}, Cint),
+                     s.handle, observations, size(observations, 1), block_size, reference, size(reference, 1))); s
 end
 # every block stratified by itself (src/initialize.jl:92-109 / src/update.jl:193-210 on each sub-state), one launch; strata: the values of the model's discrete latent
 function pf_initialize_blocks(model::NativeModel, model_args::Tuple, observations::Matrix{Float64}, strata::Vector{Float64}, n_particles::Int, block_size::Int; layout::Symbol=:contiguous, kw...)
