@@ -440,6 +440,13 @@ inline int move_grid(const gpf_filter* h) { return std::min(grid_for(h, h->n, MO
         case 4: { constexpr int WW = 4; CALL; } break;                                           \
         case 8: { constexpr int WW = 8; CALL; } break;                                           \
     }
+// the latent dimension of the filter (1, 2 or 4 columns; the caller has refused any other) as constexpr int DD
+#define DISPATCH_D(h, CALL)                                                                      \
+    switch ((h)->d) {                                                                            \
+        case 1: { constexpr int DD = 1; CALL; } break;                                           \
+        case 2: { constexpr int DD = 2; CALL; } break;                                           \
+        case 4: { constexpr int DD = 4; CALL; } break;                                           \
+    }
 
 // f(std::bool_constant<a>{}[, std::bool_constant<b>{}]): runtime flags as template arguments, e.g. launch_x<MM, KEEP, BP> with KEEP, BP the arguments
 template <class F>

@@ -467,9 +467,29 @@ __global__ __launch_bounds__(BLOCK) void k_block_moments(const double* __restric
         }
     }
 }
-// proportionmap: out[blk][j] = sum of the normalised weights of block blk's particles whose `col` equals v[j], j < n  (statistics.jl:91-101)
+// proportionmap of one block: out[blk][j] = sum of the weights w of the lane's values x that equal mv.v[j], j < mv.n
 constexpr int BLK_MATCH_MAX = 16;
 struct BlockMatch { double v[BLK_MATCH_MAX]; int n; };
+template <int TEAM, int ITEMS>
+__device__ __forceinline__ void block_match_pass(const double (&w)[ITEMS], const double (&x)[ITEMS], int cnt, int tl, const BlockMatch& mv,
+                                                 double* __restrict__ out, int64_t blk, double (*s_t)[2])
+{
+#pragma unroll 1
+    for (int j = 0; j < mv.n; j += 2) {                            // two match values per pass (mv.v is padded to an even count)
+        const double a0 = mv.v[j], a1 = mv.v[j + 1];
+        double t0[ITEMS], t1[ITEMS];
+#pragma unroll
+        for (int k = 0; k < ITEMS; ++k) {
+            const bool in = ITEMS * tl + k < cnt;
+            t0[k] = in ? w[k] * (x[k] == a0 ? 1.0 : 0.0) : 0.0;
+            t1[k] = in ? w[k] * (x[k] == a1 ? 1.0 : 0.0) : 0.0;
+        }
+        double p[2] = {lane_tree<ITEMS>(t0), lane_tree<ITEMS>(t1)};
+        team_tree2<TEAM>(p, s_t);
+        if (tl == 0) { out[blk * mv.n + j] = p[0]; if (j + 1 < mv.n) out[blk * mv.n + j + 1] = p[1]; }
+    }
+}
+// proportionmap: out[blk][j] = sum of the normalised weights of block blk's particles whose `col` equals v[j], j < n  (statistics.jl:91-101)
 template <int TEAM, int ITEMS>
 __global__ __launch_bounds__(BLOCK) void k_block_proportion(const double* __restrict__ rows, int W, int col, const double* __restrict__ lw, int64_t n, int64_t nb,
                                                             int64_t nblocks, BlockMatch mv, double* __restrict__ out)
@@ -494,20 +514,7 @@ __global__ __launch_bounds__(BLOCK) void k_block_proportion(const double* __rest
     double x[ITEMS];
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) { const int i = ITEMS * tl + k; x[k] = i < cnt ? rows[(b0 + i) * W + col] : 0.0; }
-#pragma unroll 1
-    for (int j = 0; j < mv.n; j += 2) {                            // two match values per pass (mv.v is padded to an even count)
-        const double a0 = mv.v[j], a1 = mv.v[j + 1];
-        double t0[ITEMS], t1[ITEMS];
-#pragma unroll
-        for (int k = 0; k < ITEMS; ++k) {
-            const bool in = ITEMS * tl + k < cnt;
-            t0[k] = in ? w[k] * (x[k] == a0 ? 1.0 : 0.0) : 0.0;
-            t1[k] = in ? w[k] * (x[k] == a1 ? 1.0 : 0.0) : 0.0;
-        }
-        double p[2] = {lane_tree<ITEMS>(t0), lane_tree<ITEMS>(t1)};
-        team_tree2<TEAM>(p, s_t);
-        if (tl == 0) { out[blk * mv.n + j] = p[0]; if (j + 1 < mv.n) out[blk * mv.n + j + 1] = p[1]; }
-    }
+    block_match_pass<TEAM, ITEMS>(w, x, cnt, tl, mv, out, blk, s_t);
 }
 
 // ----------------------------------------------------------------------------- per-block estimates of a PAST choice: the trajectory store, block by block
@@ -615,20 +622,7 @@ __global__ __launch_bounds__(BLOCK) void k_block_hist_proportion(const int32_t* 
     double x[ITEMS];
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) x[k] = ITEMS * tl + k < cnt ? hx[idx[k] * d + col] : 0.0;
-#pragma unroll 1
-    for (int j = 0; j < mv.n; j += 2) {                            // two match values per pass (mv.v is padded to an even count)
-        const double a0 = mv.v[j], a1 = mv.v[j + 1];
-        double t0[ITEMS], t1[ITEMS];
-#pragma unroll
-        for (int k = 0; k < ITEMS; ++k) {
-            const bool in = ITEMS * tl + k < cnt;
-            t0[k] = in ? w[k] * (x[k] == a0 ? 1.0 : 0.0) : 0.0;
-            t1[k] = in ? w[k] * (x[k] == a1 ? 1.0 : 0.0) : 0.0;
-        }
-        double p[2] = {lane_tree<ITEMS>(t0), lane_tree<ITEMS>(t1)};
-        team_tree2<TEAM>(p, s_t);
-        if (tl == 0) { out[blk * mv.n + j] = p[0]; if (j + 1 < mv.n) out[blk * mv.n + j + 1] = p[1]; }
-    }
+    block_match_pass<TEAM, ITEMS>(w, x, cnt, tl, mv, out, blk, s_t);
 }
 
 // ----------------------------------------------------------------------------- whole trajectories per block: the ancestral paths of the store

@@ -35,14 +35,24 @@ void launch_move_blk(gpf_filter* h, int grid, int n_iters)
                        h->cfg.gid0, h->n, (int)h->has_prev, n_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw,
                        h->acc_part, RW ? next_slots(h) : MaxSlots{nullptr, nullptr});
 }
-// a block of <= 128 / <= 512 particles is the work of one wave (2 / 8 particles per lane, four blocks per workgroup), a larger one of a workgroup
+// a block of <= 128 / <= 512 particles is the work of one wave (2 / 8 particles per lane, BLOCK / WAVE blocks per workgroup), a larger one of a workgroup:
+// f(TEAM, ITEMS, grid) with TEAM and ITEMS as std::integral_constant -- the template arguments of the block kernels (gpf_k_block.hpp) -- and their grid
+template <class F>
+inline void team_dispatch(int64_t block_size, int64_t nblocks, F&& f)
+{
+    constexpr int TEAMS = BLOCK / WAVE;                          // wave teams of a workgroup
+    const dim3 waves((unsigned)((nblocks + TEAMS - 1) / TEAMS)), groups((unsigned)nblocks);
+    if (block_size <= 2 * WAVE)      f(std::integral_constant<int, WAVE>{}, std::integral_constant<int, 2>{}, waves);
+    else if (block_size <= 8 * WAVE) f(std::integral_constant<int, WAVE>{}, std::integral_constant<int, 8>{}, waves);
+    else                             f(std::integral_constant<int, BLOCK>{}, std::integral_constant<int, 8>{}, groups);
+}
 // METHOD_COND: the conditional multinomial step (slot 0 of every resampling block keeps itself), PRIO = false only
 template <int METHOD, int Wc, bool PRIO>
 void launch_block_resample_w(gpf_filter* h, const BlockArgs& a)
 {
-    if (a.nb <= 2 * WAVE)      GPF_LAUNCH((k_block_resample<METHOD, Wc, WAVE, 2, PRIO>), dim3((unsigned)((a.nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, a);
-    else if (a.nb <= 8 * WAVE) GPF_LAUNCH((k_block_resample<METHOD, Wc, WAVE, 8, PRIO>), dim3((unsigned)((a.nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, a);
-    else                       GPF_LAUNCH((k_block_resample<METHOD, Wc, BLOCK, 8, PRIO>), dim3((unsigned)a.nblocks), dim3(BLOCK), 0, h->stream, a);
+    team_dispatch(a.nb, a.nblocks, [&](auto TEAM, auto ITEMS, dim3 grid) {
+        GPF_LAUNCH((k_block_resample<METHOD, Wc, TEAM, ITEMS, PRIO>), grid, dim3(BLOCK), 0, h->stream, a);
+    });
 }
 template <int METHOD>
 void launch_block_resample(gpf_filter* h, const BlockArgs& a, bool prio)
@@ -68,24 +78,37 @@ static gpf_status block_buffers(gpf_filter* h, int64_t nblocks)
     }
     return GPF_OK;
 }
-static gpf_status block_checks(gpf_handle h, int64_t block_size, const char* who)
+// The preconditions of a block-wise call, in ONE order for every entry point ("the gate of the block-wise calls"); `steps` names the ones
+// the entry point has.  Nothing here touches the handle -- check_ready, which brings a lazy move or a view up to date, comes after the gate and after the
+// entry point's own checks -- so a refused call changes nothing.  The null handle is refused always.
+enum : unsigned {
+    GATE_VIEW = 1, GATE_SHARD = 2,
+    GATE_STORE = 4,            // a filter with the plain trajectory store (gpf_history_enable) takes no block-wise call
+    GATE_STORE_VIEWS = 8,      //   ... and says why: the estimates of big blocks are the work of sub-state views, which it does not have
+    GATE_SIZE = 16,            // block_size < 1
+    GATE_CLAMP = 32,           // block_size comes back clamped to the particle count: "one block" may be asked for as any size >= n, 2^32 included (the
+                               // step kernels divide by it as a 32-bit number, ModelArgs::blk_size, and n < 2^31)
+    GATE_CLAMP_STORE = 64,     //   ... only on a filter with the block-wise store (elsewhere a size >= n stays what it is: above BLK_MAX the work of a view)
+    GATE_MAX = 128,            // blocks of more than BLK_MAX particles are the work of view handles (below), which a filter with the block-wise store
+                               // (gpf_history_enable_blocks) does not have
+    GATE_PARAMS = 256,         // the block size of the per-block parameters, where they are set
+    GATE_FILTER = GATE_VIEW | GATE_SHARD | GATE_STORE | GATE_SIZE,
+};
+static gpf_status block_gate(gpf_handle h, int64_t& block_size, const char* who, unsigned steps)
 {
-    gpf_status s = check_ready(h);
-    if (s) return s;
-    if (h->parent) return fail(h, GPF_ERR_STATE, std::string(who) + " on a sub-state view: call it on the filter");
-    if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, std::string(who) + " on a shard of a sharded filter");
-    if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");
-    return GPF_OK;
-}
-// A filter with a trajectory store has no sub-state views, and blocks of more than BLK_MAX particles are the work of view handles (below): on a
-// filter with the block-wise store (gpf_history_enable_blocks) such a call is refused.  block_size comes back clamped to the particle count
-// ("one block" asked for as any size >= n is one block of n particles).
-static gpf_status block_store_size(gpf_filter* h, int64_t& block_size, const char* who)
-{
-    if (!h->hist_blocks) return GPF_OK;
-    block_size = std::min<int64_t>(block_size, std::max<int64_t>(h->n, 1));
-    if (block_size > BLK_MAX)
+    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+    if ((steps & GATE_VIEW) && h->parent) return fail(h, GPF_ERR_STATE, std::string(who) + " on a sub-state view: call it on the filter");
+    if ((steps & GATE_SHARD) && h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, std::string(who) + " on a shard of a sharded filter");
+    if ((steps & GATE_STORE) && h->hist_on && !h->hist_blocks)
+        return fail(h, GPF_ERR_STATE, std::string(who) + " on a filter with a trajectory store" + ((steps & GATE_STORE_VIEWS) ? " (it has no sub-state views)" : ""));
+    if ((steps & GATE_SIZE) && block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");
+    const int64_t clamped = std::min<int64_t>(block_size, std::max<int64_t>(h->n, 1));
+    if ((steps & GATE_CLAMP) || ((steps & GATE_CLAMP_STORE) && h->hist_blocks)) block_size = clamped;
+    if ((steps & GATE_MAX) && h->hist_blocks && clamped > BLK_MAX)
         return fail(h, GPF_ERR_STATE, std::string(who) + ": blocks of more than " + std::to_string(BLK_MAX) + " particles on a filter with a trajectory store (they would need sub-state views)");
+    if ((steps & GATE_PARAMS) && h->bp_size > 0 && block_size != h->bp_size)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": block_size " + std::to_string(block_size) + " differs from the " +
+                    std::to_string(h->bp_size) + " of the per-block parameters (gpf_set_block_params)");
     return GPF_OK;
 }
 // Blocks of more than BLK_MAX = 2048 particles do not fit the one-workgroup-per-block kernels (gpf_k_block.hpp keeps a block's weights, CDF
@@ -108,13 +131,27 @@ static gpf_status big_block_views(gpf_filter* h, int64_t block_size)
     h->blk_views_size = block_size; h->blk_views_gen = h->generation;
     return GPF_OK;
 }
+} // extern "C"
+namespace gpfh {
+// the loop over the sub-states: f(view of block b, b) for every block; a view's failure is the filter's and ends the loop
+template <class F>
+static gpf_status for_big_blocks(gpf_filter* h, int64_t block_size, F&& f)
+{
+    gpf_status s = big_block_views(h, block_size);
+    for (size_t b = 0; !s && b < h->blk_views.size(); ++b) {
+        gpf_filter* v = h->blk_views[b];
+        if ((s = f(v, (int64_t)b))) h->err = v->err;
+    }
+    return s;
+}
+} // namespace gpfh
+extern "C" {
 static gpf_status resample_big_blocks(gpf_handle h, int32_t method, int64_t block_size, double priority_alpha, int32_t sort_particles,
                                       double ess_frac, int32_t check, int32_t* invalid, int64_t* n_resampled)
 {
-    gpf_status s = big_block_views(h, block_size);
-    if (s) return s;
+    gpf_status s = big_block_views(h, block_size);                // (a failure up to here has changed nothing: no bookkeeping)
     const int64_t nblocks = (int64_t)h->blk_views.size();
-    if ((s = block_buffers(h, nblocks))) return s;
+    if (s || (s = block_buffers(h, nblocks))) return s;
     const uint32_t E = h->epoch;                                 // every block resamples under the call's ONE epoch (like the batched kernel)
     std::vector<int32_t> words((size_t)nblocks, 0);
     bool any_invalid = false, any_nan = false, any_neginf_err = false;
@@ -122,30 +159,30 @@ static gpf_status resample_big_blocks(gpf_handle h, int32_t method, int64_t bloc
     const bool gate = ess_frac == ess_frac && ess_frac >= 0.0;
     // (every view reads its validity flags, also under check = false: a NaN block must be left as it stands, as the batched kernel leaves
     //  it -- which costs one pinned-memory wait per block; at > 2048 particles per block the kernels of the block dominate)
-    gpf_status hard = GPF_OK;                                    // a failure other than invalid weights: the loop stops, the bookkeeping below still runs
-    for (int64_t b = 0; b < nblocks; ++b) {
-        gpf_filter* v = h->blk_views[(size_t)b];
+    // a failure other than invalid weights: the loop stops, the bookkeeping below still runs
+    const gpf_status hard = for_big_blocks(h, block_size, [&](gpf_filter* v, int64_t b) -> gpf_status {
         h->epoch = E;
         if (gate) {
             double ess = 0.0;
-            if ((s = gpf_effective_sample_size(v, &ess))) { h->err = v->err; hard = s; break; }
-            if (!(ess < ess_frac * (double)v->n)) continue;      // (an invalid block: ESS NaN -- it does not resample, nothing is reported)
+            if (gpf_status es = gpf_effective_sample_size(v, &ess)) return es;
+            if (!(ess < ess_frac * (double)v->n)) return GPF_OK; // (an invalid block: ESS NaN -- it does not resample, nothing is reported)
         }
         int32_t inv = 0;
         v->last_flags = 0;
-        s = gpf_resample(v, method, priority_alpha, sort_particles, check == GPF_CHECK_TRUE ? GPF_CHECK_TRUE : GPF_CHECK_WARN, &inv);
-        if (s == GPF_ERR_INVALID_WEIGHTS) {                      // the block is left as it stands; the others go on
+        const gpf_status rs = gpf_resample(v, method, priority_alpha, sort_particles, check == GPF_CHECK_TRUE ? GPF_CHECK_TRUE : GPF_CHECK_WARN, &inv);
+        if (rs == GPF_ERR_INVALID_WEIGHTS) {                     // the block is left as it stands; the others go on
             any_invalid = true;
             const bool nan_block = (v->last_flags & (FLAG_NAN | FLAG_POSINF)) != 0;   // (the view's own flags, not its error text)
             if (nan_block) any_nan = true; else any_neginf_err = true;
             words[(size_t)b] = (nan_block ? FLAG_NAN : FLAG_ALL_NEGINF) << 8;      // (the word layout of the batched kernel: flags << 8 | resampled)
-            continue;
+            return GPF_OK;
         }
-        if (s) { h->err = v->err; hard = s; break; }
+        if (rs) return rs;
         if (inv) { any_invalid = true; words[(size_t)b] |= FLAG_ALL_NEGINF << 8; }
         words[(size_t)b] |= 1;
         ++count;
-    }
+        return GPF_OK;
+    });
     // (also on the error path: the blocks before the failing one HAVE resampled under epoch E -- a later call must not reuse their streams,
     //  the mask must name them and the cached summaries are stale)
     h->epoch = E + 1;
@@ -167,28 +204,18 @@ static gpf_status resample_blocks_impl(gpf_handle h, int32_t method, int64_t blo
                                        double ess_frac, int32_t check, int32_t* invalid, int64_t* n_resampled, bool conditional)
 {
     const char* const who = conditional ? "gpf_resample_blocks_conditional" : "gpf_resample_blocks";
-    if (conditional) {                                           // (what can be refused without touching the handle comes first: block_checks brings a lazy move up to date)
-        if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
-        if (h->parent) return fail(h, GPF_ERR_STATE, std::string(who) + " on a sub-state view: call it on the filter");
-        if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, std::string(who) + " on a shard of a sharded filter");
-        if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");
-        if (method == GPF_RESAMPLE_RESIDUAL || method == GPF_RESAMPLE_STRATIFIED)
-            return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": multinomial only -- forcing one slot to keep its particle is not a valid conditional scheme "
-                        "for residual or stratified resampling (their slots are not exchangeable)");
-        if (method != GPF_RESAMPLE_MULTINOMIAL) return fail(h, GPF_ERR_UNKNOWN_METHOD, "Resampling method not recognized.");   // resample.jl:28
-        if (h->hist_on && !h->hist_blocks) return fail(h, GPF_ERR_STATE, std::string(who) + " on a filter with a trajectory store");
-        if (std::min<int64_t>(block_size, std::max<int64_t>(h->n, 1)) > BLK_MAX)
-            return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": blocks of more than " + std::to_string(BLK_MAX) + " particles resample through sub-state views, which have no conditional form");
-    }
-    gpf_status s = block_checks(h, block_size, who);
+    // (the conditional step has no form for blocks that resample through views: "one block" asked for as any size >= n is one block of n particles)
+    gpf_status s = block_gate(h, block_size, who, GATE_FILTER | (conditional ? GATE_CLAMP : GATE_CLAMP_STORE | GATE_MAX));
     if (s) return s;
+    if (conditional && (method == GPF_RESAMPLE_RESIDUAL || method == GPF_RESAMPLE_STRATIFIED))
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": multinomial only -- forcing one slot to keep its particle is not a valid conditional scheme "
+                    "for residual or stratified resampling (their slots are not exchangeable)");
     if (method != GPF_RESAMPLE_MULTINOMIAL && method != GPF_RESAMPLE_RESIDUAL && method != GPF_RESAMPLE_STRATIFIED)
         return fail(h, GPF_ERR_UNKNOWN_METHOD, "Resampling method not recognized.");          // resample.jl:28
-    if (h->hist_on && !h->hist_blocks) return fail(h, GPF_ERR_STATE, std::string(who) + " on a filter with a trajectory store");
-    if ((s = block_store_size(h, block_size, who))) return s;
+    if (conditional && block_size > BLK_MAX)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": blocks of more than " + std::to_string(BLK_MAX) + " particles resample through sub-state views, which have no conditional form");
     if (h->W != 2 && h->W != 4 && h->W != 8) return fail(h, GPF_ERR_STATE, "row width");
-    if ((s = materialize(h))) return s;
-    if (conditional) block_size = std::min<int64_t>(block_size, std::max<int64_t>(h->n, 1));   // ("one block" asked for as any size >= n)
+    if ((s = check_ready(h)) || (s = materialize(h))) return s;
     if (block_size > BLK_MAX) return resample_big_blocks(h, method, block_size, priority_alpha, sort_particles, ess_frac, check, invalid, n_resampled);
     const int64_t nblocks = (h->n + block_size - 1) / block_size;
     if ((s = block_buffers(h, nblocks))) return s;
@@ -252,37 +279,37 @@ gpf_status gpf_block_resampled(gpf_handle h, int32_t* out)
     for (int64_t i = 0; i < h->blk_last; ++i) out[i] &= 1;       // (the words also carry the blocks' validity flags)
     return GPF_OK;
 }
+// two per-block results of `cells` doubles each from the device to the host, each where the caller wants it
+static gpf_status block_out2(gpf_filter* h, size_t cells, const double* a, double* a_out, const double* b, double* b_out)
+{
+    if (a_out) HIP_TRY(h, hipMemcpyAsync(a_out, a, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (b_out) HIP_TRY(h, hipMemcpyAsync(b_out, b, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GPF_OK;
+}
 // the ESS and the log-ML estimate of every block of <= BLK_MAX particles into blk_stats = [ess | lml] (device)
 static gpf_status launch_block_stats(gpf_filter* h, int64_t block_size, int64_t nblocks)
 {
     gpf_status s = block_buffers(h, nblocks);
     if (s) return s;
-    if (block_size <= 2 * WAVE)      GPF_LAUNCH((k_block_stats<WAVE, 2>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->lw, h->n, block_size, nblocks, &h->sc->lml_est, h->blk_stats, h->blk_stats + nblocks);
-    else if (block_size <= 8 * WAVE) GPF_LAUNCH((k_block_stats<WAVE, 8>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->lw, h->n, block_size, nblocks, &h->sc->lml_est, h->blk_stats, h->blk_stats + nblocks);
-    else                             GPF_LAUNCH((k_block_stats<BLOCK, 8>), dim3((unsigned)nblocks), dim3(BLOCK), 0, h->stream, h->lw, h->n, block_size, nblocks, &h->sc->lml_est, h->blk_stats, h->blk_stats + nblocks);
+    team_dispatch(block_size, nblocks, [&](auto TEAM, auto ITEMS, dim3 grid) {
+        GPF_LAUNCH((k_block_stats<TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, h->lw, h->n, block_size, nblocks, &h->sc->lml_est, h->blk_stats, h->blk_stats + nblocks);
+    });
     HIP_TRY(h, hipGetLastError());
     return GPF_OK;
 }
 gpf_status gpf_block_stats(gpf_handle h, int64_t block_size, double* ess_out, double* lml_out)
 {
-    gpf_status s = block_checks(h, block_size, "gpf_block_stats");
-    if (s || (s = block_store_size(h, block_size, "gpf_block_stats"))) return s;
-    if ((s = materialize(h))) return s;
+    gpf_status s = block_gate(h, block_size, "gpf_block_stats", GATE_VIEW | GATE_SHARD | GATE_SIZE | GATE_CLAMP_STORE | GATE_MAX);
+    if (s || (s = check_ready(h)) || (s = materialize(h))) return s;
     const int64_t nblocks = (h->n + block_size - 1) / block_size;
-    if (block_size > BLK_MAX) {                                  // the loop over sub-states (big_block_views)
-        if ((s = big_block_views(h, block_size))) return s;
-        for (int64_t b = 0; b < nblocks; ++b) {
-            gpf_filter* v = h->blk_views[(size_t)b];
-            if (ess_out && (s = gpf_effective_sample_size(v, ess_out + b))) { h->err = v->err; return s; }
-            if (lml_out && (s = gpf_log_ml_estimate(v, lml_out + b))) { h->err = v->err; return s; }
-        }
-        return GPF_OK;
-    }
+    if (block_size > BLK_MAX)                                    // the loop over sub-states (big_block_views)
+        return for_big_blocks(h, block_size, [&](gpf_filter* v, int64_t b) -> gpf_status {
+            if (gpf_status es = ess_out ? gpf_effective_sample_size(v, ess_out + b) : GPF_OK) return es;
+            return lml_out ? gpf_log_ml_estimate(v, lml_out + b) : GPF_OK;
+        });
     if ((s = launch_block_stats(h, block_size, nblocks))) return s;
-    if (ess_out) HIP_TRY(h, hipMemcpyAsync(ess_out, h->blk_stats, (size_t)nblocks * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (lml_out) HIP_TRY(h, hipMemcpyAsync(lml_out, h->blk_stats + nblocks, (size_t)nblocks * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return GPF_OK;
+    return block_out2(h, (size_t)nblocks, h->blk_stats, ess_out, h->blk_stats + nblocks, lml_out);
 }
 
 } // extern "C"
@@ -291,9 +318,9 @@ namespace gpfh {
 template <int Wc>
 void launch_block_moments_w(gpf_filter* h, int64_t nb, int64_t nblocks, int want_var, double* mean, double* var)
 {
-    if (nb <= 2 * WAVE)      GPF_LAUNCH((k_block_moments<Wc, WAVE, 2>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->rows[h->cur], h->lw, h->n, nb, nblocks, want_var, mean, var);
-    else if (nb <= 8 * WAVE) GPF_LAUNCH((k_block_moments<Wc, WAVE, 8>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->rows[h->cur], h->lw, h->n, nb, nblocks, want_var, mean, var);
-    else                     GPF_LAUNCH((k_block_moments<Wc, BLOCK, 8>), dim3((unsigned)nblocks), dim3(BLOCK), 0, h->stream, h->rows[h->cur], h->lw, h->n, nb, nblocks, want_var, mean, var);
+    team_dispatch(nb, nblocks, [&](auto TEAM, auto ITEMS, dim3 grid) {
+        GPF_LAUNCH((k_block_moments<Wc, TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, h->rows[h->cur], h->lw, h->n, nb, nblocks, want_var, mean, var);
+    });
 }
 // the device buffer of the per-block estimates: at least `need` doubles
 static gpf_status block_est_buffer(gpf_filter* h, int64_t need)
@@ -304,27 +331,23 @@ static gpf_status block_est_buffer(gpf_filter* h, int64_t need)
     h->blk_est_cap = need;
     return GPF_OK;
 }
-// what the per-block estimates ask beyond block_checks: a filter that can have sub-state views, rows of column pairs
-static gpf_status block_est_checks(gpf_handle h, int64_t& block_size, const char* who)
-{
-    // (what can be refused without touching the handle comes first: block_checks brings a lazy move or a view up to date)
-    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
-    if (h->parent) return fail(h, GPF_ERR_STATE, std::string(who) + " on a sub-state view: call it on the filter");
-    if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, std::string(who) + " on a shard of a sharded filter");
-    if (h->hist_on && !h->hist_blocks) return fail(h, GPF_ERR_STATE, std::string(who) + " on a filter with a trajectory store (it has no sub-state views)");
-    if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");
-    gpf_status s = block_store_size(h, block_size, who);
-    if (s || (s = block_checks(h, block_size, who))) return s;
-    if (h->W != 2 && h->W != 4 && h->W != 8) return fail(h, GPF_ERR_STATE, "row width");
-    return GPF_OK;
-}
+// the gate of the per-block estimates: a filter that can have sub-state views
+constexpr unsigned GATE_EST = GATE_FILTER | GATE_STORE_VIEWS | GATE_CLAMP_STORE | GATE_MAX;
 // the view of one big block (big_block_views) brought up to date, its weight summary on the host: *bad = NaN / +Inf weights
-static gpf_status big_block_flags(gpf_filter* h, gpf_filter* v, bool* bad)
+static gpf_status big_block_flags(gpf_filter* v, bool* bad)
 {
     gpf_status s = check_ready(v);
-    if (s || (s = ensure_raw(v)) || (s = fetch_scalars(v))) { h->err = v->err; return s; }
+    if (s || (s = ensure_raw(v)) || (s = fetch_scalars(v))) return s;
     *bad = (v->h_sc->raw.flags & (FLAG_NAN | FLAG_POSINF)) != 0;
     return GPF_OK;
+}
+// the match values of a proportion kernel, padded with the last one (the kernels take them two at a time)
+static BlockMatch make_block_match(const double* values, int32_t n_values)
+{
+    BlockMatch mv{};
+    for (int k = 0; k < BLK_MATCH_MAX; ++k) mv.v[k] = k < n_values ? values[k] : values[n_values - 1];
+    mv.n = n_values;
+    return mv;
 }
 } // namespace gpfh
 
@@ -333,73 +356,61 @@ extern "C" {
 // for b in blocks: [mean(state[b], c) for c in columns], [var(state[b], c) ...] (src/statistics.jl:13-14, 48-50 on sub-states) -- gpf.h
 gpf_status gpf_block_moments(gpf_handle h, int64_t block_size, double* mean_out, double* var_out)
 {
-    if (h && !mean_out && !var_out) return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_block_moments: both outputs are NULL");
-    gpf_status s = block_est_checks(h, block_size, "gpf_block_moments");
+    gpf_status s = block_gate(h, block_size, "gpf_block_moments", GATE_EST);
     if (s) return s;
-    if ((s = materialize(h))) return s;
+    if (!mean_out && !var_out) return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_block_moments: both outputs are NULL");
+    if (h->W != 2 && h->W != 4 && h->W != 8) return fail(h, GPF_ERR_STATE, "row width");
+    if ((s = check_ready(h)) || (s = materialize(h))) return s;
     const int64_t nblocks = (h->n + block_size - 1) / block_size;
     const int W = h->W;
-    if (block_size > BLK_MAX) {                                  // the loop over sub-states (big_block_views)
-        if ((s = big_block_views(h, block_size))) return s;
-        for (int64_t b = 0; b < nblocks; ++b) {
-            gpf_filter* v = h->blk_views[(size_t)b];
+    if (block_size > BLK_MAX)                                    // the loop over sub-states (big_block_views)
+        return for_big_blocks(h, block_size, [&](gpf_filter* v, int64_t b) -> gpf_status {
             bool bad = false;
-            if ((s = big_block_flags(h, v, &bad))) return s;
-            for (int c = 0; c < W; ++c) {
+            gpf_status vs = big_block_flags(v, &bad);
+            for (int c = 0; !vs && c < W; ++c) {
                 double* mo = mean_out ? mean_out + b * W + c : nullptr;
                 double* vo = var_out ? var_out + b * W + c : nullptr;
                 if (bad) { if (mo) *mo = __builtin_nan(""); if (vo) *vo = __builtin_nan(""); continue; }
-                if (mo && (s = gpf_mean(v, c, mo))) { h->err = v->err; return s; }
-                if (vo && (s = gpf_var(v, c, vo))) { h->err = v->err; return s; }
+                if (mo) vs = gpf_mean(v, c, mo);
+                if (vo && !vs) vs = gpf_var(v, c, vo);
             }
-        }
-        return GPF_OK;
-    }
+            return vs;
+        });
     const size_t cells = (size_t)nblocks * (size_t)W;
     if ((s = block_est_buffer(h, (int64_t)(2 * cells)))) return s;
     double* const mean = h->blk_est; double* const var = h->blk_est + cells;
     DISPATCH_W(h, (launch_block_moments_w<WW>(h, block_size, nblocks, var_out ? 1 : 0, mean, var)));
     HIP_TRY(h, hipGetLastError());
-    if (mean_out) HIP_TRY(h, hipMemcpyAsync(mean_out, mean, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (var_out) HIP_TRY(h, hipMemcpyAsync(var_out, var, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return GPF_OK;
+    return block_out2(h, cells, mean, mean_out, var, var_out);
 }
 // for b in blocks: proportionmap(state[b], column)[values[k]] (src/statistics.jl:91-101 on sub-states) -- gpf.h
 gpf_status gpf_block_proportion(gpf_handle h, int64_t block_size, int32_t column, const double* values, int32_t n_values, double* out)
 {
-    if (h) {                                                     // (the arguments first: a refused call has not touched the handle)
-        if (!values || !out) return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_block_proportion: null values / output");
-        if (column < 0 || column >= h->W) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad column");
-        if (n_values < 1 || n_values > BLK_MATCH_MAX) return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_block_proportion: need 1 <= n_values <= " + std::to_string(BLK_MATCH_MAX));
-    }
-    gpf_status s = block_est_checks(h, block_size, "gpf_block_proportion");
+    gpf_status s = block_gate(h, block_size, "gpf_block_proportion", GATE_EST);
     if (s) return s;
-    if ((s = materialize(h))) return s;
+    if (!values || !out) return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_block_proportion: null values / output");
+    if (column < 0 || column >= h->W) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad column");
+    if (n_values < 1 || n_values > BLK_MATCH_MAX) return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_block_proportion: need 1 <= n_values <= " + std::to_string(BLK_MATCH_MAX));
+    if (h->W != 2 && h->W != 4 && h->W != 8) return fail(h, GPF_ERR_STATE, "row width");
+    if ((s = check_ready(h)) || (s = materialize(h))) return s;
     const int64_t nblocks = (h->n + block_size - 1) / block_size;
-    if (block_size > BLK_MAX) {                                  // the loop over sub-states (big_block_views)
-        if ((s = big_block_views(h, block_size))) return s;
-        for (int64_t b = 0; b < nblocks; ++b) {
-            gpf_filter* v = h->blk_views[(size_t)b];
+    if (block_size > BLK_MAX)                                    // the loop over sub-states (big_block_views)
+        return for_big_blocks(h, block_size, [&](gpf_filter* v, int64_t b) -> gpf_status {
             bool bad = false;
-            if ((s = big_block_flags(h, v, &bad))) return s;
-            for (int k = 0; k < n_values; ++k) {
+            gpf_status vs = big_block_flags(v, &bad);
+            for (int k = 0; !vs && k < n_values; ++k) {
                 double* o = out + b * n_values + k;
-                if (bad) { *o = __builtin_nan(""); continue; }
-                if ((s = gpf_proportion(v, 0, column, values[k], o))) { h->err = v->err; return s; }
+                if (bad) *o = __builtin_nan(""); else vs = gpf_proportion(v, 0, column, values[k], o);
             }
-        }
-        return GPF_OK;
-    }
+            return vs;
+        });
     const size_t cells = (size_t)nblocks * (size_t)n_values;
     if ((s = block_est_buffer(h, (int64_t)cells))) return s;
-    BlockMatch mv{};
-    for (int k = 0; k < BLK_MATCH_MAX; ++k) mv.v[k] = k < n_values ? values[k] : values[n_values - 1];
-    mv.n = n_values;
+    const BlockMatch mv = make_block_match(values, n_values);
     const double* rows = h->rows[h->cur];
-    if (block_size <= 2 * WAVE)      GPF_LAUNCH((k_block_proportion<WAVE, 2>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, rows, h->W, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
-    else if (block_size <= 8 * WAVE) GPF_LAUNCH((k_block_proportion<WAVE, 8>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, rows, h->W, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
-    else                             GPF_LAUNCH((k_block_proportion<BLOCK, 8>), dim3((unsigned)nblocks), dim3(BLOCK), 0, h->stream, rows, h->W, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
+    team_dispatch(block_size, nblocks, [&](auto TEAM, auto ITEMS, dim3 grid) {
+        GPF_LAUNCH((k_block_proportion<TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, rows, h->W, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
+    });
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(out, h->blk_est, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -475,19 +486,11 @@ static gpf_status set_block_obs(gpf_filter* h, const double* obs, int32_t n_obs,
     h->blk_obs_size = block_size;
     return GPF_OK;
 }
-// block_size comes back clamped to the particle count ("one block" may be asked for as any size >= n, 2^32 included): the kernels divide by it as a
-// 32-bit number (ModelArgs::blk_size), and n < 2^31
+// the gate of the block-wise steps (they index observations by i / block_size: any size, clamped), then the observations
 static gpf_status block_step_checks(gpf_handle h, int64_t& block_size, const char* who, const double* obs = nullptr, int32_t n_obs = 0, bool with_obs = false)
 {
-    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
-    if (h->parent) return fail(h, GPF_ERR_STATE, std::string(who) + " on a sub-state view: call it on the filter");
-    if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, std::string(who) + " on a shard of a sharded filter");
-    if (h->hist_on && !h->hist_blocks) return fail(h, GPF_ERR_STATE, std::string(who) + " on a filter with a trajectory store");
-    if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");      // (the per-block steps index observations by i / block_size: any size)
-    block_size = std::min<int64_t>(block_size, std::max<int64_t>(h->n, 1));
-    if (h->bp_size > 0 && block_size != h->bp_size)
-        return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": block_size " + std::to_string(block_size) + " differs from the " +
-                    std::to_string(h->bp_size) + " of the per-block parameters (gpf_set_block_params)");
+    gpf_status s = block_gate(h, block_size, who, GATE_FILTER | GATE_CLAMP | GATE_PARAMS);
+    if (s) return s;
     // (callers that change the handle's arguments before set_block_obs -- the strata -- validate the observations first, so that a bad call changes nothing)
     if (with_obs && (!obs || n_obs != model_obs_dim(h->cfg.model)))
         return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model takes " + std::to_string(model_obs_dim(h->cfg.model)) + " observation values per step and block");
@@ -680,17 +683,14 @@ gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, 
 // to the device once, zero-padded to MAX_PARAMS; the block-wise steps read them through ModelArgs::blk_params for as long as they are set
 gpf_status gpf_set_block_params(gpf_handle h, const double* params, int32_t n_params, int64_t block_size)
 {
-    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
-    if (h->parent) return fail(h, GPF_ERR_STATE, "gpf_set_block_params on a sub-state view: call it on the filter");
-    if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, "gpf_set_block_params on a shard of a sharded filter");
-    if (h->hist_on && !h->hist_blocks) return fail(h, GPF_ERR_STATE, "gpf_set_block_params on a filter with a trajectory store");
+    // (a call that clears the rows takes any block size)
+    gpf_status s = block_gate(h, block_size, "gpf_set_block_params", GATE_VIEW | GATE_SHARD | GATE_STORE | (params ? GATE_SIZE | GATE_CLAMP : 0u));
+    if (s) return s;
     if (!params) {                                               // clear: the filter's own parameter vector again (the buffer stays for reuse)
         h->bp_size = 0; h->args.blk_params = nullptr;
         return GPF_OK;
     }
     if (n_params < 1 || n_params > MAX_PARAMS) return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_set_block_params: need 1 <= n_params <= " + std::to_string(MAX_PARAMS));
-    if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");
-    block_size = std::min<int64_t>(block_size, std::max<int64_t>(h->n, 1));          // (as block_step_checks)
     const int64_t nblocks = (h->n + block_size - 1) / block_size;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     std::vector<double> rows((size_t)nblocks * MAX_PARAMS, 0.0);
@@ -712,8 +712,8 @@ gpf_status gpf_set_block_params(gpf_handle h, const double* params, int32_t n_pa
 // the per-block parameter rows as they stand (after gpf_resample_across_blocks: permuted by its block ancestors) -- gpf.h
 gpf_status gpf_get_block_params(gpf_handle h, double* out, int32_t n_params, int64_t n_blocks)
 {
-    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
-    if (h->parent) return fail(h, GPF_ERR_STATE, "gpf_get_block_params on a sub-state view: call it on the filter");
+    int64_t none = 1;
+    if (gpf_status s = block_gate(h, none, "gpf_get_block_params", GATE_VIEW)) return s;
     if (h->bp_size < 1 || !h->blk_params) return fail(h, GPF_ERR_STATE, "gpf_get_block_params: no per-block parameters are set (gpf_set_block_params)");
     const int64_t nblocks = (h->n + h->bp_size - 1) / h->bp_size;
     if (!out || n_params < 1 || n_params > MAX_PARAMS || n_blocks != nblocks)
@@ -757,27 +757,19 @@ static gpf_status across_alt(gpf_filter* h, double*& alt, int64_t& alt_cap, int6
 gpf_status gpf_resample_across_blocks(gpf_handle h, int32_t method, int64_t block_size, int32_t sort_particles, double ess_frac, int32_t check,
                                       int32_t* invalid, int32_t* resampled, double* ess_out)
 {
-    // (what can be refused without touching the handle comes first)
-    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
-    if (h->parent) return fail(h, GPF_ERR_STATE, "gpf_resample_across_blocks on a sub-state view: call it on the filter");
-    if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, "gpf_resample_across_blocks on a shard of a sharded filter");
-    if (h->hist_on && !h->hist_blocks) return fail(h, GPF_ERR_STATE, "gpf_resample_across_blocks on a filter with a trajectory store");
-    if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");
-    { int64_t clamped = block_size; if (gpf_status bs = block_store_size(h, clamped, "gpf_resample_across_blocks")) return bs; }
+    // (no clamp: the blocks must be congruent, so a size above n is refused below)
+    gpf_status s = block_gate(h, block_size, "gpf_resample_across_blocks", GATE_FILTER | GATE_MAX | GATE_PARAMS);
+    if (s) return s;
     if (h->n % block_size != 0)
         return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_resample_across_blocks: " + std::to_string(h->n) + " particles are no whole number of blocks of " +
                     std::to_string(block_size) + " (blocks are copied whole: they must be congruent)");
-    if (h->bp_size > 0 && block_size != h->bp_size)
-        return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_resample_across_blocks: block_size " + std::to_string(block_size) + " differs from the " +
-                    std::to_string(h->bp_size) + " of the per-block parameters (gpf_set_block_params)");
     if (h->blk_obs_size > 0 && block_size != h->blk_obs_size)
         return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_resample_across_blocks: block_size " + std::to_string(block_size) + " differs from the " +
                     std::to_string(h->blk_obs_size) + " of the per-block observations (gpf_update_blocks)");
     if (method != GPF_RESAMPLE_MULTINOMIAL && method != GPF_RESAMPLE_RESIDUAL && method != GPF_RESAMPLE_STRATIFIED)
         return fail(h, GPF_ERR_UNKNOWN_METHOD, "Resampling method not recognized.");          // resample.jl:28
     if (h->W != 2 && h->W != 4 && h->W != 8) return fail(h, GPF_ERR_STATE, "row width");
-    gpf_status s = check_ready(h);
-    if (s || (s = materialize(h))) return s;
+    if ((s = check_ready(h)) || (s = materialize(h))) return s;
     const int64_t nblocks = h->n / block_size;
     // 1. L[b] = log_ml_estimate(state[b]): the double gpf_block_stats reports
     std::vector<double> L((size_t)nblocks);
@@ -1431,19 +1423,24 @@ gpf_status gpf_proportion(gpf_handle h, int32_t step, int32_t column, double val
 // ---- past choices per block (gpf.h gpf_block_history_moments / _proportion): the block-wise store queried block by block, one launch
 } // extern "C"
 namespace gpfh {
-// what both queries check once their own arguments have passed; block_size comes back clamped.  Then the current step is snapshotted and the maps of
-// the steps T, T-1, ..., step+1 go to h->hist_dev_maps (as history_values): *n_maps of them
-static gpf_status block_hist_prepare(gpf_handle h, int32_t step, int64_t& block_size, const char* who, int* n_maps)
+// the gate of the three queries of the block-wise store; block_size comes back clamped
+static gpf_status block_store_gate(gpf_handle h, int64_t& block_size, const char* who)
 {
-    if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");
+    gpf_status s = block_gate(h, block_size, who, GATE_SIZE | GATE_CLAMP_STORE | GATE_MAX);
+    if (s) return s;
     if (!h->hist_on || !h->hist_blocks)
         return fail(h, GPF_ERR_STATE, std::string(who) + " needs the block-wise trajectory store (gpf_history_enable_blocks before gpf_initialize_blocks)");
+    if (h->d != 1 && h->d != 2 && h->d != 4) return fail(h, GPF_ERR_STATE, "latent dimension");
+    return GPF_OK;
+}
+// what both estimate queries do once the gate and their own arguments have passed: the current step is snapshotted and the maps of the steps
+// T, T-1, ..., step+1 go to h->hist_dev_maps (as history_values): *n_maps of them
+static gpf_status block_hist_prepare(gpf_handle h, int32_t step, int* n_maps)
+{
     gpf_status s = check_ready(h);
     if (s) return s;
     const int T = (int)h->hist_x.size();
     if (step < 1 || step > T) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad step");
-    if ((s = block_store_size(h, block_size, who))) return s;
-    if (h->d != 1 && h->d != 2 && h->d != 4) return fail(h, GPF_ERR_STATE, "latent dimension");
     if ((s = hist_snapshot(h))) return s;                         // the current step, in its current order
     std::vector<const int32_t*> maps;
     for (int q = T - 1; q >= step; --q) maps.push_back(h->hist_map[q]);
@@ -1456,9 +1453,9 @@ static gpf_status block_hist_prepare(gpf_handle h, int32_t step, int64_t& block_
 template <int D>
 void launch_block_hist_moments(gpf_filter* h, int n_maps, const double* hx, int64_t nb, int64_t nblocks, int want_var, double* mean, double* var)
 {
-    if (nb <= 2 * WAVE)      GPF_LAUNCH((k_block_hist_moments<D, WAVE, 2>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->hist_dev_maps, n_maps, hx, h->lw, h->n, nb, nblocks, want_var, mean, var);
-    else if (nb <= 8 * WAVE) GPF_LAUNCH((k_block_hist_moments<D, WAVE, 8>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->hist_dev_maps, n_maps, hx, h->lw, h->n, nb, nblocks, want_var, mean, var);
-    else                     GPF_LAUNCH((k_block_hist_moments<D, BLOCK, 8>), dim3((unsigned)nblocks), dim3(BLOCK), 0, h->stream, h->hist_dev_maps, n_maps, hx, h->lw, h->n, nb, nblocks, want_var, mean, var);
+    team_dispatch(nb, nblocks, [&](auto TEAM, auto ITEMS, dim3 grid) {
+        GPF_LAUNCH((k_block_hist_moments<D, TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, h->hist_dev_maps, n_maps, hx, h->lw, h->n, nb, nblocks, want_var, mean, var);
+    });
 }
 } // namespace gpfh
 extern "C" {
@@ -1466,47 +1463,38 @@ extern "C" {
 // (src/statistics.jl:13-14, 48-50 with a past address on sub-states, src/view.jl:35-48) -- gpf.h
 gpf_status gpf_block_history_moments(gpf_handle h, int32_t step, int64_t block_size, double* mean_out, double* var_out)
 {
-    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+    gpf_status s = block_store_gate(h, block_size, "gpf_block_history_moments");
+    if (s) return s;
     if (!mean_out && !var_out) return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_block_history_moments: both outputs are NULL");
     int n_maps = 0;
-    gpf_status s = block_hist_prepare(h, step, block_size, "gpf_block_history_moments", &n_maps);
-    if (s) return s;
+    if ((s = block_hist_prepare(h, step, &n_maps))) return s;
     const int64_t nblocks = (h->n + block_size - 1) / block_size;
     const size_t cells = (size_t)nblocks * (size_t)h->d;
     if ((s = block_est_buffer(h, (int64_t)(2 * cells)))) return s;
     double* const mean = h->blk_est; double* const var = h->blk_est + cells;
     const double* hx = h->hist_x[step - 1];
-    switch (h->d) {
-        case 1: launch_block_hist_moments<1>(h, n_maps, hx, block_size, nblocks, var_out ? 1 : 0, mean, var); break;
-        case 2: launch_block_hist_moments<2>(h, n_maps, hx, block_size, nblocks, var_out ? 1 : 0, mean, var); break;
-        default: launch_block_hist_moments<4>(h, n_maps, hx, block_size, nblocks, var_out ? 1 : 0, mean, var); break;
-    }
+    DISPATCH_D(h, (launch_block_hist_moments<DD>(h, n_maps, hx, block_size, nblocks, var_out ? 1 : 0, mean, var)));
     HIP_TRY(h, hipGetLastError());
-    if (mean_out) HIP_TRY(h, hipMemcpyAsync(mean_out, mean, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (var_out) HIP_TRY(h, hipMemcpyAsync(var_out, var, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return GPF_OK;
+    return block_out2(h, cells, mean, mean_out, var, var_out);
 }
 // for b in blocks: proportionmap(state[b], step => column)[values[k]] (src/statistics.jl:91-101 with a past address on sub-states) -- gpf.h
 gpf_status gpf_block_history_proportion(gpf_handle h, int32_t step, int64_t block_size, int32_t column, const double* values, int32_t n_values, double* out)
 {
-    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+    gpf_status s = block_store_gate(h, block_size, "gpf_block_history_proportion");
+    if (s) return s;
     if (!values || !out) return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_block_history_proportion: null values / output");
     if (column < 0 || column >= h->d) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad column");
     if (n_values < 1 || n_values > BLK_MATCH_MAX) return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_block_history_proportion: need 1 <= n_values <= " + std::to_string(BLK_MATCH_MAX));
     int n_maps = 0;
-    gpf_status s = block_hist_prepare(h, step, block_size, "gpf_block_history_proportion", &n_maps);
-    if (s) return s;
+    if ((s = block_hist_prepare(h, step, &n_maps))) return s;
     const int64_t nblocks = (h->n + block_size - 1) / block_size;
     const size_t cells = (size_t)nblocks * (size_t)n_values;
     if ((s = block_est_buffer(h, (int64_t)cells))) return s;
-    BlockMatch mv{};
-    for (int k = 0; k < BLK_MATCH_MAX; ++k) mv.v[k] = k < n_values ? values[k] : values[n_values - 1];
-    mv.n = n_values;
+    const BlockMatch mv = make_block_match(values, n_values);
     const double* hx = h->hist_x[step - 1];
-    if (block_size <= 2 * WAVE)      GPF_LAUNCH((k_block_hist_proportion<WAVE, 2>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->hist_dev_maps, n_maps, hx, h->d, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
-    else if (block_size <= 8 * WAVE) GPF_LAUNCH((k_block_hist_proportion<WAVE, 8>), dim3((unsigned)((nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, h->hist_dev_maps, n_maps, hx, h->d, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
-    else                             GPF_LAUNCH((k_block_hist_proportion<BLOCK, 8>), dim3((unsigned)nblocks), dim3(BLOCK), 0, h->stream, h->hist_dev_maps, n_maps, hx, h->d, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
+    team_dispatch(block_size, nblocks, [&](auto TEAM, auto ITEMS, dim3 grid) {
+        GPF_LAUNCH((k_block_hist_proportion<TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, h->hist_dev_maps, n_maps, hx, h->d, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
+    });
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(out, h->blk_est, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1519,11 +1507,10 @@ struct TrajLaunch { int T, lo0, hi0; int64_t nb, nblocks; int n_samples; double*
 template <int D>
 void launch_block_sample_traj(gpf_filter* h, const TrajLaunch& a)
 {
-#define GPF_TRAJ_ARGS h->hist_dev_maps, h->hist_dev_x, a.T, a.lo0, a.hi0, h->lw, h->n, a.nb, a.nblocks, a.n_samples, h->cfg.seed, h->epoch, a.traj, a.idx
-    if (a.nb <= 2 * WAVE)      GPF_LAUNCH((k_block_sample_traj<D, WAVE, 2>), dim3((unsigned)((a.nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, GPF_TRAJ_ARGS);
-    else if (a.nb <= 8 * WAVE) GPF_LAUNCH((k_block_sample_traj<D, WAVE, 8>), dim3((unsigned)((a.nblocks + 3) / 4)), dim3(BLOCK), 0, h->stream, GPF_TRAJ_ARGS);
-    else                       GPF_LAUNCH((k_block_sample_traj<D, BLOCK, 8>), dim3((unsigned)a.nblocks), dim3(BLOCK), 0, h->stream, GPF_TRAJ_ARGS);
-#undef GPF_TRAJ_ARGS
+    team_dispatch(a.nb, a.nblocks, [&](auto TEAM, auto ITEMS, dim3 grid) {
+        GPF_LAUNCH((k_block_sample_traj<D, TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, h->hist_dev_maps, h->hist_dev_x, a.T, a.lo0, a.hi0, h->lw, h->n, a.nb, a.nblocks,
+                   a.n_samples, h->cfg.seed, h->epoch, a.traj, a.idx);
+    });
 }
 } // namespace gpfh
 extern "C" {
@@ -1532,18 +1519,13 @@ gpf_status gpf_block_sample_trajectories(gpf_handle h, int64_t block_size, int32
                                          double* traj_out, int64_t* idx_out)
 {
     const char* who = "gpf_block_sample_trajectories";
-    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+    gpf_status s = block_store_gate(h, block_size, who);
+    if (s) return s;
     if (!traj_out && !idx_out) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": both outputs are NULL");
     if (n_samples < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": n_samples < 1");
-    if (block_size < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "block_size < 1");
-    if (!h->hist_on || !h->hist_blocks)
-        return fail(h, GPF_ERR_STATE, std::string(who) + " needs the block-wise trajectory store (gpf_history_enable_blocks before gpf_initialize_blocks)");
-    gpf_status s = check_ready(h);
-    if (s) return s;
+    if ((s = check_ready(h))) return s;
     const int T = (int)h->hist_x.size();
     if (step_lo < 1 || step_hi < step_lo || step_hi > T) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": need 1 <= step_lo <= step_hi <= gpf_history_steps");
-    if ((s = block_store_size(h, block_size, who))) return s;
-    if (h->d != 1 && h->d != 2 && h->d != 4) return fail(h, GPF_ERR_STATE, "latent dimension");
     const int64_t nblocks = (h->n + block_size - 1) / block_size, n_steps = step_hi - step_lo + 1;
     const int64_t lim = (int64_t)1 << 31;
     // (nblocks <= n < 2^31, n_samples < 2^31, n_steps d < 2^31: no product below overflows 64 bits before it is compared)
@@ -1563,11 +1545,7 @@ gpf_status gpf_block_sample_trajectories(gpf_handle h, int64_t block_size, int32
     if (traj_out) HIP_TRY(h, hipMalloc(&d_traj.p, cells * sizeof(double)));
     if (idx_out) HIP_TRY(h, hipMalloc(&d_idx.p, (size_t)draws * sizeof(int64_t)));
     const TrajLaunch a{T, step_lo - 1, step_hi - 1, block_size, nblocks, (int)n_samples, static_cast<double*>(d_traj.p), static_cast<int64_t*>(d_idx.p)};
-    switch (h->d) {
-        case 1: launch_block_sample_traj<1>(h, a); break;
-        case 2: launch_block_sample_traj<2>(h, a); break;
-        default: launch_block_sample_traj<4>(h, a); break;
-    }
+    DISPATCH_D(h, (launch_block_sample_traj<DD>(h, a)));
     HIP_TRY(h, hipGetLastError());
     if (traj_out) HIP_TRY(h, hipMemcpyAsync(traj_out, d_traj.p, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (idx_out) HIP_TRY(h, hipMemcpyAsync(idx_out, d_idx.p, (size_t)draws * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
