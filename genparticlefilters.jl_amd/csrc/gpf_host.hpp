@@ -113,8 +113,7 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     bool lazy_move = true;         // GPF_LAZY_MOVE=0 in the environment: every pf_rejuvenate! launches its kernel at once
     bool lazy_search = false;      // gpf_set_lazy_search (default: GPF_LAZY_SEARCH=1 in the environment, else off)
     // the 16-bit offset levels of the weight channel (k_search_multi / k_push_multi) cost the scan ~1.4 us: only written when a
-    // multinomial search will read them
-    bool want_offsets = true;      // what the next scan of channel 0 writes
+    // multinomial search will read them (ScanRequest::offsets)
     bool ch0_offsets = false;      // what the last scan of channel 0 wrote
     bool offsets_hint = true;      // was the last resample multinomial?  (scans that run ahead of a resample: the ESS getter)
     bool pending_packed = false;   // sharded: the resampled population is still the received exchange buffer (gpf_shard_commit)
@@ -123,9 +122,6 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     // own-direct commit (k_search_own): the packed buffer holds pend_m < n entries (the slots other shards serve), the shard's own hits
     // sit in h->anc as global ancestor ids (-1 elsewhere) and are gathered through it
     bool pend_own = false; int64_t pend_m = 0; bool pend_own_range = false;   // (own hits named by ShardPlan::own_range: stratified)
-    double* fuse_mf_out = nullptr; // set by shard_summary around gpf_shard_weight_scan: the scan produces / pushes the (max, flags) summary itself
-    bool own_direct = false;       // set by the library engine around its phase calls: gpf_shard_push_count resolves the own slots in place
-    bool own_direct_range = false; // ... stratified: the own hits are one slot range (ShardPlan::own_range), written by k_search_strat's pack loop
     // trajectory store (gpf_history_enable): per recorded step the d latent columns in the step's final particle
     // order, and the composed ancestor map of the resamples that happened during that step (nullptr = identity)
     bool hist_on = false;
@@ -165,7 +161,6 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     // residual one runs no weight scan at all (shard_resample_impl)
     bool gsum_ok = false; uint64_t gsum_mut = 0, gsum_mf_seq = 0, gsum_tot_seq = 0; WSum gsum{};
     bool comm_poisoned = false;          // a sharded call failed on THIS rank after its mailbox rounds / collectives had begun: the peers are out of step with it
-    bool mb_engine = false;              // set by the library engine around its phase calls: they push / wait through the mailbox
     // the slot-addressed receive window (gpf_k_common.hpp RingOut / RingIn): one entry of W + 2 words per local slot and parity, mapped by every peer
     uint64_t* ring = nullptr;            // this rank's window (device memory, exported through hipIpc)
     uint64_t** ring_peers = nullptr;     // device array [world]: every rank's window as mapped in this process
@@ -174,14 +169,8 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     int64_t ring_parity_words = 0;       // words of one parity: (slots of the largest shard) x (W + 2)
     uint64_t ring_seq = 0;               // window exchanges so far: the same on every rank (SPMD call order)
     int exchange_mode = 0;               // gpf_comm_set_exchange: GPF_SHARD_EXCHANGE_RCCL | _P2P (the resamplers with ascending targets)
-    bool ring_now = false;               // set by the library engine around its phase calls: this resample exchanges through the windows
-    bool splan_ride = false;             // ... this resample is stratified: its plan rides in the weight scan's launch (k_scan MODE 3, ScanExtras::splan)
-    bool splan_done = false;             // ... and did: gpf_shard_push_count launches no k_strat_plan
     bool pend_ring = false; uint64_t pend_ring_seq = 0;   // the pending commit's entries sit in the window (exchange pend_ring_seq)
     int64_t* tr_dev = nullptr;           // device {entries sent, received} of the window exchanges (the host never learns their counts: gpf_comm_traffic reads these)
-    // what the shard phases summarise / pack on behalf of the engine (defaults: the raw log-weights, no extra field)
-    PrioView sum_pv{nullptr, nullptr, 0.0, 0}; bool sum_pv_set = false; WSum* sum_slot = nullptr; bool sum_no_cdf = false;
-    int push_extra = 0; PrioView push_pv{nullptr, nullptr, 0.0, 0};
     uint64_t sh_round = 0;               // summary rounds so far: the local / gathered arrays are rings of SH_RING rounds
     const double* cur_mf_all = nullptr; const int64_t* cur_tot_all = nullptr; const int64_t* cur_cr_all = nullptr;   // the gathered summaries of the current round
     uint64_t mb_seq[MB_KINDS] = {0, 0, 0, 0};   // rounds so far per kind: the same on every rank (SPMD call order)
@@ -193,7 +182,6 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     int64_t* h_shard_counts = nullptr;
     // block-wise resampling (gpf_resample_blocks): {flags, count} words, the per-block mask, per-block statistics
     int64_t* h_qpub = nullptr; int64_t q_ticket = 0;   // the ESS getter's scan publishes {flags, S, limbs of sum q^2} itself (ScanExtras::q_host)
-    bool q_published = false;                          // ... and the scan of THIS call did
     int32_t* blk_words = nullptr; int32_t* blk_mask = nullptr; double* blk_stats = nullptr; int64_t blk_cap = 0, blk_last = 0;
     double* blk_est = nullptr; int64_t blk_est_cap = 0;         // per-block estimates (gpf_block_moments / gpf_block_proportion): blk_est_cap doubles
     // blocks of more than BLK_MAX particles: gpf_resample_blocks / gpf_block_stats run the loop over sub-states themselves, through view
@@ -230,7 +218,7 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     bool counts_published = false;
     // GPF_RESAMPLE_MULTINOMIAL_SORTED: gamma totals of the tiles of SP_TILE slots (k_sorted_gammas) and, for many tiles, their starting points (k_sorted_tiles)
     uint64_t* sp_g = nullptr; uint64_t* sp_vlo = nullptr; int64_t sp_cap = 0;
-    SortedGammaJob sp_job{}; bool sp_job_set = false;    // tile totals wanted: the next weight scan of this call carries them (scan_launch), else k_sorted_gammas
+    SortedGammaJob sp_job{};             // the latest job that draws them (sorted_job_prepare): a weight scan of the same call carries it (ScanRequest::sp), else k_sorted_gammas
     ulonglong2* push_stage = nullptr;    // push exchange: staged hits, one 16-byte entry per global output slot at most
     // sharded stratified resampling with sort_particles = true (gpf_shard_resample_sorted; gpf_k_shard.hpp AncPlan): the planner filter of n_global particles
     // every rank sorts / scans / searches the gathered log-weights with, the all-gather staging of unequal shards, the pack cursors
@@ -268,6 +256,32 @@ inline gpf_status fail(gpf_handle h, gpf_status s, const std::string& msg)
     return s;
 }
 
+// Poll pinned memory that a kernel on h->stream publishes into, until ready() holds.  A failed kernel never publishes: any stream status other than
+// "not ready" is terminal (ready() once more, then report), so a faulting kernel cannot hang the host -- or, in a multi-rank job, its peers in the
+// next collective.  The failure text: [what: ] + `drained` when the stream is idle and nothing came, else the stream's own error.
+template <class Ready>
+gpf_status poll_published(gpf_filter* h, Ready&& ready, const char* what, const char* drained)
+{
+    uint64_t spins = 0;
+    while (!ready()) {
+        cpu_relax();
+        if ((++spins & 0x3fff) != 0) continue;
+        const hipError_t q = hipStreamQuery(h->stream);
+        if (q == hipErrorNotReady) continue;
+        if (ready()) break;
+        return fail(h, GPF_ERR_HIP, (what ? std::string(what) + ": " : std::string()) + (q == hipSuccess ? drained : hipGetErrorString(q)));
+    }
+    return GPF_OK;
+}
+inline gpf_status wait_ticket(gpf_filter* h, volatile int64_t* tk, int64_t want, const char* what)
+{ return poll_published(h, [&] { return __atomic_load_n(tk, __ATOMIC_ACQUIRE) == want; }, what, "the stream drained without the ticket being published"); }
+// a lazily allocated block of n pinned words a kernel publishes into (flags, tickets, summaries), zeroed
+inline gpf_status pinned_words(gpf_filter* h, int64_t*& words, int n)
+{
+    if (!words) { HIP_TRY(h, hipHostMalloc(&words, (size_t)n * sizeof(int64_t))); std::fill(words, words + n, (int64_t)0); }
+    return GPF_OK;
+}
+
 // gpf_set_block_params: while the rows are set on a filter, a call on it or on a view of it that would use the filter's one parameter vector fails
 inline gpf_status bp_refused(gpf_filter* h, const char* who)
 {
@@ -278,7 +292,6 @@ inline gpf_status bp_refused(gpf_filter* h, const char* who)
 }
 
 constexpr int row_width(int D, bool keep) { return ((keep ? 2 * D : D) + 1) & ~1; }
-// one buffer per scan channel holds the per-256 level (8 u64 per tile) followed by the 4-byte key level (64 u32 per tile)
 // one buffer per scan channel: the per-256 level (8 u64 per tile), the 4-byte key level (64 u32 per tile), the 16-bit
 // in-group offsets (2048 u16 per tile) and their coarse rows (<= 512 u16 per tile) -- gpf_kernels.hpp ScanOut
 // ... and, beyond 2.5 M particles, the compact copy of every 4th / 8th / 16th key (<= 16 u32 per tile)
@@ -374,11 +387,11 @@ inline ChainScope::~ChainScope()
 }
 
 // ------------------------------------------------------------------ shard mailboxes (host side)
-// begin a new round of `kind` (the producing kernel of this call pushes it); no mailbox / not the library engine: push nowhere
-inline MboxPush mb_begin(gpf_filter* h, int kind)
+// begin a new round of `kind` (the producing kernel of this call pushes it); no mailbox / not the library engine (ShardCall::engine): push nowhere
+inline MboxPush mb_begin(gpf_filter* h, bool engine, int kind)
 {
     MboxPush p{};
-    if (!(h->mb_active && h->mb_engine)) return p;
+    if (!(h->mb_active && engine)) return p;
     const uint64_t seq = ++h->mb_seq[kind];
     h->mb_cur[kind] = seq;
     const int slot = (int)(seq & (MB_SLOTS - 1));
@@ -387,10 +400,10 @@ inline MboxPush mb_begin(gpf_filter* h, int kind)
     return p;
 }
 // what a consumer of the current round of `kind` waits for
-inline MboxWait mb_wait(const gpf_filter* h, int kind)
+inline MboxWait mb_wait(const gpf_filter* h, bool engine, int kind)
 {
     MboxWait w{};
-    if (!(h->mb_active && h->mb_engine)) return w;
+    if (!(h->mb_active && engine)) return w;
     const uint64_t seq = h->mb_cur[kind];
     w.tags = h->mbox + mb_tag_off(kind, (int)(seq & (MB_SLOTS - 1))); w.want = seq; w.n = h->comm_world; w.nwords = mb_words(kind); w.timeout = h->h_timeout;
     return w;
@@ -479,6 +492,36 @@ inline bool proposal_valid(const gpf_filter* h, int32_t proposal)
 
 inline PrioView raw_view(const gpf_filter* h) { return PrioView{h->lw, nullptr, 0.0, 0}; }
 
+// ------------------------------------------------------------------ per-call options (arguments, not state: the handle keeps only what outlives a call)
+// What one weight-scan launch is to produce (scan_launch, summarize).  The default: the CDF with its offset levels, one k_max_partial pass in front.
+struct ScanRequest {
+    bool cdf = true;                     // the CDF and its coarser levels (else the sums alone)
+    bool q = false;                      // also accumulate sum q^2 (only the ESS needs it)
+    bool publish_flags = false;          // the validity flags go to pinned memory (h_flags, flag_ticket)
+    bool max_ready = false;              // the maximum slots describe the weights already (the sorted resample needs the maximum for its sort keys) ...
+    bool producer_max = false;           // ... else: the slots of the kernel that produced the raw log-weights will do while they are current (ensure_max)
+    bool offsets = true;                 // the 16-bit offset levels of channel 0 (~1.4 us: only a multinomial search / push reads them)
+    const int32_t* order = nullptr;      // scan in this order (after sort_desc: the sorted keys are in h->keys)
+    const SortedGammaJob* sp = nullptr;  // a sorted multinomial resample's tile totals ride in this launch as extra workgroups
+};
+// What the caller of the sharded phases wants of them.  The default is a public phase call (gpf_shard_weight_max ... gpf_shard_commit, one by one from
+// sharded.py): no mailbox, nothing resolved in place, no windows, no plan in the scan's launch, the raw weights into sc->raw with a CDF, no extra field.
+// The library engine (shard_resample_impl, gpf_shard_step_ess, the sharded getters) builds one per call and passes it down.
+struct ShardCall {
+    bool engine = false;                 // the phases push / wait through the shard mailboxes when they are up (mb_begin / mb_wait)
+    bool own = false;                    // own hits are resolved in place: ancestors into h->anc, only the other shards' slots travel
+    bool own_range = false;              // ... stratified / sorted multinomial: they are one slot range (ShardPlan::own_range), written by k_search_strat's pack loop
+    bool ring = false;                   // the rows go through the receive windows
+    bool plan_in_scan = false;           // stratified: the plan rides in the weight scan's launch (k_scan MODE 3, ScanExtras::splan) ...
+    bool plan_rode = false;              // ... and did (written by the weight scan for the push count of the same call: no k_strat_plan)
+    bool gammas_pending = false;         // sorted multinomial: h->sp_job is still to be drawn -- by the next weight scan, else by the push count
+    bool offsets = true;                 // ScanRequest::offsets of the weight scans
+    const PrioView* view = nullptr;      // summarise this view of the weights (a prioritised resample: alpha lw, then log_ws) instead of the raw ones ...
+    WSum* slot = nullptr;                // ... into this slot instead of sc->raw ...
+    bool cdf = true;                     // ... with or without the CDF
+    int extra = 0; PrioView extra_pv{nullptr, nullptr, 0.0, 0};   // the extra field of a prioritised entry (PushArgs::extra / pv)
+};
+
 // ------------------------------------------------------------------ weight summary = (max) + scan
 // The scan's inter-workgroup protocol needs every workgroup of the launch resident at once (block b owns tiles b, b + G, ...
 // and waits for lower tiles of its round): at most scan_blocks_per_cu per CU, from the occupancy query at gpf_create.
@@ -522,13 +565,12 @@ void speculative_step_done(gpf_filter* h, bool ran);
 // ---- defined in libgpf_resample.hip
 // one scan launch on descriptor channel `ch` (0 weights, 1 residual counts, 2 residual weights): the sharded weight scans (MODE 3: pushes
 // the shard's total itself; 4: also the limbs of sum q^2) and the scans of pf_optimal_resize!
-gpf_status scan_launch_shard(gpf_filter* h, int mode, const InFixQ& in, int np, WSum* slot, bool want_cdf, uint64_t* total_out, const double* mf_all, const ScanExtras& ex);
+gpf_status scan_launch_shard(gpf_filter* h, int mode, const InFixQ& in, int np, WSum* slot, const ScanRequest& rq, uint64_t* total_out, const double* mf_all, const ScanExtras& ex);
 gpf_status scan_launch_optimal(gpf_filter* h, int ch, const InOptimal& in, uint64_t* total_out);
 gpf_status resample_device_setup(gpf_filter* h);      // occupancy of the scan kernels, LDS attributes of the searches (gpf_create)
 gpf_status ensure_max(gpf_filter* h, const PrioView& pv, bool use_producer_max);
-gpf_status summarize(gpf_filter* h, const PrioView& pv, WSum* slot, bool want_cdf, const int32_t* order, bool use_producer_max,
-                     bool want_q = false, bool publish_flags = false, bool max_ready = false);
-gpf_status ensure_raw(gpf_filter* h, bool want_q = false);
+gpf_status summarize(gpf_filter* h, const PrioView& pv, WSum* slot, const ScanRequest& rq, bool* published = nullptr);   // *published: this scan publishes its summary itself (read_published_summary)
+gpf_status ensure_raw(gpf_filter* h, bool want_q = false, bool* published = nullptr);
 gpf_status ensure_raw_summary(gpf_filter* h, bool want_q, bool* done);
 gpf_status read_published_summary(gpf_filter* h, WSum& w);
 bool sum_host_ok(const gpf_filter* h);
@@ -537,7 +579,6 @@ gpf_status sum_host_fold(gpf_filter* h, const double* thr, int* go_out = nullptr
 gpf_status sum_gate_check(gpf_filter* h, int host_go, int64_t ticket);
 gpf_status shard_sum_launch(gpf_filter* h, const ShardSum& ss, bool* ok);
 bool shard_sum_collect();                                        // GPF_SHARD_SUM=collect: k_sum_reduce<SHARD> instead of k_sum_shard
-gpf_status wait_ticket(gpf_filter* h, volatile int64_t* tk, int64_t want, const char* what);
 gpf_status check_scan_timeout(gpf_filter* h);
 gpf_status fetch_scalars(gpf_filter* h, bool fold_raw_q = false);
 gpf_status sort_desc(gpf_filter* h, const PrioView& pv, int64_t n);
@@ -548,7 +589,7 @@ void launch_multinomial_search(gpf_filter* h, const SearchArgs& sa);
 void launch_search_plain(gpf_filter* h, int which, int grid, size_t lds, const SearchArgs& sa);   // k_search<which>, which = 1 (residual) | 3 (systematic)
 void launch_search_strat(gpf_filter* h, const SearchArgs& sa, int64_t n_slots, bool sorted_uniforms);   // k_search_strat<sorted_uniforms>
 gpf_status sorted_job_prepare(gpf_filter* h, int64_t gid0, int64_t n_slots);
-gpf_status sorted_gammas_finish(gpf_filter* h, bool with_tiles);
+gpf_status sorted_gammas_finish(gpf_filter* h, bool with_tiles, bool gammas_pending);
 gpf_status finish_search(gpf_filter* h);
 gpf_status resample_impl(gpf_filter* h, int method, PrioView pv, int sort_particles, int check, int32_t* invalid, bool local = false);
 // ---- defined in libgpf_aux.hip

@@ -452,15 +452,9 @@ static gpf_status set_block_obs(gpf_filter* h, const double* obs, int32_t n_obs,
     const int k = (int)(h->blk_stage_next % gpf_filter::BLK_STAGE);
     if (h->blk_stage_next >= gpf_filter::BLK_STAGE) {
         const int64_t need = h->blk_stage_next - gpf_filter::BLK_STAGE + 1;
-        uint64_t spins = 0;
-        while (__atomic_load_n(h->h_blk_done, __ATOMIC_ACQUIRE) < need) {
-            cpu_relax();
-            if ((++spins & 0x3fff) != 0) continue;
-            const hipError_t q = hipStreamQuery(h->stream);
-            if (q == hipErrorNotReady) continue;
-            if (__atomic_load_n(h->h_blk_done, __ATOMIC_ACQUIRE) >= need) break;
-            return fail(h, GPF_ERR_HIP, q == hipSuccess ? "observation staging: the stream drained without the copy's ticket" : hipGetErrorString(q));
-        }
+        const gpf_status ws = poll_published(h, [&] { return __atomic_load_n(h->h_blk_done, __ATOMIC_ACQUIRE) >= need; }, nullptr,
+                                             "observation staging: the stream drained without the copy's ticket");
+        if (ws) return ws;
     }
     h->blk_stage_next += 1;
     double* const stage = h->h_blk_obs[k];
@@ -1045,7 +1039,9 @@ static gpf_status resize_optimal(gpf_handle h, int64_t n_new, int32_t check, int
     if ((s = sort_desc(h, pv, n_old))) return s;
     WSum* ws = &h->sc->raw;
     h->raw_valid = false; h->raw_sum_valid = false;
-    if ((s = summarize(h, pv, ws, true, h->order, true, false, false, true))) return s;
+    ScanRequest rq;
+    rq.order = h->order; rq.max_ready = true;
+    if ((s = summarize(h, pv, ws, rq))) return s;
     HIP_TRY(h, hipMemsetAsync(&h->sc->opt_d, 0xff, sizeof(long long), h->stream));
     GPF_LAUNCH(k_opt_threshold, dim3(grid_for(h, n_new, 8)), dim3(BLOCK), 0, h->stream, h->cdf[0], ws, n_new, n_old, h->sc);
     GPF_LAUNCH(k_opt_params, dim3(1), dim3(1), 0, h->stream, h->cdf[0], ws, n_new, h->sc);
@@ -1112,8 +1108,11 @@ gpf_status gpf_resize(gpf_handle h, int64_t n_new, int32_t method, double priori
     h->K = fix_K(std::max(n_old, n_new));
     h->raw_valid = false; h->raw_sum_valid = false;
     WSum* ws = &h->sc->raw;
-    if ((s = summarize(h, raw_view(h), &h->sc->raw, true, nullptr, true))) return s;          // logsumexp(log_weights), resize.jl:58
-    if (pv.mode != 0) { ws = &h->sc->prio; if ((s = summarize(h, pv, ws, true, nullptr, false))) return s; }
+    ScanRequest rq;
+    rq.producer_max = true;
+    if ((s = summarize(h, raw_view(h), &h->sc->raw, rq))) return s;                            // logsumexp(log_weights), resize.jl:58
+    rq.producer_max = false;
+    if (pv.mode != 0) { ws = &h->sc->prio; if ((s = summarize(h, pv, ws, rq))) return s; }
     if (check == GPF_CHECK_TRUE || invalid) {
         if ((s = fetch_scalars(h))) return s;
         const WSum& w = pv.mode == 0 ? h->h_sc->raw : h->h_sc->prio;
@@ -1146,7 +1145,8 @@ gpf_status gpf_resize(gpf_handle h, int64_t n_new, int32_t method, double priori
     launch_gather_ex(h, h->anc, old.rows[old.cur], h->rows[0], pv, pv.mode == 0 ? h->lw : h->lws, n_new);
     if (pv.mode != 0) {
         PrioView post{h->lws, nullptr, 0.0, 0};
-        if ((s = summarize(h, post, &h->sc->post, false, nullptr, false))) { free_bufs(old); return s; }
+        rq.cdf = false;
+        if ((s = summarize(h, post, &h->sc->post, rq))) { free_bufs(old); return s; }
         GPF_LAUNCH(k_apply_post, dim3(grid_for(h, n_new, 8)), dim3(BLOCK), 0, h->stream, h->sc, h->K, h->logN, h->lws, h->lw, n_new);
         h->max_valid = false;
     }

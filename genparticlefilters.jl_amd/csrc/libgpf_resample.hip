@@ -9,18 +9,18 @@ namespace gpfh {
 
 // one scan launch on descriptor channel `ch` (0 weights, 1 residual counts, 2 residual weights)
 template <class In, int FIXQ>
-gpf_status scan_launch(gpf_filter* h, int ch, const In& in, int np, WSum* slot, bool want_cdf, uint64_t* total_out,
+gpf_status scan_launch(gpf_filter* h, int ch, const In& in, int np, WSum* slot, const ScanRequest& rq, uint64_t* total_out,
                        const double* mf_all = nullptr, ScanExtras ex = ScanExtras{nullptr, nullptr, 0, 0})
 {
     uint64_t* dc = h->desc[ch][h->dcur[ch]];
     uint64_t* dn = h->desc[ch][1 - h->dcur[ch]];
     int gs = std::is_same<In, InFixQ>::value ? wscan_grid(h) : scan_grid(h);
     // a sorted multinomial resample is waiting for its tile totals: they ride in this launch as extra workgroups behind the scan's own
-    if (h->sp_job_set && std::is_same<In, InFixQ>::value) { ex.sp = h->sp_job; ex.sp.blocks = (int)((h->sp_job.ntl + SCAN_BLOCK - 1) / SCAN_BLOCK); h->sp_job_set = false; }
+    if (rq.sp && std::is_same<In, InFixQ>::value) { ex.sp = *rq.sp; ex.sp.blocks = (int)((rq.sp->ntl + SCAN_BLOCK - 1) / SCAN_BLOCK); }
     const int g_launch = gs + ex.sp.blocks;
-    const bool offsets = ch == 0 && h->want_offsets && want_cdf;
-    const ScanOut so = scan_out(want_cdf ? h->cdf[ch] : nullptr, h->t16[ch], h->t256[ch], h->ntiles, offsets);
-    if (ch == 0 && want_cdf) h->ch0_offsets = offsets && so.off16 != nullptr;
+    const bool offsets = ch == 0 && rq.offsets && rq.cdf;
+    const ScanOut so = scan_out(rq.cdf ? h->cdf[ch] : nullptr, h->t16[ch], h->t256[ch], h->ntiles, offsets);
+    if (ch == 0 && rq.cdf) h->ch0_offsets = offsets && so.off16 != nullptr;
     const ChainScope chain(h);                                   // (several filters on this device: their chained kernels take turns, gpf_host.hpp)
     gpf_status s = timed(h, GPF_K_SCAN, [&] {
         GPF_LAUNCH((k_scan<In, FIXQ>), dim3(g_launch), dim3(SCAN_BLOCK), 0, h->stream, in, h->n, h->ntiles, mf_all, h->mslots[h->mcur], np, slot,
@@ -32,13 +32,13 @@ gpf_status scan_launch(gpf_filter* h, int ch, const In& in, int np, WSum* slot, 
     return GPF_OK;
 }
 
-gpf_status scan_launch_shard(gpf_filter* h, int mode, const InFixQ& in, int np, WSum* slot, bool want_cdf, uint64_t* total_out, const double* mf_all, const ScanExtras& ex)
+gpf_status scan_launch_shard(gpf_filter* h, int mode, const InFixQ& in, int np, WSum* slot, const ScanRequest& rq, uint64_t* total_out, const double* mf_all, const ScanExtras& ex)
 {
-    return mode == 4 ? scan_launch<InFixQ, 4>(h, 0, in, np, slot, want_cdf, total_out, mf_all, ex) : scan_launch<InFixQ, 3>(h, 0, in, np, slot, want_cdf, total_out, mf_all, ex);
+    return mode == 4 ? scan_launch<InFixQ, 4>(h, 0, in, np, slot, rq, total_out, mf_all, ex) : scan_launch<InFixQ, 3>(h, 0, in, np, slot, rq, total_out, mf_all, ex);
 }
 gpf_status scan_launch_optimal(gpf_filter* h, int ch, const InOptimal& in, uint64_t* total_out)
 {
-    return scan_launch<InOptimal, 0>(h, ch, in, 0, nullptr, true, total_out);
+    return scan_launch<InOptimal, 0>(h, ch, in, 0, nullptr, ScanRequest{}, total_out);
 }
 
 // what gpf_create asks of this unit's kernels: how many scan workgroups a CU keeps resident (the scans' inter-workgroup protocol relies on
@@ -93,57 +93,56 @@ gpf_status ensure_max(gpf_filter* h, const PrioView& pv, bool use_producer_max)
     h->max_valid = use_producer_max;           // (otherwise the slots describe pv, which may not be the raw log-weights)
     return GPF_OK;
 }
-// pv: the weights to summarise; max_ready: ensure_max(pv) has run already (the sorted resample needs the maximum for its sort keys)
-gpf_status summarize(gpf_filter* h, const PrioView& pv, WSum* slot, bool want_cdf, const int32_t* order, bool use_producer_max,
-                     bool want_q, bool publish_flags, bool max_ready)
+// pv: the weights to summarise into `slot`, as rq asks
+gpf_status summarize(gpf_filter* h, const PrioView& pv, WSum* slot, const ScanRequest& rq, bool* published)
 {
     ScanExtras ex{nullptr, nullptr, 0, h->cfg.n_global};
-    if (publish_flags) {
-        if (!h->h_flags) { HIP_TRY(h, hipHostMalloc(&h->h_flags, 2 * sizeof(int64_t))); h->h_flags[0] = h->h_flags[1] = 0; }
+    gpf_status s;
+    if (rq.publish_flags) {
+        if ((s = pinned_words(h, h->h_flags, 2))) return s;
         h->flag_ticket += 1;
         ex.host_flags = h->h_flags; ex.ticket = h->flag_ticket;
     }
     const int np = 0;               // (only the sharded scans fold gathered pairs)
-    gpf_status s;
-    h->q_published = false;
+    if (published) *published = false;
     static const bool q_publish_off = getenv("GPF_ESS_PUBLISH") && !strcmp(getenv("GPF_ESS_PUBLISH"), "kernel");   // (A/B: the separate publish launch)
     // (tag << 48 | limb sum: only while a workgroup folds <= Q_TAG_MAX_TILES tiles -- beyond, e.g. N > 2^26 at 4 x 256 workgroups, the
     // untagged partials + k_publish_scalars)
     const int64_t tiles_per_wg = (h->ntiles + wscan_grid(h) - 1) / wscan_grid(h);
-    if (want_q && slot == &h->sc->raw && !q_publish_off && tiles_per_wg <= Q_TAG_MAX_TILES) {
+    if (rq.q && slot == &h->sc->raw && !q_publish_off && tiles_per_wg <= Q_TAG_MAX_TILES) {
         // the ESS getter's scan: the workgroup of its last tile folds sum q^2 and publishes {flags, S, limbs} to pinned memory itself
-        if (!h->h_qpub) { HIP_TRY(h, hipHostMalloc(&h->h_qpub, 8 * sizeof(int64_t))); for (int i = 0; i < 8; ++i) h->h_qpub[i] = 0; }
+        if ((s = pinned_words(h, h->h_qpub, 8))) return s;
         h->q_ticket += 1;
         ex.q_host = h->h_qpub; ex.q_ticket = h->q_ticket;
-        h->q_published = true;
+        if (published) *published = true;
     }
-    if (!max_ready && (s = ensure_max(h, pv, use_producer_max))) return s;
-    InFixQ in{pv, order, order ? h->keys : nullptr, h->K, 0.0, 0};     // (after sort_desc the sorted keys are in h->keys)
-    if (want_q) s = scan_launch<InFixQ, 2>(h, 0, in, np, slot, want_cdf, &slot->S, nullptr, ex);
-    else        s = scan_launch<InFixQ, 1>(h, 0, in, np, slot, want_cdf, &slot->S, nullptr, ex);
+    if (!rq.max_ready && (s = ensure_max(h, pv, rq.producer_max))) return s;
+    InFixQ in{pv, rq.order, rq.order ? h->keys : nullptr, h->K, 0.0, 0};     // (after sort_desc the sorted keys are in h->keys)
+    if (rq.q) s = scan_launch<InFixQ, 2>(h, 0, in, np, slot, rq, &slot->S, nullptr, ex);
+    else      s = scan_launch<InFixQ, 1>(h, 0, in, np, slot, rq, &slot->S, nullptr, ex);
     if (s) return s;
     HIP_TRY(h, hipGetLastError());
     return GPF_OK;
 }
 
 // want_q: also accumulate sum q^2 (only the ESS needs it)
-gpf_status ensure_raw(gpf_filter* h, bool want_q)
+gpf_status ensure_raw(gpf_filter* h, bool want_q, bool* published)
 {
+    bool self_published = false; if (published) *published = false;
     gpf_status s = materialize(h);
     if (s) return s;
     if (h->raw_valid && (!want_q || h->raw_has_q)) return GPF_OK;
-    h->want_offsets = h->offsets_hint;                           // a resample that follows may reuse this CDF
-    s = summarize(h, raw_view(h), &h->sc->raw, true, nullptr, true, want_q);
-    h->want_offsets = true;
-    if (s) return s;
+    ScanRequest rq;
+    rq.producer_max = true; rq.q = want_q;
+    rq.offsets = h->offsets_hint;                                // a resample that follows may reuse this CDF
+    if ((s = summarize(h, raw_view(h), &h->sc->raw, rq, &self_published))) return s;
     h->raw_valid = true;
     h->raw_has_q = want_q;
-    h->raw_q_folded = h->q_published;                            // (a publishing scan folds the limbs itself; its partials are tagged words)
+    h->raw_q_folded = self_published;                            // (a publishing scan folds the limbs itself; its partials are tagged words)
+    if (published) *published = self_published;
     return GPF_OK;
 }
 
-gpf_status wait_ticket(gpf_filter* h, volatile int64_t* tk, int64_t want, const char* what);
-gpf_status check_scan_timeout(gpf_filter* h);
 // {flags, S, limbs} as published by the ESS scan or by k_sum_reduce (8 words, unordered on their way to pinned memory: re-read until the
 // check word -- ticket ^ payload -- agrees)
 gpf_status read_published_summary(gpf_filter* h, WSum& w)
@@ -151,19 +150,20 @@ gpf_status read_published_summary(gpf_filter* h, WSum& w)
     gpf_status s;
     if ((s = wait_ticket(h, h->h_qpub + 6, h->q_ticket, "weight summary"))) return s;
     if ((s = check_scan_timeout(h))) return s;
-    for (uint64_t spins = 0;; ++spins) {
-        int64_t v[8];
+    int64_t v[8];
+    bool consistent = false;
+    uint64_t reads = 0;                                          // (its own bound, as ever: 2^26 reads, whatever the stream is doing)
+    s = poll_published(h, [&] {
         for (int k = 0; k < 8; ++k) v[k] = __atomic_load_n(h->h_qpub + k, __ATOMIC_ACQUIRE);
         uint64_t chk = (uint64_t)v[6];
         for (int k = 0; k < 6; ++k) chk ^= (uint64_t)v[k];
-        if (v[6] == h->q_ticket && chk == (uint64_t)v[7]) {
-            w.flags = (int32_t)v[0]; w.S = (uint64_t)v[1];
-            for (int k = 0; k < 4; ++k) w.Ql[k] = (uint64_t)v[2 + k];
-            return GPF_OK;
-        }
-        cpu_relax();
-        if (spins > (1ull << 26)) return fail(h, GPF_ERR_HIP, "weight summary: the published words never became consistent");
-    }
+        consistent = v[6] == h->q_ticket && chk == (uint64_t)v[7];
+        return consistent || ++reads > (1ull << 26) + 1;
+    }, nullptr, "weight summary: the published words never became consistent");
+    if (s || !consistent) return s ? s : fail(h, GPF_ERR_HIP, "weight summary: the published words never became consistent");
+    w.flags = (int32_t)v[0]; w.S = (uint64_t)v[1];
+    for (int k = 0; k < 4; ++k) w.Ql[k] = (uint64_t)v[2 + k];
+    return GPF_OK;
 }
 // The summary of the raw log-weights WITHOUT the CDF (the ESS and log-ML getters): reuses a valid scan, else ONE reduction launch
 // (k_sum_reduce) instead of the scan -- no inter-workgroup chain, no 10 MB of CDF and levels.  false in *done: the filter is too large
@@ -180,7 +180,6 @@ gpf_status ensure_raw_summary(gpf_filter* h, bool want_q, bool* done)
     static const bool device_fold = getenv("GPF_SUM_REDUCE") && !strcmp(getenv("GPF_SUM_REDUCE"), "device");
     const int hgrid = (int)std::max<int64_t>(1, std::min<int64_t>((h->n + SH_TILE - 1) / SH_TILE, (int64_t)h->n_cu));
     if (!device_fold && (h->n + hgrid - 1) / hgrid <= (int64_t)Q_TAG_MAX_TILES * TILE) {
-        (void)hgrid;
         // every workgroup's partial sums go straight to pinned memory; this thread adds them up
         if ((s = sum_host_launch(h, nullptr))) return s;
         if ((s = sum_host_fold(h, nullptr))) return s;
@@ -193,7 +192,7 @@ gpf_status ensure_raw_summary(gpf_filter* h, bool want_q, bool* done)
         HIP_TRY(h, hipMalloc(&h->sum_part, (size_t)6 * 4 * h->n_cu * sizeof(uint64_t)));
         HIP_TRY(h, hipMemsetAsync(h->sum_part, 0, (size_t)6 * 4 * h->n_cu * sizeof(uint64_t), h->stream));
     }
-    if (!h->h_qpub) { HIP_TRY(h, hipHostMalloc(&h->h_qpub, 8 * sizeof(int64_t))); for (int i = 0; i < 8; ++i) h->h_qpub[i] = 0; }
+    if ((s = pinned_words(h, h->h_qpub, 8))) return s;
     if ((s = ensure_max(h, raw_view(h), true))) return s;
     h->q_ticket += 1;
     InFixQ in{raw_view(h), nullptr, nullptr, h->K, 0.0, 0};
@@ -265,15 +264,9 @@ gpf_status sum_host_fold(gpf_filter* h, const double* thr, int* go_out)
         volatile int64_t* line = h->h_spart + (size_t)b * 8;
         uint64_t v[8];
         for (int k = 0; k < 8; ++k) {
-            uint64_t spins = 0;
-            while (((v[k] = (uint64_t)__atomic_load_n(line + k, __ATOMIC_ACQUIRE)) >> 48) != tag) {
-                cpu_relax();
-                if ((++spins & 0x3fff) != 0) continue;
-                const hipError_t q = hipStreamQuery(h->stream);
-                if (q == hipErrorNotReady) continue;
-                if (((uint64_t)__atomic_load_n(line + k, __ATOMIC_ACQUIRE) >> 48) == tag) continue;
-                return fail(h, GPF_ERR_HIP, q == hipSuccess ? "weight summary: the stream drained without the partial sums being published" : hipGetErrorString(q));
-            }
+            const gpf_status s = poll_published(h, [&] { return ((v[k] = (uint64_t)__atomic_load_n(line + k, __ATOMIC_ACQUIRE)) >> 48) == tag; }, nullptr,
+                                                "weight summary: the stream drained without the partial sums being published");
+            if (s) return s;
             v[k] &= 0xffffffffffffull;
         }
         // the consumed line goes back to zero (tag 0 is never valid): the 15-bit tag alone cannot tell this launch's words from those of a
@@ -305,21 +298,11 @@ gpf_status sum_host_fold(gpf_filter* h, const double* thr, int* go_out)
 // resample, an update or a getter between the launch and this check may summarise again)
 gpf_status sum_gate_check(gpf_filter* h, int host_go, int64_t ticket)
 {
-    {
-        gpf_status s;
-        uint64_t spins = 0;
-        int64_t gv;
-        while (((gv = __atomic_load_n(h->h_gate, __ATOMIC_ACQUIRE)) >> 1) != ticket) {
-            cpu_relax();
-            if ((++spins & 0x3fff) != 0) continue;
-            const hipError_t q = hipStreamQuery(h->stream);
-            if (q == hipErrorNotReady) continue;
-            if ((__atomic_load_n(h->h_gate, __ATOMIC_ACQUIRE) >> 1) == ticket) continue;
-            return fail(h, GPF_ERR_HIP, q == hipSuccess ? "ESS gate: the stream drained without the verdict being published" : hipGetErrorString(q));
-        }
-        if ((s = check_scan_timeout(h))) return s;
-        if (host_go != (int)(gv & 1)) return fail(h, GPF_ERR_HIP, "ESS gate: the device's verdict differs from the host's (state may be inconsistent)");
-    }
+    int64_t gv;
+    gpf_status s = poll_published(h, [&] { return ((gv = __atomic_load_n(h->h_gate, __ATOMIC_ACQUIRE)) >> 1) == ticket; }, nullptr,
+                                  "ESS gate: the stream drained without the verdict being published");
+    if (s || (s = check_scan_timeout(h))) return s;
+    if (host_go != (int)(gv & 1)) return fail(h, GPF_ERR_HIP, "ESS gate: the device's verdict differs from the host's (state may be inconsistent)");
     return GPF_OK;
 }
 
@@ -333,7 +316,7 @@ gpf_status shard_sum_launch(gpf_filter* h, const ShardSum& ss, bool* ok)
     if (!shard_sum_collect()) {
         gpf_status s0 = ensure_gate_buffers(h);
         if (s0) return s0;
-        if (!h->h_qpub) { HIP_TRY(h, hipHostMalloc(&h->h_qpub, 8 * sizeof(int64_t))); for (int i = 0; i < 8; ++i) h->h_qpub[i] = 0; }
+        if ((s0 = pinned_words(h, h->h_qpub, 8))) return s0;
         h->gate_cur ^= 1;
         h->q_ticket += 1;
         const int hgrid = (int)std::max<int64_t>(1, std::min<int64_t>((h->n + SH_TILE - 1) / SH_TILE, (int64_t)h->n_cu));
@@ -351,10 +334,11 @@ gpf_status shard_sum_launch(gpf_filter* h, const ShardSum& ss, bool* ok)
         HIP_TRY(h, hipMalloc(&h->sum_part, (size_t)6 * 4 * h->n_cu * sizeof(uint64_t)));
         HIP_TRY(h, hipMemsetAsync(h->sum_part, 0, (size_t)6 * 4 * h->n_cu * sizeof(uint64_t), h->stream));
     }
-    if (!h->h_qpub) { HIP_TRY(h, hipHostMalloc(&h->h_qpub, 8 * sizeof(int64_t))); for (int i = 0; i < 8; ++i) h->h_qpub[i] = 0; }
+    gpf_status s = pinned_words(h, h->h_qpub, 8);
+    if (s) return s;
     h->q_ticket += 1;
     InFixQ in{raw_view(h), nullptr, nullptr, h->K, 0.0, 0};
-    gpf_status s = timed(h, GPF_K_SCAN, [&] {
+    s = timed(h, GPF_K_SCAN, [&] {
         GPF_LAUNCH(k_sum_reduce<true>, dim3(grid), dim3(SCAN_BLOCK), 0, h->stream, in, h->n, h->ntiles, h->mslots[h->mcur], &h->sc->raw, h->sum_part, h->h_qpub,
                    h->q_ticket, h->h_timeout, ss);
     });
@@ -364,23 +348,6 @@ gpf_status shard_sum_launch(gpf_filter* h, const ShardSum& ss, bool* ok)
     return GPF_OK;
 }
 
-// Poll a pinned ticket that a kernel on h->stream publishes.  A failed kernel never writes it: any stream status other than
-// "not ready" is terminal (re-read once, then report), so a faulting kernel cannot hang the host -- or, in a multi-rank job,
-// its peers in the next collective.
-gpf_status wait_ticket(gpf_filter* h, volatile int64_t* tk, int64_t want, const char* what)
-{
-    uint64_t spins = 0;
-    while (__atomic_load_n(tk, __ATOMIC_ACQUIRE) != want) {
-        cpu_relax();
-        if ((++spins & 0x3fff) != 0) continue;
-        const hipError_t q = hipStreamQuery(h->stream);
-        if (q == hipErrorNotReady) continue;
-        if (__atomic_load_n(tk, __ATOMIC_ACQUIRE) == want) break;
-        if (q == hipSuccess) return fail(h, GPF_ERR_HIP, std::string(what) + ": the stream drained without the ticket being published");
-        return fail(h, GPF_ERR_HIP, std::string(what) + ": " + hipGetErrorString(q));
-    }
-    return GPF_OK;
-}
 // a scan whose bounded inter-workgroup wait gave up leaves garbage prefixes behind: fail loudly at the next host touch point
 gpf_status check_scan_timeout(gpf_filter* h)
 {
@@ -496,7 +463,7 @@ gpf_status sort_desc_begin(gpf_filter* h, const PrioView& pv, int64_t n, bool* p
     uint32_t* ws = nullptr;
     gpf_status s = sort_passes(h, pv, n, true, &ws, buckets);    // (either form leaves keys / payload in h->keys_out / h->idx_in)
     if (s) return s;
-    if (!h->h_sort_flag) { HIP_TRY(h, hipHostMalloc(&h->h_sort_flag, 2 * sizeof(int64_t))); h->h_sort_flag[0] = h->h_sort_flag[1] = 0; }
+    if ((s = pinned_words(h, h->h_sort_flag, 2))) return s;
     uint32_t* done = ws + SORT_PASSES * SORT_BINS + 64;                                  // (behind this sort's zeroed tickets)
     const double* m_ptr = reinterpret_cast<const double*>(ws + SORT_PASSES * SORT_BINS + SORT_M_WORD);
     h->sort_ticket += 1;
@@ -520,16 +487,10 @@ gpf_status sort_desc_flagged(gpf_filter* h, bool* flagged)
 {
     // (the finish publishes ticket << 1 | verdict as one word)
     volatile int64_t* tk = h->h_sort_flag + 1;
-    uint64_t spins = 0;
     int64_t v;
-    while (((v = __atomic_load_n(tk, __ATOMIC_ACQUIRE)) >> 1) != h->sort_ticket) {
-        cpu_relax();
-        if ((++spins & 0x3fff) != 0) continue;
-        const hipError_t q = hipStreamQuery(h->stream);
-        if (q == hipErrorNotReady) continue;
-        if ((__atomic_load_n(tk, __ATOMIC_ACQUIRE) >> 1) == h->sort_ticket) continue;
-        return fail(h, GPF_ERR_HIP, q == hipSuccess ? "sort finish: the stream drained without the ticket being published" : hipGetErrorString(q));
-    }
+    const gpf_status s = poll_published(h, [&] { return ((v = __atomic_load_n(tk, __ATOMIC_ACQUIRE)) >> 1) == h->sort_ticket; }, nullptr,
+                                        "sort finish: the stream drained without the ticket being published");
+    if (s) return s;
     *flagged = (v & 1) != 0 || sort_mode() == 2;
     return GPF_OK;
 }
@@ -620,7 +581,7 @@ void launch_search_strat(gpf_filter* h, const SearchArgs& sa, int64_t n_slots, b
     else                 GPF_LAUNCH((k_search_strat<false>), dim3((unsigned)((n_slots + MJB_STRAT - 1) / MJB_STRAT)), dim3(MBLOCK), 0, h->stream, sa);
 }
 // GPF_RESAMPLE_MULTINOMIAL_SORTED: buffers for the tile totals of n_slots slots whose first slot has the RNG id gid0, and the job that draws them
-// (left pending: the next weight scan of the call carries it as extra workgroups -- scan_launch --, else sorted_gammas_finish launches it)
+// (h->sp_job; the caller has the next weight scan of its call carry it as extra workgroups -- ScanRequest::sp --, else sorted_gammas_finish launches it)
 gpf_status sorted_job_prepare(gpf_filter* h, int64_t gid0, int64_t n_slots)
 {
     const int64_t ntl = (n_slots + SP_TILE - 1) / SP_TILE;
@@ -631,17 +592,13 @@ gpf_status sorted_job_prepare(gpf_filter* h, int64_t gid0, int64_t n_slots)
         h->sp_cap = ntl + 1;
     }
     h->sp_job = SortedGammaJob{h->cfg.seed, h->sp_g, gid0, n_slots, ntl, h->epoch, gamma_E(ntl), 0};
-    h->sp_job_set = true;
     return GPF_OK;
 }
-// the pending tile totals now, if no weight scan has carried them; with_tiles: also where every tile starts (k_sorted_tiles)
-gpf_status sorted_gammas_finish(gpf_filter* h, bool with_tiles)
+// the tile totals now, if no weight scan has carried them (gammas_pending); with_tiles: also where every tile starts (k_sorted_tiles)
+gpf_status sorted_gammas_finish(gpf_filter* h, bool with_tiles, bool gammas_pending)
 {
     const int64_t ntl = h->sp_job.ntl;
-    if (h->sp_job_set) {
-        h->sp_job_set = false;
-        GPF_LAUNCH(k_sorted_gammas, dim3((unsigned)((ntl + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, h->stream, h->sp_job);
-    }
+    if (gammas_pending) GPF_LAUNCH(k_sorted_gammas, dim3((unsigned)((ntl + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, h->stream, h->sp_job);
     if (with_tiles) GPF_LAUNCH(k_sorted_tiles, dim3(1), dim3(STILES_BLOCK), 0, h->stream, h->sp_g, ntl, h->sp_vlo);
     HIP_TRY(h, hipGetLastError());
     return GPF_OK;
@@ -678,8 +635,6 @@ gpf_status resample_impl(gpf_filter* h, int method, PrioView pv, int sort_partic
     const bool need_sync = check == GPF_CHECK_TRUE || invalid != nullptr;
     // only the multinomial search reads the offset levels: the scans of this call write them for it alone
     const bool need_off = method == GPF_RESAMPLE_MULTINOMIAL && (multi_logg(h->ntiles) >= 0 || multi_sample(h->ntiles) > 0);
-    struct OffScope { gpf_filter* h; ~OffScope() { h->want_offsets = true; } } off_scope{h};
-    h->want_offsets = need_off;
     h->offsets_hint = need_off;
     gpf_status s;
     if ((s = check_scan_timeout(h))) return s;                   // an earlier scan gave up: do not build on its CDF
@@ -699,7 +654,9 @@ gpf_status resample_impl(gpf_filter* h, int method, PrioView pv, int sort_partic
         // that for its own tile
         if ((s = sorted_job_prepare(h, h->cfg.gid0, h->n))) return s;
     }
-    struct SpScope { gpf_filter* h; ~SpScope() { h->sp_job_set = false; } } sp_scope{h};
+    bool gammas_pending = method == GPF_RESAMPLE_MULTINOMIAL_SORTED;   // ... until a weight scan of this call has carried them
+    ScanRequest rq;                                              // the weight scans of this call: over the sorted order, the maximum there already for the sort keys
+    rq.order = sorted ? h->order : nullptr; rq.max_ready = sorted; rq.offsets = need_off; rq.publish_flags = need_sync;
     // safe_softmax(log_priorities) (resample.jl:54) and logsumexp(log_weights) (resample.jl:180)
     WSum* ws;
     bool published = false;                                      // the scan of THIS call publishes the flags to pinned memory
@@ -717,14 +674,15 @@ gpf_status resample_impl(gpf_filter* h, int method, PrioView pv, int sort_partic
     if (pv.mode == 0) {
         ws = &h->sc->raw;
         if (!h->raw_valid || sorted || (need_off && !h->ch0_offsets)) {
-            if ((s = summarize(h, pv, ws, true, sorted ? h->order : nullptr, true, false, need_sync, sorted))) return s;
-            published = need_sync;
+            rq.producer_max = true; rq.sp = gammas_pending ? &h->sp_job : nullptr;
+            if ((s = summarize(h, pv, ws, rq))) return s;
+            published = need_sync; gammas_pending = false;
         }
     } else {
-        h->want_offsets = need_off;
         ws = &h->sc->prio;
-        if ((s = summarize(h, pv, ws, true, sorted ? h->order : nullptr, false, false, need_sync, sorted))) return s;
-        published = need_sync;
+        rq.sp = gammas_pending ? &h->sp_job : nullptr;
+        if ((s = summarize(h, pv, ws, rq))) return s;
+        published = need_sync; gammas_pending = false;
     }
     h->raw_valid = false; h->raw_sum_valid = false;                                        // cdf[0] no longer the plain raw CDF / lw about to change
     h->raw_q_folded = false;
@@ -763,7 +721,7 @@ gpf_status resample_impl(gpf_filter* h, int method, PrioView pv, int sort_partic
     if (method == GPF_RESAMPLE_MULTINOMIAL_SORTED) {
         const int64_t ntl = (h->n + SP_TILE - 1) / SP_TILE;
         // (the tile totals in a launch of their own if no weight scan ran in this call -- the CDF of an earlier getter is reused)
-        if ((s = sorted_gammas_finish(h, ntl > SP_DIRECT_TILES))) return s;
+        if ((s = sorted_gammas_finish(h, ntl > SP_DIRECT_TILES, gammas_pending))) return s;
         sa.sp_g = h->sp_g; sa.sp_vlo = ntl > SP_DIRECT_TILES ? h->sp_vlo : nullptr;
     }
     const int64_t nt = method == GPF_RESAMPLE_RESIDUAL && !sa.head_done ? 2 : 1;   // (top tables the search keeps in LDS: its shape depends on their number)
@@ -795,13 +753,14 @@ gpf_status resample_impl(gpf_filter* h, int method, PrioView pv, int sort_partic
         if ((s = sort_desc_flagged(h, &flagged))) return s;
         if (flagged) {
             if ((s = sort_passes(h, pv, h->n, false))) return s;
-            h->want_offsets = need_off;
-            if ((s = summarize(h, pv, ws, true, h->order, pv.mode == 0, false, false, true))) return s;
+            rq.publish_flags = false; rq.sp = nullptr;
+            if ((s = summarize(h, pv, ws, rq))) return s;
             sa.w = levels(h, 0); sa.c = levels(h, 0); sa.update_lml = 0;
             if ((s = search())) return s;
         }
     }
     if ((s = hist_on_resample(h))) return s;
+    ScanRequest sums_only; sums_only.cdf = false;                // logsumexp(log_ws): no CDF
     if (h->parent) {
         // sub-state (resample.jl:205-218): eager gather; weights keep the block's total mass
         s = timed(h, GPF_K_GATHER, [&] { launch_gather(h, pv, pv.mode == 0 ? h->lw : h->lws); });
@@ -811,7 +770,7 @@ gpf_status resample_impl(gpf_filter* h, int method, PrioView pv, int sort_partic
             GPF_LAUNCH(k_view_fill_weights, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->lw, h->n, &h->sc->raw, h->K, h->logN);
         } else {
             PrioView post{h->lws, nullptr, 0.0, 0};
-            if ((s = summarize(h, post, &h->sc->post, false, nullptr, false))) return s;
+            if ((s = summarize(h, post, &h->sc->post, sums_only))) return s;
             GPF_LAUNCH(k_view_apply_post, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->sc, h->K, h->lws, h->lw, h->n);
         }
         h->max_valid = false;
@@ -832,7 +791,7 @@ gpf_status resample_impl(gpf_filter* h, int method, PrioView pv, int sort_partic
         if (s) return s;
         h->cur ^= 1;
         PrioView post{h->lws, nullptr, 0.0, 0};
-        if ((s = summarize(h, post, &h->sc->post, false, nullptr, false))) return s;
+        if ((s = summarize(h, post, &h->sc->post, sums_only))) return s;
         GPF_LAUNCH(k_apply_post, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->sc, h->K, h->logN, h->lws, h->lw, h->n);
         h->max_valid = false;
     }
@@ -896,11 +855,10 @@ gpf_status gpf_effective_sample_size(gpf_handle h, double* out)
     if ((s = ensure_raw_summary(h, true, &reduced))) return s;
     if (reduced) w = h->sum_cache;                                // S and sum q^2 from the reduction: no CDF was written
     else {
-        h->q_published = false;
-        if ((s = ensure_raw(h, true))) return s;
-        if (h->q_published) {
+        bool published = false;
+        if ((s = ensure_raw(h, true, &published))) return s;
+        if (published) {
             // the scan of this call publishes {flags, S, limbs of sum q^2} itself: wait for its ticket, no publish launch
-            h->q_published = false;
             if ((s = read_published_summary(h, w))) return s;
         } else {
             const bool fold = !h->raw_q_folded;                      // the scan blocks' limb partials of sum q^2: folded by the publish kernel

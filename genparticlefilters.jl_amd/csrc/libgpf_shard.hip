@@ -2,6 +2,7 @@
 // the shard mailboxes, gpf_shard_resample in one call.
 #include "gpf_host.hpp"
 #include <chrono>
+#include <utility>
 
 using namespace gpf;
 using namespace gpfh;
@@ -49,7 +50,6 @@ static gpf_status shard_ready(gpf_handle h)
     return GPF_OK;
 }
 
-static gpf_status shard_max_slots(gpf_handle h);
 static gpf_status ensure_shard_counts(gpf_handle h)
 {
     if (h->shard_counts) return GPF_OK;
@@ -59,81 +59,86 @@ static gpf_status ensure_shard_counts(gpf_handle h)
     h->h_shard_counts[2 * MAX_SHARDS] = 0;
     return GPF_OK;
 }
-gpf_status gpf_shard_weight_max(gpf_handle h, double* out2)
-{
-    gpf_status s = shard_ready(h);
-    if (s) return s;
-    if (!out2) return fail(h, GPF_ERR_INVALID_ARGUMENT, "null out");
-    if ((s = shard_max_slots(h))) return s;
-    GPF_LAUNCH(k_pack_mflags, dim3(1), dim3(BLOCK), 0, h->stream, h->mslots[h->mcur], out2, mb_begin(h, MB_MF));
-    HIP_TRY(h, hipGetLastError());
-    return GPF_OK;
-}
+// ---- the phases, each as the function the library engine calls -- everything behind shard_ready, with the caller's options (gpf_host.hpp ShardCall) --
+// and as its public entry point gpf_shard_*: shard_ready, then the same function with a default ShardCall
 // the maximum slots describe the weights to summarise (the producer's slots, or one k_max_partial pass)
-static gpf_status shard_max_slots(gpf_handle h)
+static gpf_status shard_max_slots(gpf_handle h, const ShardCall& c)
 {
     gpf_status s;
     if ((s = materialize(h))) return s;
-    const PrioView pv = h->sum_pv_set ? h->sum_pv : raw_view(h);  // (the engine's prioritised resample summarises alpha lw and log_ws too)
-    if (!h->max_valid || h->sum_pv_set) {
+    if (!h->max_valid || c.view) {                               // (the engine's prioritised resample summarises alpha lw and log_ws too)
+        const PrioView pv = c.view ? *c.view : raw_view(h);
         const int gp = (int)std::min<int64_t>(MAX_PARTIALS, (h->n + BLOCK - 1) / BLOCK);
         s = timed(h, GPF_K_MAX, [&] {
             GPF_LAUNCH(k_max_partial, dim3(gp), dim3(BLOCK), 0, h->stream, pv, h->n, next_slots(h));
         });
         if (s) return s;
-        h->max_valid = !h->sum_pv_set;
+        h->max_valid = !c.view;
     }
     return GPF_OK;
 }
-
-gpf_status gpf_shard_weight_scan(gpf_handle h, const double* mf_all, int32_t G, int32_t want_q, int64_t* out5)
+static gpf_status shard_weight_max(gpf_handle h, const ShardCall& c, double* out2)
 {
-    gpf_status s = shard_ready(h);
+    if (!out2) return fail(h, GPF_ERR_INVALID_ARGUMENT, "null out");
+    gpf_status s = shard_max_slots(h, c);
     if (s) return s;
+    GPF_LAUNCH(k_pack_mflags, dim3(1), dim3(BLOCK), 0, h->stream, h->mslots[h->mcur], out2, mb_begin(h, c.engine, MB_MF));
+    HIP_TRY(h, hipGetLastError());
+    return GPF_OK;
+}
+gpf_status gpf_shard_weight_max(gpf_handle h, double* out2) { gpf_status s = shard_ready(h); return s ? s : shard_weight_max(h, ShardCall{}, out2); }
+
+// fused_mf: the scan produces / pushes the (max, flags) summary itself, into this (shard_summary)
+static gpf_status shard_weight_scan(gpf_handle h, ShardCall& c, const double* mf_all, int32_t G, int32_t want_q, int64_t* out5, double* fused_mf = nullptr)
+{
     if (!mf_all || !out5 || G < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad arguments");
-    if ((s = ensure_shard_counts(h))) return s;
-    InFixQ in{h->sum_pv_set ? h->sum_pv : raw_view(h), nullptr, nullptr, h->K, 0.0, 0};
-    WSum* const slot = h->sum_slot ? h->sum_slot : &h->sc->raw;
-    const bool want_cdf = !h->sum_no_cdf;
+    gpf_status s = ensure_shard_counts(h);
+    if (s) return s;
+    InFixQ in{c.view ? *c.view : raw_view(h), nullptr, nullptr, h->K, 0.0, 0};
+    WSum* const slot = c.slot ? c.slot : &h->sc->raw;
+    ScanRequest rq;
+    rq.cdf = c.cdf; rq.offsets = c.offsets;
+    rq.sp = std::exchange(c.gammas_pending, false) ? &h->sp_job : nullptr;   // (a sorted multinomial resample's tile totals ride in the first weight scan of its call)
     const int gs = wscan_grid(h);
     // the scan folds the gathered (max, flags) pairs itself and writes the shard total straight into out5[0]; it also
     // publishes the global validity flags to pinned host memory (gpf_shard_flags)
-    if (!h->h_flags) { HIP_TRY(h, hipHostMalloc(&h->h_flags, 2 * sizeof(int64_t))); h->h_flags[0] = h->h_flags[1] = 0; }
+    if ((s = pinned_words(h, h->h_flags, 2))) return s;
     h->flag_ticket += 1;
     // shard mailboxes: the scan waits for the ranks' (max, flags) entries itself and the kernel that ends up with the shard's
     // {S, limbs} stores them into every peer's mailbox (the scan's last workgroup, or k_export_q when the limbs are wanted)
     ScanExtras ex{h->shard_counts, h->h_flags, h->flag_ticket, 0};
     ex.zero_stride = COUNT_STRIDE;
-    if (h->fuse_mf_out) {                                        // (library engine: the scan produces and pushes the first summary itself)
-        ex.fuse_mf = 1; ex.mf_me = h->comm_rank; ex.mf_out = h->fuse_mf_out; ex.mf_push = mb_begin(h, MB_MF);
-        if (h->mb_active && h->mb_engine) mf_all = static_cast<const double*>(mb_gathered(h, MB_MF));   // the round that has just begun
+    if (fused_mf) {                                              // (library engine: the scan produces and pushes the first summary itself)
+        ex.fuse_mf = 1; ex.mf_me = h->comm_rank; ex.mf_out = fused_mf; ex.mf_push = mb_begin(h, c.engine, MB_MF);
+        if (h->mb_active && c.engine) mf_all = static_cast<const double*>(mb_gathered(h, MB_MF));   // the round that has just begun
     }
-    ex.wait = mb_wait(h, MB_MF);
-    const MboxPush tot_push = mb_begin(h, MB_TOT);
-    h->splan_done = false;
+    ex.wait = mb_wait(h, c.engine, MB_MF);
+    const MboxPush tot_push = mb_begin(h, c.engine, MB_TOT);
+    c.plan_rode = false;
     static const bool splan_off = getenv("GPF_SHARD_PLAN_IN_SCAN") && !strcmp(getenv("GPF_SHARD_PLAN_IN_SCAN"), "0");   // (A/B measurements, tests of k_strat_plan)
-    if (h->splan_ride && !splan_off && !want_q && h->mb_active && h->mb_engine && (int)G == h->comm_world) {
+    if (c.plan_in_scan && !splan_off && !want_q && h->mb_active && c.engine && (int)G == h->comm_world) {
         // a stratified resample: the plan needs nothing but the G shard totals of THIS round, and the scan's workgroup that ends up with this shard's total
         // pushes the last one of them -- it derives the plan right there (no k_strat_plan launch, no gap in front of the merge kernel)
         if (!h->shard_plan) HIP_TRY(h, hipMalloc(&h->shard_plan, sizeof(ShardPlan)));
         h->push_ticket += 1;
-        int64_t* const host_counts = ((h->own_direct && G == 1) || h->ring_now) ? nullptr : h->h_shard_counts;   // (as gpf_shard_push_count)
-        ex.splan = StratPlanJob{h->shard_plan, h->cfg.seed, h->epoch, (int)G, h->comm_rank, h->cfg.n_global, static_cast<const int64_t*>(mb_gathered(h, MB_TOT)), mb_wait(h, MB_TOT),
-                                h->shard_counts, host_counts, h->push_ticket, h->ring_now ? h->tr_dev : nullptr, (int)(2 * MAX_SHARDS * COUNT_STRIDE)};
+        int64_t* const host_counts = ((c.own && G == 1) || c.ring) ? nullptr : h->h_shard_counts;   // (as the push count)
+        ex.splan = StratPlanJob{h->shard_plan, h->cfg.seed, h->epoch, (int)G, h->comm_rank, h->cfg.n_global, static_cast<const int64_t*>(mb_gathered(h, MB_TOT)), mb_wait(h, c.engine, MB_TOT),
+                                h->shard_counts, host_counts, h->push_ticket, c.ring ? h->tr_dev : nullptr, (int)(2 * MAX_SHARDS * COUNT_STRIDE)};
         ex.zero128 = nullptr;                                     // (the plan's workgroup clears the counters itself: two workgroups must not store to them)
-        h->splan_done = true;
+        c.plan_rode = true;
     }
     if (want_q) {
-        if ((s = scan_launch_shard(h, 4, in, (int)G, slot, want_cdf, reinterpret_cast<uint64_t*>(out5), mf_all, ex))) return s;
+        if ((s = scan_launch_shard(h, 4, in, (int)G, slot, rq, reinterpret_cast<uint64_t*>(out5), mf_all, ex))) return s;
         GPF_LAUNCH(k_export_q, dim3(1), dim3(BLOCK), 0, h->stream, h->blockQ, gs, out5, tot_push);
     } else {
         ex.push = tot_push;
-        if ((s = scan_launch_shard(h, 3, in, (int)G, slot, want_cdf, reinterpret_cast<uint64_t*>(out5), mf_all, ex))) return s;
+        if ((s = scan_launch_shard(h, 3, in, (int)G, slot, rq, reinterpret_cast<uint64_t*>(out5), mf_all, ex))) return s;
     }
     HIP_TRY(h, hipGetLastError());
     h->raw_valid = false; h->raw_sum_valid = false;            // sc->raw holds the GLOBAL max but no sum: not the unsharded summary
     return GPF_OK;
 }
+gpf_status gpf_shard_weight_scan(gpf_handle h, const double* mf_all, int32_t G, int32_t want_q, int64_t* out5) { ShardCall c; gpf_status s = shard_ready(h); return s ? s : shard_weight_scan(h, c, mf_all, G, want_q, out5); }
 
 gpf_status gpf_shard_flags(gpf_handle h, int32_t* flags_out)
 {
@@ -145,30 +150,30 @@ gpf_status gpf_shard_flags(gpf_handle h, int32_t* flags_out)
     return GPF_OK;
 }
 
-gpf_status gpf_shard_residual_scan(gpf_handle h, const int64_t* tot_all, int32_t G, int64_t* out2)
+static gpf_status shard_residual_scan(gpf_handle h, const ShardCall& c, const int64_t* tot_all, int32_t G, int64_t* out2)
 {
-    gpf_status s = shard_ready(h);
-    if (s) return s;
     if (!tot_all || !out2 || G < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad arguments");
     // global S into sc->prio (the local CDF in cdf[0] stays local)
-    GPF_LAUNCH(k_set_global, dim3(1), dim3(64), 0, h->stream, tot_all, (int)G, &h->sc->prio, mb_wait(h, MB_TOT));
-    if ((s = residual_scans(h, &h->sc->prio, h->cfg.n_global))) return s;
-    GPF_LAUNCH(k_export_residual, dim3(1), dim3(64), 0, h->stream, h->sc, out2, mb_begin(h, MB_CR), nullptr, 0);
+    GPF_LAUNCH(k_set_global, dim3(1), dim3(64), 0, h->stream, tot_all, (int)G, &h->sc->prio, mb_wait(h, c.engine, MB_TOT));
+    gpf_status s = residual_scans(h, &h->sc->prio, h->cfg.n_global);
+    if (s) return s;
+    GPF_LAUNCH(k_export_residual, dim3(1), dim3(64), 0, h->stream, h->sc, out2, mb_begin(h, c.engine, MB_CR), nullptr, 0);
     HIP_TRY(h, hipGetLastError());
     h->residual_scanned = true;
     return GPF_OK;
 }
+gpf_status gpf_shard_residual_scan(gpf_handle h, const int64_t* tot_all, int32_t G, int64_t* out2) { gpf_status s = shard_ready(h); return s ? s : shard_residual_scan(h, ShardCall{}, tot_all, G, out2); }
 // ... the same WITHOUT a weight scan in front (shard_resample_impl: the one-launch summary reduction of the ESS read has left the global S with the
 // host and the gathered (max, flags) in the mailbox -- the unsharded filter's direct form, k_scan_residual2<DIRECT>): the weights are converted in the
 // residual scan itself, the exchange counters the weight scan would have cleared are cleared by k_export_residual
-static gpf_status shard_residual_scan_direct(gpf_handle h, const double* mf_all, uint64_t S_global, int32_t G, int64_t* out2)
+static gpf_status shard_residual_scan_direct(gpf_handle h, const ShardCall& c, const double* mf_all, uint64_t S_global, int32_t G, int64_t* out2)
 {
     gpf_status s = ensure_shard_counts(h);
     if (s) return s;
     if ((s = materialize(h))) return s;
-    const ResidDirect rd{h->lw, 0.0, 0, h->K, S_global, &h->sc->prio, mf_all, G, (int32_t)(h->mb_active && h->mb_engine)};
+    const ResidDirect rd{h->lw, 0.0, 0, h->K, S_global, &h->sc->prio, mf_all, G, (int32_t)(h->mb_active && c.engine)};
     if ((s = residual_scans(h, &h->sc->prio, h->cfg.n_global, nullptr, &rd))) return s;
-    GPF_LAUNCH(k_export_residual, dim3(1), dim3(64), 0, h->stream, h->sc, out2, mb_begin(h, MB_CR), h->shard_counts, (int)(2 * MAX_SHARDS * COUNT_STRIDE));
+    GPF_LAUNCH(k_export_residual, dim3(1), dim3(64), 0, h->stream, h->sc, out2, mb_begin(h, c.engine, MB_CR), h->shard_counts, (int)(2 * MAX_SHARDS * COUNT_STRIDE));
     HIP_TRY(h, hipGetLastError());
     h->residual_scanned = true;
     h->raw_valid = false; h->raw_sum_valid = false;
@@ -176,7 +181,7 @@ static gpf_status shard_residual_scan_direct(gpf_handle h, const double* mf_all,
 }
 
 // fill the argument block of the push kernels; bounds: HOST int64[G+1], first global slot of every shard
-static gpf_status push_args(gpf_handle h, int32_t method, const int64_t* tot_all, const int64_t* cr_all, int32_t G, int32_t me,
+static gpf_status push_args(gpf_handle h, const ShardCall& c, int32_t method, const int64_t* tot_all, const int64_t* cr_all, int32_t G, int32_t me,
                             const int64_t* bounds, PushArgs& a)
 {
     if ((method < 0 || method > 2) && method != GPF_RESAMPLE_MULTINOMIAL_SORTED) return fail(h, GPF_ERR_UNKNOWN_METHOD, "Resampling method not recognized.");
@@ -185,40 +190,39 @@ static gpf_status push_args(gpf_handle h, int32_t method, const int64_t* tot_all
     if (bounds[0] != 0 || bounds[G] != h->cfg.n_global || bounds[me] != h->cfg.gid0 || bounds[me + 1] != h->cfg.gid0 + h->n)
         return fail(h, GPF_ERR_INVALID_ARGUMENT, "shard bounds do not match this filter's global range");
     a.seed = h->cfg.seed; a.epoch = h->epoch; a.n_global = h->cfg.n_global; a.G = G; a.me = me;
-    int64_t c = 0;
+    int64_t nch = 0;
     for (int g = 0; g < G; ++g) {
         if (bounds[g + 1] < bounds[g]) return fail(h, GPF_ERR_INVALID_ARGUMENT, "shard bounds must be non-decreasing");
-        a.bounds[g] = bounds[g]; a.chunk0[g] = c;
-        c += (bounds[g + 1] - bounds[g] + PUSH_CHUNK - 1) / PUSH_CHUNK;
+        a.bounds[g] = bounds[g]; a.chunk0[g] = nch;
+        nch += (bounds[g + 1] - bounds[g] + PUSH_CHUNK - 1) / PUSH_CHUNK;
     }
-    a.bounds[G] = bounds[G]; a.chunk0[G] = c; a.nchunks = c;
+    a.bounds[G] = bounds[G]; a.chunk0[G] = nch; a.nchunks = nch;
     if (h->cfg.n_global > h->push_cap) {                       // staging list: one 16-byte entry per GLOBAL output slot at most
         if (h->push_stage) (void)hipFree(h->push_stage);
         h->push_stage = nullptr; h->push_cap = 0;
         HIP_TRY(h, hipMalloc(&h->push_stage, (size_t)h->cfg.n_global * sizeof(ulonglong2)));
         h->push_cap = h->cfg.n_global;
     }
-    a.extra = h->push_extra; a.pv = h->push_pv; a.skip_own = 0;
-    a.wait_tot = mb_wait(h, MB_TOT);
-    a.wait_cr = method == GPF_RESAMPLE_RESIDUAL ? mb_wait(h, MB_CR) : MboxWait{};
+    a.extra = c.extra; a.pv = c.extra_pv; a.skip_own = 0;
+    a.wait_tot = mb_wait(h, c.engine, MB_TOT);
+    a.wait_cr = method == GPF_RESAMPLE_RESIDUAL ? mb_wait(h, c.engine, MB_CR) : MboxWait{};
     a.tot_all = tot_all; a.cr_all = method == GPF_RESAMPLE_RESIDUAL ? cr_all : nullptr; a.stage = h->push_stage; a.counts = h->shard_counts; a.host_counts = h->h_shard_counts; a.ticket = h->push_ticket;
-    a.traffic = h->ring_now ? h->tr_dev : nullptr;                // (window exchange: nobody on the host reads the counts; the plan kernel keeps the traffic statistics)
+    a.traffic = c.ring ? h->tr_dev : nullptr;                // (window exchange: nobody on the host reads the counts; the plan kernel keeps the traffic statistics)
     a.ring = RingOut{nullptr, 0, 0};
     return GPF_OK;
 }
 
-gpf_status gpf_shard_push_count(gpf_handle h, int32_t method, const int64_t* tot_all, const int64_t* cr_all, int32_t G, int32_t me,
-                                const int64_t* bounds)
+static gpf_status shard_push_count(gpf_handle h, ShardCall& c, int32_t method, const int64_t* tot_all, const int64_t* cr_all, int32_t G, int32_t me, const int64_t* bounds)
 {
-    gpf_status s = shard_ready(h);
-    if (s) return s;
+    gpf_status s;
     if (!h->shard_counts) return fail(h, GPF_ERR_STATE, "gpf_shard_push_count needs gpf_shard_weight_scan of the same resample first");
     PushArgs a;
-    if ((s = push_args(h, method, tot_all, cr_all, G, me, bounds, a))) return s;    // the counters were cleared by the weight scan
+    if ((s = push_args(h, c, method, tot_all, cr_all, G, me, bounds, a))) return s;    // the counters were cleared by the weight scan
+    const bool no_host_counts = (c.own && G == 1) || c.ring;    // one shard, own-direct -- or the window exchange --: nobody waits for the counts, no system-scope publish
     h->counts_published = false;
     if (method == GPF_RESAMPLE_MULTINOMIAL_SORTED) {
         // sorted uniforms: ascending targets, so the plan is again ONE served slot range per shard (k_sorted_plan); every shard draws ALL tile
-        // totals itself -- with its weight scan when the library engine prepared the job, else now
+        // totals itself -- with its weight scan when the library engine prepared the job (ShardCall::gammas_pending, carried since), else now
         if (!h->shard_plan) HIP_TRY(h, hipMalloc(&h->shard_plan, sizeof(ShardPlan)));
         if (!h->splan_F) {
             HIP_TRY(h, hipMalloc(&h->splan_F, (MAX_SHARDS + 1) * sizeof(int64_t)));
@@ -226,12 +230,14 @@ gpf_status gpf_shard_push_count(gpf_handle h, int32_t method, const int64_t* tot
             HIP_TRY(h, hipMemsetAsync(h->splan_arrive, 0, sizeof(unsigned int), h->stream));
         }
         const int64_t ntl = (h->cfg.n_global + SP_TILE - 1) / SP_TILE;
-        if (!(h->sp_cap >= ntl + 1 && h->sp_job.g == h->sp_g && h->sp_job.epoch == h->epoch && h->sp_job.n == h->cfg.n_global && h->sp_job.gid0 == 0 && h->sp_job.ntl == ntl)
-            && (s = sorted_job_prepare(h, 0, h->cfg.n_global))) return s;
-        if ((s = sorted_gammas_finish(h, ntl > SP_DIRECT_TILES))) return s;
+        if (!(h->sp_cap >= ntl + 1 && h->sp_job.g == h->sp_g && h->sp_job.epoch == h->epoch && h->sp_job.n == h->cfg.n_global && h->sp_job.gid0 == 0 && h->sp_job.ntl == ntl)) {
+            if ((s = sorted_job_prepare(h, 0, h->cfg.n_global))) return s;
+            c.gammas_pending = true;
+        }
+        if ((s = sorted_gammas_finish(h, ntl > SP_DIRECT_TILES, std::exchange(c.gammas_pending, false)))) return s;
         h->push_ticket += 1;
         a.ticket = h->push_ticket;
-        if ((h->own_direct && G == 1) || h->ring_now) a.host_counts = nullptr;      // (one shard, own-direct -- or the window exchange --: nobody waits for the counts, no system-scope publish)
+        if (no_host_counts) a.host_counts = nullptr;
         const SortedPlanJob job{h->sp_g, h->sp_vlo, ntl, ntl > SP_DIRECT_TILES ? 1 : 0, h->splan_F, h->splan_arrive};
         s = timed(h, GPF_K_SEARCH, [&] { GPF_LAUNCH(k_sorted_plan, dim3((unsigned)(G > 1 ? G - 1 : 1)), dim3(MBLOCK), 0, h->stream, a, h->shard_plan, job); });
         if (s) return s;
@@ -240,10 +246,10 @@ gpf_status gpf_shard_push_count(gpf_handle h, int32_t method, const int64_t* tot
         h->push_counted = true;
         return GPF_OK;
     }
-    if (method == GPF_RESAMPLE_STRATIFIED && h->splan_done) {
-        // the plan rode in the weight scan's launch (gpf_shard_weight_scan, ScanExtras::splan): nothing to launch
-        h->splan_done = false;
-        h->counts_published = !((h->own_direct && G == 1) || h->ring_now);
+    if (method == GPF_RESAMPLE_STRATIFIED && c.plan_rode) {
+        // the plan rode in the weight scan's launch (shard_weight_scan, ScanExtras::splan): nothing to launch
+        c.plan_rode = false;
+        h->counts_published = !no_host_counts;
         h->push_counted = true;
         return GPF_OK;
     }
@@ -253,7 +259,7 @@ gpf_status gpf_shard_push_count(gpf_handle h, int32_t method, const int64_t* tot
         if (!h->shard_plan) HIP_TRY(h, hipMalloc(&h->shard_plan, sizeof(ShardPlan)));
         h->push_ticket += 1;
         a.ticket = h->push_ticket;
-        if ((h->own_direct && G == 1) || h->ring_now) a.host_counts = nullptr;      // (as above)
+        if (no_host_counts) a.host_counts = nullptr;
         s = timed(h, GPF_K_SEARCH, [&] { GPF_LAUNCH(k_strat_plan, dim3(1), dim3(128), 0, h->stream, a, h->shard_plan); });
         if (s) return s;
         HIP_TRY(h, hipGetLastError());
@@ -265,8 +271,8 @@ gpf_status gpf_shard_push_count(gpf_handle h, int32_t method, const int64_t* tot
 #define PUSH_SCAN_BLOCKS_PER_CU 8
 #endif
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(a.nchunks, (int64_t)h->n_cu * PUSH_SCAN_BLOCKS_PER_CU));
-    a.skip_own = h->own_direct ? 1 : 0;
-    if (h->own_direct) {
+    a.skip_own = c.own ? 1 : 0;
+    if (c.own) {
         // the shard's own slots: ancestors in place (k_search_own), nothing staged or packed for them; pass 1 walks the other shards' slots
         // only -- with one shard there are none
         const int gso = (int)std::max<int64_t>(1, std::min<int64_t>((h->n + GPF_MULTI_NS * SBLOCK - 1) / (GPF_MULTI_NS * SBLOCK), (int64_t)h->n_cu));
@@ -304,6 +310,8 @@ gpf_status gpf_shard_push_count(gpf_handle h, int32_t method, const int64_t* tot
     h->push_counted = true;
     return GPF_OK;
 }
+gpf_status gpf_shard_push_count(gpf_handle h, int32_t method, const int64_t* tot_all, const int64_t* cr_all, int32_t G, int32_t me, const int64_t* bounds)
+{ ShardCall c; gpf_status s = shard_ready(h); return s ? s : shard_push_count(h, c, method, tot_all, cr_all, G, me, bounds); }
 
 gpf_status gpf_shard_counts(gpf_handle h, int32_t G, int64_t* host_counts)
 {
@@ -329,18 +337,17 @@ gpf_status gpf_shard_counts(gpf_handle h, int32_t G, int64_t* host_counts)
     return GPF_OK;
 }
 
-gpf_status gpf_shard_push(gpf_handle h, int32_t method, const int64_t* tot_all, const int64_t* cr_all, int32_t G, int32_t me,
-                          const int64_t* bounds, int64_t capacity, double* packed_out)
+static gpf_status shard_push(gpf_handle h, const ShardCall& c, int32_t method, const int64_t* tot_all, const int64_t* cr_all, int32_t G, int32_t me,
+                             const int64_t* bounds, int64_t capacity, double* packed_out)
 {
-    gpf_status s = shard_ready(h);
-    if (s) return s;
+    gpf_status s;
     if (!h->push_counted) return fail(h, GPF_ERR_STATE, "gpf_shard_push needs gpf_shard_push_count of the same resample first");
-    if (capacity < 0 || (capacity > 0 && !packed_out && !h->ring_now)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad arguments");
+    if (capacity < 0 || (capacity > 0 && !packed_out && !c.ring)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad arguments");
     PushArgs a;
     if (method == GPF_RESAMPLE_STRATIFIED || method == GPF_RESAMPLE_MULTINOMIAL_SORTED) {
         const bool su = method == GPF_RESAMPLE_MULTINOMIAL_SORTED;
         if (!h->shard_plan) return fail(h, GPF_ERR_STATE, "gpf_shard_push needs gpf_shard_push_count of the same resample first");
-        if ((s = push_args(h, method, tot_all, cr_all, G, me, bounds, a))) return s;
+        if ((s = push_args(h, c, method, tot_all, cr_all, G, me, bounds, a))) return s;
         if (capacity == 0) return GPF_OK;
         // ancestors of the served slots (a streaming merge over the shard's own CDF) and, in the same kernel, their rows packed in
         // slot order; the grid is sized for the send buffer and stops at the served count, which only the device knows
@@ -351,10 +358,10 @@ gpf_status gpf_shard_push(gpf_handle h, int32_t method, const int64_t* tot_all, 
         sa.n = cap; sa.n_cells = h->n; sa.n_global = h->cfg.n_global; sa.gid0 = h->cfg.gid0; sa.seed = h->cfg.seed; sa.epoch = h->epoch;
         sa.K = h->K; sa.logN = h->logN; sa.anc = nullptr; sa.invN = 1.0 / (double)h->cfg.n_global;
         sa.update_lml = 0;                                            // the commit carries the log-ML update
-        sa.pack = PackOut{h->rows[h->cur], packed_out, capacity, h->cfg.gid0, h->W, h->push_extra, h->push_pv, h->own_direct ? h->anc : nullptr, (int)me, RingOut{nullptr, 0, 0}};
-        if (h->ring_now) {
+        sa.pack = PackOut{h->rows[h->cur], packed_out, capacity, h->cfg.gid0, h->W, c.extra, c.extra_pv, c.own ? h->anc : nullptr, (int)me, RingOut{nullptr, 0, 0}};
+        if (c.ring) {
             // the window exchange: own slots in place (own-direct), every other served slot straight into the window of the rank that holds it
-            if (!h->own_direct || !h->ring_active) return fail(h, GPF_ERR_STATE, "window exchange without own-direct resolution / without windows");
+            if (!c.own || !h->ring_active) return fail(h, GPF_ERR_STATE, "window exchange without own-direct resolution / without windows");
             sa.pack.ring = RingOut{h->ring_peers, (int64_t)(h->ring_seq & (RING_PARITIES - 1)) * h->ring_parity_words, h->ring_seq};
         }
         if (su) {                                                     // the GLOBAL tiles: their totals, or (many tiles) their starting points from k_sorted_tiles
@@ -370,13 +377,13 @@ gpf_status gpf_shard_push(gpf_handle h, int32_t method, const int64_t* tot_all, 
         return GPF_OK;
     }
     h->push_ticket += 1;
-    if ((s = push_args(h, method, tot_all, cr_all, G, me, bounds, a))) return s;
+    if ((s = push_args(h, c, method, tot_all, cr_all, G, me, bounds, a))) return s;
     if (capacity == 0) return GPF_OK;
     h->counts_published = true;
-    if (h->ring_now) {
+    if (c.ring) {
         // the window exchange of the i.i.d. resamplers (GPF_SHARD_EXCHANGE_P2P_ALL): every looked-up row goes straight into the window slot of the rank
         // that holds it; the traffic statistic is kept by the kernel, nobody publishes or waits for counts
-        if (!h->own_direct || !h->ring_active) return fail(h, GPF_ERR_STATE, "window exchange without own-direct resolution / without windows");
+        if (!c.own || !h->ring_active) return fail(h, GPF_ERR_STATE, "window exchange without own-direct resolution / without windows");
         a.ring = RingOut{h->ring_peers, (int64_t)(h->ring_seq & (RING_PARITIES - 1)) * h->ring_parity_words, h->ring_seq};
         a.host_counts = nullptr; h->counts_published = false;
     }
@@ -398,22 +405,22 @@ gpf_status gpf_shard_push(gpf_handle h, int32_t method, const int64_t* tot_all, 
     HIP_TRY(h, hipGetLastError());
     return GPF_OK;
 }
+gpf_status gpf_shard_push(gpf_handle h, int32_t method, const int64_t* tot_all, const int64_t* cr_all, int32_t G, int32_t me, const int64_t* bounds, int64_t capacity, double* packed_out)
+{ gpf_status s = shard_ready(h); return s ? s : shard_push(h, ShardCall{}, method, tot_all, cr_all, G, me, bounds, capacity, packed_out); }
 
-gpf_status gpf_shard_commit(gpf_handle h, const double* packed, int64_t m, const double* mf_all, const int64_t* tot_all, int32_t G)
+static gpf_status shard_commit(gpf_handle h, const ShardCall& c, const double* packed, int64_t m, const double* mf_all, const int64_t* tot_all, int32_t G)
 {
-    gpf_status s = shard_ready(h);
-    if (s) return s;
     if (!packed || !mf_all || !tot_all || G < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad arguments");
-    if (m != h->n && !(h->own_direct && m >= 0 && m <= h->n)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "a shard must receive exactly one entry per output slot");
+    if (m != h->n && !(c.own && m >= 0 && m <= h->n)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "a shard must receive exactly one entry per output slot");
     h->pend_ring = false;
-    h->pend_own = h->own_direct; h->pend_m = m;                  // (own-direct engine: m entries from the other shards, the rest through h->anc)
-    h->pend_own_range = h->own_direct && h->own_direct_range;
+    h->pend_own = c.own; h->pend_m = m;                          // (own-direct engine: m entries from the other shards, the rest through h->anc)
+    h->pend_own_range = c.own && c.own_range;
     // Deferred like the single-GPU gather: the next gpf_update propagates the entries straight out of
     // the exchange buffer into their slots (k_step<PACKED>); any other consumer scatters first (materialize()).
     // packed / mf_all / tot_all must stay alive and unchanged until then (the caller keeps them until the next commit).
     h->pending_packed = true;
     h->pend_packed = packed; h->pend_mf = mf_all; h->pend_tot = tot_all; h->pend_G = G;
-    h->pend_mailbox = h->mb_active && h->mb_engine;
+    h->pend_mailbox = h->mb_active && c.engine;
     h->epoch += 1;
     h->raw_valid = false; h->raw_sum_valid = false;
     h->max_valid = false;
@@ -422,6 +429,7 @@ gpf_status gpf_shard_commit(gpf_handle h, const double* packed, int64_t m, const
     mutated(h);
     return GPF_OK;
 }
+gpf_status gpf_shard_commit(gpf_handle h, const double* packed, int64_t m, const double* mf_all, const int64_t* tot_all, int32_t G) { gpf_status s = shard_ready(h); return s ? s : shard_commit(h, ShardCall{}, packed, m, mf_all, tot_all, G); }
 
 gpf_status gpf_shard_lml_est(gpf_handle h, double* out)
 {
@@ -523,14 +531,13 @@ gpf_status shard_scratch(gpf_filter* h)
 // phases 1 + 2 of DESIGN.md §6: (max, flags) and {S, sum q^2 limbs} of every shard, gathered on every rank -- through the shard
 // mailboxes (peer stores from the producing kernels, waits in the consuming ones: no collective) or two RCCL all-gathers.
 // Leaves h->cur_mf_all / cur_tot_all naming the gathered arrays of this round.
-struct EngineScope { gpf_filter* h; explicit EngineScope(gpf_filter* f) : h(f) { h->mb_engine = true; } ~EngineScope() { h->mb_engine = false; } };
 // is the global summary of the latest one-launch reduction (k_sum_shard) still a description of the current weights and of the mailbox's current rounds?
 bool gsum_valid(const gpf_filter* h)
 {
     return h->gsum_ok && h->mb_active && h->gsum_mut == h->mutations && h->gsum_mf_seq == h->mb_cur[MB_MF] && h->gsum_tot_seq == h->mb_cur[MB_TOT] &&
-           !h->pending_packed && !h->pending_gather && !h->pending_fill && !h->pending_move && !h->sum_pv_set;
+           !h->pending_packed && !h->pending_gather && !h->pending_fill && !h->pending_move;
 }
-gpf_status shard_summary(gpf_filter* h, int want_q, bool reuse_mf = false)
+gpf_status shard_summary(gpf_filter* h, ShardCall& c, int want_q, bool reuse_mf = false)
 {
     gpf_status s = shard_scratch(h);
     if (s) return s;
@@ -539,7 +546,7 @@ gpf_status shard_summary(gpf_filter* h, int want_q, bool reuse_mf = false)
         // the ESS read in front of this resample has exchanged (max, flags) already (its MB_MF round is the mailbox's current one): only the scan + its {S} round
         h->sh_round++;
         int64_t* tot = h->sh_tot + 5 * (int)((h->sh_round - 1) % SH_RING);
-        if ((s = gpf_shard_weight_scan(h, h->cur_mf_all, h->comm_world, want_q, tot))) return s;
+        if ((s = shard_ready(h)) || (s = shard_weight_scan(h, c, h->cur_mf_all, h->comm_world, want_q, tot))) return s;
         h->cur_tot_all = static_cast<const int64_t*>(mb_gathered(h, MB_TOT));
         return GPF_OK;
     }
@@ -557,14 +564,11 @@ gpf_status shard_summary(gpf_filter* h, int want_q, bool reuse_mf = false)
     // the summary needs its own launch ahead of the collective.
     const bool fuse_mb = mailbox_fuse_mf(h);
     const bool fuse = alias || (mb && fuse_mb);
-    if (fuse) { if ((s = shard_ready(h)) || (s = shard_max_slots(h))) return s; }
-    else if ((s = gpf_shard_weight_max(h, mf))) return s;
+    if ((s = shard_ready(h)) || (s = fuse ? shard_max_slots(h, c) : shard_weight_max(h, c, mf))) return s;
     if (!mb && !alias && (s = shard_all_gather(h, mf, mf_all, 2, ncclDouble, sizeof(double)))) return s;
-    struct FuseScope { gpf_filter* h; ~FuseScope() { h->fuse_mf_out = nullptr; } } fuse_scope{h};
-    h->fuse_mf_out = fuse ? mf : nullptr;
-    // (fused: MB_MF's round begins inside gpf_shard_weight_scan -- name the gathered array after it)
+    // (fused: MB_MF's round begins inside the weight scan -- name the gathered array after it)
     if (!fuse) h->cur_mf_all = mb ? static_cast<const double*>(mb_gathered(h, MB_MF)) : mf_all;
-    if ((s = gpf_shard_weight_scan(h, fuse ? mf_all : h->cur_mf_all, h->comm_world, want_q, tot))) return s;      // (fused + mailboxes: the callee names the gathered array)
+    if ((s = shard_ready(h)) || (s = shard_weight_scan(h, c, fuse ? mf_all : h->cur_mf_all, h->comm_world, want_q, tot, fuse ? mf : nullptr))) return s;   // (fused + mailboxes: the callee names the gathered array)
     if (fuse) h->cur_mf_all = mb ? static_cast<const double*>(mb_gathered(h, MB_MF)) : mf_all;
     if (!mb && !alias && (s = shard_all_gather(h, tot, tot_all, 5, ncclInt64, sizeof(int64_t)))) return s;
     h->cur_tot_all = mb ? static_cast<const int64_t*>(mb_gathered(h, MB_TOT)) : tot_all;
@@ -572,20 +576,22 @@ gpf_status shard_summary(gpf_filter* h, int want_q, bool reuse_mf = false)
 }
 // the same over another view of the weights (a prioritised resample: alpha lw, then log_ws), into summary slot `slot`, with or
 // without the CDF levels
-gpf_status shard_summary_of(gpf_filter* h, const PrioView& pv, WSum* slot, bool want_cdf)
+gpf_status shard_summary_of(gpf_filter* h, ShardCall& c, const PrioView& pv, WSum* slot, bool want_cdf)
 {
-    struct Scope { gpf_filter* h; ~Scope() { h->sum_pv_set = false; h->sum_slot = nullptr; h->sum_no_cdf = false; } } scope{h};
-    h->sum_pv = pv; h->sum_pv_set = true; h->sum_slot = slot; h->sum_no_cdf = !want_cdf;
-    return shard_summary(h, 0);
+    ShardCall d = c;
+    d.view = &pv; d.slot = slot; d.cdf = want_cdf;
+    const gpf_status s = shard_summary(h, d, 0);
+    c.plan_rode = d.plan_rode; c.gammas_pending = d.gammas_pending;   // (what a phase wrote for a later phase of the same call)
+    return s;
 }
 // the gathered summaries on the host: global max, flags, S and sum q^2
-gpf_status shard_scalars(gpf_filter* h, double& m, int& flags, uint64_t& S, uint64_t& Qhi, uint64_t& Qlo)
+gpf_status shard_scalars(gpf_filter* h, const ShardCall& c, double& m, int& flags, uint64_t& S, uint64_t& Qhi, uint64_t& Qlo)
 {
     const int G = h->comm_world;
     std::vector<double> mf(2 * (size_t)G); std::vector<int64_t> tot(5 * (size_t)G);
     if (h->mb_active) {                                          // wait for the peers' entries, then out of the mailbox into plain device memory
-        GPF_LAUNCH(k_mbox_collect, dim3(1), dim3(BLOCK), 0, h->stream, mb_wait(h, MB_MF), reinterpret_cast<const uint64_t*>(h->cur_mf_all),
-                   reinterpret_cast<uint64_t*>(h->sh_mf_all), 2 * G, mb_wait(h, MB_TOT), reinterpret_cast<const uint64_t*>(h->cur_tot_all),
+        GPF_LAUNCH(k_mbox_collect, dim3(1), dim3(BLOCK), 0, h->stream, mb_wait(h, c.engine, MB_MF), reinterpret_cast<const uint64_t*>(h->cur_mf_all),
+                   reinterpret_cast<uint64_t*>(h->sh_mf_all), 2 * G, mb_wait(h, c.engine, MB_TOT), reinterpret_cast<const uint64_t*>(h->cur_tot_all),
                    reinterpret_cast<uint64_t*>(h->sh_tot_all), 5 * G);
         HIP_TRY(h, hipGetLastError());
     }
@@ -1005,11 +1011,11 @@ static gpf_status pull_buffers(gpf_filter* h, int G)
     }
     return GPF_OK;
 }
-static gpf_status pull_requests(gpf_filter* h, int32_t method, const int64_t* tot_all, const int64_t* cr_all, int G, int me, const int64_t* bounds,
+static gpf_status pull_requests(gpf_filter* h, const ShardCall& c, int32_t method, const int64_t* tot_all, const int64_t* cr_all, int G, int me, const int64_t* bounds,
                                 bool exchange, bool force_self, std::vector<int64_t>& counts)
 {
     PushArgs a;
-    gpf_status s = push_args(h, method, tot_all, cr_all, G, me, bounds, a);
+    gpf_status s = push_args(h, c, method, tot_all, cr_all, G, me, bounds, a);
     if (s) return s;
     const int64_t n = h->n;
     HIP_TRY(h, hipMemsetAsync(h->pull_counts, 0, (size_t)MAX_SHARDS * COUNT_STRIDE * sizeof(int64_t), h->stream));
@@ -1112,7 +1118,7 @@ static gpf_status shard_sorted_gather(gpf_filter* h, int G, int me)
     return GPF_OK;
 }
 // ... second half: the unsharded sort + scan + search on them (the planner), the exchange counts
-static gpf_status shard_sorted_plan(gpf_filter* h, int G, int me, bool own)
+static gpf_status shard_sorted_plan(gpf_filter* h, const ShardCall& c, int G, int me)
 {
     gpf_status s;
     gpf_filter* p = h->planner;
@@ -1127,14 +1133,14 @@ static gpf_status shard_sorted_plan(gpf_filter* h, int G, int me, bool own)
     if (s) return fail(h, s, "planner: " + p->err);
     HIP_TRY(h, hipMemsetAsync(h->shard_counts, 0, (size_t)2 * MAX_SHARDS * COUNT_STRIDE * sizeof(int64_t), h->stream));
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((N + ANC_CHUNK - 1) / ANC_CHUNK, (int64_t)h->n_cu * 4));
-    s = timed(h, GPF_K_SEARCH, [&] { GPF_LAUNCH(k_anc_count, dim3(grid), dim3(ANC_BLOCK), 0, h->stream, anc_plan(h, G, me), own ? 1 : 0, h->anc, h->shard_counts); });
+    s = timed(h, GPF_K_SEARCH, [&] { GPF_LAUNCH(k_anc_count, dim3(grid), dim3(ANC_BLOCK), 0, h->stream, anc_plan(h, G, me), c.own ? 1 : 0, h->anc, h->shard_counts); });
     if (s) return s;
     HIP_TRY(h, hipGetLastError());
     h->counts_published = false;                                  // (gpf_shard_counts copies them from the device)
     h->push_counted = true;
     return GPF_OK;
 }
-static gpf_status shard_sorted_push(gpf_filter* h, int G, int me, bool own, int64_t capacity, double* packed_out)
+static gpf_status shard_sorted_push(gpf_filter* h, const ShardCall& c, int G, int me, int64_t capacity, double* packed_out)
 {
     if (capacity <= 0 || !packed_out) return GPF_OK;
     HIP_TRY(h, hipMemsetAsync(h->anc_cursors, 0, MAX_SHARDS * sizeof(unsigned long long), h->stream));
@@ -1143,7 +1149,7 @@ static gpf_status shard_sorted_push(gpf_filter* h, int G, int me, bool own, int6
     const AncPlan ap = anc_plan(h, G, me);
     const double* rows = h->rows[h->cur];
     gpf_status s = timed(h, GPF_K_GATHER, [&] {
-        DISPATCH_W(h, GPF_LAUNCH((k_anc_pack<WW>), dim3(grid), dim3(ANC_BLOCK), 0, h->stream, ap, own ? 1 : 0, rows, h->shard_counts, h->anc_cursors, capacity, packed_out));
+        DISPATCH_W(h, GPF_LAUNCH((k_anc_pack<WW>), dim3(grid), dim3(ANC_BLOCK), 0, h->stream, ap, c.own ? 1 : 0, rows, h->shard_counts, h->anc_cursors, capacity, packed_out));
     });
     if (s) return s;
     HIP_TRY(h, hipGetLastError());
@@ -1151,12 +1157,12 @@ static gpf_status shard_sorted_push(gpf_filter* h, int G, int me, bool own, int6
 }
 
 // phase 5 of a window exchange: the new population = the shard's own range through the ancestor array + the window entries of the other slots
-static gpf_status shard_commit_ring(gpf_handle h, const double* mf_all, const int64_t* tot_all, int G, bool own_is_a_range)
+static gpf_status shard_commit_ring(gpf_handle h, const ShardCall& c, const double* mf_all, const int64_t* tot_all, int G)
 {
-    h->pend_own = true; h->pend_m = 0; h->pend_own_range = own_is_a_range;   // (else: the own hits are the slots with anc >= 0, k_search_own)
+    h->pend_own = true; h->pend_m = 0; h->pend_own_range = c.own_range;   // (else: the own hits are the slots with anc >= 0, k_search_own)
     h->pending_packed = true;
     h->pend_packed = nullptr; h->pend_mf = mf_all; h->pend_tot = tot_all; h->pend_G = G;
-    h->pend_mailbox = h->mb_active && h->mb_engine;
+    h->pend_mailbox = h->mb_active && c.engine;
     h->pend_ring = true; h->pend_ring_seq = h->ring_seq;
     h->epoch += 1;
     h->raw_valid = false; h->raw_sum_valid = false;
@@ -1186,7 +1192,7 @@ static gpf_status shard_resample_impl(gpf_handle h, int32_t method, double prior
     const bool prio = priority_alpha == priority_alpha;
     const int64_t n = h->n, E = h->W + 1 + (prio ? 1 : 0);
     if (sorted && prio) return fail(h, GPF_ERR_INVALID_ARGUMENT, "sort_particles = true with a priority_fn is not available across shards");
-    EngineScope engine(h);                                        // the phases below push / wait through the shard mailboxes when they are up
+    ShardCall c; c.engine = true;                                 // what this call wants of the phases below (they push / wait through the shard mailboxes when they are up)
     phase_mark(h, -1);
     if (h->phases.on) h->phases.resamples += 1;
     // shard bounds from the contiguous-range rule every rank applies to its own gpf_config (ranks ordered by gid0)
@@ -1230,21 +1236,21 @@ static gpf_status shard_resample_impl(gpf_handle h, int32_t method, double prior
                                             multi_lds_bytes(h->ntiles, multi_logg(h->ntiles)) + 4096 <= (size_t)160 * 1024) ||
                                            (method == GPF_RESAMPLE_RESIDUAL && !pull && search_lds_bytes(h->ntiles, 2) + 40 * 1024 <= (size_t)160 * 1024) ||
                                            ranged || sorted);
-    struct OwnScope { gpf_filter* h; ~OwnScope() { h->own_direct = false; h->own_direct_range = false; h->ring_now = false; h->splan_ride = false; h->splan_done = false; } } own_scope{h};
-    h->splan_ride = method == GPF_RESAMPLE_STRATIFIED && !prio && !sorted;
-    h->own_direct = own; h->own_direct_range = own && ranged;
+    c.plan_in_scan = method == GPF_RESAMPLE_STRATIFIED && !prio && !sorted;
+    c.own = own; c.own_range = own && ranged;
+    c.offsets = method == GPF_RESAMPLE_MULTINOMIAL;               // (the offset levels serve k_push_multi only)
     // The window exchange (gpf_k_common.hpp RingOut / RingIn; gpf_comm_set_exchange): the resamplers with ascending targets exchange boundary slabs -- the
     // merge kernel stores them straight into the destination ranks' slot-addressed receive windows, the next propagate reads them there.  No split
     // sizes for the host to wait for, no ncclGroup, no send / receive buffer, no overflow; the call returns as soon as its kernels are enqueued.
     // (GPF_SHARD_EXCHANGE_P2P_ALL: the i.i.d. resamplers' rows too -- every entry names its slot, so the window takes them as it takes the slabs; that
     //  exchange is bandwidth-bound, (G-1)/G of all rows as scattered 8 (W + 2)-byte peer stores: opt-in until a multi-GPU run has timed it against RCCL)
     const bool p2p = own && h->ring_active && ((ranged && h->exchange_mode >= GPF_SHARD_EXCHANGE_P2P) || (!ranged && !pull && !sorted && h->exchange_mode == GPF_SHARD_EXCHANGE_P2P_ALL));
-    h->ring_now = p2p;
+    c.ring = p2p;
     // sorted multinomial: the tile totals of ALL global slots (they depend on seed, epoch and N alone) -- the job rides in the weight scan below
-    struct SpScope { gpf_filter* h; ~SpScope() { h->sp_job_set = false; } } sp_scope{h};
     if (method == GPF_RESAMPLE_MULTINOMIAL_SORTED) {
         if ((s = materialize(h))) return s;
         if ((s = sorted_job_prepare(h, 0, h->cfg.n_global))) return s;
+        c.gammas_pending = true;
         if (!h->shard_plan) HIP_TRY(h, hipMalloc(&h->shard_plan, sizeof(ShardPlan)));
         if (!h->splan_F) {
             HIP_TRY(h, hipMalloc(&h->splan_F, (MAX_SHARDS + 1) * sizeof(int64_t)));
@@ -1254,15 +1260,11 @@ static gpf_status shard_resample_impl(gpf_handle h, int32_t method, double prior
     }
 
     const double* raw_mf = nullptr; const int64_t* raw_tot = nullptr;
-    struct PushScope { gpf_filter* h; ~PushScope() { h->push_extra = 0; } } push_scope{h};
     if (prio) {
         if ((s = materialize(h))) return s;
-        h->want_offsets = false;
-        s = shard_summary_of(h, raw_view(h), &h->sc->raw, false);  // logsumexp(log_weights), every shard (resample.jl:180)
-        h->want_offsets = true;
-        if (s) return s;
+        if ((s = shard_summary_of(h, c, raw_view(h), &h->sc->raw, false))) return s;   // logsumexp(log_weights), every shard (resample.jl:180)
         raw_mf = h->cur_mf_all; raw_tot = h->cur_tot_all;
-        h->push_extra = 1; h->push_pv = PrioView{h->lw, nullptr, priority_alpha, 1};
+        c.extra = 1; c.extra_pv = PrioView{h->lw, nullptr, priority_alpha, 1};
     }
     // An ESS read stands in front of this resample (README.md:68-70; gpf_shard_step_ess, or the getter) and its one-launch reduction (k_sum_shard) has
     // exchanged (max, flags) and {S, limbs} already -- the weights and the mailbox's rounds are still those: the (max, flags) round is not repeated, and a
@@ -1273,12 +1275,7 @@ static gpf_status shard_resample_impl(gpf_handle h, int32_t method, double prior
     const bool resid_direct = reuse && method == GPF_RESAMPLE_RESIDUAL;
     const WSum gsum = h->gsum;
     h->gsum_ok = false;                                           // (whatever follows starts new rounds or changes the weights)
-    if (!resid_direct) {
-        h->want_offsets = method == GPF_RESAMPLE_MULTINOMIAL;     // (the offset levels serve k_push_multi only)
-        s = prio ? shard_summary_of(h, h->push_pv, &h->sc->prio, true) : shard_summary(h, 0, reuse);   // phases 1, 2 (safe_softmax of the priorities, :54)
-        h->want_offsets = true;
-        if (s) return s;
-    }
+    if (!resid_direct && (s = prio ? shard_summary_of(h, c, c.extra_pv, &h->sc->prio, true) : shard_summary(h, c, 0, reuse))) return s;   // phases 1, 2 (safe_softmax of the priorities, :54)
     if (check != GPF_CHECK_FALSE || invalid) {                    // safe_softmax validity (utils.jl:117-140): pinned flags, no stream sync
         // (the flags describe the GLOBAL weights: every rank takes the same branch here)
         int32_t flags = resid_direct ? gsum.flags : 0;
@@ -1290,47 +1287,53 @@ static gpf_status shard_resample_impl(gpf_handle h, int32_t method, double prior
     const int64_t* cr_all = nullptr;
     const int64_t* tot_all = h->cur_tot_all;
     if (method == GPF_RESAMPLE_RESIDUAL) {                        // phase 2b
-        if (resid_direct) { if ((s = shard_residual_scan_direct(h, h->cur_mf_all, gsum.S, G, h->sh_cr))) return s; }
-        else if ((s = gpf_shard_residual_scan(h, tot_all, G, h->sh_cr))) return s;
+        if (resid_direct) { if ((s = shard_residual_scan_direct(h, c, h->cur_mf_all, gsum.S, G, h->sh_cr))) return s; }
+        else if ((s = shard_ready(h)) || (s = shard_residual_scan(h, c, tot_all, G, h->sh_cr))) return s;
         if (!h->mb_active && (s = shard_all_gather(h, h->sh_cr, h->sh_cr_all, 2, ncclInt64, sizeof(int64_t)))) return s;
         cr_all = h->cur_cr_all = h->mb_active ? static_cast<const int64_t*>(mb_gathered(h, MB_CR)) : h->sh_cr_all;
     }
     phase_mark(h, GPF_PHASE_SUMMARIES);
+    // phases 3 and 4 (shard_ready in front of each, as the public entry points have it)
+    auto push_count = [&]() -> gpf_status { gpf_status r = shard_ready(h); return r ? r : shard_push_count(h, c, method, tot_all, cr_all, G, me, bounds.data()); };
+    auto push = [&](int64_t capacity, double* out) -> gpf_status {
+        if (sorted) return shard_sorted_push(h, c, G, me, capacity, out);
+        gpf_status r = shard_ready(h); return r ? r : shard_push(h, c, method, tot_all, cr_all, G, me, bounds.data(), capacity, out);
+    };
     if (p2p) {
         h->ring_seq += 1;                                         // (the same on every rank: SPMD call order)
-        if ((s = gpf_shard_push_count(h, method, tot_all, cr_all, G, me, bounds.data()))) return s;             // the plan: served range, own range (device only)
+        if ((s = push_count())) return s;                         // the plan: served range, own range (device only)
         phase_mark(h, GPF_PHASE_PLAN);
         // own slots in place, the others into their ranks' windows (one rank, i.i.d. targets: every slot is an own hit, nothing to look up for anybody else)
-        if ((ranged || G > 1) && (s = gpf_shard_push(h, method, tot_all, cr_all, G, me, bounds.data(), h->cfg.n_global, nullptr))) return s;
+        if ((ranged || G > 1) && (s = push(h->cfg.n_global, nullptr))) return s;
         phase_mark(h, GPF_PHASE_PACK);
         h->tr_calls += 1; h->tr_entry_bytes = (int64_t)(h->W + 2) * (int64_t)sizeof(double);
-        return shard_commit_ring(h, h->cur_mf_all, tot_all, G, ranged);   // deferred: the next propagate reads window and own hits in ONE launch
+        return shard_commit_ring(h, c, h->cur_mf_all, tot_all, G);   // deferred: the next propagate reads window and own hits in ONE launch
     }
     std::vector<int64_t> counts(2 * (size_t)G);
     int64_t pushed_cap = std::min(cap, h->sh_send_cap);
     int64_t n_send = 0, n_recv = 0;
     if (pull) {
         // phase 3 of the pull plan: requests out, counts known on the host BEFORE pass 2 is enqueued (no speculative capacity)
-        if ((s = pull_requests(h, method, tot_all, cr_all, G, me, bounds.data(), exchange, force && G == 1, counts))) return s;
+        if ((s = pull_requests(h, c, method, tot_all, cr_all, G, me, bounds.data(), exchange, force && G == 1, counts))) return s;
         phase_mark(h, GPF_PHASE_PLAN);
         for (int g = 0; g < G; ++g) { n_send += counts[g]; n_recv += counts[G + g]; }
         pushed_cap = std::min(n_send, h->sh_send_cap);
-        if ((s = gpf_shard_push(h, method, tot_all, cr_all, G, me, bounds.data(), pushed_cap, h->sh_send))) return s;
+        if ((s = push(pushed_cap, h->sh_send))) return s;
         phase_mark(h, GPF_PHASE_PACK);
     } else {
-        if ((s = sorted ? ((s = shard_sorted_gather(h, G, me)) ? s : shard_sorted_plan(h, G, me, own)) : gpf_shard_push_count(h, method, tot_all, cr_all, G, me, bounds.data()))) return s;   // phase 3
+        if ((s = sorted ? ((s = shard_sorted_gather(h, G, me)) ? s : shard_sorted_plan(h, c, G, me)) : push_count())) return s;   // phase 3
         phase_mark(h, GPF_PHASE_PLAN);
         if (own && G == 1) {
             // one shard, own-direct: every slot is an own hit -- nothing to exchange, so no split sizes to wait for (the host wait left a
             // gap in the queue on every resample); the i.i.d. methods have nothing to push either, stratified writes its ancestors in
             // place from the merge kernel
             counts[0] = ranged ? n : 0; counts[1] = n;
-            if (ranged && (s = gpf_shard_push(h, method, tot_all, cr_all, G, me, bounds.data(), pushed_cap, h->sh_send))) return s;
+            if (ranged && (s = push(pushed_cap, h->sh_send))) return s;
             phase_mark(h, GPF_PHASE_PACK);
         } else {
         // phase 4 is enqueued before the host learns the counts; the kernel stops at the capacity and the push is repeated if the
         // counts say it overflowed
-        if ((s = sorted ? shard_sorted_push(h, G, me, own, pushed_cap, h->sh_send) : gpf_shard_push(h, method, tot_all, cr_all, G, me, bounds.data(), pushed_cap, h->sh_send))) return s;
+        if ((s = push(pushed_cap, h->sh_send))) return s;
         phase_mark(h, GPF_PHASE_PACK);
         const auto w0 = std::chrono::steady_clock::now();
         if ((s = gpf_shard_counts(h, G, counts.data()))) return s;   // ONE host wait (the exchange's split sizes), behind phase 4
@@ -1356,7 +1359,7 @@ static gpf_status shard_resample_impl(gpf_handle h, int32_t method, double prior
         }
     }
     if (n_send > pushed_cap)
-        remember(sorted ? shard_sorted_push(h, G, me, own, n_send, h->sh_send) : gpf_shard_push(h, method, tot_all, cr_all, G, me, bounds.data(), n_send, h->sh_send));
+        remember(push(n_send, h->sh_send));
     // the exchange: [row | slot | ancestor id], grouped point-to-point sends and receives (one pair per PEER; the shard's own
     // entries never touch RCCL: one device-to-device copy on the same stream)
     const double* commit_from = h->sh_send;
@@ -1387,7 +1390,7 @@ static gpf_status shard_resample_impl(gpf_handle h, int32_t method, double prior
     }
     phase_mark(h, GPF_PHASE_EXCHANGE);
     if (late) { h->err = late_msg; h->comm_poisoned = true; return late; }
-    if (!prio) return gpf_shard_commit(h, commit_from, own ? n - counts[(size_t)G + me] : n, h->cur_mf_all, tot_all, G);   // phase 5 (deferred)
+    if (!prio) return (s = shard_ready(h)) ? s : shard_commit(h, c, commit_from, own ? n - counts[(size_t)G + me] : n, h->cur_mf_all, tot_all, G);   // phase 5 (deferred)
     // phase 5 of a prioritised resample, at once: scatter rows / parents / log_ws, log-ML from the raw summary ...
     {
         const int grid = grid_for(h, n, 8);
@@ -1398,12 +1401,9 @@ static gpf_status shard_resample_impl(gpf_handle h, int32_t method, double prior
         h->cur ^= 1;
     }
     // ... then logsumexp(log_ws) over all shards and lw = log_ws + (log N - logsumexp) (resample.jl:200)
-    h->want_offsets = false;
-    s = shard_summary_of(h, PrioView{h->lws, nullptr, 0.0, 0}, &h->sc->post, false);
-    h->want_offsets = true;
-    if (s) return s;
+    if ((s = shard_summary_of(h, c, PrioView{h->lws, nullptr, 0.0, 0}, &h->sc->post, false))) return s;
     GPF_LAUNCH(k_shard_apply_post, dim3(grid_for(h, n, 8)), dim3(BLOCK), 0, h->stream, h->cur_mf_all, h->cur_tot_all, G, h->K, h->logN, h->lws, h->lw, n,
-               mb_wait(h, MB_TOT));
+               mb_wait(h, c.engine, MB_TOT));
     HIP_TRY(h, hipGetLastError());
     h->epoch += 1;
     h->raw_valid = false; h->raw_sum_valid = false; h->max_valid = false; h->residual_scanned = false; h->push_counted = false;
@@ -1414,7 +1414,7 @@ static gpf_status shard_resample_impl(gpf_handle h, int32_t method, double prior
 
 } // extern "C"
 namespace {
-gpf_status shard_global_summary_launch(gpf_filter* h, double thr, bool* done);
+gpf_status shard_global_summary_launch(gpf_filter* h, const ShardCall& c, double thr, bool* done);
 bool shard_sum_fits(const gpf_filter* h);
 } // namespace
 extern "C" {
@@ -1446,7 +1446,8 @@ gpf_status gpf_shard_step_ess(gpf_handle h, const double* obs, int32_t n_obs, do
                       !h->hist_on && h->blk_obs_size == 0 && obs != nullptr && n_obs == model_obs_dim(h->cfg.model);
     // (the launch says "not available" before it has begun any mailbox round: the plain sequence is still open then)
     bool done = false;
-    if (fast && (s = shard_global_summary_launch(h, thr, &done))) return s;
+    ShardCall c; c.engine = true;
+    if (fast && (s = shard_global_summary_launch(h, c, thr, &done))) return s;
     if (!done) {
         double ess = 0.0;
         if ((s = gpf_shard_effective_sample_size(h, &ess))) return s;
@@ -1522,7 +1523,7 @@ gpf_status gpf_shard_sorted_count(gpf_handle h, const double* lw_all, int32_t G,
         return fail(h, GPF_ERR_STATE, "this shard's (gid0, n_particles) is not rank's contiguous share of n_global");
     if ((s = materialize(h)) || (s = shard_sorted_buffers(h, G))) return s;
     HIP_TRY(h, hipMemcpyAsync(h->planner->lw, lw_all, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    return shard_sorted_plan(h, G, me, h->own_direct);
+    return shard_sorted_plan(h, ShardCall{}, G, me);
 }
 gpf_status gpf_shard_sorted_push(gpf_handle h, int32_t G, int32_t me, int64_t capacity, double* packed_out)
 {
@@ -1530,7 +1531,7 @@ gpf_status gpf_shard_sorted_push(gpf_handle h, int32_t G, int32_t me, int64_t ca
     if (s) return s;
     if (!h->planner || !h->push_counted) return fail(h, GPF_ERR_STATE, "gpf_shard_sorted_push needs gpf_shard_sorted_count of the same resample first");
     if (G < 1 || G > MAX_SHARDS || me < 0 || me >= G || capacity < 0 || (capacity > 0 && !packed_out)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad arguments");
-    return shard_sorted_push(h, G, me, h->own_direct, capacity, packed_out);
+    return shard_sorted_push(h, ShardCall{}, G, me, capacity, packed_out);
 }
 gpf_status gpf_shard_resample_sorted(gpf_handle h, int32_t check, int32_t* invalid)
 {
@@ -1551,21 +1552,19 @@ namespace {
 // flags) to the peers (k_pack_mflags), then ONE reduction launch whose workgroup 0 exchanges the shard totals through the mailboxes, folds
 // the global summary and publishes it to pinned memory (k_sum_reduce<SHARD>); thr >= 0: it also leaves the verdict ESS < thr on the device.
 // *done = false: not available (RCCL all-gathers carry the summaries, or the filter is too large): the caller takes shard_summary.
-gpf_status shard_global_summary_launch(gpf_filter* h, double thr, bool* done);
-gpf_status shard_global_summary(gpf_filter* h, double thr, WSum& w, bool* done)
+gpf_status shard_global_summary(gpf_filter* h, const ShardCall& c, double thr, WSum& w, bool* done)
 {
-    gpf_status s = shard_global_summary_launch(h, thr, done);
+    gpf_status s = shard_global_summary_launch(h, c, thr, done);
     if (s || !*done) return s;
     if ((s = read_published_summary(h, w))) return s;
     h->gsum = w; h->gsum_ok = true;
     return GPF_OK;
 }
-gpf_status shard_global_summary_launch(gpf_filter* h, double thr, bool* done)
+gpf_status shard_global_summary_launch(gpf_filter* h, const ShardCall& c, double thr, bool* done)
 {
     *done = false;
     gpf_status s;
     if (!h->mb_active || !h->h_timeout) return GPF_OK;
-    EngineScope engine(h);
     if ((s = shard_scratch(h))) return s;
     const int r = (int)(h->sh_round++ % SH_RING);
     double* mf = h->sh_mf + 2 * r;
@@ -1576,13 +1575,13 @@ gpf_status shard_global_summary_launch(gpf_filter* h, double thr, bool* done)
     // one device, 256 workgroups of 1024 threads each) starve each other until the mailbox wait gives up.  Behind a separate launch the push needs
     // 256 free thread slots somewhere, which a waiting reduction always leaves.
     const bool fuse_mb = mailbox_fuse_mf(h);
-    if (shard_sum_collect() || !fuse_mb) { if ((s = gpf_shard_weight_max(h, mf))) return s; }
+    if (shard_sum_collect() || !fuse_mb) { if ((s = shard_ready(h)) || (s = shard_weight_max(h, c, mf))) return s; }
     else {
-        if ((s = shard_max_slots(h))) return s;
-        ss.slots = h->mslots[h->mcur]; ss.mf_out = mf; ss.push_mf = mb_begin(h, MB_MF);
+        if ((s = shard_max_slots(h, c))) return s;
+        ss.slots = h->mslots[h->mcur]; ss.mf_out = mf; ss.push_mf = mb_begin(h, c.engine, MB_MF);
     }
-    ss.mf_all = static_cast<const double*>(mb_gathered(h, MB_MF)); ss.np = h->comm_world; ss.wait_mf = mb_wait(h, MB_MF);
-    ss.push_tot = mb_begin(h, MB_TOT); ss.wait_tot = mb_wait(h, MB_TOT); ss.tot_all = static_cast<const int64_t*>(mb_gathered(h, MB_TOT));
+    ss.mf_all = static_cast<const double*>(mb_gathered(h, MB_MF)); ss.np = h->comm_world; ss.wait_mf = mb_wait(h, c.engine, MB_MF);
+    ss.push_tot = mb_begin(h, c.engine, MB_TOT); ss.wait_tot = mb_wait(h, c.engine, MB_TOT); ss.tot_all = static_cast<const int64_t*>(mb_gathered(h, MB_TOT));
     ss.G = h->comm_world; ss.me = h->comm_rank; ss.thr = thr; ss.go = &h->sc->gate_go;
     bool ok = false;
     if ((s = shard_sum_launch(h, ss, &ok))) return s;
@@ -1609,10 +1608,11 @@ gpf_status gpf_shard_effective_sample_size(gpf_handle h, double* out)
     if (!h->sh_mf) return fail(h, GPF_ERR_STATE, "needs gpf_comm_create first");
     static const bool fast_off = getenv("GPF_SHARD_GETTERS") && !strcmp(getenv("GPF_SHARD_GETTERS"), "scan");      // (A/B measurements, tests of the scan + copy path)
     if (!fast_off && h->comm_world == 1 && !h->comm && !h->pending_packed) return gpf_effective_sample_size(h, out);   // one shard IS the unsharded filter
+    ShardCall c; c.engine = true;
     if (!fast_off && h->mb_active && shard_sum_fits(h)) {
         if ((s = materialize(h))) return s;
         WSum w{}; bool done = false;
-        if ((s = shard_global_summary(h, -1.0, w, &done))) return s;
+        if ((s = shard_global_summary(h, c, -1.0, w, &done))) return s;
         if (done) {
             uint64_t hi, lo;
             normalise_Q(w, hi, lo);
@@ -1620,10 +1620,9 @@ gpf_status gpf_shard_effective_sample_size(gpf_handle h, double* out)
             return GPF_OK;
         }
     }
-    EngineScope engine(h);
-    if ((s = shard_summary(h, 1))) return s;
+    if ((s = shard_summary(h, c, 1))) return s;
     double m; int flags; uint64_t S, Qhi, Qlo;
-    if ((s = shard_scalars(h, m, flags, S, Qhi, Qlo))) return s;
+    if ((s = shard_scalars(h, c, m, flags, S, Qhi, Qlo))) return s;
     *out = flags ? std::nan("") : ess_from(S, Qhi, Qlo);
     return GPF_OK;
 }
@@ -1636,10 +1635,10 @@ gpf_status gpf_shard_log_ml_estimate(gpf_handle h, double* out)
     if (!h->sh_mf) return fail(h, GPF_ERR_STATE, "needs gpf_comm_create first");
     static const bool fast_off = getenv("GPF_SHARD_GETTERS") && !strcmp(getenv("GPF_SHARD_GETTERS"), "scan");
     if (!fast_off && h->comm_world == 1 && !h->comm && !h->pending_packed) return gpf_log_ml_estimate(h, out);   // one shard IS the unsharded filter
-    EngineScope engine(h);
-    if ((s = shard_summary(h, 0))) return s;
+    ShardCall c; c.engine = true;
+    if ((s = shard_summary(h, c, 0))) return s;
     double m; int flags; uint64_t S, Qhi, Qlo;
-    if ((s = shard_scalars(h, m, flags, S, Qhi, Qlo))) return s;
+    if ((s = shard_scalars(h, c, m, flags, S, Qhi, Qlo))) return s;
     double base;
     if ((s = gpf_shard_lml_est(h, &base))) return s;
     *out = base + lse_from(m, S, h->K, flags) - h->logN;

@@ -87,6 +87,88 @@ def run_exchange_switch(rank, world, port, model_name, n_global, T, out_dir):
         dist.destroy_process_group()
 
 
+ALTERNATE_METHODS = ("multinomial", "stratified", "residual", "multinomial_sorted")
+ALTERNATE_STEPS = 16
+
+
+def alternate_engines(g, sharded, a, b, ys, ess_reads=()):
+    """The two hosts of the sharded resample take turns on ONE handle: `a` (sharded, world 1, created by the library engine) against the unsharded `b`, bit for bit
+    after every resample and every update.  The engine is chosen per step by flipping a.backend.lib_comm: gpf_shard_resample (library) or sharded.py's
+    phase-by-phase composition of the public gpf_shard_* calls (python).  Method (t // 2) % 4; library on even t in the first eight steps, on odd t in the second
+    eight: every method runs under both engines and both transitions occur for each.  In front of two phase-by-phase steps a library call that sets every
+    per-call option it has: a tempered resample (t = 5), and a checked resample of all -Inf weights that is refused behind its weight scan (t = 10).
+    ess_reads: steps whose library-engine resample has an ESS read in front (summary reuse, the direct residual form)."""
+    assert a.backend.lib_comm
+    ErrorException = g.ErrorException
+
+    def same(what, t):
+        assert np.array_equal(a.local.parents, b.parents), (what, t, "parents")
+        assert np.array_equal(a.local.traces, b.traces), (what, t, "traces")
+        assert np.array_equal(a.local.log_weights, b.log_weights), (what, t, "log_weights")
+
+    def refused(call):
+        try:
+            call()
+        except ErrorException as e:
+            assert "Invalid weights." in str(e), str(e)
+            return
+        raise AssertionError("the resample of all -Inf weights was not refused")
+
+    for t in range(ALTERNATE_STEPS):
+        method = ALTERNATE_METHODS[(t // 2) % 4]
+        kw = {"sort_particles": False} if method == "stratified" else {}
+        library = (t % 2 == 0) if t < 8 else (t % 2 == 1)
+        if t == 5:                                               # library engine, tempered: three summary rounds over other views, the extra packed field
+            assert not library
+            a.backend.lib_comm = True
+            sharded.pf_resample(a, method, priority_fn=g.Tempering(0.5), check=False)
+            g.pf_resample(b, method, priority_fn=g.Tempering(0.5), check=False, **kw)
+            same("tempered", t)
+        if t == 10:                                              # library engine, refused behind its weight scan (stratified: the plan rode in that launch)
+            assert not library
+            a.backend.lib_comm = True
+            saved = (a.local.log_weights.copy(), b.log_weights.copy())
+            a.local.log_weights = np.full(saved[0].shape, -np.inf); b.log_weights = np.full(saved[1].shape, -np.inf)
+            refused(lambda: sharded.pf_resample(a, method, check=True))
+            refused(lambda: g.pf_resample(b, method, check=True, **kw))
+            a.local.log_weights, b.log_weights = saved
+            same("restored", t)
+        a.backend.lib_comm = library
+        if t in ess_reads:
+            assert library
+            assert sharded.get_ess(a) == g.get_ess(b), ("ess", t)
+        sharded.pf_resample(a, method, check=False)
+        g.pf_resample(b, method, check=False, **kw)
+        same("resample", t)
+        sharded.pf_update(a, (t + 2,), (None,), ys[t + 1]); g.pf_update(b, (t + 2,), (None,), ys[t + 1])
+        same("update", t)
+    for library in (True, False):
+        a.backend.lib_comm = library
+        assert sharded.get_lml_est(a) == g.get_lml_est(b), library
+        assert sharded.get_ess(a) == g.get_ess(b), library
+    a.backend.lib_comm = True
+
+
+def run_alternate(rank, world, port, n_global):
+    """alternate_engines on one rank WITH a communicator of its own (GPF_RCCL_LIBRARY names the transport) and shard mailboxes; the python engine's
+    collectives go through a one-rank gloo group"""
+    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
+    os.environ["GPF_SHARD_ENGINE"] = "library"
+    os.environ["GPF_SHARD_FORCE_COLLECTIVES"] = "1"         # read at import of gpf_amd.sharded
+    import torch.distributed as dist
+    import gpf_amd as g
+    from gpf_amd import sharded
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        model = g.models.lgssm2(); ys = g.models.simulate(model, ALTERNATE_STEPS + 2)
+        a = sharded.pf_initialize(model, (1,), ys[0], n_global, seed=5, device=0)
+        b = g.pf_initialize(model, (1,), ys[0], n_global, seed=5)
+        assert a.backend.lib_comm and a.backend.comm_world() == 1 and a.backend.summary_mode() == "mailbox"
+        alternate_engines(g, sharded, a, b, ys, ess_reads=(4, 9))
+    finally:
+        dist.destroy_process_group()
+
+
 def skew_weights(n_global, pattern):
     """global log-weight vectors that put all (or nothing) of the mass on single shards"""
     i = np.arange(n_global, dtype=np.float64)

@@ -293,6 +293,25 @@ def test_plan_switch_between_resamples(g, o):
     assert sharded.get_lml_est(a) == g.get_lml_est(b)
 
 
+@pytest.mark.parametrize("N", [2049, 50_001])
+def test_engines_alternate_on_one_handle(g, o, monkeypatch, N):
+    """the library engine (gpf_shard_resample) and the phase-by-phase python engine take turns on one handle (world 1, no communicator): a call of one leaves
+    nothing behind for the other -- shard_worker_gpu.alternate_engines.  N = 2049: two scan tiles, one particle in the second; 50 001: the own-direct paths"""
+    from gpf_amd import sharded
+    monkeypatch.setenv("GPF_SHARD_ENGINE", "library")
+    model = g.models.lgssm2(); ys = g.models.simulate(model, shard_worker_gpu.ALTERNATE_STEPS + 2)
+    a = sharded.pf_initialize(model, (1,), ys[0], N, seed=5)
+    b = g.pf_initialize(model, (1,), ys[0], N, seed=5)
+    assert a.backend.lib_comm
+    shard_worker_gpu.alternate_engines(g, sharded, a, b, ys)
+
+
+def test_engines_alternate_on_one_handle_with_communicator(g, o, monkeypatch, loopback_lib):
+    """... one spawned rank with a communicator and shard mailboxes (over tests/loopback_rccl), an ESS read in front of two of the library engine's resamples"""
+    monkeypatch.setenv("GPF_RCCL_LIBRARY", loopback_lib)
+    mp.spawn(shard_worker_gpu.run_alternate, args=(1, free_port(), 50_001), nprocs=1, join=True)
+
+
 _SKEW_KEPT = (("multinomial", "all_on_first_shard"), ("stratified", "all_on_first_shard"), ("residual", "single_particle"),
               ("multinomial_sorted", "all_on_first_shard"), ("stratified", "middle_band"), ("multinomial_sorted", "single_particle"))
 
