@@ -55,6 +55,8 @@ SYMBOLS = [
     ("gpf_initialize_blocks_ref", C.c_int, [_H, _pd, C.c_int32, C.c_int64, _pd, C.c_int32]),
     ("gpf_update_blocks_ref", C.c_int, [_H, _pd, C.c_int32, C.c_int64, _pd, C.c_int32]),
     ("gpf_resample_blocks_conditional", C.c_int, [_H, C.c_int32, C.c_int64, C.c_double, C.c_int32, _pi32, C.POINTER(C.c_int64)]),
+    ("gpf_resample_blocks_ancestor", C.c_int, [_H, C.c_int32, C.c_int64, C.c_double, C.c_int32, _pd, C.c_int32, _pd, C.c_int32, _pi32, C.POINTER(C.c_int64)]),
+    ("gpf_block_ancestor_log_weights", C.c_int, [_H, C.c_int64, _pd, C.c_int32, _pd, C.c_int32, _pd]),
     ("gpf_initialize_blocks_strata", C.c_int, [_H, _pd, C.c_int32, C.c_int64, _pd, C.c_int32, C.c_int32]),
     ("gpf_update_blocks_strata", C.c_int, [_H, _pd, C.c_int32, C.c_int64, _pd, C.c_int32, C.c_int32]),
     ("gpf_update_blocks_proposal", C.c_int, [_H, _pd, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int32]),

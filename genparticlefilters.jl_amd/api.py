@@ -462,7 +462,7 @@ def pf_resample(state, method: str = "multinomial", **kwargs):
 
 
 def pf_resample_blocks(state, block_size: int, method: str = "multinomial", *, priority_fn=None, ess_frac=None, sort_particles: bool = True, check="warn",
-                       conditional: bool = False):
+                       conditional: bool = False, reference=None, observations=None):
     """Many small filters in one state: the batched form of
 
         for b in blocks:                                   # consecutive blocks of block_size particles
@@ -475,7 +475,18 @@ def pf_resample_blocks(state, block_size: int, method: str = "multinomial", *, p
 
     conditional=True: the conditional multinomial step of conditional SMC (Andrieu, Doucet & Holenstein 2010; gpf.h
     gpf_resample_blocks_conditional): in every block that resamples, slot 0 -- the retained particle -- keeps itself (parent 0), the other slots
-    draw exactly as in the plain call.  Multinomial only, no priority_fn, blocks of at most 2048 particles."""
+    draw exactly as in the plain call.  Multinomial only, no priority_fn, blocks of at most 2048 particles.
+
+    conditional=True, reference=ref_t, observations=obs_t: particle Gibbs with ancestor sampling (Lindsten, Jordan & Schoen 2014; gpf.h
+    gpf_resample_blocks_ancestor): slot 0 draws its ancestor with probability proportional to w_i f(ref_t | x_i) instead of keeping itself.
+    ref_t (n_blocks, dim) and obs_t (n_blocks, n_obs) are the arguments of the pf_update_blocks(..., reference=ref_t) that follows: the step
+    being entered.  Everything else is the conditional call."""
+    if reference is not None and not conditional:
+        raise ValueError("reference= selects ancestor sampling, a form of the conditional step: pass conditional=True")
+    if reference is not None and observations is None:
+        raise ValueError("reference= needs observations=: the data vector of the step being entered, as the update that follows takes it")
+    if observations is not None and reference is None:
+        raise ValueError("observations= is read by ancestor sampling only: pass reference= as well")
     if method not in RESAMPLE_METHODS:
         raise ErrorException(f"Resampling method {method} not recognized.")
     if conditional and method != "multinomial":
@@ -490,7 +501,14 @@ def pf_resample_blocks(state, block_size: int, method: str = "multinomial", *, p
         raise ErrorException("block-wise resampling takes priority_fn = None or Tempering(alpha) (w -> alpha w)")
     check_id = 2 if check is True else (1 if check == "warn" else 0)
     inv, cnt = C.c_int32(0), C.c_int64(0)
-    if conditional:
+    if reference is not None:
+        obs = _block_obs(state, observations, block_size)
+        ref = _block_reference(state, reference, obs.shape[0])
+        st = state._L.gpf_resample_blocks_ancestor(state._h, RESAMPLE_METHODS[method], int(block_size), float("nan") if ess_frac is None else float(ess_frac),
+                                                   check_id, _pd(obs), obs.shape[1], _pd(ref), ref.shape[1], C.byref(inv), C.byref(cnt))
+        if st not in (_lib.OK, _lib.ERR_INVALID_WEIGHTS):        # (a refused call: the state, its epoch and the mask of the last call are untouched)
+            raise ErrorException(state._L.gpf_last_error(state._h).decode())
+    elif conditional:
         st = state._L.gpf_resample_blocks_conditional(state._h, RESAMPLE_METHODS[method], int(block_size),
                                                       float("nan") if ess_frac is None else float(ess_frac), check_id, C.byref(inv), C.byref(cnt))
         if st != _lib.OK:                                        # (a refused call: the state, its epoch and the mask of the last call are untouched)
@@ -707,6 +725,19 @@ def block_stats(state, block_size: int):
     ess, lml = np.empty(nb), np.empty(nb)
     state._check(state._L.gpf_block_stats(state._h, int(block_size), _pd(ess), _pd(lml)))
     return ess, lml
+
+
+def block_ancestor_log_weights(state, block_size: int, observations, reference):
+    """lwa_i = lw_i + log f(reference[b] | x_i) up to terms that do not depend on x_i, b = i // block_size: the weights the ancestor of slot 0 is
+    drawn from in pf_resample_blocks(..., conditional=True, reference=...), and what a backward simulation needs (gpf.h
+    gpf_block_ancestor_log_weights).  One launch, any block size; the state is not changed."""
+    if isinstance(state, DeviceParticleFilterSubState):
+        raise ErrorException("block_ancestor_log_weights works on the whole filter")
+    obs = _block_obs(state, observations, block_size)
+    ref = _block_reference(state, reference, obs.shape[0])
+    out = np.empty(state.n_particles)
+    state._check(state._L.gpf_block_ancestor_log_weights(state._h, int(block_size), _pd(obs), obs.shape[1], _pd(ref), ref.shape[1], _pd(out)))
+    return out
 
 
 def _block_column(state, addr, who: str):

@@ -197,6 +197,11 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     // (ModelArgs::blk_ref for the one launch).  They are staged behind the observations in the same pinned buffer (h_blk_obs holds MAX_OBS + MAX_DIM
     // words per block) and copied by the same launch; nothing of them is kept between calls
     double* blk_ref = nullptr; int64_t blk_ref_cap = 0;
+    // ancestor sampling (gpf_resample_blocks_ancestor / gpf_block_ancestor_log_weights): the data vectors and reference values of the step being ENTERED,
+    // [n_blocks][MAX_OBS] then [n_blocks][MAX_DIM] on the device -- scratch of the one call, apart from blk_obs (a rejuvenation before the update still
+    // sees the previous step's observation).  h_anc_in: the pinned buffer the copy kernel reads; anc_ev: recorded behind that kernel, waited for before
+    // the buffer is filled again
+    double* anc_in = nullptr; double* h_anc_in = nullptr; int64_t anc_in_cap = 0; hipEvent_t anc_ev = nullptr; bool anc_ev_pending = false;
     // gpf_set_block_params: every block's own model parameters, [n_blocks][MAX_PARAMS] on the device (ModelArgs::blk_params), uploaded once;
     // bp_size > 0: the rows are in force for blocks of this (clamped) size -- the block-wise steps run their BP kernels, everything that would
     // read cfg.params is refused (bp_refused)

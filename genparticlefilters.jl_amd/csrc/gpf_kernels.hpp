@@ -23,3 +23,4 @@
 #include "gpf_k_shard.hpp"
 #include "gpf_k_resize.hpp"
 #include "gpf_k_block.hpp"
+#include "gpf_k_block_anc.hpp"

@@ -5,6 +5,8 @@
 //   sample(P, first, xprev, obs, rng-counter) -> x      the model's internal proposal for the new
 //                                                       latent choices (ancestral sampling)
 //   loglik(P, x, obs) -> log p(y_t | x_t)               the weight increment of the constrained obs
+//   logtrans(P, xp, x, obs) -> log f(x_t = x | x_{t-1} = xp) MINUS the terms that do not depend on xp (normalising constants cancel wherever
+//                                                       it is used: ancestor sampling, backward simulation) -- + - * / only, no log_
 // Parameter vectors P (incl. derived constants such as log sigma) are built on the host
 // (models.py) so the CPU oracle and the kernels receive bit-identical inputs.
 // Operation order inside each expression is part of the spec.
@@ -137,6 +139,14 @@ template <> struct Model<MODEL_LGSSM2> {
         const double z0 = (obs[0] - x[0]) * P[6], z1 = (obs[1] - x[1]) * P[6];
         return -0.5 * (z0 * z0 + z1 * z1) - P[7];
     }
+    // the quadratic of `lt` in proposal_weight (o = 8)
+    static GPF_HD double logtrans(const double* P, const double* xp, const double* x, const double*)
+    {
+        const double t0 = P[0] * xp[0] + P[1] * xp[1];
+        const double t1 = P[2] * xp[0] + P[3] * xp[1];
+        const double a0 = (x[0] - t0) * P[12], a1 = (x[1] - t1) * P[12];
+        return -0.5 * (a0 * a0 + a1 * a1);
+    }
 };
 
 // bearings-only tracking, x = (px, py, vx, vy)   (BASELINE config 4)
@@ -172,6 +182,12 @@ template <> struct Model<MODEL_BEARINGS4> {
         const double z = r * P[10];
         return -0.5 * (z * z) - P[11];
     }
+    static GPF_HD double logtrans(const double* P, const double* xp, const double* x, const double*)
+    {
+        const double z0 = (x[0] - (xp[0] + xp[2])) / P[8], z1 = (x[1] - (xp[1] + xp[3])) / P[8];
+        const double z2 = (x[2] - xp[2]) / P[9], z3 = (x[3] - xp[3]) / P[9];
+        return -0.5 * ((z0 * z0 + z1 * z1) + (z2 * z2 + z3 * z3));
+    }
 };
 
 // stochastic volatility, x = h   (BASELINE config 5)
@@ -194,6 +210,12 @@ template <> struct Model<MODEL_SV1> {
     {
         const double y = obs[0];
         return (-0.5 * ((y * y) * exp_(-x[0])) - 0.5 * x[0]) - P[4];
+    }
+    static GPF_HD double logtrans(const double* P, const double* xp, const double* x, const double*)
+    {
+        const double mean = P[0] + P[1] * (xp[0] - P[0]);
+        const double z = (x[0] - mean) / P[2];
+        return -0.5 * (z * z);
     }
 };
 
@@ -242,6 +264,15 @@ template <> struct Model<MODEL_OBJECT_MOTION> {
         const double z = (obs[0] - x[1]) * P[3];
         return -0.5 * (z * z) - P[4];
     }
+    // obs: the data vector of the step being entered (its sin(t) covariate is the velocity of a moving object)
+    static GPF_HD double logtrans(const double* P, const double* xp, const double* x, const double* obs)
+    {
+        const bool mv = x[0] != 0.0, pm = xp[0] != 0.0;
+        const double lp = pm ? (mv ? P[5] : P[6]) : (mv ? P[7] : P[8]);
+        const double vel = mv ? obs[1] : 0.0;
+        const double z = (x[1] - (xp[1] + vel)) / P[2];
+        return lp + (-0.5 * (z * z));
+    }
 };
 
 // line_model, the fixture model of the reference's own tests (reference test/runtests.jl:3-16):
@@ -268,6 +299,11 @@ template <> struct Model<MODEL_LINE> {
         const bool out = x[1] != 0.0;
         const double z = (obs[0] - obs[1] * x[0]) * (out ? P[2] : P[1]);
         return -0.5 * (z * z) - (out ? P[4] : P[3]);
+    }
+    // the slope persists; the outlier's probability does not depend on xp
+    static GPF_HD double logtrans(const double*, const double* xp, const double* x, const double*)
+    {
+        return xp[0] == x[0] ? 0.0 : -__builtin_huge_val();
     }
     // The custom proposals of the reference's tests as ONE native proposal (test/initialize.jl:16-19, test/update.jl:42-43):
     // slope ~ uniform_discrete(0, 0) at the first step, outlier ~ bernoulli(0.0) at every step.  Both are deterministic

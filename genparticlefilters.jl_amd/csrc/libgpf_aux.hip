@@ -61,6 +61,22 @@ void launch_block_resample(gpf_filter* h, const BlockArgs& a, bool prio)
     else bool_dispatch(prio, [&](auto PRIO) { DISPATCH_W(h, (launch_block_resample_w<METHOD, WW, PRIO>(h, a))); });
 }
 
+// the ancestor-sampling resample (gpf_k_block_anc.hpp): model x keep_prev x team shape; per-block parameters are a run-time branch of the kernel
+template <int M, bool KEEP>
+void launch_block_resample_anc(gpf_filter* h, const BlockArgs& a, const AncArgs& x)
+{
+    constexpr int Wc = row_width(Model<M>::D, KEEP);
+    team_dispatch(a.nb, a.nblocks, [&](auto TEAM, auto ITEMS, dim3 grid) {
+        GPF_LAUNCH((k_block_resample_anc<M, Wc, TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, a, x);
+    });
+}
+template <int M>
+void launch_block_anc_lw(gpf_filter* h, const AncArgs& x, int64_t nb, double* out)
+{
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (h->n + BLOCK - 1) / BLOCK));
+    GPF_LAUNCH((k_block_anc_lw<M>), dim3(grid), dim3(BLOCK), 0, h->stream, x, h->rows[h->cur], h->W, h->lw, h->n, nb, out);
+}
+
 } // namespace gpfh
 
 extern "C" {
@@ -146,6 +162,57 @@ static gpf_status for_big_blocks(gpf_filter* h, int64_t block_size, F&& f)
 }
 } // namespace gpfh
 extern "C" {
+// ---- ancestor sampling: the inputs of the step being entered.  Checked on the host before anything changes; staged into scratch of their own
+struct AncestorIn { const double* obs; int32_t n_obs; const double* ref; int32_t n_ref; };
+static gpf_status block_ref_checks(gpf_filter* h, int64_t block_size, const double* ref, int32_t n_ref, const char* who);
+static gpf_status ancestor_in_checks(gpf_filter* h, int64_t block_size, const AncestorIn& in, const char* who)
+{
+    if (!in.obs || in.n_obs != model_obs_dim(h->cfg.model))     // (as gpf_update_blocks refuses them)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model takes " + std::to_string(model_obs_dim(h->cfg.model)) + " observation values per step and block");
+    return block_ref_checks(h, block_size, in.ref, in.n_ref, who);
+}
+// [n_blocks][MAX_OBS] data vectors, then [n_blocks][MAX_DIM] reference rows (zero-padded) -> anc_in on the device, by a kernel on the filter's stream;
+// x: the kernels' view of them, with the parameters the call uses
+static gpf_status stage_ancestor_in(gpf_filter* h, int64_t nblocks, const AncestorIn& in, AncArgs& x)
+{
+    constexpr int ROW = MAX_OBS + MAX_DIM;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (h->anc_in_cap < nblocks) {
+        if (h->anc_in) {
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            (void)hipFree(h->anc_in); (void)hipHostFree(h->h_anc_in);
+            h->anc_in = nullptr; h->h_anc_in = nullptr; h->anc_in_cap = 0; h->anc_ev_pending = false;
+        }
+        HIP_TRY(h, hipMalloc(&h->anc_in, (size_t)nblocks * ROW * sizeof(double)));
+        HIP_TRY(h, hipHostMalloc(&h->h_anc_in, (size_t)nblocks * ROW * sizeof(double)));
+        if (!h->anc_ev) HIP_TRY(h, hipEventCreateWithFlags(&h->anc_ev, hipEventDisableTiming));
+        h->anc_in_cap = nblocks;
+    }
+    if (h->anc_ev_pending) { HIP_TRY(h, hipEventSynchronize(h->anc_ev)); h->anc_ev_pending = false; }   // (the copy that last read the pinned buffer)
+    const int dim = model_dim(h->cfg.model);
+    double* const so = h->h_anc_in; double* const sr = so + nblocks * MAX_OBS;
+    static_assert(MAX_OBS == 4 && MAX_DIM == 4, "the four columns of a staged row");
+    const int no = in.n_obs;                                     // (>= 1, checked; the fill is unrolled: at 10^4 blocks it is most of the call's host time)
+    for (int64_t b = 0; b < nblocks; ++b) {
+        double* const d = so + b * MAX_OBS; const double* const r = in.obs + b * no;
+        d[0] = r[0]; d[1] = no > 1 ? r[1] : 0.0; d[2] = no > 2 ? r[2] : 0.0; d[3] = no > 3 ? r[3] : 0.0;
+    }
+    for (int64_t b = 0; b < nblocks; ++b) {
+        double* const d = sr + b * MAX_DIM; const double* const r = in.ref + b * dim;
+        d[0] = r[0]; d[1] = dim > 1 ? r[1] : 0.0; d[2] = dim > 2 ? r[2] : 0.0; d[3] = dim > 3 ? r[3] : 0.0;
+    }
+    const int64_t n_words = nblocks * ROW;
+    GPF_LAUNCH(k_stage_words, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(64, (n_words + BLOCK - 1) / BLOCK))), dim3(BLOCK), 0, h->stream,
+               (const double*)h->h_anc_in, h->anc_in, n_words);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(h->anc_ev, h->stream));
+    h->anc_ev_pending = true;
+    for (int i = 0; i < MAX_PARAMS; ++i) x.P[i] = h->args.P[i];
+    x.blk_params = h->bp_size > 0 ? h->blk_params : nullptr;
+    x.bp_size = h->bp_size > 0 ? h->bp_size : 1;
+    x.obs = h->anc_in; x.ref = h->anc_in + nblocks * MAX_OBS;
+    return GPF_OK;
+}
 static gpf_status resample_big_blocks(gpf_handle h, int32_t method, int64_t block_size, double priority_alpha, int32_t sort_particles,
                                       double ess_frac, int32_t check, int32_t* invalid, int64_t* n_resampled)
 {
@@ -200,12 +267,13 @@ static gpf_status resample_big_blocks(gpf_handle h, int32_t method, int64_t bloc
     }
     return GPF_OK;
 }
+// anc != nullptr (conditional only): ancestor sampling -- slot 0 draws its ancestor by the transition density towards the next reference value
 static gpf_status resample_blocks_impl(gpf_handle h, int32_t method, int64_t block_size, double priority_alpha, int32_t sort_particles,
-                                       double ess_frac, int32_t check, int32_t* invalid, int64_t* n_resampled, bool conditional)
+                                       double ess_frac, int32_t check, int32_t* invalid, int64_t* n_resampled, bool conditional, const AncestorIn* anc = nullptr)
 {
-    const char* const who = conditional ? "gpf_resample_blocks_conditional" : "gpf_resample_blocks";
+    const char* const who = anc ? "gpf_resample_blocks_ancestor" : conditional ? "gpf_resample_blocks_conditional" : "gpf_resample_blocks";
     // (the conditional step has no form for blocks that resample through views: "one block" asked for as any size >= n is one block of n particles)
-    gpf_status s = block_gate(h, block_size, who, GATE_FILTER | (conditional ? GATE_CLAMP : GATE_CLAMP_STORE | GATE_MAX));
+    gpf_status s = block_gate(h, block_size, who, GATE_FILTER | (conditional ? GATE_CLAMP : GATE_CLAMP_STORE | GATE_MAX) | (anc ? GATE_PARAMS : 0u));
     if (s) return s;
     if (conditional && (method == GPF_RESAMPLE_RESIDUAL || method == GPF_RESAMPLE_STRATIFIED))
         return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": multinomial only -- forcing one slot to keep its particle is not a valid conditional scheme "
@@ -214,11 +282,14 @@ static gpf_status resample_blocks_impl(gpf_handle h, int32_t method, int64_t blo
         return fail(h, GPF_ERR_UNKNOWN_METHOD, "Resampling method not recognized.");          // resample.jl:28
     if (conditional && block_size > BLK_MAX)
         return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": blocks of more than " + std::to_string(BLK_MAX) + " particles resample through sub-state views, which have no conditional form");
+    if (anc && (s = ancestor_in_checks(h, block_size, *anc, who))) return s;
     if (h->W != 2 && h->W != 4 && h->W != 8) return fail(h, GPF_ERR_STATE, "row width");
     if ((s = check_ready(h)) || (s = materialize(h))) return s;
     if (block_size > BLK_MAX) return resample_big_blocks(h, method, block_size, priority_alpha, sort_particles, ess_frac, check, invalid, n_resampled);
     const int64_t nblocks = (h->n + block_size - 1) / block_size;
     if ((s = block_buffers(h, nblocks))) return s;
+    AncArgs x{};
+    if (anc && (s = stage_ancestor_in(h, nblocks, *anc, x))) return s;   // (scratch only: the filter is as it was if this fails)
     BlockArgs a{};
     a.rows_in = h->rows[h->cur]; a.rows_out = h->rows[1 - h->cur]; a.lw = h->lw; a.anc = h->anc;
     a.n = h->n; a.nb = block_size; a.nblocks = nblocks; a.gid0 = h->cfg.gid0; a.seed = h->cfg.seed; a.epoch = h->epoch;
@@ -229,7 +300,8 @@ static gpf_status resample_blocks_impl(gpf_handle h, int32_t method, int64_t blo
     a.check_true = check == GPF_CHECK_TRUE ? 1 : 0;
     a.resampled = h->blk_mask;
     s = timed(h, GPF_K_SEARCH, [&] {
-        if (conditional)                          launch_block_resample<METHOD_COND>(h, a, false);
+        if (anc)                                  bool_dispatch(h->cfg.keep_prev != 0, [&](auto KEEP) { DISPATCH_MODEL(h, (launch_block_resample_anc<MM, KEEP>(h, a, x))); });
+        else if (conditional)                     launch_block_resample<METHOD_COND>(h, a, false);
         else if (method == GPF_RESAMPLE_MULTINOMIAL) launch_block_resample<0>(h, a, prio);
         else if (method == GPF_RESAMPLE_RESIDUAL) launch_block_resample<1>(h, a, prio);
         else                                      launch_block_resample<2>(h, a, prio);
@@ -267,6 +339,13 @@ gpf_status gpf_resample_blocks_conditional(gpf_handle h, int32_t method, int64_t
                                            int32_t* invalid, int64_t* n_resampled)
 {
     return resample_blocks_impl(h, method, block_size, __builtin_nan(""), 0, ess_frac, check, invalid, n_resampled, true);
+}
+// particle Gibbs with ancestor sampling (Lindsten, Jordan & Schoen 2014): the conditional step in which slot 0 draws its ancestor -- gpf.h
+gpf_status gpf_resample_blocks_ancestor(gpf_handle h, int32_t method, int64_t block_size, double ess_frac, int32_t check,
+                                        const double* obs, int32_t n_obs, const double* ref, int32_t n_ref, int32_t* invalid, int64_t* n_resampled)
+{
+    const AncestorIn in{obs, n_obs, ref, n_ref};
+    return resample_blocks_impl(h, method, block_size, __builtin_nan(""), 0, ess_frac, check, invalid, n_resampled, true, &in);
 }
 gpf_status gpf_block_resampled(gpf_handle h, int32_t* out)
 {
@@ -413,6 +492,26 @@ gpf_status gpf_block_proportion(gpf_handle h, int64_t block_size, int32_t column
     });
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(out, h->blk_est, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GPF_OK;
+}
+
+// lwa_i = lw_i + logtrans(P_b, x_i, ref_b, obs_b) of every particle: the weights the ancestor of slot 0 is drawn from -- gpf.h
+gpf_status gpf_block_ancestor_log_weights(gpf_handle h, int64_t block_size, const double* obs, int32_t n_obs, const double* ref, int32_t n_ref, double* out)
+{
+    const char* const who = "gpf_block_ancestor_log_weights";
+    gpf_status s = block_gate(h, block_size, who, GATE_FILTER | GATE_CLAMP);
+    if (s) return s;
+    const AncestorIn in{obs, n_obs, ref, n_ref};
+    if ((s = ancestor_in_checks(h, block_size, in, who))) return s;
+    if (!out) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": null output");
+    if ((s = check_ready(h)) || (s = materialize(h))) return s;
+    const int64_t nblocks = (h->n + block_size - 1) / block_size;
+    AncArgs x{};
+    if ((s = block_est_buffer(h, h->n)) || (s = stage_ancestor_in(h, nblocks, in, x))) return s;
+    DISPATCH_MODEL(h, (launch_block_anc_lw<MM>(h, x, block_size, h->blk_est)));
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out, h->blk_est, (size_t)h->n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return GPF_OK;
 }

@@ -194,6 +194,39 @@ gpf_status gpf_resample_blocks(gpf_handle h, int32_t method, int64_t block_size,
  *     block_size < 1, an unknown method. */
 gpf_status gpf_resample_blocks_conditional(gpf_handle h, int32_t method, int64_t block_size, double ess_frac, int32_t check,
                                            int32_t* invalid, int64_t* n_resampled);
+/* Particle Gibbs with ANCESTOR SAMPLING, the resampling half: gpf_resample_blocks_conditional in which the retained particle of every block that
+ * resamples draws its ancestor instead of keeping itself -- Lindsten, Jordan & Schoen (2014), "Particle Gibbs with ancestor sampling", JMLR 15,
+ * 2145-2184 (algorithm 2, the ancestor sampling step); the reference package has no counterpart.  Slot 0 -- particle b * block_size -- takes
+ *     P(a_0 = i)  proportional to  w_{t-1}^i f(x'_t | x_{t-1}^i),
+ * x'_t the block's NEXT reference value and f the model's transition density: the same target stays invariant and the retained path is broken up at
+ * every step, where the plain conditional step renews its early part only when the whole genealogy coalesces away from slot 0.
+ *   obs [n_blocks][n_obs], ref [n_blocks][n_ref] (host): the arguments of the gpf_update_blocks_ref that FOLLOWS -- the data vector and the reference
+ *       value of the step being entered (object_motion's transition reads the step's sin(t) covariate).  They are staged into scratch of their own:
+ *       the filter's per-block observations are untouched (a gpf_rejuvenate_blocks between this call and the update still sees the previous step's),
+ *       no copy and no mode stay behind the call.
+ *   ancestor weights  lwa_i = lw_i + logtrans(P_b, x_{t-1}^i, x'_t, obs_b), logtrans = log f minus the terms that do not depend on x_{t-1} (they
+ *       cancel), P_b the block's parameter row under gpf_set_block_params, else the filter's.  Their maximum, validity flags, K-bit fixed-point weights
+ *       and exact CDF are formed as for every resampler here (K from the block's particle count).
+ *   the draw  a_0 = first index whose CDF exceeds mulhi64(U, S'), U the resample uniform of slot b * block_size in the call's epoch: slot 0's OWN
+ *       counter, which the unconditional call uses for slot 0 and the conditional call leaves unused.
+ *   fallback  ancestor weights that hold a NaN or +Inf, or are all -Inf (a reference no particle of the block can lead to, e.g. line_model with a
+ *       slope no particle holds): a_0 = 0, the plain conditional step, and the call succeeds.
+ * Everything else is gpf_resample_blocks_conditional's: the slots j >= 1 (same counters, same CDF of the weights), the new weights of every particle,
+ * slot 0 included, ess_frac, check, invalid, n_resampled, gpf_block_resampled, the epoch advance and the trajectory store, which composes whatever
+ * parent slot 0 records.  A block that does not resample draws no ancestor.  One launch.
+ * Refused with the state untouched, epoch included: everything gpf_resample_blocks_conditional refuses, with its status codes; obs or ref NULL, n_obs
+ * or n_ref not the model's, a non-finite value in ref (GPF_ERR_INVALID_ARGUMENT; obs as gpf_update_blocks refuses it); a block_size that differs from
+ * the per-block parameters' (GPF_ERR_INVALID_ARGUMENT). */
+gpf_status gpf_resample_blocks_ancestor(gpf_handle h, int32_t method, int64_t block_size, double ess_frac, int32_t check,
+                                        const double* obs, int32_t n_obs, const double* ref, int32_t n_ref,
+                                        int32_t* invalid, int64_t* n_resampled);
+/* The ancestor weights of gpf_resample_blocks_ancestor by themselves: out[i] = lwa_i = lw_i + logtrans(P_b, x^i, ref_b, obs_b), b = i / block_size, for
+ * all n particles in one launch -- what a caller needs for a backward simulation of its own, and the first half of the draw above, bit for bit.  Per
+ * particle, so any block size (the parameter rows of gpf_set_block_params keep their own block size).  Reads the state and changes nothing (no epoch
+ * advance, no RNG draw); synchronises the stream.  Refusals: as gpf_resample_blocks_ancestor, except the 2048-particle limit and the block size of
+ * the per-block parameters; out NULL (GPF_ERR_INVALID_ARGUMENT). */
+gpf_status gpf_block_ancestor_log_weights(gpf_handle h, int64_t block_size, const double* obs, int32_t n_obs,
+                                          const double* ref, int32_t n_ref, double* out /* HOST [n] */);
 /* which blocks the last gpf_resample_blocks resampled: out[ceil(n / block_size)] (host), 1 / 0 */
 gpf_status gpf_block_resampled(gpf_handle h, int32_t* out);
 /* effective_sample_size(state[b]) and log_ml_estimate(state[b]) = log_ml_est + logsumexp(block weights) - log(block size) of every block

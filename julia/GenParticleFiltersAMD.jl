@@ -227,6 +227,27 @@ function pf_resample_blocks_conditional!(s::DeviceParticleFilterState, block_siz
     check === :warn && invalid[] != 0 && @warn("Invalid weights in some block: resampled with uniform weights.")
     return Int(count[])
 end
+# Particle Gibbs with ancestor sampling, the resampling half (gpf.h gpf_resample_blocks_ancestor; Lindsten, Jordan & Schoen 2014): the conditional call in
+# which slot 0 of every block that resamples draws its ancestor with probability proportional to w_i f(reference[:, b] | x_i).  observations (n_obs, n_blocks)
+# and reference (dim, n_blocks), column b for block b: the arguments of the pf_update_blocks_ref! that follows -- the step being entered.
+function pf_resample_blocks_ancestor!(s::DeviceParticleFilterState, block_size::Int, observations::Matrix{Float64}, reference::Matrix{Float64};
+                                      ess_frac=nothing, check=:warn)
+    chk = check === true ? 2 : (check === :warn ? 1 : 0)
+    invalid = Ref{Cint}(0); count = Ref{Int64}(0)
+    st = ccall((:gpf_resample_blocks_ancestor, libgpf), Cint, (Ptr{Cvoid}, Cint, Int64, Cdouble, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Int64}),
+               s.handle, 0, block_size, ess_frac === nothing ? NaN : Float64(ess_frac), chk, observations, size(observations, 1),
+               reference, size(reference, 1), invalid, count)
+    _status(s, st)
+    check === :warn && invalid[] != 0 && @warn("Invalid weights in some block: resampled with uniform weights.")
+    return Int(count[])
+end
+"the ancestor log-weights lw_i + log f(reference[:, b] | x_i) of every particle, b its block (gpf.h gpf_block_ancestor_log_weights): one launch, nothing changes"
+function block_ancestor_log_weights(s::DeviceParticleFilterState, block_size::Int, observations::Matrix{Float64}, reference::Matrix{Float64})
+    out = Vector{Float64}(undef, s.n_particles)
+    _status(s, ccall((:gpf_block_ancestor_log_weights, libgpf), Cint, (Ptr{Cvoid}, Int64, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}),
+                     s.handle, block_size, observations, size(observations, 1), reference, size(reference, 1), out))
+    return out
+end
 "(effective_sample_size(state[b]), log_ml_estimate(state[b])) of every block of block_size particles (src/utils.jl:163-178), one launch"
 function block_stats(s::DeviceParticleFilterState, block_size::Int)
     nb = cld(s.n_particles, block_size)
