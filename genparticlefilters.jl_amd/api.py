@@ -81,7 +81,7 @@ class DeviceParticleFilterState:
 
     def __init__(self, model: NativeModel, n_particles: int, seed: int = 1, keep_prev: bool = False,
                  device: int = 0, n_global: int | None = None, gid0: int = 0, stream: int | None = None,
-                 history: int = 0, history_blocks: bool = False):
+                 history: int = 0, history_blocks: bool = False, history_weights: bool = False):
         self._L = _lib.load()
         self.model, self.n_particles, self.seed = model, int(n_particles), int(seed)
         self.keep_prev = bool(keep_prev)
@@ -102,8 +102,11 @@ class DeviceParticleFilterState:
         self._L.gpf_state_dim(self._h, C.byref(d), C.byref(w))
         self.dim, self.row_width = d.value, w.value
         self.history_blocks = bool(history and history_blocks)
+        self.history_weights = bool(self.history_blocks and history_weights)   # ... with the records of a backward pass (gpf_history_enable_blocks_weights)
         if history:                      # trajectory store for `history` time steps (persistent-trace queries); history_blocks: the block-wise
             enable = self._L.gpf_history_enable_blocks if history_blocks else self._L.gpf_history_enable   # calls feed it too (gpf.h)
+            if self.history_weights:
+                enable = self._L.gpf_history_enable_blocks_weights
             self._check(enable(self._h, int(history)))
 
     # -- state[idxs] / view(state, idxs): a sub-state over a range start:step:stop or over ANY vector of distinct indices
@@ -637,7 +640,7 @@ def block_ancestors(state) -> np.ndarray:
 
 def pf_initialize_blocks(model: NativeModel, model_args: tuple, observations, n_particles: int, block_size: int, *, seed: int = 1,
                          keep_prev: bool = False, device: int = 0, strata=None, layout: str = "contiguous", params=None, history: int = 0,
-                         reference=None):
+                         reference=None, history_weights: bool = False):
     """many small filters in one state, each with its own data: block b (block_size consecutive particles) is initialised with
     observations[b] -- the batched form of per-view initialisation (gpf.h gpf_initialize_blocks).  strata: every block is initialised
     stratified by itself (src/initialize.jl:92-109 per sub-state, gpf.h gpf_initialize_blocks_strata), the same strata for all blocks.
@@ -646,10 +649,15 @@ def pf_initialize_blocks(model: NativeModel, model_args: tuple, observations, n_
     block_mean / block_var / block_proportionmap, block_moments(..., step=t), and everything the whole-filter store answers.
     reference: conditional SMC (gpf.h gpf_initialize_blocks_ref) -- an (n_blocks, dim) array; slot 0 of block b (particle b * block_size) is
     pinned to reference[b] and weighted by log p(y_b | reference[b]); every other particle is what the call without a reference gives.  A
-    per-call input (nothing is kept), default proposal only, all values finite; the values of discrete latents are the caller's business."""
+    per-call input (nothing is kept), default proposal only, all values finite; the values of discrete latents are the caller's business.
+    history_weights: the store also records every step's log-weights and per-block observations (gpf.h gpf_history_enable_blocks_weights: 8 bytes more
+    per particle and step), which block_backward_trajectories needs; raises without history=T."""
     if reference is not None and strata is not None:
         raise ValueError("a reference is offered with the default proposal only, not with strata")
-    state = DeviceParticleFilterState(model, n_particles, seed=seed, keep_prev=keep_prev, device=device, history=history, history_blocks=bool(history))
+    if history_weights and not history:
+        raise ValueError("history_weights=True needs the block-wise trajectory store: pass history=T as well")
+    state = DeviceParticleFilterState(model, n_particles, seed=seed, keep_prev=keep_prev, device=device, history=history, history_blocks=bool(history),
+                                      history_weights=bool(history_weights))
     obs = _block_obs(state, observations, block_size)
     if params is not None:
         set_block_params(state, params, block_size)
@@ -1109,6 +1117,39 @@ def block_sample_trajectories(state, block_size: int, n_samples: int = 1, steps=
     idx = np.empty((nb, int(n_samples)), np.int64) if return_indices else None
     state._check(state._L.gpf_block_sample_trajectories(state._h, int(block_size), int(n_samples), lo, hi, _pd(traj),
                                                         idx.ctypes.data_as(C.POINTER(C.c_int64)) if return_indices else None))
+    return (traj, idx) if return_indices else traj
+
+
+def block_backward_trajectories(state, block_size: int, n_samples: int = 1, steps=None, return_indices: bool = False):
+    """backward simulation per block (FFBSi; gpf.h gpf_block_backward_sample): draw j of block b takes its step-T particle exactly as
+    block_sample_trajectories does, then re-draws the particle of every earlier step s among the particles of the block its lineage occupied, from
+    the step's recorded weights times the transition density towards the particle held at s + 1 -- smoothed paths that do not share the coalesced
+    genealogy.  One launch for all blocks, draws and steps; needs pf_initialize_blocks(..., history=T, history_weights=True).  Returns
+    [n_blocks, n_samples, n_steps, dim], and with return_indices=True also the [n_blocks, n_samples, n_steps] int64 indices (1-based, GLOBAL, in the
+    final order of their step) of the held particles.  steps as in block_sample_trajectories; the walk always starts at the last step.  A block with
+    NaN / +Inf weights gets indices 0 and NaN paths.  Under set_block_params every step uses the drawing block's CURRENT parameter row.  Advances the
+    RNG epoch by T - lo + 1; the filter is left untouched."""
+    if not getattr(state, "history_weights", False):
+        raise ErrorException("block_backward_trajectories needs the block-wise trajectory store with its weight records "
+                             "(pf_initialize_blocks(..., history=T, history_weights=True)), which this state does not have")
+    if steps is None:
+        k = C.c_int32(0)
+        state._check(state._L.gpf_history_steps(state._h, C.byref(k)))
+        lo, hi = 1, int(k.value)
+    elif isinstance(steps, (tuple, list)):
+        lo, hi = int(steps[0]), int(steps[1])
+    else:
+        lo = hi = int(steps)
+    if lo < 1 or hi < 1:
+        raise ErrorException("block_backward_trajectories: steps are 1-based (step 1 = the initialisation)")
+    if hi < lo or int(n_samples) < 1 or int(block_size) < 1:
+        raise ErrorException("block_backward_trajectories: need lo <= hi, n_samples >= 1 and block_size >= 1")
+    bs = min(int(block_size), max(state.n_particles, 1))
+    nb = (state.n_particles + bs - 1) // bs
+    traj = np.empty((nb, int(n_samples), hi - lo + 1, state.dim))
+    idx = np.empty((nb, int(n_samples), hi - lo + 1), np.int64) if return_indices else None
+    state._check(state._L.gpf_block_backward_sample(state._h, int(block_size), int(n_samples), lo, hi, _pd(traj),
+                                                    idx.ctypes.data_as(C.POINTER(C.c_int64)) if return_indices else None))
     return (traj, idx) if return_indices else traj
 
 

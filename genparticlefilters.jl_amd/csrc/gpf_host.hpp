@@ -132,6 +132,13 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     int hist_step = -1;                  // index of the current step (0 = after gpf_initialize)
     const int32_t** hist_dev_maps = nullptr;
     const double** hist_dev_x = nullptr;   // device table of the snapshots hist_x[s], hist_cap entries (gpf_block_sample_trajectories walks all steps in one launch)
+    // gpf_history_enable_blocks_weights: what a backward pass needs of every step, taken wherever hist_snapshot takes hist_x (none of it exists otherwise)
+    bool hist_weights = false;
+    // (both live behind the step's columns in the allocation of hist_x[step]: nothing of their own to free)
+    std::vector<double*> hist_lw;        // [step] the n log-weights in the step's final order (nullptr until snapshotted)
+    std::vector<double*> hist_obs;       // [step] the [n_blocks][MAX_OBS] observation rows the step was entered with, in the block order of the snapshot
+    std::vector<int64_t> hist_bsize;     // [step] the block size of the block-wise call that entered the step; 0: a whole-filter call (no per-block rows)
+    const double** hist_dev_lw = nullptr; const double** hist_dev_obs = nullptr;   // device tables of hist_lw / hist_obs beside hist_dev_x, hist_cap entries each
     // sub-state view (src/view.jl:16-48): this handle aliases particles [view_start, view_start + n) of `parent`
     gpf_filter* parent = nullptr;
     std::vector<gpf_filter*> views;      // the live view handles of THIS filter: gpf_destroy orphans them (a view used after its filter is gone fails loudly)

@@ -24,3 +24,4 @@
 #include "gpf_k_resize.hpp"
 #include "gpf_k_block.hpp"
 #include "gpf_k_block_anc.hpp"
+#include "gpf_k_block_back.hpp"

@@ -605,6 +605,7 @@ static gpf_status block_initialize_impl(gpf_handle h, const double* obs, int32_t
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     gpf_status s = hist_begin_step(h, true);                     // (the block-wise store: step 1)
     if (s || (s = set_block_obs(h, obs, n_obs, block_size, ref))) return s;
+    if (h->hist_weights) h->hist_bsize.back() = block_size;     // (the step has per-block observation rows for the store to record)
     if (ref) h->args.blk_ref = h->blk_ref;
     const int grid = step_grid(h);
     s = timed(h, GPF_K_STEP, [&] {
@@ -625,6 +626,7 @@ static gpf_status block_update_impl(gpf_handle h, const double* obs, int32_t n_o
     gpf_status s = materialize(h);                               // (no fused gather in the block-wise step)
     // (the block-wise store: the step that ends is snapshotted and the next one begins; the entry points have checked the observations and the store's room)
     if (s || (s = hist_begin_step(h, false)) || (s = set_block_obs(h, obs, n_obs, block_size, ref))) return s;
+    if (h->hist_weights) h->hist_bsize.back() = block_size;     // (as in block_initialize_impl)
     if (ref) h->args.blk_ref = h->blk_ref;                       // (shares its slot with blk_prop: mode 4 and a reference exclude each other)
     if (mode == 4) {
         const int64_t nblocks = (h->n + block_size - 1) / block_size;
@@ -1434,7 +1436,7 @@ gpf_status gpf_history_enable(gpf_handle h, int32_t max_steps)
     if (max_steps < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "max_steps < 1");
     if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, "the trajectory store is not available for sharded filters");
     if (h->initialized) return fail(h, GPF_ERR_STATE, "enable the trajectory store before gpf_initialize");
-    h->hist_on = true; h->hist_blocks = false; h->hist_cap = max_steps;
+    h->hist_on = true; h->hist_blocks = false; h->hist_weights = false; h->hist_cap = max_steps;
     if (h->hist_dev_maps) (void)hipFree(h->hist_dev_maps);
     HIP_TRY(h, hipMalloc(&h->hist_dev_maps, (size_t)max_steps * sizeof(int32_t*)));
     if (h->hist_dev_x) { (void)hipFree(h->hist_dev_x); h->hist_dev_x = nullptr; }
@@ -1448,6 +1450,19 @@ gpf_status gpf_history_enable_blocks(gpf_handle h, int32_t max_steps)
     gpf_status s = gpf_history_enable(h, max_steps);
     if (s) return s;
     h->hist_blocks = true;
+    return GPF_OK;
+}
+
+// ... plus the records of a backward pass: every step's log-weights and per-block observation rows (gpf.h)
+gpf_status gpf_history_enable_blocks_weights(gpf_handle h, int32_t max_steps)
+{
+    gpf_status s = gpf_history_enable_blocks(h, max_steps);
+    if (s) return s;
+    for (const double*** t : {&h->hist_dev_lw, &h->hist_dev_obs}) {
+        if (*t) { (void)hipFree(*t); *t = nullptr; }
+        HIP_TRY(h, hipMalloc(t, (size_t)max_steps * sizeof(double*)));
+    }
+    h->hist_weights = true;
     return GPF_OK;
 }
 
@@ -1650,6 +1665,76 @@ gpf_status gpf_block_sample_trajectories(gpf_handle h, int64_t block_size, int32
     if (idx_out) HIP_TRY(h, hipMemcpyAsync(idx_out, d_idx.p, (size_t)draws * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->epoch += 1;                                                // as gpf_sample_unweighted: the draws' slots are not read again
+    return GPF_OK;
+}
+// ---- backward simulation per block (gpf.h gpf_block_backward_sample): the step-T draw and the whole backward pass of all blocks and draws in one launch
+} // extern "C"
+namespace gpfh {
+template <int M>
+void launch_block_backward(gpf_filter* h, const BackArgs& a, const AncArgs& x)
+{
+    team_dispatch(a.nb, a.nblocks, [&](auto TEAM, auto ITEMS, dim3 grid) {
+        // (the draws of a block are independent: with few blocks they are dealt to gridDim.y workgroups per block, so that the launch fills the chip)
+        grid.y = (unsigned)std::max<int64_t>(1, std::min<int64_t>(a.n_samples, 2048 / std::max<int64_t>(1, (int64_t)grid.x)));
+        GPF_LAUNCH((k_block_backward<M, TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, a, x);
+    });
+}
+} // namespace gpfh
+extern "C" {
+gpf_status gpf_block_backward_sample(gpf_handle h, int64_t block_size, int32_t n_samples, int32_t step_lo, int32_t step_hi,
+                                     double* traj_out, int64_t* idx_out)
+{
+    const char* who = "gpf_block_backward_sample";
+    gpf_status s = block_store_gate(h, block_size, who);
+    if (s) return s;
+    if (!h->hist_weights)
+        return fail(h, GPF_ERR_STATE, std::string(who) + " needs the store's weight records (gpf_history_enable_blocks_weights before gpf_initialize_blocks)");
+    if ((s = block_gate(h, block_size, who, GATE_PARAMS))) return s;
+    if (!traj_out) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": null trajectory output");
+    if (n_samples < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": n_samples < 1");
+    if ((s = check_ready(h))) return s;
+    const int T = (int)h->hist_x.size();
+    if (step_lo < 1 || step_hi < step_lo || step_hi > T) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": need 1 <= step_lo <= step_hi <= gpf_history_steps");
+    const int64_t nblocks = (h->n + block_size - 1) / block_size, n_steps = step_hi - step_lo + 1;
+    const int64_t lim = (int64_t)1 << 31;
+    const int64_t draws = nblocks * n_samples;                    // (as gpf_block_sample_trajectories: no product below overflows before it is compared)
+    if (draws >= lim || n_steps * h->d >= lim || draws >= (lim + n_steps * h->d - 1) / (n_steps * h->d))
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": n_blocks * n_samples and n_blocks * n_samples * n_steps * dim must stay below 2^31");
+    // every walked step above step_lo reads the observation rows it was entered with, by the particle's block: a block-wise step of this block size
+    for (int q = T - 1; q >= step_lo; --q) {
+        if (h->hist_bsize[q] == 0)
+            return fail(h, GPF_ERR_STATE, std::string(who) + ": step " + std::to_string(q + 1) + " was entered by a whole-filter call (no per-block observations were recorded)");
+        if (h->hist_bsize[q] != block_size)
+            return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": block_size " + std::to_string(block_size) + " differs from the " +
+                        std::to_string(h->hist_bsize[q]) + " step " + std::to_string(q + 1) + " was entered with");
+    }
+    const size_t cells = (size_t)draws * (size_t)n_steps * (size_t)h->d;
+    if ((s = hist_snapshot(h))) return s;                         // whatever is deferred becomes state; the current step, in its current order
+    std::vector<const int32_t*> maps(h->hist_map.begin(), h->hist_map.end());
+    std::vector<const double*> xs(h->hist_x.begin(), h->hist_x.end()), lws(h->hist_lw.begin(), h->hist_lw.end()), obs(h->hist_obs.begin(), h->hist_obs.end());
+    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_maps, maps.data(), maps.size() * sizeof(int32_t*), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_x, xs.data(), xs.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_lw, lws.data(), lws.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_obs, obs.data(), obs.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                   // the vectors are host temporaries
+    CallScratch d_traj, d_idx;                                     // scratch of this call, as gpf_block_sample_trajectories
+    HIP_TRY(h, hipMalloc(&d_traj.p, cells * sizeof(double)));
+    if (idx_out) HIP_TRY(h, hipMalloc(&d_idx.p, (size_t)draws * (size_t)n_steps * sizeof(int64_t)));
+    BackArgs a{};
+    a.maps = h->hist_dev_maps; a.hx = h->hist_dev_x; a.hlw = h->hist_dev_lw; a.hobs = h->hist_dev_obs; a.lw = h->lw;
+    a.T = T; a.lo0 = step_lo - 1; a.hi0 = step_hi - 1; a.n_samples = (int)n_samples;
+    a.n = h->n; a.nb = block_size; a.nblocks = nblocks; a.seed = h->cfg.seed; a.epoch = h->epoch;
+    a.traj = static_cast<double*>(d_traj.p); a.idx = static_cast<int64_t*>(d_idx.p);
+    AncArgs x{};
+    for (int i = 0; i < MAX_PARAMS; ++i) x.P[i] = h->args.P[i];
+    x.blk_params = h->bp_size > 0 ? h->blk_params : nullptr;
+    x.bp_size = h->bp_size > 0 ? h->bp_size : 1;
+    DISPATCH_MODEL(h, (launch_block_backward<MM>(h, a, x)));
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(traj_out, d_traj.p, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (idx_out) HIP_TRY(h, hipMemcpyAsync(idx_out, d_idx.p, (size_t)draws * (size_t)n_steps * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->epoch += (uint32_t)(T - step_lo + 1);                      // one epoch for the step-T draw and one per backward step down to step_lo
     return GPF_OK;
 }
 // ---- checkpoint / resume: everything a filter needs to continue bit for bit -- the population, its log-weights and parents, the log-ML

@@ -230,7 +230,7 @@ void hist_clear(gpf_filter* h)
 {
     for (double* p : h->hist_x) if (p) (void)hipFree(p);
     for (int32_t* p : h->hist_map) if (p) (void)hipFree(p);
-    h->hist_x.clear(); h->hist_map.clear(); h->hist_step = -1;
+    h->hist_x.clear(); h->hist_map.clear(); h->hist_lw.clear(); h->hist_obs.clear(); h->hist_bsize.clear(); h->hist_step = -1;
 }
 // snapshot the latent columns of the CURRENT step (final order: called when the step is over, or at query time)
 gpf_status hist_snapshot(gpf_filter* h)
@@ -239,9 +239,18 @@ gpf_status hist_snapshot(gpf_filter* h)
     gpf_status s = materialize(h);
     if (s) return s;
     double*& dst = h->hist_x[h->hist_step];
-    if (!dst) HIP_TRY(h, hipMalloc(&dst, (size_t)h->n * h->d * sizeof(double)));
+    // (the weights mode: the step's log-weights and observation rows live behind its columns, in the same allocation -- one hipMalloc per step as before)
+    const int64_t bs = h->hist_weights ? h->hist_bsize[h->hist_step] : 0;
+    const int64_t n_obs_words = bs > 0 ? (h->n + bs - 1) / bs * MAX_OBS : 0;
+    if (!dst) HIP_TRY(h, hipMalloc(&dst, (size_t)(h->n * h->d + (h->hist_weights ? h->n + n_obs_words : 0)) * sizeof(double)));
     GPF_LAUNCH(k_hist_snapshot, dim3(grid_for(h, h->n * h->d, 8)), dim3(BLOCK), 0, h->stream, h->rows[h->cur], h->W, h->d, h->n, dst);
     HIP_TRY(h, hipGetLastError());
+    if (h->hist_weights) {                                         // the same moment, the same order: the step's log-weights and per-block observation rows
+        double* const dlw = h->hist_lw[h->hist_step] = dst + h->n * h->d;
+        double* const dob = h->hist_obs[h->hist_step] = n_obs_words ? dlw + h->n : nullptr;
+        GPF_LAUNCH(k_hist_record, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, (const double*)h->lw, h->n, (const double*)h->blk_obs, n_obs_words, dlw, dob);
+        HIP_TRY(h, hipGetLastError());
+    }
     return GPF_OK;
 }
 // a resample happened during the current step: compose its ancestors into the step's map.  block_size > 0: it was a gpf_resample_blocks -- h->anc is
@@ -266,6 +275,7 @@ gpf_status hist_begin_step(gpf_filter* h, bool first)
     else { gpf_status s = hist_snapshot(h); if (s) return s; }     // the step that ends now, in its final order
     if ((int)h->hist_x.size() >= h->hist_cap) return fail(h, GPF_ERR_STATE, "trajectory store full: raise max_steps of gpf_history_enable");
     h->hist_x.push_back(nullptr); h->hist_map.push_back(nullptr);
+    if (h->hist_weights) { h->hist_lw.push_back(nullptr); h->hist_obs.push_back(nullptr); h->hist_bsize.push_back(0); }   // (a block-wise call sets its block size)
     h->hist_step = (int)h->hist_x.size() - 1;
     return GPF_OK;
 }
@@ -535,6 +545,8 @@ gpf_status gpf_destroy(gpf_handle h)
     hist_clear(h);
     if (h->hist_dev_maps) (void)hipFree(h->hist_dev_maps);
     if (h->hist_dev_x) (void)hipFree(h->hist_dev_x);
+    if (h->hist_dev_lw) (void)hipFree(h->hist_dev_lw);
+    if (h->hist_dev_obs) (void)hipFree(h->hist_dev_obs);
     if (h->parent) { h->rows[0] = h->rows[1] = nullptr; h->lw = nullptr; h->anc = nullptr; }   // aliases of the parent's buffers (or of the compact copies below)
     for (void* q : {(void*)h->vrows[0], (void*)h->vrows[1], (void*)h->vlw, (void*)h->vanc, (void*)h->vidx, (void*)h->vgid}) if (q) (void)hipFree(q);
     { Bufs b = take_particle_buffers(h); free_bufs(b); }

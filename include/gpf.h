@@ -590,7 +590,7 @@ gpf_status gpf_block_history_proportion(gpf_handle h, int32_t step, int64_t bloc
  * (block_size >= n, n <= 2048) draw j reads slot j, the numbering of gpf_sample_unweighted: the indices equal that call's bit for bit.
  * The path: traj_out[b][j][s - step_lo][c] = trace[s => c] of particle b * block_size + a -- the value gpf_history_column(s, c) holds at that
  * particle -- found by following the composed ancestor maps of the steps T, T-1, ..., s+1.  The ancestor may sit in another block (after
- * gpf_resample_across_blocks or a whole-filter resample).  This is the ancestral path only, no backward simulation.
+ * gpf_resample_across_blocks or a whole-filter resample).  This is the ancestral path only; gpf_block_backward_sample below is the backward simulation.
  * DEVIATION, as in gpf_block_moments: a block whose log-weights hold a NaN or +Inf gets idx_out = 0 and NaN trajectories; the call succeeds and the
  * other blocks are unaffected (gpf_sample_unweighted on such a sub-state fails).
  * An accepted call advances the RNG epoch once, as gpf_sample_unweighted does, and changes nothing else: rows, weights, parents, log-ML estimate,
@@ -600,6 +600,50 @@ gpf_status gpf_block_history_proportion(gpf_handle h, int32_t step, int64_t bloc
  * call and freed before it returns; the two pointer tables of the walk belong to the store and go with gpf_destroy. */
 gpf_status gpf_block_sample_trajectories(gpf_handle h, int64_t block_size, int32_t n_samples, int32_t step_lo, int32_t step_hi,
                                          double* traj_out, int64_t* idx_out);
+/* Backward simulation per block (FFBSi: Godsill, Doucet & West 2004; as the path draw of particle Gibbs: Whiteley 2010, Lindsten & Schoen 2013).
+ * The ancestral paths of gpf_block_sample_trajectories coalesce: after a few dozen steps all draws of a block share one x_1.  A backward draw
+ * re-draws the particle of every earlier step from the step's recorded weights times the model's transition density.
+ *
+ * gpf_history_enable_blocks_weights is gpf_history_enable_blocks plus two records per step, taken wherever the store takes the latent columns (at the
+ * start of the next block-wise step, and at query time for the current one), so both are in the step's FINAL order, after every resample, gather
+ * across blocks and rejuvenation of that step:
+ *   the n log-weights at that moment -- a block that resampled holds its equal post-resample weights, one the ESS gate left alone its unequal ones;
+ *     either is a valid weighted sample of the step's filtering law.  COST: 8 bytes more per particle and step (the store then keeps 8 (dim + 1) n
+ *     bytes per step instead of 8 dim n, plus the ancestor map), and one more small launch per snapshot;
+ *   the [n_blocks][4] per-block observation rows the step was entered with, in the block order current at the snapshot (gpf_resample_across_blocks
+ *     moves them with the blocks).  A step entered by a whole-filter call (gpf_initialize, gpf_update) records no rows and is marked so.
+ * Without this mode nothing changes: gpf_history_enable and gpf_history_enable_blocks allocate, launch and compute what they did.
+ *
+ * gpf_block_backward_sample: ONE launch, all blocks, all draws, all steps.  T = gpf_history_steps, E = the epoch at the call, slot = b n_samples + j.
+ *   step T    exactly gpf_block_sample_trajectories' draw from block b's current weights with U = resample_u64(seed, slot, E): the indices at step T
+ *             equal that call's on a filter in the same state, bit for bit.
+ *   step s    = T-1, ..., step_lo.  p = the particle held in the final order of step s+1, pm = its recorded parent in the final order of step s (the
+ *             composed ancestor map of step s+1; p itself where that step had no resample).  The candidates are the particles of block c = pm /
+ *             block_size in the snapshot of step s -- the block the held particle was born from: b itself unless gpf_resample_across_blocks moved
+ *             it -- with the ancestor weights
+ *                 lwa_i = lw_s[i] + logtrans(P_b, x_s[i], x_{s+1}[p], obs_{s+1}[p / block_size])
+ *             (Model<M>::logtrans, what gpf_block_ancestor_log_weights adds).  Then as gpf_resample_blocks_ancestor draws its ancestor: maximum and
+ *             flags, K = fix_K(particles of block c), q_i = exp_fix(lwa_i - m', K), the inclusive CDF, a = the first index with cdf[a] >
+ *             mulhi64(U_s, S') with U_s = resample_u64(seed, slot, E + (T - s)).  The new p = c block_size + a.
+ *             P_b is the DRAWING block's CURRENT parameter row under gpf_set_block_params (rows travel with their block, so this is the lineage's
+ *             theta), else the filter's: a caller who changes the parameters between steps gets the current ones at every step.
+ *   fallback  ancestor weights whose flags hold NaN, +Inf or "all -Inf": the step takes the recorded parent pm (the ancestral step; the ancestor
+ *             sampling call falls back to slot 0 likewise).  Otherwise a particle of ancestor weight -Inf is never drawn.
+ *   bad block current weights with NaN / +Inf: indices 0 and NaN paths for that block, as gpf_block_sample_trajectories; the others are unaffected.
+ *   traj_out  HOST [n_blocks][n_samples][step_hi - step_lo + 1][dim]: the latent columns of the held particle at every step of the range; must not be
+ *             NULL.  idx_out: HOST int64, [n_blocks][n_samples][step_hi - step_lo + 1] or NULL: that particle's 1-based GLOBAL index in the final
+ *             order of its step.  The walk always starts at T: steps above step_hi are walked, not written.
+ *   epoch     an accepted call advances the epoch by T - step_lo + 1 and changes nothing else (rows, weights, parents, log-ML estimate, the "resampled
+ *             last" mask, the store's records).  A refused call changes nothing.  Like the other queries it materialises anything deferred,
+ *             snapshots the current step and synchronises the stream; the scratch of the results is allocated and freed by the call.
+ *   refused   GPF_ERR_STATE: no store, a store without the weight records, a walked step (step_lo < s <= T) entered by a whole-filter call, a clamped
+ *             block_size > 2048.  GPF_ERR_INVALID_ARGUMENT: n_samples < 1, n_blocks * n_samples >= 2^31 (or times n_steps * dim), a bad step range,
+ *             traj_out NULL, block_size < 1, a block size other than the per-block parameters' or than the one a walked step was entered with.
+ * A whole-filter gpf_resample on such a store is walked by the same rule -- the candidates are the recorded parent's block -- but the result is
+ * only a valid smoother when every resample was block-wise or across blocks (a whole-filter resample mixes the blocks' weighted samples). */
+gpf_status gpf_history_enable_blocks_weights(gpf_handle h, int32_t max_steps);   /* before gpf_initialize_blocks */
+gpf_status gpf_block_backward_sample(gpf_handle h, int64_t block_size, int32_t n_samples, int32_t step_lo, int32_t step_hi,
+                                     double* traj_out, int64_t* idx_out);
 
 /* ---- shard-level building blocks (multi-GPU) ------------------------------------------------------
  * A filter sharded over G GPUs is G handles created with the same seed / n_global and contiguous

@@ -40,9 +40,11 @@ mutable struct DeviceParticleFilterState
     model::NativeModel
     n_particles::Int
     # history = T: the trajectory store for T time steps (gpf.h gpf_history_enable); history_blocks: the block-wise store, which the block-wise
-    # calls feed too (gpf_history_enable_blocks)
+    # calls feed too (gpf_history_enable_blocks); history_weights: that store with every step's log-weights and per-block observations, which
+    # block_backward_trajectories needs (gpf_history_enable_blocks_weights)
     function DeviceParticleFilterState(model::NativeModel, n::Int; seed::Integer=1, keep_prev::Bool=false, device::Integer=0, history::Integer=0,
-                                       history_blocks::Bool=false)
+                                       history_blocks::Bool=false, history_weights::Bool=false)
+        history_weights && !(history > 0 && history_blocks) && error("history_weights needs the block-wise trajectory store (history = T)")
         h = Ref{Ptr{Cvoid}}(C_NULL)
         GC.@preserve model begin
             cfg = Ref(GpfConfig(GPF_ABI_VERSION, model.id, length(model.params), keep_prev, pointer(model.params),
@@ -53,7 +55,8 @@ mutable struct DeviceParticleFilterState
         state = new(h[], model, n)
         finalizer(s -> ccall((:gpf_destroy, libgpf), Cint, (Ptr{Cvoid},), getfield(s, :handle)), state)
         if history > 0
-            st = history_blocks ? ccall((:gpf_history_enable_blocks, libgpf), Cint, (Ptr{Cvoid}, Cint), h[], history) :
+            st = history_weights ? ccall((:gpf_history_enable_blocks_weights, libgpf), Cint, (Ptr{Cvoid}, Cint), h[], history) :
+                 history_blocks ? ccall((:gpf_history_enable_blocks, libgpf), Cint, (Ptr{Cvoid}, Cint), h[], history) :
                                   ccall((:gpf_history_enable, libgpf), Cint, (Ptr{Cvoid}, Cint), h[], history)
             st == 0 || error(unsafe_string(ccall((:gpf_last_error, libgpf), Cstring, (Ptr{Cvoid},), h[])))
         end
@@ -616,6 +619,23 @@ function block_sample_trajectories(s::DeviceParticleFilterState, block_size::Int
     nb = cld(s.n_particles, min(block_size, s.n_particles)); d = _latent_dim(s)
     traj = Array{Float64}(undef, d, length(steps), n, nb); idx = Matrix{Int64}(undef, n, nb)
     _status(s, ccall((:gpf_block_sample_trajectories, libgpf), Cint, (Ptr{Cvoid}, Int64, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Int64}),
+                     s.handle, block_size, n, first(steps), last(steps), traj, idx))
+    return traj, idx
+end
+
+# Backward simulation per block (gpf.h gpf_block_backward_sample): the step-T draw of block_sample_trajectories, then every earlier step re-drawn from the
+# step's recorded weights times the transition density -- one launch.  Needs pf_initialize_blocks(...; history=T, history_weights=true).  Returns the paths
+# as a (dim, n_steps, n, n_blocks) array and the (n_steps, n, n_blocks) 1-based GLOBAL indices of the held particles in the final order of their steps
+# (0 for a block with NaN weights, whose paths are NaN).  Advances the RNG epoch by T - first(steps) + 1.
+function block_backward_trajectories(s::DeviceParticleFilterState, block_size::Int, n::Int=1; steps::Union{Nothing,UnitRange{Int}}=nothing)
+    if steps === nothing
+        k = Ref{Cint}(0)
+        _status(s, ccall((:gpf_history_steps, libgpf), Cint, (Ptr{Cvoid}, Ref{Cint}), s.handle, k))
+        steps = 1:Int(k[])
+    end
+    nb = cld(s.n_particles, min(block_size, s.n_particles)); d = _latent_dim(s)
+    traj = Array{Float64}(undef, d, length(steps), n, nb); idx = Array{Int64}(undef, length(steps), n, nb)
+    _status(s, ccall((:gpf_block_backward_sample, libgpf), Cint, (Ptr{Cvoid}, Int64, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Int64}),
                      s.handle, block_size, n, first(steps), last(steps), traj, idx))
     return traj, idx
 end
