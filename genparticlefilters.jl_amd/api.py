@@ -1153,6 +1153,51 @@ def block_backward_trajectories(state, block_size: int, n_samples: int = 1, step
     return (traj, idx) if return_indices else traj
 
 
+def _block_smooth(state, block_size, steps, who, want_mean, want_var, want_weights, want_blocks):
+    if not getattr(state, "history_weights", False):
+        raise ErrorException(who + " needs the block-wise trajectory store with its weight records "
+                             "(pf_initialize_blocks(..., history=T, history_weights=True)), which this state does not have")
+    if steps is None:
+        k = C.c_int32(0)
+        state._check(state._L.gpf_history_steps(state._h, C.byref(k)))
+        lo, hi = 1, int(k.value)
+    elif isinstance(steps, (tuple, list)):
+        lo, hi = int(steps[0]), int(steps[1])
+    else:
+        lo = hi = int(steps)
+    if lo < 1 or hi < 1:
+        raise ErrorException(who + ": steps are 1-based (step 1 = the initialisation)")
+    if hi < lo or int(block_size) < 1:
+        raise ErrorException(who + ": need lo <= hi and block_size >= 1")
+    bs = min(int(block_size), max(state.n_particles, 1))
+    nb = (state.n_particles + bs - 1) // bs
+    mu = np.empty((nb, hi - lo + 1, state.dim)) if want_mean else None
+    s2 = np.empty((nb, hi - lo + 1, state.dim)) if want_var else None
+    w = np.empty((nb, hi - lo + 1, bs)) if want_weights else None
+    blocks = np.empty((nb, hi - lo + 1), np.int64) if want_blocks else None
+    state._check(state._L.gpf_block_smooth(state._h, int(block_size), lo, hi, _pd(mu) if want_mean else None, _pd(s2) if want_var else None,
+                                           _pd(w) if want_weights else None, blocks.ctypes.data_as(C.POINTER(C.c_int64)) if want_blocks else None))
+    return mu, s2, w, blocks
+
+
+def block_smoothed_moments(state, block_size: int, steps=None, return_weights: bool = False, return_blocks: bool = False):
+    """marginal smoothing per block (FFBSm; gpf.h gpf_block_smooth): the smoothed mean and variance of every latent column at every step of every block,
+    under the deterministic smoothing weights W_s^i = sum_j W_{s+1}^j w_s^i f(x_{s+1}^j | x_s^i) / sum_l w_s^l f(x_{s+1}^j | x_s^l) -- what
+    block_backward_trajectories estimates with draws, without their Monte-Carlo noise.  One launch for all blocks and steps, O(block_size^2) per block
+    and step; needs pf_initialize_blocks(..., history=T, history_weights=True).  Returns (mean, var), each [n_blocks, n_steps, dim]; with
+    return_weights=True also the weights [n_blocks, n_steps, block_size] (by position inside the lineage's block, 0 beyond a short block); with
+    return_blocks=True also the [n_blocks, n_steps] int64 1-based block the lineage occupied at each step.  steps as in block_backward_trajectories; the
+    walk always starts at the last step.  A block with NaN / +Inf weights, and the steps below a whole-filter resample, read NaN (blocks 0).  Under
+    set_block_params every step uses the final block's CURRENT parameter row.  Nothing is drawn: the RNG epoch and the filter are left untouched."""
+    mu, s2, w, blocks = _block_smooth(state, block_size, steps, "block_smoothed_moments", True, True, bool(return_weights), bool(return_blocks))
+    return (mu, s2) + ((w,) if return_weights else ()) + ((blocks,) if return_blocks else ())
+
+
+def block_smoothed_weights(state, block_size: int, steps=None):
+    """the smoothing weights of block_smoothed_moments alone: [n_blocks, n_steps, block_size]"""
+    return _block_smooth(state, block_size, steps, "block_smoothed_weights", False, False, True, False)[2]
+
+
 # ----------------------------------------------------------------------------- statistics (src/statistics.jl)
 def _addr_values(state, addr) -> np.ndarray:
     """the values at one address over all particles: a column of the current step, or (t, column) for a past choice"""

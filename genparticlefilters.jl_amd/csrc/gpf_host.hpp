@@ -604,8 +604,21 @@ gpf_status sorted_job_prepare(gpf_filter* h, int64_t gid0, int64_t n_slots);
 gpf_status sorted_gammas_finish(gpf_filter* h, bool with_tiles, bool gammas_pending);
 gpf_status finish_search(gpf_filter* h);
 gpf_status resample_impl(gpf_filter* h, int method, PrioView pv, int sort_particles, int check, int32_t* invalid, bool local = false);
+// a block of <= 128 / <= 512 particles is the work of one wave (2 / 8 particles per lane, BLOCK / WAVE blocks per workgroup), a larger one of a workgroup:
+// f(TEAM, ITEMS, grid) with TEAM and ITEMS as std::integral_constant -- the template arguments of the block kernels (gpf_k_block.hpp) -- and their grid
+template <class F>
+inline void team_dispatch(int64_t block_size, int64_t nblocks, F&& f)
+{
+    constexpr int TEAMS = BLOCK / WAVE;                          // wave teams of a workgroup
+    const dim3 waves((unsigned)((nblocks + TEAMS - 1) / TEAMS)), groups((unsigned)nblocks);
+    if (block_size <= 2 * WAVE)      f(std::integral_constant<int, WAVE>{}, std::integral_constant<int, 2>{}, waves);
+    else if (block_size <= 8 * WAVE) f(std::integral_constant<int, WAVE>{}, std::integral_constant<int, 8>{}, waves);
+    else                             f(std::integral_constant<int, BLOCK>{}, std::integral_constant<int, 8>{}, groups);
+}
 // ---- defined in libgpf_aux.hip
 gpf_status weighted_tree_sum(gpf_filter* h, const double* values, int stride, int col, int pw, const double* center, double match, double* out_dev);
+// ---- defined in libgpf_smooth.hip
+void launch_block_smooth(gpf_filter* h, const SmoothArgs& a, const AncArgs& x);   // k_block_smooth<model, TEAM, ITEMS> by team_dispatch
 // ---- defined in libgpf_shard.hip
 gpf_status shard_device_setup(gpf_filter* h);         // LDS attributes of the push kernels (gpf_create)
 

@@ -25,3 +25,4 @@
 #include "gpf_k_block.hpp"
 #include "gpf_k_block_anc.hpp"
 #include "gpf_k_block_back.hpp"
+#include "gpf_k_block_smooth.hpp"

@@ -35,17 +35,6 @@ void launch_move_blk(gpf_filter* h, int grid, int n_iters)
                        h->cfg.gid0, h->n, (int)h->has_prev, n_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw,
                        h->acc_part, RW ? next_slots(h) : MaxSlots{nullptr, nullptr});
 }
-// a block of <= 128 / <= 512 particles is the work of one wave (2 / 8 particles per lane, BLOCK / WAVE blocks per workgroup), a larger one of a workgroup:
-// f(TEAM, ITEMS, grid) with TEAM and ITEMS as std::integral_constant -- the template arguments of the block kernels (gpf_k_block.hpp) -- and their grid
-template <class F>
-inline void team_dispatch(int64_t block_size, int64_t nblocks, F&& f)
-{
-    constexpr int TEAMS = BLOCK / WAVE;                          // wave teams of a workgroup
-    const dim3 waves((unsigned)((nblocks + TEAMS - 1) / TEAMS)), groups((unsigned)nblocks);
-    if (block_size <= 2 * WAVE)      f(std::integral_constant<int, WAVE>{}, std::integral_constant<int, 2>{}, waves);
-    else if (block_size <= 8 * WAVE) f(std::integral_constant<int, WAVE>{}, std::integral_constant<int, 8>{}, waves);
-    else                             f(std::integral_constant<int, BLOCK>{}, std::integral_constant<int, 8>{}, groups);
-}
 // METHOD_COND: the conditional multinomial step (slot 0 of every resampling block keeps itself), PRIO = false only
 template <int METHOD, int Wc, bool PRIO>
 void launch_block_resample_w(gpf_filter* h, const BlockArgs& a)
@@ -1736,6 +1725,68 @@ gpf_status gpf_block_backward_sample(gpf_handle h, int64_t block_size, int32_t n
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->epoch += (uint32_t)(T - step_lo + 1);                      // one epoch for the step-T draw and one per backward step down to step_lo
     return GPF_OK;
+}
+// ---- marginal smoothing per block (gpf.h gpf_block_smooth): the smoothing weights and moments of all blocks and steps in one launch.  The kernels are
+// instantiated in a translation unit of their own (libgpf_smooth.hip): this unit's device code is what it was
+gpf_status gpf_block_smooth(gpf_handle h, int64_t block_size, int32_t step_lo, int32_t step_hi,
+                            double* mean_out, double* var_out, double* weights_out, int64_t* blocks_out)
+{
+    const char* who = "gpf_block_smooth";
+    gpf_status s = block_store_gate(h, block_size, who);
+    if (s) return s;
+    if (!h->hist_weights)
+        return fail(h, GPF_ERR_STATE, std::string(who) + " needs the store's weight records (gpf_history_enable_blocks_weights before gpf_initialize_blocks)");
+    if ((s = block_gate(h, block_size, who, GATE_PARAMS))) return s;
+    if (!mean_out && !var_out && !weights_out && !blocks_out) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": all outputs are NULL");
+    if ((s = check_ready(h))) return s;
+    const int T = (int)h->hist_x.size();
+    if (step_lo < 1 || step_hi < step_lo || step_hi > T) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": need 1 <= step_lo <= step_hi <= gpf_history_steps");
+    const int64_t nblocks = (h->n + block_size - 1) / block_size, n_steps = step_hi - step_lo + 1;
+    const int64_t lim = (int64_t)1 << 31;
+    const int64_t row = std::max<int64_t>(h->d, weights_out ? block_size : 1);   // (nblocks, n_steps, row < 2^31: the product below does not overflow before it is compared)
+    if (nblocks * n_steps >= lim || nblocks * n_steps >= (lim + row - 1) / row)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": n_blocks * n_steps * dim and n_blocks * n_steps * block_size must stay below 2^31");
+    // every walked step above step_lo reads the observation rows it was entered with, by block: a block-wise step of this block size
+    for (int q = T - 1; q >= step_lo; --q) {
+        if (h->hist_bsize[q] == 0)
+            return fail(h, GPF_ERR_STATE, std::string(who) + ": step " + std::to_string(q + 1) + " was entered by a whole-filter call (no per-block observations were recorded)");
+        if (h->hist_bsize[q] != block_size)
+            return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": block_size " + std::to_string(block_size) + " differs from the " +
+                        std::to_string(h->hist_bsize[q]) + " step " + std::to_string(q + 1) + " was entered with");
+    }
+    if ((s = hist_snapshot(h))) return s;                         // whatever is deferred becomes state; the current step, in its current order
+    std::vector<const int32_t*> maps(h->hist_map.begin(), h->hist_map.end());
+    std::vector<const double*> xs(h->hist_x.begin(), h->hist_x.end()), lws(h->hist_lw.begin(), h->hist_lw.end()), obs(h->hist_obs.begin(), h->hist_obs.end());
+    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_maps, maps.data(), maps.size() * sizeof(int32_t*), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_x, xs.data(), xs.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_lw, lws.data(), lws.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_obs, obs.data(), obs.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));                   // the vectors are host temporaries
+    const size_t cells = (size_t)nblocks * (size_t)n_steps;
+    const size_t b_mom = cells * (size_t)h->d * sizeof(double), b_w = cells * (size_t)block_size * sizeof(double), b_c = cells * sizeof(int64_t);
+    CallScratch d_mean, d_var, d_w, d_c;                           // scratch of this call, as gpf_block_backward_sample; only what was asked for
+    if (mean_out) HIP_TRY(h, hipMalloc(&d_mean.p, b_mom));
+    if (var_out) HIP_TRY(h, hipMalloc(&d_var.p, b_mom));
+    if (weights_out) HIP_TRY(h, hipMalloc(&d_w.p, b_w));
+    if (blocks_out) HIP_TRY(h, hipMalloc(&d_c.p, b_c));
+    SmoothArgs a{};
+    a.maps = h->hist_dev_maps; a.hx = h->hist_dev_x; a.hlw = h->hist_dev_lw; a.hobs = h->hist_dev_obs; a.lw = h->lw;
+    a.T = T; a.lo0 = step_lo - 1; a.hi0 = step_hi - 1;
+    a.n = h->n; a.nb = block_size; a.nblocks = nblocks;
+    a.mean = static_cast<double*>(d_mean.p); a.var = static_cast<double*>(d_var.p);
+    a.wout = static_cast<double*>(d_w.p); a.blocks = static_cast<int64_t*>(d_c.p);
+    AncArgs x{};
+    for (int i = 0; i < MAX_PARAMS; ++i) x.P[i] = h->args.P[i];
+    x.blk_params = h->bp_size > 0 ? h->blk_params : nullptr;
+    x.bp_size = h->bp_size > 0 ? h->bp_size : 1;
+    launch_block_smooth(h, a, x);
+    HIP_TRY(h, hipGetLastError());
+    if (mean_out) HIP_TRY(h, hipMemcpyAsync(mean_out, d_mean.p, b_mom, hipMemcpyDeviceToHost, h->stream));
+    if (var_out) HIP_TRY(h, hipMemcpyAsync(var_out, d_var.p, b_mom, hipMemcpyDeviceToHost, h->stream));
+    if (weights_out) HIP_TRY(h, hipMemcpyAsync(weights_out, d_w.p, b_w, hipMemcpyDeviceToHost, h->stream));
+    if (blocks_out) HIP_TRY(h, hipMemcpyAsync(blocks_out, d_c.p, b_c, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GPF_OK;                                                // nothing was drawn: the epoch stays
 }
 // ---- checkpoint / resume: everything a filter needs to continue bit for bit -- the population, its log-weights and parents, the log-ML
 // estimate, the RNG epoch, the latest observation and strata -- as ONE host blob; loads into a handle created with the same gpf_config

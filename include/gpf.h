@@ -644,6 +644,44 @@ gpf_status gpf_block_sample_trajectories(gpf_handle h, int64_t block_size, int32
 gpf_status gpf_history_enable_blocks_weights(gpf_handle h, int32_t max_steps);   /* before gpf_initialize_blocks */
 gpf_status gpf_block_backward_sample(gpf_handle h, int64_t block_size, int32_t n_samples, int32_t step_lo, int32_t step_hi,
                                      double* traj_out, int64_t* idx_out);
+/* Marginal smoothing per block (FFBSm: Hürzeler & Künsch 1998; Doucet, Godsill & Andrieu 2000): deterministic smoothing weights for every particle
+ * of every recorded step, and the smoothed mean and variance of every latent column under them,
+ *     W_T^j = w_T^j,        W_s^i = sum_j  W_{s+1}^j  w_s^i f(x_{s+1}^j | x_s^i) / sum_l w_s^l f(x_{s+1}^j | x_s^l).
+ * A backward draw (gpf_block_backward_sample) gives paths; a smoothed mean from k of them carries Monte-Carlo noise of order 1 / sqrt(k) on top of the
+ * particle error.  This call has none: nothing is drawn.  O(block_size^2) transition densities per block and step; ONE launch.
+ * Needs gpf_history_enable_blocks_weights.  T = gpf_history_steps, steps s are 1-based, bs = block_size (clamped to n), g_s = the composed ancestor
+ * map of step s (the identity where the step had no resample), P_b = the FINAL block b's CURRENT parameter row under gpf_set_block_params, else the
+ * filter's.  Every block b < n_blocks is handled independently:
+ *   lineage   c_T = b; c_s = g_{s+1}[c_{s+1} bs] / bs: the block the lineage occupied at step s -- b itself unless gpf_resample_across_blocks moved it.
+ *             If the particles of block c_{s+1} do not all have their recorded parent in one block (a whole-filter gpf_resample inside a block-wise
+ *             step), the lineage is undefined: from step s down block b's outputs are NaN (whole rows of weights_out included) and its blocks_out
+ *             entries 0.  The other blocks are unaffected.
+ *   step T    W_T^j = (double)q_j / (double)S: block b's current normalised weights as gpf_block_moments forms them (K = fix_K(particles of the block),
+ *             q = 1 where all log-weights are -Inf).  Current weights with a NaN or +Inf: every output of block b is NaN at every step, blocks_out 0.
+ *   step s    = T-1, ..., step_lo.  Targets j: the particles of block c_{s+1} in the snapshot of step s+1.  Candidates i: the particles of block c_s in
+ *             the snapshot of step s.  For each target, in the statements of gpf_block_backward_sample:
+ *                 lwa_ij = lw_s[i] + logtrans(P_b, x_s[i], x_{s+1}[j], obs_{s+1}[c_{s+1}]);   (m_j, f_j) = maximum and flags of lwa_.j over i;
+ *                 K = fix_K(particles of block c_s);   q_ij = exp_fix(lwa_ij - m_j, K);   D_j = sum_i q_ij (an exact 64-bit integer sum);
+ *                 r_ij = (double)q_ij / (double)D_j;
+ *             fallback, as in backward simulation: f_j != 0 (NaN, +Inf or all -Inf) -> r_ij = 1 for i = g_{s+1}[j] - c_s bs and 0 otherwise: a target
+ *             no candidate leads to hands its mass to its recorded parent.  Then
+ *                 W_s^i = sum_j W_{s+1}^j r_ij,
+ *             accumulated from +0.0 in ASCENDING j with one multiply and one add per term (no fused multiply-add), not renormalised.  A candidate of
+ *             recorded weight -Inf gets W = 0 exactly.
+ *   moments   mean_s[c] = tree(W_s^i x_s^i[c]), var_s[c] = tree(W_s^i (x_s^i[c] - mean_s[c])^2): the summation tree of gpf_block_moments
+ *             over the index within the block, for all dim latent columns.  At s = T these are gpf_block_moments' values bit for bit.
+ *   outputs   HOST, n_steps = step_hi - step_lo + 1: mean_out, var_out [n_blocks][n_steps][dim]; weights_out [n_blocks][n_steps][block_size], indexed
+ *             by the particle's position inside block c_s, 0 beyond a short block; blocks_out int64 [n_blocks][n_steps], the 1-based c_s.  Any may be
+ *             NULL, not all; what is not asked for is not allocated on the device.  The walk always starts at T: steps above step_hi are walked, not
+ *             written.
+ *   effects   none: no uniform is read, the epoch does not advance, rows, weights, parents, log-ML estimate, the "resampled last" mask and the store's
+ *             records stay.  Like the other queries it materialises anything deferred, snapshots the current step and synchronises the stream.
+ *   refused   nothing written, nothing changed.  GPF_ERR_STATE: no store, a store without the weight records, a walked step (step_lo < s <= T) entered
+ *             by a whole-filter call, a clamped block_size > 2048.  GPF_ERR_INVALID_ARGUMENT: a bad step range, all outputs NULL, block_size < 1, a block
+ *             size other than the per-block parameters' or than the one a walked step was entered with, n_blocks * n_steps * dim or (with weights_out)
+ *             n_blocks * n_steps * block_size >= 2^31, a NULL handle. */
+gpf_status gpf_block_smooth(gpf_handle h, int64_t block_size, int32_t step_lo, int32_t step_hi,
+                            double* mean_out, double* var_out, double* weights_out, int64_t* blocks_out);
 
 /* ---- shard-level building blocks (multi-GPU) ------------------------------------------------------
  * A filter sharded over G GPUs is G handles created with the same seed / n_global and contiguous

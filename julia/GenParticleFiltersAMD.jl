@@ -640,6 +640,38 @@ function block_backward_trajectories(s::DeviceParticleFilterState, block_size::I
     return traj, idx
 end
 
+# Marginal smoothing per block (gpf.h gpf_block_smooth; FFBSm): deterministic smoothing weights of every particle of every step, and the smoothed mean and
+# variance of every latent column under them -- one launch, nothing drawn, the epoch stays.  Needs pf_initialize_blocks(...; history=T,
+# history_weights=true).  Returns (mean, var) as (dim, n_steps, n_blocks) arrays, then on request the weights (block_size, n_steps, n_blocks) and the
+# (n_steps, n_blocks) 1-based blocks the lineages occupied (0 and NaN where a lineage is undefined or the block's weights are NaN).
+function block_smoothed_moments(s::DeviceParticleFilterState, block_size::Int; steps::Union{Nothing,UnitRange{Int}}=nothing,
+                                return_weights::Bool=false, return_blocks::Bool=false)
+    if steps === nothing
+        k = Ref{Cint}(0)
+        _status(s, ccall((:gpf_history_steps, libgpf), Cint, (Ptr{Cvoid}, Ref{Cint}), s.handle, k))
+        steps = 1:Int(k[])
+    end
+    bs = min(block_size, s.n_particles); nb = cld(s.n_particles, bs); d = _latent_dim(s)
+    mu = Array{Float64}(undef, d, length(steps), nb); s2 = Array{Float64}(undef, d, length(steps), nb)
+    w = return_weights ? Array{Float64}(undef, bs, length(steps), nb) : nothing
+    blocks = return_blocks ? Array{Int64}(undef, length(steps), nb) : nothing
+    _status(s, ccall((:gpf_block_smooth, libgpf), Cint, (Ptr{Cvoid}, Int64, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int64}),
+                     s.handle, block_size, first(steps), last(steps), mu, s2, return_weights ? w : C_NULL, return_blocks ? blocks : C_NULL))
+    return (mu, s2, (return_weights ? (w,) : ())..., (return_blocks ? (blocks,) : ())...)
+end
+function block_smoothed_weights(s::DeviceParticleFilterState, block_size::Int; steps::Union{Nothing,UnitRange{Int}}=nothing)
+    if steps === nothing
+        k = Ref{Cint}(0)
+        _status(s, ccall((:gpf_history_steps, libgpf), Cint, (Ptr{Cvoid}, Ref{Cint}), s.handle, k))
+        steps = 1:Int(k[])
+    end
+    bs = min(block_size, s.n_particles); nb = cld(s.n_particles, bs)
+    w = Array{Float64}(undef, bs, length(steps), nb)
+    _status(s, ccall((:gpf_block_smooth, libgpf), Cint, (Ptr{Cvoid}, Int64, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int64}),
+                     s.handle, block_size, first(steps), last(steps), C_NULL, C_NULL, w, C_NULL))
+    return w
+end
+
 # ---------------------------------------------------------------- multi-GPU: one process per GPU, the exchange inside libgpf
 # A shard of a filter of `n_global` particles: rank r of `world` holds the contiguous global range that starts at gid0 (the
 # first n_global % world ranks hold one particle more).  The communicator is libgpf's own (RCCL); the host only carries the
