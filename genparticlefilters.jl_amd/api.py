@@ -1090,15 +1090,8 @@ def sample_unweighted_traces(state, n_samples: int, return_indices: bool = False
     return (rows, idx) if return_indices else rows
 
 
-def block_sample_trajectories(state, block_size: int, n_samples: int = 1, steps=None, return_indices: bool = False):
-    """for b in blocks; sample_unweighted_traces(state[b], n_samples); end (src/utils.jl:7,189-194 on sub-states, src/view.jl:35-48): the reference's
-    traces are persistent, so every draw is a whole path of block b.  One launch for all blocks (gpf.h gpf_block_sample_trajectories); needs the
-    block-wise trajectory store (pf_initialize_blocks(..., history=T)).  Returns [n_blocks, n_samples, n_steps, dim]: the latent columns of the drawn
-    particle's ancestors, and with return_indices=True also the [n_blocks, n_samples] int64 indices (1-based, inside the block) of the drawn
-    current particles.  steps=None: all recorded steps; steps=t: that step; steps=(lo, hi): a range, 1-based and inclusive (step 1 = the
-    initialisation).  A block with NaN / +Inf weights gets index 0 and NaN paths.  Advances the RNG epoch once; the filter is left untouched."""
-    if not getattr(state, "history_blocks", False):
-        raise ErrorException("block_sample_trajectories needs a block-wise trajectory store (pf_initialize_blocks(..., history=T)), which this state does not have")
+def _store_steps(state, steps, who):
+    """the steps a query of the block-wise store walks -> (lo, hi).  steps=None: all recorded steps; steps=t: that step; steps=(lo, hi): a range"""
     if steps is None:
         k = C.c_int32(0)
         state._check(state._L.gpf_history_steps(state._h, C.byref(k)))
@@ -1108,11 +1101,32 @@ def block_sample_trajectories(state, block_size: int, n_samples: int = 1, steps=
     else:
         lo = hi = int(steps)
     if lo < 1 or hi < 1:
-        raise ErrorException("block_sample_trajectories: steps are 1-based (step 1 = the initialisation)")
-    if hi < lo or int(n_samples) < 1 or int(block_size) < 1:
-        raise ErrorException("block_sample_trajectories: need lo <= hi, n_samples >= 1 and block_size >= 1")
+        raise ErrorException(who + ": steps are 1-based (step 1 = the initialisation)")
+    return lo, hi
+
+
+def _store_blocks(state, block_size, lo, hi, who, n_samples=None):
+    """... -> (block size clamped to the particle count, number of blocks); n_samples: of a query that draws"""
+    if n_samples is None:
+        if hi < lo or int(block_size) < 1:
+            raise ErrorException(who + ": need lo <= hi and block_size >= 1")
+    elif hi < lo or int(n_samples) < 1 or int(block_size) < 1:
+        raise ErrorException(who + ": need lo <= hi, n_samples >= 1 and block_size >= 1")
     bs = min(int(block_size), max(state.n_particles, 1))
-    nb = (state.n_particles + bs - 1) // bs
+    return bs, (state.n_particles + bs - 1) // bs
+
+
+def block_sample_trajectories(state, block_size: int, n_samples: int = 1, steps=None, return_indices: bool = False):
+    """for b in blocks; sample_unweighted_traces(state[b], n_samples); end (src/utils.jl:7,189-194 on sub-states, src/view.jl:35-48): the reference's
+    traces are persistent, so every draw is a whole path of block b.  One launch for all blocks (gpf.h gpf_block_sample_trajectories); needs the
+    block-wise trajectory store (pf_initialize_blocks(..., history=T)).  Returns [n_blocks, n_samples, n_steps, dim]: the latent columns of the drawn
+    particle's ancestors, and with return_indices=True also the [n_blocks, n_samples] int64 indices (1-based, inside the block) of the drawn
+    current particles.  steps=None: all recorded steps; steps=t: that step; steps=(lo, hi): a range, 1-based and inclusive (step 1 = the
+    initialisation).  A block with NaN / +Inf weights gets index 0 and NaN paths.  Advances the RNG epoch once; the filter is left untouched."""
+    if not getattr(state, "history_blocks", False):
+        raise ErrorException("block_sample_trajectories needs a block-wise trajectory store (pf_initialize_blocks(..., history=T)), which this state does not have")
+    lo, hi = _store_steps(state, steps, "block_sample_trajectories")
+    _, nb = _store_blocks(state, block_size, lo, hi, "block_sample_trajectories", n_samples)
     traj = np.empty((nb, int(n_samples), hi - lo + 1, state.dim))
     idx = np.empty((nb, int(n_samples)), np.int64) if return_indices else None
     state._check(state._L.gpf_block_sample_trajectories(state._h, int(block_size), int(n_samples), lo, hi, _pd(traj),
@@ -1132,20 +1146,8 @@ def block_backward_trajectories(state, block_size: int, n_samples: int = 1, step
     if not getattr(state, "history_weights", False):
         raise ErrorException("block_backward_trajectories needs the block-wise trajectory store with its weight records "
                              "(pf_initialize_blocks(..., history=T, history_weights=True)), which this state does not have")
-    if steps is None:
-        k = C.c_int32(0)
-        state._check(state._L.gpf_history_steps(state._h, C.byref(k)))
-        lo, hi = 1, int(k.value)
-    elif isinstance(steps, (tuple, list)):
-        lo, hi = int(steps[0]), int(steps[1])
-    else:
-        lo = hi = int(steps)
-    if lo < 1 or hi < 1:
-        raise ErrorException("block_backward_trajectories: steps are 1-based (step 1 = the initialisation)")
-    if hi < lo or int(n_samples) < 1 or int(block_size) < 1:
-        raise ErrorException("block_backward_trajectories: need lo <= hi, n_samples >= 1 and block_size >= 1")
-    bs = min(int(block_size), max(state.n_particles, 1))
-    nb = (state.n_particles + bs - 1) // bs
+    lo, hi = _store_steps(state, steps, "block_backward_trajectories")
+    _, nb = _store_blocks(state, block_size, lo, hi, "block_backward_trajectories", n_samples)
     traj = np.empty((nb, int(n_samples), hi - lo + 1, state.dim))
     idx = np.empty((nb, int(n_samples), hi - lo + 1), np.int64) if return_indices else None
     state._check(state._L.gpf_block_backward_sample(state._h, int(block_size), int(n_samples), lo, hi, _pd(traj),
@@ -1157,20 +1159,8 @@ def _block_smooth(state, block_size, steps, who, want_mean, want_var, want_weigh
     if not getattr(state, "history_weights", False):
         raise ErrorException(who + " needs the block-wise trajectory store with its weight records "
                              "(pf_initialize_blocks(..., history=T, history_weights=True)), which this state does not have")
-    if steps is None:
-        k = C.c_int32(0)
-        state._check(state._L.gpf_history_steps(state._h, C.byref(k)))
-        lo, hi = 1, int(k.value)
-    elif isinstance(steps, (tuple, list)):
-        lo, hi = int(steps[0]), int(steps[1])
-    else:
-        lo = hi = int(steps)
-    if lo < 1 or hi < 1:
-        raise ErrorException(who + ": steps are 1-based (step 1 = the initialisation)")
-    if hi < lo or int(block_size) < 1:
-        raise ErrorException(who + ": need lo <= hi and block_size >= 1")
-    bs = min(int(block_size), max(state.n_particles, 1))
-    nb = (state.n_particles + bs - 1) // bs
+    lo, hi = _store_steps(state, steps, who)
+    bs, nb = _store_blocks(state, block_size, lo, hi, who)
     mu = np.empty((nb, hi - lo + 1, state.dim)) if want_mean else None
     s2 = np.empty((nb, hi - lo + 1, state.dim)) if want_var else None
     w = np.empty((nb, hi - lo + 1, bs)) if want_weights else None

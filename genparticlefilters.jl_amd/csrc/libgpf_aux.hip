@@ -83,6 +83,49 @@ static gpf_status block_buffers(gpf_filter* h, int64_t nblocks)
     }
     return GPF_OK;
 }
+// a device array of doubles that only ever grows: at least cap * width of them (kernels enqueued earlier may read the old one: the stream drains first)
+static gpf_status grow_doubles(gpf_filter* h, double*& p, int64_t& have, int64_t cap, int width = 1)
+{
+    if (have >= cap) return GPF_OK;
+    if (p) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(p); p = nullptr; have = 0; }
+    HIP_TRY(h, hipMalloc(&p, (size_t)cap * width * sizeof(double)));
+    have = cap;
+    return GPF_OK;
+}
+// the results of a call from the device to the host, each where the caller wants it (nullptr: not asked for), then the one synchronisation
+struct OutCopy { const void* dev; void* host; size_t bytes; };
+static gpf_status block_out(gpf_filter* h, std::initializer_list<OutCopy> outs)
+{
+    for (const OutCopy& o : outs)
+        if (o.host) HIP_TRY(h, hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GPF_OK;
+}
+// the rows of w <= 4 values -> rows of four, zero-padded (the staged observation and reference rows).  Unrolled: at 10^4 blocks this fill is most of
+// the host time of a call that stages them
+static void pack4(double* dst, const double* src, int64_t n_rows, int w)
+{
+    static_assert(MAX_OBS == 4 && MAX_DIM == 4, "the four columns of a staged row");
+    for (int64_t b = 0; b < n_rows; ++b) {
+        double* const d = dst + b * 4; const double* const r = src + b * w;
+        d[0] = r[0]; d[1] = w > 1 ? r[1] : 0.0; d[2] = w > 2 ? r[2] : 0.0; d[3] = w > 3 ? r[3] : 0.0;
+    }
+}
+// the observations of a block-wise step or of the step an ancestor is sampled towards: [n_blocks][n_obs] with the model's n_obs
+static gpf_status block_obs_check(gpf_filter* h, const double* obs, int32_t n_obs)
+{
+    if (obs && n_obs == model_obs_dim(h->cfg.model)) return GPF_OK;
+    return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model takes " + std::to_string(model_obs_dim(h->cfg.model)) + " observation values per step and block");
+}
+// the parameters a transition density is evaluated with: the filter's own, and the per-block rows where they are set
+static AncArgs anc_args(const gpf_filter* h)
+{
+    AncArgs x{};
+    for (int i = 0; i < MAX_PARAMS; ++i) x.P[i] = h->args.P[i];
+    x.blk_params = h->bp_size > 0 ? h->blk_params : nullptr;
+    x.bp_size = h->bp_size > 0 ? h->bp_size : 1;
+    return x;
+}
 // The preconditions of a block-wise call, in ONE order for every entry point ("the gate of the block-wise calls"); `steps` names the ones
 // the entry point has.  Nothing here touches the handle -- check_ready, which brings a lazy move or a view up to date, comes after the gate and after the
 // entry point's own checks -- so a refused call changes nothing.  The null handle is refused always.
@@ -156,8 +199,7 @@ struct AncestorIn { const double* obs; int32_t n_obs; const double* ref; int32_t
 static gpf_status block_ref_checks(gpf_filter* h, int64_t block_size, const double* ref, int32_t n_ref, const char* who);
 static gpf_status ancestor_in_checks(gpf_filter* h, int64_t block_size, const AncestorIn& in, const char* who)
 {
-    if (!in.obs || in.n_obs != model_obs_dim(h->cfg.model))     // (as gpf_update_blocks refuses them)
-        return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model takes " + std::to_string(model_obs_dim(h->cfg.model)) + " observation values per step and block");
+    if (gpf_status s = block_obs_check(h, in.obs, in.n_obs)) return s;   // (as gpf_update_blocks refuses them)
     return block_ref_checks(h, block_size, in.ref, in.n_ref, who);
 }
 // [n_blocks][MAX_OBS] data vectors, then [n_blocks][MAX_DIM] reference rows (zero-padded) -> anc_in on the device, by a kernel on the filter's stream;
@@ -178,27 +220,15 @@ static gpf_status stage_ancestor_in(gpf_filter* h, int64_t nblocks, const Ancest
         h->anc_in_cap = nblocks;
     }
     if (h->anc_ev_pending) { HIP_TRY(h, hipEventSynchronize(h->anc_ev)); h->anc_ev_pending = false; }   // (the copy that last read the pinned buffer)
-    const int dim = model_dim(h->cfg.model);
-    double* const so = h->h_anc_in; double* const sr = so + nblocks * MAX_OBS;
-    static_assert(MAX_OBS == 4 && MAX_DIM == 4, "the four columns of a staged row");
-    const int no = in.n_obs;                                     // (>= 1, checked; the fill is unrolled: at 10^4 blocks it is most of the call's host time)
-    for (int64_t b = 0; b < nblocks; ++b) {
-        double* const d = so + b * MAX_OBS; const double* const r = in.obs + b * no;
-        d[0] = r[0]; d[1] = no > 1 ? r[1] : 0.0; d[2] = no > 2 ? r[2] : 0.0; d[3] = no > 3 ? r[3] : 0.0;
-    }
-    for (int64_t b = 0; b < nblocks; ++b) {
-        double* const d = sr + b * MAX_DIM; const double* const r = in.ref + b * dim;
-        d[0] = r[0]; d[1] = dim > 1 ? r[1] : 0.0; d[2] = dim > 2 ? r[2] : 0.0; d[3] = dim > 3 ? r[3] : 0.0;
-    }
+    pack4(h->h_anc_in, in.obs, nblocks, in.n_obs);               // (n_obs, dim >= 1: checked)
+    pack4(h->h_anc_in + nblocks * MAX_OBS, in.ref, nblocks, model_dim(h->cfg.model));
     const int64_t n_words = nblocks * ROW;
     GPF_LAUNCH(k_stage_words, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(64, (n_words + BLOCK - 1) / BLOCK))), dim3(BLOCK), 0, h->stream,
                (const double*)h->h_anc_in, h->anc_in, n_words);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipEventRecord(h->anc_ev, h->stream));
     h->anc_ev_pending = true;
-    for (int i = 0; i < MAX_PARAMS; ++i) x.P[i] = h->args.P[i];
-    x.blk_params = h->bp_size > 0 ? h->blk_params : nullptr;
-    x.bp_size = h->bp_size > 0 ? h->bp_size : 1;
+    x = anc_args(h);
     x.obs = h->anc_in; x.ref = h->anc_in + nblocks * MAX_OBS;
     return GPF_OK;
 }
@@ -347,14 +377,6 @@ gpf_status gpf_block_resampled(gpf_handle h, int32_t* out)
     for (int64_t i = 0; i < h->blk_last; ++i) out[i] &= 1;       // (the words also carry the blocks' validity flags)
     return GPF_OK;
 }
-// two per-block results of `cells` doubles each from the device to the host, each where the caller wants it
-static gpf_status block_out2(gpf_filter* h, size_t cells, const double* a, double* a_out, const double* b, double* b_out)
-{
-    if (a_out) HIP_TRY(h, hipMemcpyAsync(a_out, a, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (b_out) HIP_TRY(h, hipMemcpyAsync(b_out, b, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return GPF_OK;
-}
 // the ESS and the log-ML estimate of every block of <= BLK_MAX particles into blk_stats = [ess | lml] (device)
 static gpf_status launch_block_stats(gpf_filter* h, int64_t block_size, int64_t nblocks)
 {
@@ -377,7 +399,8 @@ gpf_status gpf_block_stats(gpf_handle h, int64_t block_size, double* ess_out, do
             return lml_out ? gpf_log_ml_estimate(v, lml_out + b) : GPF_OK;
         });
     if ((s = launch_block_stats(h, block_size, nblocks))) return s;
-    return block_out2(h, (size_t)nblocks, h->blk_stats, ess_out, h->blk_stats + nblocks, lml_out);
+    const size_t bytes = (size_t)nblocks * sizeof(double);
+    return block_out(h, {{h->blk_stats, ess_out, bytes}, {h->blk_stats + nblocks, lml_out, bytes}});
 }
 
 } // extern "C"
@@ -391,14 +414,7 @@ void launch_block_moments_w(gpf_filter* h, int64_t nb, int64_t nblocks, int want
     });
 }
 // the device buffer of the per-block estimates: at least `need` doubles
-static gpf_status block_est_buffer(gpf_filter* h, int64_t need)
-{
-    if (h->blk_est_cap >= need) return GPF_OK;
-    if (h->blk_est) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->blk_est); h->blk_est = nullptr; h->blk_est_cap = 0; }
-    HIP_TRY(h, hipMalloc(&h->blk_est, (size_t)need * sizeof(double)));
-    h->blk_est_cap = need;
-    return GPF_OK;
-}
+static gpf_status block_est_buffer(gpf_filter* h, int64_t need) { return grow_doubles(h, h->blk_est, h->blk_est_cap, need); }
 // the gate of the per-block estimates: a filter that can have sub-state views
 constexpr unsigned GATE_EST = GATE_FILTER | GATE_STORE_VIEWS | GATE_CLAMP_STORE | GATE_MAX;
 // the view of one big block (big_block_views) brought up to date, its weight summary on the host: *bad = NaN / +Inf weights
@@ -449,7 +465,7 @@ gpf_status gpf_block_moments(gpf_handle h, int64_t block_size, double* mean_out,
     double* const mean = h->blk_est; double* const var = h->blk_est + cells;
     DISPATCH_W(h, (launch_block_moments_w<WW>(h, block_size, nblocks, var_out ? 1 : 0, mean, var)));
     HIP_TRY(h, hipGetLastError());
-    return block_out2(h, cells, mean, mean_out, var, var_out);
+    return block_out(h, {{mean, mean_out, cells * sizeof(double)}, {var, var_out, cells * sizeof(double)}});
 }
 // for b in blocks: proportionmap(state[b], column)[values[k]] (src/statistics.jl:91-101 on sub-states) -- gpf.h
 gpf_status gpf_block_proportion(gpf_handle h, int64_t block_size, int32_t column, const double* values, int32_t n_values, double* out)
@@ -480,9 +496,7 @@ gpf_status gpf_block_proportion(gpf_handle h, int64_t block_size, int32_t column
         GPF_LAUNCH((k_block_proportion<TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, rows, h->W, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
     });
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(out, h->blk_est, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return GPF_OK;
+    return block_out(h, {{h->blk_est, out, cells * sizeof(double)}});
 }
 
 // lwa_i = lw_i + logtrans(P_b, x_i, ref_b, obs_b) of every particle: the weights the ancestor of slot 0 is drawn from -- gpf.h
@@ -500,9 +514,7 @@ gpf_status gpf_block_ancestor_log_weights(gpf_handle h, int64_t block_size, cons
     if ((s = block_est_buffer(h, h->n)) || (s = stage_ancestor_in(h, nblocks, in, x))) return s;
     DISPATCH_MODEL(h, (launch_block_anc_lw<MM>(h, x, block_size, h->blk_est)));
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(out, h->blk_est, (size_t)h->n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return GPF_OK;
+    return block_out(h, {{h->blk_est, out, (size_t)h->n * sizeof(double)}});
 }
 
 // the blocks' observation vectors -> device ([n_blocks][MAX_OBS], zero-padded), ModelArgs::blk_* set
@@ -510,8 +522,8 @@ gpf_status gpf_block_ancestor_log_weights(gpf_handle h, int64_t block_size, cons
 // same launch into blk_ref ([n_blocks][MAX_DIM], zero-padded)
 static gpf_status set_block_obs(gpf_filter* h, const double* obs, int32_t n_obs, int64_t block_size, const double* ref = nullptr)
 {
-    if (!obs || n_obs != model_obs_dim(h->cfg.model))
-        return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model takes " + std::to_string(model_obs_dim(h->cfg.model)) + " observation values per step and block");
+    gpf_status s = block_obs_check(h, obs, n_obs);
+    if (s) return s;
     const int64_t nblocks = (h->n + block_size - 1) / block_size;
     if (h->blk_obs_cap < nblocks) {
         if (h->blk_obs) {
@@ -530,11 +542,7 @@ static gpf_status set_block_obs(gpf_filter* h, const double* obs, int32_t n_obs,
         }
         h->blk_obs_cap = nblocks;
     }
-    if (ref && h->blk_ref_cap < nblocks) {
-        if (h->blk_ref) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->blk_ref); h->blk_ref = nullptr; h->blk_ref_cap = 0; }
-        HIP_TRY(h, hipMalloc(&h->blk_ref, (size_t)nblocks * MAX_DIM * sizeof(double)));
-        h->blk_ref_cap = nblocks;
-    }
+    if (ref && (s = grow_doubles(h, h->blk_ref, h->blk_ref_cap, nblocks, MAX_DIM))) return s;
     // the staging buffers are used in turn: wait only until the copy that last read THIS buffer (four calls ago) has finished -- its
     // kernel publishes a ticket to pinned memory -- not for the stream
     const int k = (int)(h->blk_stage_next % gpf_filter::BLK_STAGE);
@@ -546,17 +554,10 @@ static gpf_status set_block_obs(gpf_filter* h, const double* obs, int32_t n_obs,
     }
     h->blk_stage_next += 1;
     double* const stage = h->h_blk_obs[k];
-    for (int64_t b = 0; b < nblocks; ++b)
-        for (int i = 0; i < MAX_OBS; ++i) stage[b * MAX_OBS + i] = i < n_obs ? obs[b * n_obs + i] : 0.0;
+    pack4(stage, obs, nblocks, n_obs);                           // (n_obs = the model's, >= 1: checked above)
     const int64_t n_words = nblocks * MAX_OBS;
     if (ref) {
-        const int dim = model_dim(h->cfg.model);
-        double* const rs = stage + n_words;
-        static_assert(MAX_DIM == 4, "the four columns of a staged reference row");
-        for (int64_t b = 0; b < nblocks; ++b) {
-            double* const d = rs + b * MAX_DIM; const double* const r = ref + b * dim;
-            d[0] = r[0]; d[1] = dim > 1 ? r[1] : 0.0; d[2] = dim > 2 ? r[2] : 0.0; d[3] = dim > 3 ? r[3] : 0.0;
-        }
+        pack4(stage + n_words, ref, nblocks, model_dim(h->cfg.model));
         const int64_t n_ref_words = nblocks * MAX_DIM;
         GPF_LAUNCH(k_stage_obs_ref, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(64, (n_words + n_ref_words + BLOCK - 1) / BLOCK))), dim3(BLOCK), 0, h->stream,
                    stage, h->blk_obs, n_words, h->blk_ref, n_ref_words, h->blk_stage_counter, h->h_blk_done, h->blk_stage_next);
@@ -574,9 +575,7 @@ static gpf_status block_step_checks(gpf_handle h, int64_t& block_size, const cha
     gpf_status s = block_gate(h, block_size, who, GATE_FILTER | GATE_CLAMP | GATE_PARAMS);
     if (s) return s;
     // (callers that change the handle's arguments before set_block_obs -- the strata -- validate the observations first, so that a bad call changes nothing)
-    if (with_obs && (!obs || n_obs != model_obs_dim(h->cfg.model)))
-        return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model takes " + std::to_string(model_obs_dim(h->cfg.model)) + " observation values per step and block");
-    return GPF_OK;
+    return with_obs ? block_obs_check(h, obs, n_obs) : GPF_OK;
 }
 // a block-wise update begins a step of the trajectory store: a full store refuses here, before strata, observations, rows or epoch change
 static gpf_status block_store_room(gpf_filter* h)
@@ -829,15 +828,6 @@ static gpf_status across_planner(gpf_filter* h, int64_t nblocks)
     }
     return GPF_OK;
 }
-// the second buffer of a per-block row array, at least as large as the first
-static gpf_status across_alt(gpf_filter* h, double*& alt, int64_t& alt_cap, int64_t cap, int width)
-{
-    if (alt_cap >= cap) return GPF_OK;
-    if (alt) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(alt); alt = nullptr; alt_cap = 0; }
-    HIP_TRY(h, hipMalloc(&alt, (size_t)cap * width * sizeof(double)));
-    alt_cap = cap;
-    return GPF_OK;
-}
 gpf_status gpf_resample_across_blocks(gpf_handle h, int32_t method, int64_t block_size, int32_t sort_particles, double ess_frac, int32_t check,
                                       int32_t* invalid, int32_t* resampled, double* ess_out)
 {
@@ -894,8 +884,9 @@ gpf_status gpf_resample_across_blocks(gpf_handle h, int32_t method, int64_t bloc
         p->pending_gather = false; p->pending_fill = false;      // (its ancestors are all this call wants: the planner has no rows worth gathering)
         if (s) return fail(h, s, "planner: " + p->err);
         const bool with_par = h->bp_size > 0, with_obs = h->blk_obs_size > 0;
-        if (with_par && (s = across_alt(h, h->blk_params_alt, h->blk_params_alt_cap, h->blk_params_cap, MAX_PARAMS))) return s;
-        if (with_obs && (s = across_alt(h, h->blk_obs_alt, h->blk_obs_alt_cap, h->blk_obs_cap, MAX_OBS))) return s;
+        // (the second buffer of a per-block row array, at least as large as the first)
+        if (with_par && (s = grow_doubles(h, h->blk_params_alt, h->blk_params_alt_cap, h->blk_params_cap, MAX_PARAMS))) return s;
+        if (with_obs && (s = grow_doubles(h, h->blk_obs_alt, h->blk_obs_alt_cap, h->blk_obs_cap, MAX_OBS))) return s;
         // 4. whole blocks: rows, log-weights + (M - L[a]), parents, per-block rows -- one launch
         BlockGatherArgs a{};
         a.rows_in = h->rows[h->cur]; a.rows_out = h->rows[1 - h->cur]; a.lw_in = h->lw; a.lw_out = h->lws; a.anc_out = h->anc;
@@ -1526,14 +1517,75 @@ gpf_status gpf_proportion(gpf_handle h, int32_t step, int32_t column, double val
 // ---- past choices per block (gpf.h gpf_block_history_moments / _proportion): the block-wise store queried block by block, one launch
 } // extern "C"
 namespace gpfh {
-// the gate of the three queries of the block-wise store; block_size comes back clamped
-static gpf_status block_store_gate(gpf_handle h, int64_t& block_size, const char* who)
+// The preamble of a query of the block-wise store, in ONE order ("the gate of the block-wise calls"): the gate, the query's own arguments,
+// the step range (which brings the filter up to date), the 2^31 limits, the recorded block sizes, the device tables.  All but the tables change nothing.
+// the gate of the queries; block_size comes back clamped.  needs_weights: the queries that read the store's weight records and evaluate the transition density
+static gpf_status block_store_gate(gpf_handle h, int64_t& block_size, const char* who, bool needs_weights = false)
 {
     gpf_status s = block_gate(h, block_size, who, GATE_SIZE | GATE_CLAMP_STORE | GATE_MAX);
     if (s) return s;
     if (!h->hist_on || !h->hist_blocks)
         return fail(h, GPF_ERR_STATE, std::string(who) + " needs the block-wise trajectory store (gpf_history_enable_blocks before gpf_initialize_blocks)");
     if (h->d != 1 && h->d != 2 && h->d != 4) return fail(h, GPF_ERR_STATE, "latent dimension");
+    if (!needs_weights) return GPF_OK;
+    if (!h->hist_weights)
+        return fail(h, GPF_ERR_STATE, std::string(who) + " needs the store's weight records (gpf_history_enable_blocks_weights before gpf_initialize_blocks)");
+    return block_gate(h, block_size, who, GATE_PARAMS);
+}
+// the steps a query walks, 1 <= step_lo <= step_hi <= T, on a filter brought up to date
+struct StoreSteps { int T; int64_t nblocks, n_steps; };
+static gpf_status block_store_steps(gpf_handle h, int64_t block_size, int32_t step_lo, int32_t step_hi, const char* who, StoreSteps& r)
+{
+    gpf_status s = check_ready(h);
+    if (s) return s;
+    r.T = (int)h->hist_x.size();
+    if (step_lo < 1 || step_hi < step_lo || step_hi > r.T) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": need 1 <= step_lo <= step_hi <= gpf_history_steps");
+    r.nblocks = (h->n + block_size - 1) / block_size; r.n_steps = step_hi - step_lo + 1;
+    return GPF_OK;
+}
+// what the samplers return stays below 2^31 draws and cells: *draws = n_blocks * n_samples
+// (nblocks <= n < 2^31, n_samples < 2^31, n_steps d < 2^31: no product below overflows 64 bits before it is compared)
+static gpf_status block_store_draws(gpf_handle h, const StoreSteps& r, int32_t n_samples, const char* who, int64_t* draws)
+{
+    const int64_t lim = (int64_t)1 << 31, row = r.n_steps * h->d;
+    *draws = r.nblocks * n_samples;
+    if (*draws >= lim || row >= lim || *draws >= (lim + row - 1) / row)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": n_blocks * n_samples and n_blocks * n_samples * n_steps * dim must stay below 2^31");
+    return GPF_OK;
+}
+// every walked step above step_lo reads the observation rows it was entered with, by the particle's block: a block-wise step of this block size
+static gpf_status block_store_sizes(gpf_handle h, int64_t block_size, int T, int32_t step_lo, const char* who)
+{
+    for (int q = T - 1; q >= step_lo; --q) {
+        if (h->hist_bsize[q] == 0)
+            return fail(h, GPF_ERR_STATE, std::string(who) + ": step " + std::to_string(q + 1) + " was entered by a whole-filter call (no per-block observations were recorded)");
+        if (h->hist_bsize[q] != block_size)
+            return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": block_size " + std::to_string(block_size) + " differs from the " +
+                        std::to_string(h->hist_bsize[q]) + " step " + std::to_string(q + 1) + " was entered with");
+    }
+    return GPF_OK;
+}
+// whatever is deferred becomes state (the current step is snapshotted, in its current order); then the device tables, indexed by the 0-based step: the
+// snapshots and the composed ancestor maps (nullptr: a step without a resample), with_weights: the log-weights and the observation rows as well
+static gpf_status block_store_tables(gpf_handle h, bool with_weights)
+{
+    gpf_status s = hist_snapshot(h);
+    if (s) return s;
+    std::vector<const void*> host[4];                             // (host temporaries until the synchronisation)
+    auto put = [&](int k, void* dev, const auto& v) {
+        host[k].assign(v.begin(), v.end());
+        return hipMemcpyAsync(dev, host[k].data(), host[k].size() * sizeof(void*), hipMemcpyHostToDevice, h->stream);
+    };
+    HIP_TRY(h, put(0, h->hist_dev_maps, h->hist_map));
+    HIP_TRY(h, put(1, h->hist_dev_x, h->hist_x));
+    if (with_weights) { HIP_TRY(h, put(2, h->hist_dev_lw, h->hist_lw)); HIP_TRY(h, put(3, h->hist_dev_obs, h->hist_obs)); }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GPF_OK;
+}
+// device scratch of one query for an output that was asked for (up to 16 GB of trajectories are nothing to keep on a handle)
+static gpf_status block_store_scratch(gpf_handle h, CallScratch& c, const void* wanted, size_t bytes)
+{
+    if (wanted) HIP_TRY(h, hipMalloc(&c.p, bytes));
     return GPF_OK;
 }
 // what both estimate queries do once the gate and their own arguments have passed: the current step is snapshotted and the maps of the steps
@@ -1578,7 +1630,7 @@ gpf_status gpf_block_history_moments(gpf_handle h, int32_t step, int64_t block_s
     const double* hx = h->hist_x[step - 1];
     DISPATCH_D(h, (launch_block_hist_moments<DD>(h, n_maps, hx, block_size, nblocks, var_out ? 1 : 0, mean, var)));
     HIP_TRY(h, hipGetLastError());
-    return block_out2(h, cells, mean, mean_out, var, var_out);
+    return block_out(h, {{mean, mean_out, cells * sizeof(double)}, {var, var_out, cells * sizeof(double)}});
 }
 // for b in blocks: proportionmap(state[b], step => column)[values[k]] (src/statistics.jl:91-101 with a past address on sub-states) -- gpf.h
 gpf_status gpf_block_history_proportion(gpf_handle h, int32_t step, int64_t block_size, int32_t column, const double* values, int32_t n_values, double* out)
@@ -1599,9 +1651,7 @@ gpf_status gpf_block_history_proportion(gpf_handle h, int32_t step, int64_t bloc
         GPF_LAUNCH((k_block_hist_proportion<TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, h->hist_dev_maps, n_maps, hx, h->d, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
     });
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(out, h->blk_est, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return GPF_OK;
+    return block_out(h, {{h->blk_est, out, cells * sizeof(double)}});
 }
 // ---- whole trajectories per block (gpf.h gpf_block_sample_trajectories): weights, draws, genealogy walk and gather of all blocks in one launch
 } // extern "C"
@@ -1626,33 +1676,16 @@ gpf_status gpf_block_sample_trajectories(gpf_handle h, int64_t block_size, int32
     if (s) return s;
     if (!traj_out && !idx_out) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": both outputs are NULL");
     if (n_samples < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": n_samples < 1");
-    if ((s = check_ready(h))) return s;
-    const int T = (int)h->hist_x.size();
-    if (step_lo < 1 || step_hi < step_lo || step_hi > T) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": need 1 <= step_lo <= step_hi <= gpf_history_steps");
-    const int64_t nblocks = (h->n + block_size - 1) / block_size, n_steps = step_hi - step_lo + 1;
-    const int64_t lim = (int64_t)1 << 31;
-    // (nblocks <= n < 2^31, n_samples < 2^31, n_steps d < 2^31: no product below overflows 64 bits before it is compared)
-    const int64_t draws = nblocks * n_samples;
-    if (draws >= lim || n_steps * h->d >= lim || draws >= (lim + n_steps * h->d - 1) / (n_steps * h->d))
-        return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": n_blocks * n_samples and n_blocks * n_samples * n_steps * dim must stay below 2^31");
-    const size_t cells = (size_t)draws * (size_t)n_steps * (size_t)h->d;
-    if ((s = hist_snapshot(h))) return s;                         // whatever is deferred becomes state; the current step, in its current order
-    // the device tables, indexed by the 0-based step: the snapshots and the composed ancestor maps (nullptr: a step without a resample)
-    std::vector<const int32_t*> maps(h->hist_map.begin(), h->hist_map.end());
-    std::vector<const double*> xs(h->hist_x.begin(), h->hist_x.end());
-    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_maps, maps.data(), maps.size() * sizeof(int32_t*), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_x, xs.data(), xs.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));                   // the two vectors are host temporaries
-    // scratch of this call: freed before it returns (up to 16 GB of trajectories are nothing to keep on a handle)
-    CallScratch d_traj, d_idx;
-    if (traj_out) HIP_TRY(h, hipMalloc(&d_traj.p, cells * sizeof(double)));
-    if (idx_out) HIP_TRY(h, hipMalloc(&d_idx.p, (size_t)draws * sizeof(int64_t)));
-    const TrajLaunch a{T, step_lo - 1, step_hi - 1, block_size, nblocks, (int)n_samples, static_cast<double*>(d_traj.p), static_cast<int64_t*>(d_idx.p)};
+    StoreSteps r{};
+    int64_t draws = 0;
+    if ((s = block_store_steps(h, block_size, step_lo, step_hi, who, r)) || (s = block_store_draws(h, r, n_samples, who, &draws))) return s;
+    const size_t b_traj = (size_t)draws * (size_t)r.n_steps * (size_t)h->d * sizeof(double), b_idx = (size_t)draws * sizeof(int64_t);
+    CallScratch d_traj, d_idx;                                     // scratch of this call: freed before it returns
+    if ((s = block_store_tables(h, false)) || (s = block_store_scratch(h, d_traj, traj_out, b_traj)) || (s = block_store_scratch(h, d_idx, idx_out, b_idx))) return s;
+    const TrajLaunch a{r.T, step_lo - 1, step_hi - 1, block_size, r.nblocks, (int)n_samples, static_cast<double*>(d_traj.p), static_cast<int64_t*>(d_idx.p)};
     DISPATCH_D(h, (launch_block_sample_traj<DD>(h, a)));
     HIP_TRY(h, hipGetLastError());
-    if (traj_out) HIP_TRY(h, hipMemcpyAsync(traj_out, d_traj.p, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (idx_out) HIP_TRY(h, hipMemcpyAsync(idx_out, d_idx.p, (size_t)draws * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if ((s = block_out(h, {{d_traj.p, traj_out, b_traj}, {d_idx.p, idx_out, b_idx}}))) return s;
     h->epoch += 1;                                                // as gpf_sample_unweighted: the draws' slots are not read again
     return GPF_OK;
 }
@@ -1674,56 +1707,27 @@ gpf_status gpf_block_backward_sample(gpf_handle h, int64_t block_size, int32_t n
                                      double* traj_out, int64_t* idx_out)
 {
     const char* who = "gpf_block_backward_sample";
-    gpf_status s = block_store_gate(h, block_size, who);
+    gpf_status s = block_store_gate(h, block_size, who, true);
     if (s) return s;
-    if (!h->hist_weights)
-        return fail(h, GPF_ERR_STATE, std::string(who) + " needs the store's weight records (gpf_history_enable_blocks_weights before gpf_initialize_blocks)");
-    if ((s = block_gate(h, block_size, who, GATE_PARAMS))) return s;
     if (!traj_out) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": null trajectory output");
     if (n_samples < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": n_samples < 1");
-    if ((s = check_ready(h))) return s;
-    const int T = (int)h->hist_x.size();
-    if (step_lo < 1 || step_hi < step_lo || step_hi > T) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": need 1 <= step_lo <= step_hi <= gpf_history_steps");
-    const int64_t nblocks = (h->n + block_size - 1) / block_size, n_steps = step_hi - step_lo + 1;
-    const int64_t lim = (int64_t)1 << 31;
-    const int64_t draws = nblocks * n_samples;                    // (as gpf_block_sample_trajectories: no product below overflows before it is compared)
-    if (draws >= lim || n_steps * h->d >= lim || draws >= (lim + n_steps * h->d - 1) / (n_steps * h->d))
-        return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": n_blocks * n_samples and n_blocks * n_samples * n_steps * dim must stay below 2^31");
-    // every walked step above step_lo reads the observation rows it was entered with, by the particle's block: a block-wise step of this block size
-    for (int q = T - 1; q >= step_lo; --q) {
-        if (h->hist_bsize[q] == 0)
-            return fail(h, GPF_ERR_STATE, std::string(who) + ": step " + std::to_string(q + 1) + " was entered by a whole-filter call (no per-block observations were recorded)");
-        if (h->hist_bsize[q] != block_size)
-            return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": block_size " + std::to_string(block_size) + " differs from the " +
-                        std::to_string(h->hist_bsize[q]) + " step " + std::to_string(q + 1) + " was entered with");
-    }
-    const size_t cells = (size_t)draws * (size_t)n_steps * (size_t)h->d;
-    if ((s = hist_snapshot(h))) return s;                         // whatever is deferred becomes state; the current step, in its current order
-    std::vector<const int32_t*> maps(h->hist_map.begin(), h->hist_map.end());
-    std::vector<const double*> xs(h->hist_x.begin(), h->hist_x.end()), lws(h->hist_lw.begin(), h->hist_lw.end()), obs(h->hist_obs.begin(), h->hist_obs.end());
-    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_maps, maps.data(), maps.size() * sizeof(int32_t*), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_x, xs.data(), xs.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_lw, lws.data(), lws.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_obs, obs.data(), obs.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));                   // the vectors are host temporaries
+    StoreSteps r{};
+    int64_t draws = 0;
+    if ((s = block_store_steps(h, block_size, step_lo, step_hi, who, r)) || (s = block_store_draws(h, r, n_samples, who, &draws)) ||
+        (s = block_store_sizes(h, block_size, r.T, step_lo, who))) return s;
+    const size_t b_traj = (size_t)draws * (size_t)r.n_steps * (size_t)h->d * sizeof(double), b_idx = (size_t)draws * (size_t)r.n_steps * sizeof(int64_t);
     CallScratch d_traj, d_idx;                                     // scratch of this call, as gpf_block_sample_trajectories
-    HIP_TRY(h, hipMalloc(&d_traj.p, cells * sizeof(double)));
-    if (idx_out) HIP_TRY(h, hipMalloc(&d_idx.p, (size_t)draws * (size_t)n_steps * sizeof(int64_t)));
+    if ((s = block_store_tables(h, true)) || (s = block_store_scratch(h, d_traj, traj_out, b_traj)) || (s = block_store_scratch(h, d_idx, idx_out, b_idx))) return s;
     BackArgs a{};
     a.maps = h->hist_dev_maps; a.hx = h->hist_dev_x; a.hlw = h->hist_dev_lw; a.hobs = h->hist_dev_obs; a.lw = h->lw;
-    a.T = T; a.lo0 = step_lo - 1; a.hi0 = step_hi - 1; a.n_samples = (int)n_samples;
-    a.n = h->n; a.nb = block_size; a.nblocks = nblocks; a.seed = h->cfg.seed; a.epoch = h->epoch;
+    a.T = r.T; a.lo0 = step_lo - 1; a.hi0 = step_hi - 1; a.n_samples = (int)n_samples;
+    a.n = h->n; a.nb = block_size; a.nblocks = r.nblocks; a.seed = h->cfg.seed; a.epoch = h->epoch;
     a.traj = static_cast<double*>(d_traj.p); a.idx = static_cast<int64_t*>(d_idx.p);
-    AncArgs x{};
-    for (int i = 0; i < MAX_PARAMS; ++i) x.P[i] = h->args.P[i];
-    x.blk_params = h->bp_size > 0 ? h->blk_params : nullptr;
-    x.bp_size = h->bp_size > 0 ? h->bp_size : 1;
+    const AncArgs x = anc_args(h);
     DISPATCH_MODEL(h, (launch_block_backward<MM>(h, a, x)));
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(traj_out, d_traj.p, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (idx_out) HIP_TRY(h, hipMemcpyAsync(idx_out, d_idx.p, (size_t)draws * (size_t)n_steps * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->epoch += (uint32_t)(T - step_lo + 1);                      // one epoch for the step-T draw and one per backward step down to step_lo
+    if ((s = block_out(h, {{d_traj.p, traj_out, b_traj}, {d_idx.p, idx_out, b_idx}}))) return s;
+    h->epoch += (uint32_t)(r.T - step_lo + 1);                    // one epoch for the step-T draw and one per backward step down to step_lo
     return GPF_OK;
 }
 // ---- marginal smoothing per block (gpf.h gpf_block_smooth): the smoothing weights and moments of all blocks and steps in one launch.  The kernels are
@@ -1732,61 +1736,30 @@ gpf_status gpf_block_smooth(gpf_handle h, int64_t block_size, int32_t step_lo, i
                             double* mean_out, double* var_out, double* weights_out, int64_t* blocks_out)
 {
     const char* who = "gpf_block_smooth";
-    gpf_status s = block_store_gate(h, block_size, who);
+    gpf_status s = block_store_gate(h, block_size, who, true);
     if (s) return s;
-    if (!h->hist_weights)
-        return fail(h, GPF_ERR_STATE, std::string(who) + " needs the store's weight records (gpf_history_enable_blocks_weights before gpf_initialize_blocks)");
-    if ((s = block_gate(h, block_size, who, GATE_PARAMS))) return s;
     if (!mean_out && !var_out && !weights_out && !blocks_out) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": all outputs are NULL");
-    if ((s = check_ready(h))) return s;
-    const int T = (int)h->hist_x.size();
-    if (step_lo < 1 || step_hi < step_lo || step_hi > T) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": need 1 <= step_lo <= step_hi <= gpf_history_steps");
-    const int64_t nblocks = (h->n + block_size - 1) / block_size, n_steps = step_hi - step_lo + 1;
-    const int64_t lim = (int64_t)1 << 31;
+    StoreSteps r{};
+    if ((s = block_store_steps(h, block_size, step_lo, step_hi, who, r))) return s;
+    const int64_t lim = (int64_t)1 << 31, cells = r.nblocks * r.n_steps;
     const int64_t row = std::max<int64_t>(h->d, weights_out ? block_size : 1);   // (nblocks, n_steps, row < 2^31: the product below does not overflow before it is compared)
-    if (nblocks * n_steps >= lim || nblocks * n_steps >= (lim + row - 1) / row)
+    if (cells >= lim || cells >= (lim + row - 1) / row)
         return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": n_blocks * n_steps * dim and n_blocks * n_steps * block_size must stay below 2^31");
-    // every walked step above step_lo reads the observation rows it was entered with, by block: a block-wise step of this block size
-    for (int q = T - 1; q >= step_lo; --q) {
-        if (h->hist_bsize[q] == 0)
-            return fail(h, GPF_ERR_STATE, std::string(who) + ": step " + std::to_string(q + 1) + " was entered by a whole-filter call (no per-block observations were recorded)");
-        if (h->hist_bsize[q] != block_size)
-            return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": block_size " + std::to_string(block_size) + " differs from the " +
-                        std::to_string(h->hist_bsize[q]) + " step " + std::to_string(q + 1) + " was entered with");
-    }
-    if ((s = hist_snapshot(h))) return s;                         // whatever is deferred becomes state; the current step, in its current order
-    std::vector<const int32_t*> maps(h->hist_map.begin(), h->hist_map.end());
-    std::vector<const double*> xs(h->hist_x.begin(), h->hist_x.end()), lws(h->hist_lw.begin(), h->hist_lw.end()), obs(h->hist_obs.begin(), h->hist_obs.end());
-    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_maps, maps.data(), maps.size() * sizeof(int32_t*), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_x, xs.data(), xs.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_lw, lws.data(), lws.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_obs, obs.data(), obs.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));                   // the vectors are host temporaries
-    const size_t cells = (size_t)nblocks * (size_t)n_steps;
-    const size_t b_mom = cells * (size_t)h->d * sizeof(double), b_w = cells * (size_t)block_size * sizeof(double), b_c = cells * sizeof(int64_t);
+    if ((s = block_store_sizes(h, block_size, r.T, step_lo, who))) return s;
+    const size_t b_mom = (size_t)cells * (size_t)h->d * sizeof(double), b_w = (size_t)cells * (size_t)block_size * sizeof(double), b_c = (size_t)cells * sizeof(int64_t);
     CallScratch d_mean, d_var, d_w, d_c;                           // scratch of this call, as gpf_block_backward_sample; only what was asked for
-    if (mean_out) HIP_TRY(h, hipMalloc(&d_mean.p, b_mom));
-    if (var_out) HIP_TRY(h, hipMalloc(&d_var.p, b_mom));
-    if (weights_out) HIP_TRY(h, hipMalloc(&d_w.p, b_w));
-    if (blocks_out) HIP_TRY(h, hipMalloc(&d_c.p, b_c));
+    if ((s = block_store_tables(h, true)) || (s = block_store_scratch(h, d_mean, mean_out, b_mom)) || (s = block_store_scratch(h, d_var, var_out, b_mom)) ||
+        (s = block_store_scratch(h, d_w, weights_out, b_w)) || (s = block_store_scratch(h, d_c, blocks_out, b_c))) return s;
     SmoothArgs a{};
     a.maps = h->hist_dev_maps; a.hx = h->hist_dev_x; a.hlw = h->hist_dev_lw; a.hobs = h->hist_dev_obs; a.lw = h->lw;
-    a.T = T; a.lo0 = step_lo - 1; a.hi0 = step_hi - 1;
-    a.n = h->n; a.nb = block_size; a.nblocks = nblocks;
+    a.T = r.T; a.lo0 = step_lo - 1; a.hi0 = step_hi - 1;
+    a.n = h->n; a.nb = block_size; a.nblocks = r.nblocks;
     a.mean = static_cast<double*>(d_mean.p); a.var = static_cast<double*>(d_var.p);
     a.wout = static_cast<double*>(d_w.p); a.blocks = static_cast<int64_t*>(d_c.p);
-    AncArgs x{};
-    for (int i = 0; i < MAX_PARAMS; ++i) x.P[i] = h->args.P[i];
-    x.blk_params = h->bp_size > 0 ? h->blk_params : nullptr;
-    x.bp_size = h->bp_size > 0 ? h->bp_size : 1;
-    launch_block_smooth(h, a, x);
+    launch_block_smooth(h, a, anc_args(h));
     HIP_TRY(h, hipGetLastError());
-    if (mean_out) HIP_TRY(h, hipMemcpyAsync(mean_out, d_mean.p, b_mom, hipMemcpyDeviceToHost, h->stream));
-    if (var_out) HIP_TRY(h, hipMemcpyAsync(var_out, d_var.p, b_mom, hipMemcpyDeviceToHost, h->stream));
-    if (weights_out) HIP_TRY(h, hipMemcpyAsync(weights_out, d_w.p, b_w, hipMemcpyDeviceToHost, h->stream));
-    if (blocks_out) HIP_TRY(h, hipMemcpyAsync(blocks_out, d_c.p, b_c, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return GPF_OK;                                                // nothing was drawn: the epoch stays
+    // (nothing was drawn: the epoch stays)
+    return block_out(h, {{d_mean.p, mean_out, b_mom}, {d_var.p, var_out, b_mom}, {d_w.p, weights_out, b_w}, {d_c.p, blocks_out, b_c}});
 }
 // ---- checkpoint / resume: everything a filter needs to continue bit for bit -- the population, its log-weights and parents, the log-ML
 // estimate, the RNG epoch, the latest observation and strata -- as ONE host blob; loads into a handle created with the same gpf_config
