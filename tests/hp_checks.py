@@ -1,6 +1,7 @@
 """The checks of tests/test_hp_models.py (CPU oracle under test) and tests/test_gpu_hp.py (device filter under test): drive a filter through
 an adapter, and after every operation compare every particle's row and log-weight with tests/hp_reference.py's prediction from
-(seed, particle id, epoch, previous row), within the reference's own derived bound.  Helper module, no tests."""
+(seed, particle id, epoch, previous row), within the reference's own derived bound.  tests/test_hp_weights.py and
+tests/test_gpu_hp_weights.py drive the weight side and the resize family (tests/hp_weights.py) through the same Run.  Helper module, no tests."""
 import numpy as np
 
 import hp_reference as hp
@@ -31,9 +32,10 @@ class OracleAdapter:
     lw = property(lambda s: s.f.lw.copy())
     parents = property(lambda s: s.f.parents.copy())
     history = False
+    keep_prev = True
 
     def initialize(self, obs, proposal=False, strata=None, layout="contiguous"):
-        self.f = self.o.OracleFilter(self.model.model_id, self.model.params, self.n, self.seed, keep_prev=True, history=self.history)      # a new filter: epoch 0
+        self.f = self.o.OracleFilter(self.model.model_id, self.model.params, self.n, self.seed, keep_prev=self.keep_prev, history=self.history)      # a new filter: epoch 0
         self.f.initialize(obs, proposal=proposal, strata=strata, layout=layout)
 
     def update(self, obs, proposal=False, strata=None, layout="interleaved"):
@@ -44,6 +46,34 @@ class OracleAdapter:
 
     def resize(self, n_new, method, alpha=None):
         return bool(self.f.resize(n_new, method, priority_alpha=alpha, check=False))
+
+    def resize_refused(self, n_new, method):
+        """check=True on invalid weights: the call raises"""
+        try:
+            self.f.resize(n_new, method, check=True)
+        except self.o.OracleError:
+            return True
+        return False
+
+    def replicate(self, k, layout):
+        self.f.replicate(k, layout=layout)
+
+    def dereplicate(self, k, layout, method):
+        self.f.dereplicate(k, layout=layout, method=method)
+
+    def coalesce(self, cols):
+        """pf_coalesce has no function of its own in oracle.py: what is under test here is the test-side specification the GPU parity
+        tests hold the device to (tests/coalesce_spec.py), applied to the oracle filter's state"""
+        import coalesce_spec as cs
+        f = self.f
+        rows, lw, par = cs.coalesce_expected(self.o, f.rows, f.lw, cols if cols is not None else range(2 * f.d if f.keep_prev else f.d))
+        cs.set_state(f, rows, lw, par, f.lml_est)
+
+    def introduce(self, hist, n_add, proposal=False):
+        """pf_introduce has no function of its own in oracle.py either: the test-side specification of tests/coalesce_spec.py"""
+        import coalesce_spec as cs
+        rows, lw, par, lml = cs.introduce_expected(self.o, self.f, n_add, hist, proposal=proposal)
+        cs.set_state(self.f, rows, lw, par, lml, epoch_step=1)
 
     def sample_unweighted(self, k):
         return self.f.sample_unweighted(k)[1] - 1
@@ -125,6 +155,7 @@ class DeviceAdapter:
     lw = property(lambda s: s.st.log_weights)
     parents = property(lambda s: s.st.parents)
     history = False
+    keep_prev = True
 
     def _prop(self):
         return self.g.locally_optimal if self.model.name == "lgssm2" else self.g.line_fixed
@@ -136,7 +167,7 @@ class DeviceAdapter:
         if proposal:
             rest += [self._prop(), ()]
         kw = {"history": 8} if self.history else {}
-        self.st = g.pf_initialize(self.model, (), obs, *rest, self.n, seed=self.seed, keep_prev=True, layout=layout, **kw)
+        self.st = g.pf_initialize(self.model, (), obs, *rest, self.n, seed=self.seed, keep_prev=self.keep_prev, layout=layout, **kw)
 
     def update(self, obs, proposal=False, strata=None, layout="interleaved"):
         if strata is not None:
@@ -168,7 +199,31 @@ class DeviceAdapter:
         return any("Invalid weights" in str(x.message) for x in w)
 
     def resize(self, n_new, method, alpha=None):
+        if method == "optimal":                                                      # takes no priority (resize.jl:149)
+            return self._invalid(lambda check: self.g.pf_resize(self.st, n_new, method, check=check))
         return self._invalid(lambda check: self.g.pf_resize(self.st, n_new, method, priority_fn=self._prio(alpha), check=check))
+
+    def resize_refused(self, n_new, method):
+        try:
+            self.g.pf_resize(self.st, n_new, method, check=True)
+        except self.g.ErrorException:
+            return True
+        return False
+
+    def replicate(self, k, layout):
+        self.g.pf_replicate(self.st, k, layout=layout)
+
+    def dereplicate(self, k, layout, method):
+        self.g.pf_dereplicate(self.st, k, layout=layout, method=method)
+
+    def coalesce(self, cols):
+        self.g.pf_coalesce(self.st, by=None if cols is None else tuple(cols))
+
+    def introduce(self, hist, n_add, proposal=False):
+        if proposal:
+            self.g.pf_introduce(self.st, hist, self._prop(), (), n_add)
+        else:
+            self.g.pf_introduce(self.st, hist, n_add)
 
     def sample_unweighted(self, k):
         return self.g.sample_unweighted_traces(self.st, k, return_indices=True)[1] - 1
@@ -394,6 +449,205 @@ class Run:
         assert left_out <= MAX_UNDECIDABLE
         self.epoch += 1
         return left_out
+
+    # ---- the rest of the resize family (resize.jl:149-334) against tests/hp_weights.py
+    def _same_rows(self, label, rows, rows0, parents0):
+        assert rows.shape[0] == len(parents0) and np.array_equal(np.ascontiguousarray(rows).view(np.uint64), np.ascontiguousarray(rows0[parents0]).view(np.uint64)), f"{label}: gathered rows"
+
+    def _weights(self, v, what, lw, want):
+        """one expected weight per slot; None: -Inf exactly"""
+        assert len(lw) == len(want), (what, len(lw), len(want))
+        for j, w in enumerate(want):
+            if w is None:
+                assert lw[j] == -np.inf, (what, j, lw[j])
+            else:
+                v.value(what[j] if isinstance(what, list) else what, j, lw[j], w)
+
+    def _getter_after(self, v, lw):
+        """the getter over new weights, the running estimate untouched"""
+        sm = hw.Softmax(lw)
+        if sm.invalid:
+            assert self.a.lml_estimate() == -np.inf
+        else:
+            self._lml_estimate(v, "log_ml_estimate", sm)
+
+    def resize_optimal(self, n_new):
+        """pf_resize(..., "optimal") (resize.jl:149-219).  The threshold and every keep decision must be decidable by the reference: a wrong
+        keep set changes every slot after it.  Returns the number of undecidable picks."""
+        a, rows0, lw0 = self.a, self.a.rows, self.a.lw
+        label = f"optimal resize {len(lw0)} -> {n_new}"
+        ref = hw.optimal_resize(lw0, n_new, self.seed, self.epoch)
+        assert not ref.und_threshold and not ref.und_keep, f"{label}: threshold {ref.und_threshold[:4]} / keep tests {ref.und_keep[:4]} within the bound: not a case"
+        invalid = a.resize(n_new, "optimal")
+        assert invalid is None or invalid == ref.invalid, (label, invalid, ref.invalid)
+        parents0 = np.asarray(a.parents) - 1
+        assert parents0.shape == (n_new,) and ((parents0 >= 0) & (parents0 < len(lw0))).all(), label
+        assert np.array_equal(parents0[:ref.n_keep], ref.keep), f"{label}: the kept particles, ascending"
+        skip = set(ref.picks.undecidable)
+        wrong = [(j, int(g_), w) for j, (g_, w) in enumerate(zip(parents0[ref.n_keep:], ref.picks.anc)) if j not in skip and g_ != w]
+        assert not wrong, f"{label}: {len(wrong)} picks off the reference (eps {ref.picks.eps:.3g}), first (slot, got, want) {wrong[:4]}"
+        assert len(skip) <= MAX_UNDECIDABLE, (label, ref.picks.undecidable)
+        assert not np.isin(parents0[ref.n_keep:], ref.keep).any(), f"{label}: a kept particle was picked again"
+        if not ref.invalid:
+            assert not ref.sm.dead[parents0].any(), f"{label}: a particle more than 708 below the maximum was chosen"
+        rows, lw, v = a.rows, a.lw, Violations()
+        self._same_rows(label, rows, rows0, parents0)
+        self._weights(v, ["optimal resize: lw of a kept particle"] * ref.n_keep + ["optimal resize: lw of a resampled particle"] * (n_new - ref.n_keep), lw, ref.weights)
+        self._getter_after(v, lw)
+        self._note(label, v)
+        self.n = a.n = n_new
+        self.n_keep = ref.n_keep
+        self.epoch += 1
+        return len(skip)
+
+    def resize_refused(self, n_new, method="optimal"):
+        """check=True on invalid weights raises and leaves the filter as it was"""
+        rows0, lw0, par0 = self.a.rows, self.a.lw, np.asarray(self.a.parents).copy()
+        assert self.a.resize_refused(n_new, method)
+        assert np.array_equal(self.a.rows, rows0, equal_nan=True) and np.array_equal(self.a.lw, lw0) and np.array_equal(self.a.parents, par0)
+
+    def dereplicate_sample(self, k, layout="contiguous"):
+        """pf_dereplicate(..., method="sample") (resize.jl:281-293).  Returns the number of undecidable draws."""
+        a, rows0, lw0 = self.a, self.a.rows, self.a.lw
+        label = f"dereplicate {len(lw0)} / {k} {layout}"
+        ref, want, sms = hw.dereplicate_sample(lw0, k, layout, self.seed, self.epoch)
+        a.dereplicate(k, layout, "sample")
+        n_new = len(lw0) // k
+        parents0 = np.asarray(a.parents) - 1
+        assert parents0.shape == (n_new,), label
+        groups, skip, wrong = hw.replicate_groups(len(lw0), k, layout), set(ref.undecidable), []
+        for j, (got, wnt) in enumerate(zip(parents0, ref.anc)):
+            assert got in groups[j], f"{label}: output {j} holds {got}, no member of its group"
+            assert sms[j].invalid or not sms[j].dead[groups[j].index(got)], f"{label}: output {j} drew a flushed particle"
+            if j not in skip and got != wnt:
+                wrong.append((j, int(got), wnt))
+        assert not wrong, f"{label}: {len(wrong)} draws off the reference (eps {ref.eps:.3g}), first (output, got, want) {wrong[:4]}"
+        assert len(skip) <= MAX_UNDECIDABLE, (label, ref.undecidable)
+        rows, lw, v = a.rows, a.lw, Violations()
+        self._same_rows(label, rows, rows0, parents0)
+        self._weights(v, "dereplicate sample: lw", lw, want)
+        self.n = a.n = n_new
+        self._getter_after(v, lw)
+        self._note(label, v)
+        self.epoch += 1
+        return len(skip)
+
+    def replicate_round_trip(self, k, layout="contiguous"):
+        """pf_replicate then pf_dereplicate(method="keepfirst"): both exact, no randomness, the log-ML getter unchanged in real arithmetic"""
+        a, rows0, lw0, n = self.a, self.a.rows, self.a.lw, len(self.a.lw)
+        idx = np.repeat(np.arange(n), k) if layout == "contiguous" else np.tile(np.arange(n), k)      # repeat(x; inner=k) / repeat(x, k), :238
+        a.replicate(k, layout)
+        v = Violations()
+        assert np.array_equal(np.asarray(a.parents) - 1, idx), layout
+        self._same_rows(f"replicate {layout}", a.rows, rows0, idx)
+        assert np.array_equal(a.lw.view(np.uint64), lw0[idx].view(np.uint64))
+        self.n = a.n = n * k
+        self._getter_after(v, a.lw)
+        a.dereplicate(k, layout, "keepfirst")
+        first = np.arange(0, n * k, k) if layout == "contiguous" else np.arange(n)                  # :274
+        assert np.array_equal(np.asarray(a.parents) - 1, first), layout
+        assert np.array_equal(np.ascontiguousarray(a.rows).view(np.uint64), np.ascontiguousarray(rows0).view(np.uint64))
+        assert np.array_equal(a.lw.view(np.uint64), lw0.view(np.uint64))
+        self.n = a.n = n
+        self._getter_after(v, a.lw)
+        self._note(f"replicate / dereplicate {layout}", v)
+
+    def coalesce(self, cols=None):
+        """pf_coalesce (resize.jl:309-334); cols: the key columns, None = every state column.  Returns the number of groups."""
+        a, rows0, lw0 = self.a, self.a.rows, self.a.lw
+        n_old = len(lw0)
+        label = f"coalesce {n_old} by {cols}"
+        key = list(cols) if cols is not None else list(range(2 * self.d if a.keep_prev else self.d))
+        first, want, groups = hw.coalesce(rows0, lw0, key)
+        sm0, before = hw.Softmax(lw0), a.lml_estimate()
+        a.coalesce(cols)
+        parents0 = np.asarray(a.parents) - 1
+        assert len(a.lw) == len(groups), f"{label}: {len(a.lw)} groups, the definition has {len(groups)}"
+        assert np.array_equal(parents0, first), f"{label}: parents are the groups' first members in order of first occurrence"
+        assert np.all(np.diff(parents0) > 0)
+        rows, lw, v = a.rows, a.lw, Violations()
+        self._same_rows(label, rows, rows0, parents0)
+        self._weights(v, "coalesce: lw", lw, want)
+        self.n = a.n = len(groups)
+        # log_ml_estimate is unchanged in real arithmetic: the two getters agree within the sum of their bounds, each derived
+        sm1 = hw.Softmax(lw)
+        if sm0.invalid:
+            assert before == -np.inf and a.lml_estimate() == -np.inf
+        elif self.lml.v != -hp.M.inf:
+            e0, e1 = hw.lml_estimate_from(self.lml, sm0), hw.lml_estimate_from(self.lml, sm1)
+            assert e0.e < sum_guard(sm0) * max(1.0, abs(float(e0.v))) and abs(a.lml_estimate() - before) <= e0.e + e1.e, (label, before, a.lml_estimate(), e0, e1)
+            self._lml_estimate(v, "log_ml_estimate", sm1)
+        self._note(label, v)
+        return len(groups)
+
+    def introduce(self, hist, n_add, proposal=False):
+        """pf_introduce (resize.jl:351-421, include/gpf.h gpf_introduce).  New particle j: particle id n_old + j, the streams of the seed
+        mix(seed, epoch at the call), epochs 0 .. T-1: initialize, then T - 1 updates from the prior (the proposal at the last step when one is
+        given); its weight the sum of the step log-likelihoods in step order.  A keep_prev row stores x_T and x_{T-1}: both are checked against
+        the chain, which then goes on from the STORED values (and scores them), so only x_1 .. x_{T-2} are carried with their bounds."""
+        a, d = self.a, self.d
+        hist = np.ascontiguousarray(np.atleast_2d(np.asarray(hist, np.float64)))
+        T, n_old = hist.shape[0], self.n
+        rows0, lw0, par0 = a.rows, a.lw, np.asarray(a.parents).copy()
+        a.introduce(hist, n_add, proposal)
+        rows, lw, par, v = a.rows, a.lw, np.asarray(a.parents), Violations()
+        assert rows.shape[0] == lw.shape[0] == par.shape[0] == n_old + n_add
+        # ---- the old particles: lw += log_ml_est where it is not 0, ONE Float64 addition of one running estimate c inside the bound carried
+        assert np.array_equal(np.ascontiguousarray(rows[:n_old]).view(np.uint64), np.ascontiguousarray(rows0).view(np.uint64))
+        assert np.array_equal(par[:n_old], par0) and (par[n_old:] == 0).all()
+        if self.lml.v == 0 and self.lml.e == 0.0:
+            assert np.array_equal(lw[:n_old].view(np.uint64), lw0.view(np.uint64)), "introduce with log_ml_est = 0 touched the old weights"
+        else:
+            c, cands = float(self.lml.v), []
+            lo, hi = float(self.lml.v) - self.lml.e, float(self.lml.v) + self.lml.e
+            assert self.lml.e < MEDIAN_REL_TOL * max(1.0, abs(c))
+            for step in (-np.inf, np.inf):
+                x = c if step < 0 else np.nextafter(c, np.inf)
+                while lo <= x <= hi:
+                    if np.array_equal((lw0 + x).view(np.uint64), lw[:n_old].view(np.uint64)):
+                        cands.append(x)
+                    x = np.nextafter(x, step)
+            assert cands, "introduce: the old weights are not lw + c for any Float64 c within the bound of the running log-ML estimate"
+        self.lml = E(0.0)
+        # ---- the new particles
+        s2 = hp.mix(self.seed, self.epoch)
+        for j in range(n_add):
+            i, gid = n_old + j, n_old + j
+            got_x, got_p = rows[i, :d], rows[i, d:2 * d]
+            x, ws = None, []
+            for e in range(T):
+                last, first = e == T - 1, e == 0
+                if e == T - 1 and T >= 2:                    # x_{T-1} is stored: checked against the chain, which goes on from the stored value
+                    self._row(v, "introduce x_prev", i, got_p, x)
+                    x = [float(t) for t in got_p]
+                if e >= 1:
+                    ws.append(self.ref.loglik(x, hist[e - 1]))
+                if last and proposal:
+                    xn, wf = hp.update_proposal(self.ref, s2, e, gid, x, hist[e], first=first)
+                elif first:
+                    xn, wf = hp.initialize(self.ref, s2, e, gid, hist[e])
+                else:
+                    xn, wf = hp.update(self.ref, s2, e, gid, x, hist[e])
+                xprev, x = x, xn
+            self._row(v, "introduce", i, got_x, x)
+            if T == 1:
+                for k in range(d):
+                    v.exact("introduce x_prev (T = 1)", i, got_p[k], 0.0)
+            ws.append(wf(list(got_x)))
+            tot = ws[0]
+            for w in ws[1:]:
+                tot = tot + w
+            v.value("introduce lw", i, lw[i], tot)
+            if proposal and self.model.name == "lgssm2":   # conjugacy: the last increment is log N(y; A x', (sq^2 + sr^2) I) whatever x was drawn
+                tot = None
+                for w in ws[:-1] + [E(self.ref.marginal_loglik(T == 1, None if T == 1 else xprev, hist[T - 1]), ws[-1].e)]:
+                    tot = w if tot is None else tot + w
+                v.value("introduce conjugacy lw", i, lw[i], tot)
+        self.n = a.n = n_old + n_add
+        self._lml_estimate(v, "log_ml_estimate", hw.Softmax(lw))
+        self._note("introduce", v)
+        self.epoch += 1
+        self.obs = hist[-1]
 
     # ---- getters and statistics against the definitions
     def check_summaries(self, addrs=(), discrete=()):

@@ -174,6 +174,17 @@ def block(seed, gid, blk, epoch, tag):
     return philox4x32_10(gid & _MASK, blk & _MASK, epoch & _MASK, tag, seed & _MASK, (seed >> 32) & _MASK)
 
 
+def mix(seed, epoch):
+    """the seed of the streams of pf_introduce's new particles, as the comment of include/gpf.h gpf_introduce states it:
+    z = s ^ (e * 0x9e3779b97f4a7c15 + 0xd1b54a32d192ed03); z = (z ^ z >> 30) * 0xbf58476d1ce4e5b9; z = (z ^ z >> 27) * 0x94d049bb133111eb;
+    mix = z ^ z >> 31, in 64-bit wrap-around arithmetic"""
+    m64 = (1 << 64) - 1
+    z = seed ^ ((epoch * 0x9e3779b97f4a7c15 + 0xd1b54a32d192ed03) & m64)
+    z = ((z ^ (z >> 30)) * 0xbf58476d1ce4e5b9) & m64
+    z = ((z ^ (z >> 27)) * 0x94d049bb133111eb) & m64
+    return z ^ (z >> 31)
+
+
 def u52(hi, lo):
     """(k + 1/2) 2^-52, k = the top 52 of the 64 bits hi:lo -- a Float64 without rounding, strictly inside (0, 1)"""
     k = (hi << 20) | (lo >> 12)
@@ -270,8 +281,8 @@ class Ref:
             z = list(s.normal2(0)) + list(s.normal2(1))
             if first:
                 return [E(I["mu"][k]) + I["s"][k] * z[k] for k in range(4)]
-            return [(E(xp[0]) + xp[2]) + I["sp"] * z[0], (E(xp[1]) + xp[3]) + I["sp"] * z[1],
-                    E(xp[2]) + I["sv"] * z[2], E(xp[3]) + I["sv"] * z[3]]
+            return [(E.lift(xp[0]) + xp[2]) + I["sp"] * z[0], (E.lift(xp[1]) + xp[3]) + I["sp"] * z[1],
+                    E.lift(xp[2]) + I["sv"] * z[2], E.lift(xp[3]) + I["sv"] * z[3]]
         if self.name == "sv1":
             z0, _ = s.normal2(0)
             mu, phi, sg = I["mu"], I["phi"], I["sigma"]
@@ -279,11 +290,11 @@ class Ref:
                 if "sd0" not in self._c:
                     self._c["sd0"] = E(sg) / (1.0 - E(phi) * phi).sqrt()
                 return [E(mu) + self._c["sd0"] * z0]
-            return [(E(mu) + E(phi) * (E(xp[0]) - mu)) + sg * z0]
+            return [(E(mu) + E(phi) * (E.lift(xp[0]) - mu)) + sg * z0]
         if self.name == "object_motion":
             w = s.words(0)
             z0, _ = s.normal2(1)
-            pm, py = (0.0, 0.0) if first else (xp[0], xp[1])
+            pm, py = (0.0, 0.0) if first else (_f(xp[0]), xp[1])                  # (the indicator is exact; xp may come as E: pf_introduce's chain)
             mv = u52(w[0], w[1]) < (I["p_stay"] if pm != 0.0 else I["p_start"])
             return self._om_row(mv, py, obs, z0)
         if self.name == "line_model":
@@ -291,12 +302,12 @@ class Ref:
             slopes = I["slopes"]
             slope = float(slopes[mulhi64(u64(w[0], w[1]), len(slopes))]) if first else xp[0]      # uniform_discrete
             out = obs[1] != 0.0 and u52(w[2], w[3]) < I["p_out"]                                  # bernoulli(p_out); no step at x_t = 0
-            return [E(slope), E(1.0 if out else 0.0)]
+            return [E.lift(slope), E(1.0 if out else 0.0)]
         raise ValueError(self.name)
 
     def _om_row(self, moving, py, obs, z0):
         vel = obs[1] if moving else 0.0
-        return [E(1.0 if moving else 0.0), (E(py) + vel) + self.info["sy"] * z0]
+        return [E(1.0 if moving else 0.0), (E.lift(py) + vel) + self.info["sy"] * z0]
 
     # ---- log p(y_t | x_t)
     def loglik(self, x, obs, wraps=None):

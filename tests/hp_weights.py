@@ -30,7 +30,36 @@ documents, per particle, in counts of the fixed-point weight q_i ~ exp(lp_i - m)
     uniform fallback (all -Inf): q_i = 1, S = N: no quantisation at all, every bound is 0.
 
 A slot whose target lies within the bound of a CDF boundary of THIS reference is undecidable and is not compared.  No figure here is fitted
-to an output of the oracle or of the device.  Helper module, no tests."""
+to an output of the oracle or of the device.
+
+The rest of the resize family, from src/resize.jl of the reference:
+
+  * pf_optimal_resize! (:149-219): w = safe_softmax(lw); find_inv_w_threshold is the ascending loop `A -= 1; B += kappa`, the first kappa with
+    B / kappa + A <= n', then c = (n' - A) / B, else c = n'; keep_i <=> c w_i >= 1; the rest by the literal systematic loop of :170-178 over
+    safe_softmax(lw[strat]) from u0 = U / 2^64 of resample slot 0; kept slots carry lw + (log n' - log n), the others logsumexp(lw) - log c + that.
+  * pf_dereplicate!(method = :sample) (:281-293): per group of k replicates the inverse CDF of softmax(lw[group]) at the group's uniform, and
+    logsumexp(group) - log k.  Output j reads words (0,1) of the block with counter (j, 0, epoch, resample tag).
+  * pf_coalesce! (:309-334): groups by equality of the key, log sum_{i in g} exp(w_i) + log G - log n_old.
+
+Their bounds, in the counts of above (q~_i = exp(lp_i - m) 2^K real, q_i the integer, |q_i - q~_i| <= delta_i):
+
+    threshold     the spec sums integers: over the set summed so far |B - B~| <= dB = sum delta_i, and the candidate kappa is off by delta_k, so
+                  |B / q_k - B~ / q~_k| <= (dB + (B~ / q~_k) delta_k) / (q~_k - delta_k): kappa is decidable when n_check is further than that
+                  from n'.  B contains kappa, so n_check >= 1 + A in real and in integer arithmetic alike: a kappa with 1 + A > n' is no threshold,
+                  exactly.  A zero weight gives 0 / 0, which `<=` rejects.  At the smallest positive weight B = kappa and n_check = 1 + A is an
+                  identity of integers, decided exactly.
+    keep set      c w_i >= 1 <=> a q_i >= B, a = n' - A an exact integer: decidable when |a q~_i - B~| > a delta_i + dB.  The threshold
+                  particle at the smallest positive weight (B = kappa, a >= 1) is kept exactly; the uniform fallback has no quantisation.
+    picks         the loop's test `u < 0` at particle i of the unkept set is cdf'_i > (m + u0) / n_res on the normalised CDF of the unkept
+                  weights, m the picks so far: the stratified bound over that set, (2 D' + 3) / S'_lo with D' = sum of its delta_i and
+                  S'_lo = S~' - D'.  The spec reads all 64 bits of U.  Unkept weights all zero: the uniform weights are exact, the bound is 0.
+                  Unkept weights all the same Float64: the same input gives the same count q, the normalised CDF is i / n_strat whatever q
+                  is, and the floors cost nothing against the integer i q: the bound is 0 as well (`dominant`, `equal`).
+    weights       log_ of (double)B 2^-K: B's relative bound dB / (B~ - dB), the conversion, log_'s 2 ulp; every + and - half an ulp (E).
+    dereplicate   the multinomial bound 2 D / S_lo of the group's own Softmax at K = fix_K(k); logsumexp as Softmax.lse().
+    coalesce      Softmax(w[g], K = fix_K(n_old)).lse() of the group, then the additions.
+
+Helper module, no tests."""
 import bisect
 import math
 
@@ -332,3 +361,153 @@ def log_norm_weights(sm):
 
 def norm_weights(sm):
     return [E(p, e) for p, e in zip(sm.p, sm.w_err())]
+
+
+# ------------------------------------------------------------------------------------------- pf_optimal_resize! (resize.jl:149-219)
+class OptimalResize:
+    """what the definition says of one call: the kept particles (ascending), the systematic picks with their undecidable slots, one
+    expected weight per new slot (None: -Inf), and where the reference itself cannot decide the threshold or a keep test"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _lse_counts(sm, B, dB):
+    """m + log_((double)B 2^-K) of an integer sum B of counts whose real value is `B` (in units of exp(lp - m)), off by at most dB counts"""
+    Bt = float(M.ldexp(B, sm.K))
+    return E(sm.m) + E(B, float(B) * (dB / (Bt - dB) + U)).log(2.0)
+
+
+def optimal_resize(lw, n_new, seed, epoch, K=None, threshold_shift=0):
+    """`threshold_shift`: take the threshold that many positions further up the ascending order -- only the negative controls of
+    tests/test_hp_weights.py pass it"""
+    sm = Softmax(lw, K)
+    n, W, delta = sm.n, sm.W, sm.delta
+    assert 1 <= n_new <= n
+    order = [int(i) for i in np.argsort(sm.lp, kind="stable")]                 # sort(weights), :204
+    # ---- find_inv_w_threshold (:203-219)
+    A, B, dB, thr, exact, und_thr = n, mpf(0), 0.0, None, False, []
+    for pos, i in enumerate(order):
+        A -= 1
+        B += W[i]
+        dB += float(delta[i])
+        if A + 1 > n_new or W[i] == 0:                                         # n_check >= 1 + A;  0 / 0 is NaN and `<=` is false
+            continue
+        if B == W[i]:                                                          # n_check = 1 + A <= n': an identity of integers
+            thr, exact = pos, True
+            break
+        r = B / W[i]
+        qk = float(M.ldexp(W[i], sm.K))
+        bound = (dB + float(r) * float(delta[i])) / (qk - float(delta[i])) if qk > delta[i] else math.inf
+        if bound > 0.0 and abs(float(r + A - n_new)) <= bound:
+            und_thr.append(i)
+        if r + A <= n_new:
+            thr = pos
+            break
+    if thr is not None and threshold_shift:
+        thr, exact = thr + threshold_shift, False
+        A, B, dB = n - thr - 1, M.fsum(W[i] for i in order[:thr + 1]), float(sum(delta[i] for i in order[:thr + 1]))
+    if thr is None:
+        a, B, dB = n_new, sm.tot, sm.D                                         # float(n_particles), :218
+    else:
+        a = n_new - A                                                          # c = (n' - A) / B, :215
+    # ---- keep_idxs = c .* weights .>= 1 (:156)
+    keep, und_keep = [], []
+    for i in range(n):
+        if exact and sm.lp[i] == sm.lp[order[thr]]:
+            keep.append(i)
+            continue
+        lhs = a * W[i] - B
+        bound = a * float(delta[i]) + dB
+        if bound > 0.0 and abs(float(M.ldexp(lhs, sm.K))) <= bound:
+            und_keep.append(i)
+        if lhs >= 0:
+            keep.append(i)
+    kept = set(keep)
+    strat = [i for i in range(n) if i not in kept]
+    n_keep = len(keep)
+    n_res = n_new - n_keep
+    assert n_res >= 0, "not a case: more kept particles than slots"
+    # ---- the systematic loop (:170-178) over safe_softmax(lw[strat])
+    picks, und, eps, rest_uniform = [], [], 0.0, False
+    if n_res > 0:
+        Ws = [W[i] for i in strat]
+        tot = M.fsum(Ws)
+        if tot == 0:                                                           # safe_softmax of the rest: uniform, `invalid`
+            Ws, tot, rest_uniform = [mpf(1)] * len(strat), mpf(len(strat)), True
+        elif not sm.invalid and len({float(sm.lp[i]) for i in strat}) > 1:       # (one value: equal counts, the CDF is i / n exactly)
+            Dp = float(sum(delta[i] for i in strat))
+            eps = (2 * Dp + 3) / (float(M.ldexp(tot, sm.K)) - Dp)
+        step = mpf(1) / n_res
+        u = uniform(seed, 0, epoch) * step
+        for i, w in zip(strat, Ws):
+            u -= w / tot
+            if eps > 0.0 and abs(float(u)) <= eps and len(picks) < n_res:
+                und.append(len(picks))
+            if u < 0:
+                picks.append(i)
+                u += step
+    assert len(picks) == n_res, "not a case: the reference's own @assert (:181) throws"
+    # ---- the weights (:189-195)
+    ratio = log_n(n_new) - log_n(n)
+    weights = [E(float(lw[i])) + ratio for i in keep]
+    if sm.invalid:
+        weights += [None] * n_res
+    elif n_res:
+        weights += [(_lse_counts(sm, B, dB) - log_n(a)) + ratio] * n_res
+    return OptimalResize(sm=sm, keep=keep, n_keep=n_keep, picks=Ancestors(picks, sorted(set(und)), eps), weights=weights, a=a,
+                         und_threshold=und_thr, und_keep=und_keep, invalid=sm.invalid or rest_uniform, rest_uniform=rest_uniform)
+
+
+# ------------------------------------------------------------------------------------------- pf_dereplicate!(method = :sample) (resize.jl:281-293)
+def dereplicate_u64(seed, j, epoch, block_of=lambda j: j):
+    """output j reads words (0,1) of the block with counter (j, 0, epoch, resample tag) -- block j, not j >> 1"""
+    w = hp.block(seed, block_of(j), 0, epoch, hp.TAG_RESAMPLE)
+    return hp.u64(w[0], w[1])
+
+
+def replicate_groups(n_old, k, layout):
+    n_new = n_old // k
+    if layout == "contiguous":
+        return [list(range(j * k, (j + 1) * k)) for j in range(n_new)]
+    return [list(range(j, n_old, n_new)) for j in range(n_new)]
+
+
+def dereplicate_sample(lw, k, layout, seed, epoch, block_of=lambda j: j):
+    """(Ancestors over the n_new outputs as global 0-based indices, expected weights (None: -Inf), the groups' Softmax)"""
+    lw = np.asarray(lw, np.float64)
+    assert lw.size % k == 0
+    anc, und, weights, sms, eps = [], [], [], [], 0.0
+    for j, idx in enumerate(replicate_groups(lw.size, k, layout)):
+        sm = Softmax(lw[idx], fix_K(k))
+        e = 0.0 if sm.invalid else 2 * sm.D / sm.S_lo
+        a, ud = _inverse_cdf(sm.cdf(), [M.ldexp(mpf(dereplicate_u64(seed, j, epoch, block_of)), -64)], e)
+        assert sm.invalid or not sm.dead[a[0]] or ud, "the definition draws a particle the fixed point cannot see: not a case"
+        anc.append(idx[a[0]])
+        if ud:
+            und.append(j)
+        weights.append(None if sm.invalid else sm.lse() - log_n(k))
+        sms.append(sm)
+        eps = max(eps, e)
+    return Ancestors(anc, und, eps), weights, sms
+
+
+# ------------------------------------------------------------------------------------------- pf_coalesce! (resize.jl:309-334)
+def coalesce(rows, lw, cols, drop_smallest_of=None):
+    """(first members, expected weights (None: -Inf), groups): the groups of a dict over the key columns' bit patterns, in order of first
+    occurrence (the deviation include/gpf.h documents).  `drop_smallest_of`: a group whose sum leaves out its smallest member -- only the
+    negative controls pass it."""
+    rows, lw = np.ascontiguousarray(rows, np.float64), np.asarray(lw, np.float64)
+    groups = {}
+    for i in range(lw.size):
+        groups.setdefault(rows[i, list(cols)].tobytes(), []).append(i)
+    groups = list(groups.values())
+    K = fix_K(lw.size)
+    ratio = log_n(len(groups)) - log_n(lw.size)
+    weights = []
+    for g, idx in enumerate(groups):
+        if g == drop_smallest_of:
+            idx = sorted(idx, key=lambda i: lw[i])[1:]
+        sm = Softmax(lw[idx], K)
+        weights.append(None if sm.invalid else sm.lse() + ratio)
+    return [idx[0] for idx in groups], weights, groups

@@ -224,6 +224,24 @@ def test_hip_coalesce_all_distinct_unchanged(g, o):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("keys", ["mod5", "distinct"])
+def test_hip_coalesce_two_tiles_per_scan_thread(g, o, keys):
+    """n = 2048 * 256 + 1 = 524 289: 257 tiles of 2048, so the single workgroup of k_coal_scan gives a thread two tiles (its `per > 1`
+    branch, otherwise reached only by the soak case at 10^6).  Five groups, every one spread over every tile, and all rows distinct (no group
+    crosses a tile); against the specification bit for bit."""
+    n = 2048 * 256 + 1
+    m = g.models.lgssm2()
+    st, f, ys = _pair(g, o, m, n, resample=False)
+    if keys == "mod5":
+        rows = f.rows.copy()
+        rows[:, :] = (np.arange(n) % 5)[:, None]
+        st.traces = rows; f.rows = rows.copy()
+    _coalesce_both(g, o, st, f)
+    assert f.n == (5 if keys == "mod5" else n)
+    st.close()
+
+
+@pytest.mark.gpu
 def test_hip_coalesce_neginf_group_and_nan(g, o):
     m = g.models.lgssm2()
     st, f, ys = _pair(g, o, m, 1000)
