@@ -140,12 +140,11 @@ __global__ __launch_bounds__(BLOCK) void k_block_resample(BlockArgs a)
     __shared__ int s_f[NWAVES];
     __shared__ double s_lw_[PRIO ? BLOCK * ITEMS : 1];             // PRIO: the block's incoming log-weights, then log_ws of its slots
     __shared__ double s_lws_[PRIO ? BLOCK * ITEMS : 1];
-    const int tm = (int)threadIdx.x / TEAM, tl = (int)threadIdx.x % TEAM, lane = lane_id(), wv = wave_id();
+    const int tm = (int)threadIdx.x / TEAM, tl = (int)threadIdx.x % TEAM;
     const int64_t blk = (int64_t)blockIdx.x * TEAMS + tm;
     if (TEAM != BLOCK && blk >= a.nblocks) return;                 // (an idle wave: the wave-team path has no workgroup barrier)
     double* const s_lw = s_lw_ + (PRIO ? tm * CAP : 0);
     double* const s_lws = s_lws_ + (PRIO ? tm * CAP : 0);
-    (void)lane; (void)wv;
     uint64_t* const s_cdf = s_cdf_ + tm * CAP;
     uint64_t* const s_aux = s_aux_ + (METHOD == 0 ? 0 : tm * CAP);
     uint16_t* const s_idx = s_idx_ + (METHOD == 2 ? tm * CAP : 0);
@@ -791,22 +790,27 @@ __global__ __launch_bounds__(BLOCK) void k_block_gather(BlockGatherArgs a)
     }
 }
 
-// the blocks' observation vectors from a pinned host buffer into device memory, by a KERNEL (coalesced reads over PCIe) rather than a
-// hipMemcpyAsync: the copy stays on the compute queue (an SDMA copy costs a cross-queue dependency of ~10-20 us in front of the step
-// kernel that reads it).  The last workgroup publishes `ticket` to pinned memory: the host may then refill that staging buffer.
-static __global__ __launch_bounds__(BLOCK) void k_stage_obs(const double* __restrict__ src_host, double* __restrict__ dst, int64_t n_words,
-                                                     unsigned int* counter, int64_t* host_done, int64_t ticket)
+// the end of a staging kernel: the last workgroup to arrive publishes `ticket` to pinned memory; the host may then refill that staging buffer.  The
+// ticket says "the staging buffer has been READ": every load of a workgroup has returned -- its value went into a store that has been issued --
+// before the barrier; nothing the host reads is published, so no fence: an agent / system release is an L2 write-back
+__device__ __forceinline__ void stage_ticket(unsigned int* counter, int64_t* host_done, int64_t ticket)
 {
-    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n_words; i += (int64_t)gridDim.x * BLOCK) dst[i] = src_host[i];
     __syncthreads();
-    // (the ticket says "the staging buffer has been READ": every load of this workgroup has returned -- its value went into a store that has
-    //  been issued -- before the barrier; nothing the host reads is published, so no fence: an agent / system release is an L2 write-back)
     if (threadIdx.x == 0) {
         if (__hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
             __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(host_done, ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
+}
+// the blocks' observation vectors from a pinned host buffer into device memory, by a KERNEL (coalesced reads over PCIe) rather than a
+// hipMemcpyAsync: the copy stays on the compute queue (an SDMA copy costs a cross-queue dependency of ~10-20 us in front of the step
+// kernel that reads it).  Ends with stage_ticket.
+static __global__ __launch_bounds__(BLOCK) void k_stage_obs(const double* __restrict__ src_host, double* __restrict__ dst, int64_t n_words,
+                                                     unsigned int* counter, int64_t* host_done, int64_t ticket)
+{
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n_words; i += (int64_t)gridDim.x * BLOCK) dst[i] = src_host[i];
+    stage_ticket(counter, host_done, ticket);
 }
 
 // k_stage_obs with the reference rows of a pinned step behind the observations in the SAME staging buffer: src_host = [n_obs_words | n_ref_words],
@@ -819,13 +823,7 @@ static __global__ __launch_bounds__(BLOCK) void k_stage_obs_ref(const double* __
         const double v = src_host[i];
         if (i < n_obs_words) dst_obs[i] = v; else dst_ref[i - n_obs_words] = v;
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {                                        // (the ticket: as k_stage_obs)
-        if (__hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
-            __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(host_done, ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
+    stage_ticket(counter, host_done, ticket);
 }
 
 } // namespace gpf

@@ -70,7 +70,7 @@ def run_steps(g, o, st, f, ys, nb, steps=3, method="multinomial"):
 
 # 1. the three team shapes and their edges (<= 128: a wave, 2 per lane; <= 512: a wave, 8 per lane; else a workgroup), ragged last blocks
 @pytest.mark.parametrize("N,nb", [(100, 100), (1000, 100), (4096, 2048), (5000, 2048), (777, 64), (37, 1), (2500, 1000), (300, 7),
-                                  (3000, 300), (2100, 512), (1000, 129), (640, 128), (1539, 513)])
+                                  (3000, 300), (2100, 512), (1000, 129), (640, 128), (1539, 513), (11, 2)])
 def test_moments_equal_the_oracle_per_block(g, o, N, nb):
     m, ys, st, f = make(g, o, "lgssm2", N)
     run_steps(g, o, st, f, ys, nb)
@@ -134,7 +134,7 @@ def line_filters(g, o, N, seed=5, T=4):
     return m, st, f
 
 
-@pytest.mark.parametrize("N,nb", [(1030, 100), (2100, 512), (4500, 2048), (600, 7)])
+@pytest.mark.parametrize("N,nb", [(1030, 100), (2100, 512), (4500, 2048), (600, 7), (300, 1), (301, 2), (700, 128), (1000, 129), (1539, 513)])
 @pytest.mark.parametrize("which", ["object_motion.moving", "line_model.outlier", "line_model.slope"])
 def test_proportions_equal_the_oracle(g, o, which, N, nb):
     if which == "object_motion.moving":

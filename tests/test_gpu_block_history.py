@@ -25,6 +25,7 @@ MODELS = ["sv1", "object_motion", "lgssm2", "bearings4"]                     # d
 # every block always resamples (a wider one is used).  Checked against the CPU oracle of the same loop: every case below sees both kinds.
 NOISE = {"sv1": 2.0, "object_motion": 0.3, "lgssm2": 0.3, "bearings4": 0.3}
 SIZES = [7, 100, 300, 999]
+EDGES = [("sv1", 1), ("object_motion", 2), ("bearings4", 128), ("lgssm2", 129), ("sv1", 512), ("bearings4", 513), ("object_motion", 2048)]
 CYCLE = [("multinomial", True), ("residual", True), ("stratified", True), ("stratified", False), ("multinomial", False)]
 
 
@@ -226,11 +227,9 @@ def twin_expectation(st, tw, bs, t):
     return mu[:, :st.dim], s2[:, :st.dim], props
 
 
-@pytest.mark.parametrize("bs", SIZES)
-@pytest.mark.parametrize("model_name", MODELS)
-def test_queries_equal_the_estimates_of_a_twin(g, model_name, bs):
-    st, gen, _, _ = run(g, model_name, 1000, bs)
-    d, B = st.dim, n_blocks(1000, bs)
+def queries_equal_the_twin(g, model_name, n, bs):
+    st, gen, _, _ = run(g, model_name, n, bs)
+    d, B = st.dim, n_blocks(n, bs)
     # (a) step = T is the current step
     mu_now, s2_now = g.block_moments(st, bs)
     mu_T, s2_T = g.block_moments(st, bs, step=T)
@@ -254,6 +253,18 @@ def test_queries_equal_the_estimates_of_a_twin(g, model_name, bs):
                 assert eq(c_proportion(st, bs, c, v, step=t), want), (model_name, bs, t, c, k, "proportion")
     assert np.all(np.isfinite(mu))
     tw.close(); st.close()
+
+
+@pytest.mark.parametrize("bs", SIZES)
+@pytest.mark.parametrize("model_name", MODELS)
+def test_queries_equal_the_estimates_of_a_twin(g, model_name, bs):
+    queries_equal_the_twin(g, model_name, 1000, bs)
+
+
+# the edges of the three team shapes (<= 128: a wave, 2 per lane; <= 512: a wave, 8 per lane; else the workgroup), five whole blocks and a short one
+@pytest.mark.parametrize("model_name,bs", EDGES)
+def test_queries_equal_the_estimates_of_a_twin_at_the_team_edges(g, model_name, bs):
+    queries_equal_the_twin(g, model_name, 5 * bs + (bs + 1) // 2, bs)
 
 
 def test_block_proportionmap_of_a_past_choice(g):

@@ -27,6 +27,7 @@ T = 6
 NOISE = {"sv1": 2.0, "object_motion": 0.3, "lgssm2": 0.3, "bearings4": 0.3}
 CYCLE = [("multinomial", True), ("residual", True), ("stratified", True), ("stratified", False), ("multinomial", False)]
 CASES = [("sv1", 7), ("object_motion", 100), ("bearings4", 300), ("object_motion", 999)]      # d = 1, 2, 4; every team shape
+EDGES = [("sv1", 1), ("object_motion", 2), ("bearings4", 128), ("object_motion", 129), ("sv1", 512), ("bearings4", 513), ("object_motion", 2048)]
 DRAWS = [1, 70, 300]
 I64 = ctypes.POINTER(ctypes.c_int64)
 
@@ -144,10 +145,9 @@ def test_indices_equal_the_spec(g, o, model_name, bs):
 
 
 # ----------------------------------------------------------------------------- 2. paths, bit for bit
-@pytest.mark.parametrize("model_name,bs", CASES)
-def test_paths_follow_the_genealogy(g, o, model_name, bs):
-    L = Loop(g, model_name, 1000, bs)
-    st, d, B = L.st, L.st.dim, n_blocks(1000, bs)
+def paths_follow_the_genealogy(g, o, model_name, n, bs):
+    L = Loop(g, model_name, n, bs)
+    st, d, B = L.st, L.st.dim, n_blocks(n, bs)
     L.gen.set_rows(latent(st))
     cols = {(s, c): st.history_column(s, c) for s in range(1, T + 1) for c in range(d)}
     base = (np.arange(B) * bs)[:, None]
@@ -173,6 +173,17 @@ def test_paths_follow_the_genealogy(g, o, model_name, bs):
     L.epoch += 1
     assert np.array_equal(only_traj, spec.paths(L.gen, want, bs, 2, 4, d))
     L.close()
+
+
+@pytest.mark.parametrize("model_name,bs", CASES)
+def test_paths_follow_the_genealogy(g, o, model_name, bs):
+    paths_follow_the_genealogy(g, o, model_name, 1000, bs)
+
+
+# the edges of the three team shapes (<= 128: a wave, 2 per lane; <= 512: a wave, 8 per lane; else the workgroup), five whole blocks and a short one
+@pytest.mark.parametrize("model_name,bs", EDGES)
+def test_paths_follow_the_genealogy_at_the_team_edges(g, o, model_name, bs):
+    paths_follow_the_genealogy(g, o, model_name, 5 * bs + (bs + 1) // 2, bs)
 
 
 # ----------------------------------------------------------------------------- 3. one block equals the whole-filter call

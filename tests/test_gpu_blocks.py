@@ -31,7 +31,7 @@ def same(st, f):
 @pytest.mark.parametrize("method", METHODS)
 @pytest.mark.parametrize("sort_particles", [False, True])
 @pytest.mark.parametrize("N,nb", [(100, 100), (1000, 100), (4096, 2048), (5000, 2048), (777, 64), (37, 1), (2500, 1000), (300, 7),
-                                  (3000, 300), (2100, 512), (1000, 129), (640, 128), (1539, 513)])   # (<= 128: a wave, 2 per lane; <= 512: a wave, 8 per lane; else a workgroup)
+                                  (3000, 300), (2100, 512), (1000, 129), (640, 128), (1539, 513), (11, 2)])   # (<= 128: a wave, 2 per lane; <= 512: a wave, 8 per lane; else a workgroup)
 def test_blocks_equal_the_loop_over_substates(g, o, method, sort_particles, N, nb):
     if sort_particles and method != "stratified":
         pytest.skip("sort_particles is a stratified option")
@@ -97,10 +97,9 @@ def test_first_block_equals_a_device_view(g, o, method):
     st.close(); st2.close()
 
 
-@pytest.mark.parametrize("method", METHODS)
-def test_adversarial_block_weights(g, o, method):
+def adversarial_block_weights(g, o, method, nb):
     """blocks with equal weights, one dominant particle, all -Inf (uniform fallback, flagged invalid), wide ranges, -Inf-heavy"""
-    N, nb = 1000, 100
+    N = 10 * nb
     m, ys, st, f = make(g, o, "lgssm2", N)
     rng = np.random.default_rng(5)
     lw = np.concatenate([np.zeros(nb), np.where(np.arange(nb) == 17, 0.0, -800.0), np.full(nb, -np.inf), -700.0 * rng.random(nb),
@@ -116,6 +115,16 @@ def test_adversarial_block_weights(g, o, method):
     g.pf_update(st, (2,), (None,), ys[1]); f.update(ys[1])
     assert same(st, f)
     st.close()
+
+
+@pytest.mark.parametrize("method", METHODS)
+def test_adversarial_block_weights(g, o, method):
+    adversarial_block_weights(g, o, method, 100)
+
+
+@pytest.mark.parametrize("method", METHODS)
+def test_adversarial_block_weights_of_a_workgroup_team(g, o, method):
+    adversarial_block_weights(g, o, method, 600)
 
 
 def test_invalid_blocks_are_reported_and_left_alone(g, o):
