@@ -53,6 +53,26 @@ struct PhaseTimer {
     double host_wait_us = 0.0;          // wall clock the host spent blocked on the exchange's split sizes
     int64_t resamples = 0;
 };
+// What the handle remembers about the CURRENT raw log-weights.  Three independent facts -- the maximum in the slots, a scan with its
+// CDF, a reduction without one -- and the details that mean something only under their fact.  Nothing outside this struct assigns a member: the call
+// sites go through the transitions below (and weights_written(), which adds the mutation counter), the producers through the three setters.
+struct WeightSummary {
+    bool max_valid = false;        // mslots[mcur] hold the maximum + flags of the log-weights (left by the kernel that wrote them, or by k_max_partial); always meaningful
+    bool raw_valid = false;        // sc->raw = {m, flags, S} and cdf[0] with its levels / table[0] are the plain scan of the log-weights at the filter's K; always meaningful
+    bool raw_has_q = false;        // only under raw_valid: that scan also accumulated sum q^2 (blockQ)
+    bool raw_q_folded = false;     // only under raw_valid && raw_has_q: sc->raw.Ql is folded from blockQ (by the publishing scan or by fetch_scalars)
+    bool raw_sum_valid = false;    // sum_cache = {flags, S, Ql} of the log-weights from a reduction WITHOUT a CDF (the ESS / log-ML getters, gpf_step_ess); always meaningful
+    bool sum_on_host = false;      // only under raw_sum_valid: k_sum_host made it -- sum_cache holds m too and sc->raw on the device was NOT updated (else k_sum_reduce: m is in sc->raw)
+    WSum sum_cache{};              // only under raw_sum_valid
+    // -- transitions
+    void forget() { *this = WeightSummary{}; }                    // nothing is known about the weights any more (whoever changed them answers for the mutation counter)
+    void drop_sums() { const bool m = max_valid; forget(); max_valid = m; }   // sc->raw / cdf[0] were overwritten or rescaled (priorities, a sorted order, a global maximum, another K): the weights and their maximum stand
+    // -- producers
+    void max_produced(bool of_raw_weights) { max_valid = of_raw_weights; }   // k_max_partial filled the slots (of a priority view: they no longer describe the raw weights)
+    void scanned(bool with_q, bool q_folded) { raw_valid = true; raw_has_q = with_q; raw_q_folded = q_folded; }   // ensure_raw's scan into sc->raw
+    void q_folded() { raw_q_folded = true; }                      // the publish kernel folded blockQ into sc->raw.Ql
+    void reduced(const WSum& w, bool on_host) { sum_cache = w; sum_on_host = on_host; raw_sum_valid = true; }   // k_sum_reduce / k_sum_host
+};
 
 } // namespace gpfh
 
@@ -90,16 +110,11 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     Scalars* h_sc = nullptr;       // pinned mirror
     long long* h_sc_ticket = nullptr; long long sc_ticket = 0;   // k_publish_scalars -> host polling (fetch_scalars)
     uint32_t epoch = 0;
-    bool initialized = false, has_prev = false, raw_valid = false, residual_scanned = false;
-    bool max_valid = false;        // mslots[mcur] describes the current log-weights (written by the kernel that produced them)
-    bool raw_sum_valid = false;    // sc->raw holds {m, flags, S, Ql} of the current log-weights WITHOUT a CDF (k_sum_reduce: the ESS / log-ML getters)
-    WSum sum_cache{};              // ... and the host's copy of it
+    bool initialized = false, has_prev = false, residual_scanned = false;
+    gpfh::WeightSummary summary;   // the cached summaries of the current log-weights
     uint64_t* sum_part = nullptr;  // [6][workgroups] tagged partials of k_sum_reduce
     int64_t* h_spart = nullptr;    // pinned: [n_cu][8] tagged partials of k_sum_host, folded by the host
-    bool sum_on_host = false;      // sum_cache came from k_sum_host: it holds m too, and sc->raw on the device was NOT updated
     uint64_t* gate_part = nullptr; int gate_cur = 0; int64_t* h_gate = nullptr;   // gpf_step_ess: two sets of k_sum_host<GATE>'s accumulator lines (gate_verdict), pinned {ticket << 1 | verdict} of the launch that read them
-    bool raw_has_q = false;        // the raw summary's scan also accumulated sum q^2 (blockQ)
-    bool raw_q_folded = false;     // sc->raw.Ql folded from blockQ
     bool pending_gather = false;   // a resample left (rows[cur], anc) un-gathered; log-weights are 0
     bool pending_fill = false;     // ... or, after gpf_resample_local, the constant sc->lw_fill
     // "lazy search" (gpf_k_fused.hpp): pf_resample!(:multinomial) enqueued only the weight scan; the ancestors (h->anc) and the log-ML
@@ -564,6 +579,7 @@ gpf_status hist_snapshot(gpf_filter* h);
 gpf_status hist_on_resample(gpf_filter* h, int64_t block_size = 0);
 gpf_status hist_begin_step(gpf_filter* h, bool first);
 void mutated(gpf_filter* h);
+void weights_written(gpf_filter* h, bool max_in_slots);
 gpf_status after_initialize(gpf_filter* h, int grid);
 void after_propagate(gpf_filter* h);
 gpf_status view_enter(gpf_filter* v);

@@ -275,8 +275,7 @@ static gpf_status resample_big_blocks(gpf_handle h, int32_t method, int64_t bloc
     HIP_TRY(h, hipMemcpyAsync(h->blk_mask, words.data(), (size_t)nblocks * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));                // (the host vector goes out of scope)
     h->blk_last = nblocks;
-    h->raw_valid = false; h->raw_sum_valid = false; h->raw_has_q = false; h->raw_q_folded = false; h->max_valid = false;
-    mutated(h);
+    weights_written(h, false);
     if (invalid) *invalid = any_invalid ? 1 : 0;
     if (n_resampled) *n_resampled = count;
     if (hard) return hard;
@@ -330,9 +329,8 @@ static gpf_status resample_blocks_impl(gpf_handle h, int32_t method, int64_t blo
     h->cur ^= 1;
     h->blk_last = nblocks;
     h->pending_gather = false; h->pending_fill = false;
-    h->raw_valid = false; h->raw_sum_valid = false; h->raw_has_q = false; h->raw_q_folded = false; h->max_valid = false;
     h->epoch += 1;
-    mutated(h);
+    weights_written(h, false);
     // (the block-wise store: this call's parents into the step's ancestor map -- behind the bookkeeping, so that a failure here leaves a consistent filter)
     if ((s = hist_on_resample(h, block_size))) return s;
     if (check != GPF_CHECK_FALSE || invalid || n_resampled) {
@@ -736,8 +734,8 @@ gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, 
     HIP_TRY(h, hipGetLastError());
     h->cur ^= 1;
     h->epoch += 1;
-    if (method == GPF_REJUVENATE_REWEIGHT) { h->raw_valid = false; h->raw_sum_valid = false; h->max_valid = true; }
-    mutated(h);
+    if (method == GPF_REJUVENATE_REWEIGHT) weights_written(h, true);
+    else mutated(h);                                             // (a plain move: the weights and their summaries stand)
     if (n_accepted) {
         // (move-reweight: every particle of a participating block moves; the per-workgroup counts cover both cases)
         if (method == GPF_REJUVENATE_REWEIGHT && !only_resampled) *n_accepted = (uint64_t)h->n * (uint64_t)n_iters;
@@ -869,8 +867,7 @@ gpf_status gpf_resample_across_blocks(gpf_handle h, int32_t method, int64_t bloc
     const uint32_t E = h->epoch;
     p->epoch = E; p->initialized = true;
     p->pending_gather = false; p->pending_fill = false; p->pending_search = false;
-    p->max_valid = false; p->raw_valid = false; p->raw_sum_valid = false; p->raw_has_q = false; p->raw_q_folded = false;
-    mutated(p);
+    weights_written(p, false);
     double ess = 0.0, M = 0.0;
     if ((s = gpf_effective_sample_size(p, &ess)) || (s = gpf_log_ml_estimate(p, &M))) return fail(h, s, "planner: " + p->err);
     if (ess_out) *ess_out = ess;
@@ -909,9 +906,8 @@ gpf_status gpf_resample_across_blocks(gpf_handle h, int32_t method, int64_t bloc
         std::swap(h->lw, h->lws);
         if (with_par) { std::swap(h->blk_params, h->blk_params_alt); std::swap(h->blk_params_cap, h->blk_params_alt_cap); h->args.blk_params = h->blk_params; }
         if (with_obs) { std::swap(h->blk_obs, h->blk_obs_alt); std::swap(h->blk_obs_cap, h->blk_obs_alt_cap); h->args.blk_obs = h->blk_obs; }
-        h->raw_valid = false; h->raw_sum_valid = false; h->raw_has_q = false; h->raw_q_folded = false; h->max_valid = false;
         h->blk_last = 0;                                         // only_resampled refers to a gpf_resample_blocks of the CURRENT block layout
-        mutated(h);
+        weights_written(h, false);
     }
     // 5. one epoch per accepted call, fired or not (as gpf_resample_blocks)
     h->epoch = E + 1;
@@ -1095,8 +1091,9 @@ static void set_count(gpf_filter* h, int64_t n_new)
     h->n = n_new; h->cfg.n_particles = n_new; h->cfg.n_global = n_new; h->cfg.gid0 = 0;
     if (h->blk_obs_size != 0) h->blk_obs_size = -1;              // per-block observations do not survive a change of the particle count
     h->blk_last = 0;
-    h->raw_valid = false; h->raw_sum_valid = false; h->raw_has_q = false; h->raw_q_folded = false; h->max_valid = false; h->pending_gather = false; h->pending_fill = false;
-    h->pending_packed = false; h->pending_search = false;
+    // (forget(), not weights_written(): the resize family has never counted a mutation -- the views of a resized filter are stale by its generation)
+    h->summary.forget();
+    h->pending_gather = false; h->pending_fill = false; h->pending_packed = false; h->pending_search = false;
 }
 
 gpf_status gpf_n_particles(gpf_handle h, int64_t* out)
@@ -1119,7 +1116,7 @@ static gpf_status resize_optimal(gpf_handle h, int64_t n_new, int32_t check, int
     if ((s = ensure_max(h, pv, true))) return s;
     if ((s = sort_desc(h, pv, n_old))) return s;
     WSum* ws = &h->sc->raw;
-    h->raw_valid = false; h->raw_sum_valid = false;
+    h->summary.drop_sums();                                      // (cdf[0] is about to hold the scan over the sorted order)
     ScanRequest rq;
     rq.order = h->order; rq.max_ready = true;
     if ((s = summarize(h, pv, ws, rq))) return s;
@@ -1187,7 +1184,7 @@ gpf_status gpf_resize(gpf_handle h, int64_t n_new, int32_t method, double priori
     if (priority_alpha == priority_alpha) { pv.alpha = priority_alpha; pv.mode = 1; }
     // fixed-point scale for max(n_old, n_new): both N_old 2^K and n_new 2^K must stay below 2^62
     h->K = fix_K(std::max(n_old, n_new));
-    h->raw_valid = false; h->raw_sum_valid = false;
+    h->summary.drop_sums();                                      // (sums at another K)
     WSum* ws = &h->sc->raw;
     ScanRequest rq;
     rq.producer_max = true;
@@ -1228,8 +1225,7 @@ gpf_status gpf_resize(gpf_handle h, int64_t n_new, int32_t method, double priori
         PrioView post{h->lws, nullptr, 0.0, 0};
         rq.cdf = false;
         if ((s = summarize(h, post, &h->sc->post, rq))) { free_bufs(old); return s; }
-        GPF_LAUNCH(k_apply_post, dim3(grid_for(h, n_new, 8)), dim3(BLOCK), 0, h->stream, h->sc, h->K, h->logN, h->lws, h->lw, n_new);
-        h->max_valid = false;
+        GPF_LAUNCH(k_apply_post, dim3(grid_for(h, n_new, 8)), dim3(BLOCK), 0, h->stream, h->sc, h->K, h->logN, h->lws, h->lw, n_new);      // (the slots describe log_ws: ensure_max said so)
     }
     (void)Kp;
     HIP_TRY(h, hipStreamSynchronize(h->stream));                 // the old buffers are read by the kernels above
@@ -1847,9 +1843,8 @@ gpf_status gpf_checkpoint_load(gpf_handle h, const void* in, int64_t bytes)
     for (int i = 0; i < MAX_STRATA; ++i) h->args.strata[i] = hd.strata[i];
     for (int i = 0; i < 4; ++i) h->args.q[i] = hd.q[i];
     h->blk_obs_size = 0;
-    h->raw_valid = false; h->raw_sum_valid = false; h->max_valid = false; h->raw_has_q = false; h->raw_q_folded = false;
     h->residual_scanned = false; h->push_counted = false; h->gsum_ok = false; h->ch0_offsets = false;
-    mutated(h);
+    weights_written(h, false);
     return GPF_OK;
 }
 

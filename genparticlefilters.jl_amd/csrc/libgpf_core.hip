@@ -210,7 +210,7 @@ gpf_status materialize(gpf_filter* h)
         HIP_TRY(h, hipGetLastError());
         h->cur ^= 1;
         h->pending_packed = false; h->pend_own = false; h->pend_ring = false;
-        h->max_valid = false;
+        h->summary.forget();            // (the commit dropped the sums and counted the mutation; the weights land now, their maximum is in no slot)
         return GPF_OK;
     }
     if (!h->pending_gather) return GPF_OK;
@@ -221,7 +221,7 @@ gpf_status materialize(gpf_filter* h)
     HIP_TRY(h, hipGetLastError());
     h->cur ^= 1;                    // update_refs! (utils.jl:10-15)
     h->pending_gather = false; h->pending_fill = false;
-    h->max_valid = false;           // log-weights are all 0 now
+    h->summary.forget();            // log-weights are all 0 now (the resample dropped the sums and counted the mutation)
     return GPF_OK;
 }
 
@@ -289,29 +289,34 @@ void mutated(gpf_filter* h)
     root->mutations += 1;
     if (h->parent) h->seen_mutations = root->mutations;          // its own change: this view's bookkeeping is already current
 }
+// The log-weights of h were written (or are promised: a deferred gather / commit): every cached summary is forgotten and the mutation is counted.
+// max_in_slots: the writer left their maximum in mslots[mcur] (the propagate, the initialise, the reweight move) -- the others did not.
+void weights_written(gpf_filter* h, bool max_in_slots)
+{
+    h->summary.forget();
+    h->summary.max_produced(max_in_slots);
+    mutated(h);
+}
 
 // the bookkeeping behind an initialise's k_init launch (whole filter or block-wise): parents = 1:N (initialize.jl:43), log_ml_est = 0, nothing pending
 gpf_status after_initialize(gpf_filter* h, int grid)
 {
     h->pending_gather = false; h->pending_fill = false; h->pending_packed = false; h->pending_search = false; h->pending_move = false;
-    h->max_valid = true;
     GPF_LAUNCH(k_iota, dim3(grid), dim3(BLOCK), 0, h->stream, h->anc, h->n);
     HIP_TRY(h, hipMemsetAsync(&h->sc->lml_est, 0, sizeof(double), h->stream));
     HIP_TRY(h, hipGetLastError());
     h->epoch += 1;
-    h->initialized = true; h->has_prev = false; h->raw_valid = false; h->raw_sum_valid = false;
-    mutated(h);
+    h->initialized = true; h->has_prev = false;
+    weights_written(h, true);
     return GPF_OK;
 }
 // ... and behind a propagate that wrote rows[1 - cur] and the log-weights with their maximum (update_refs!, utils.jl:10-15)
 void after_propagate(gpf_filter* h)
 {
-    h->max_valid = true;
     h->cur ^= 1;
     h->epoch += 1;
     h->has_prev = true;
-    h->raw_valid = false; h->raw_sum_valid = false;
-    mutated(h);
+    weights_written(h, true);
 }
 
 // A view re-derives its aliased pointers from the parent on every call (the parent may have swapped its row buffers),
@@ -346,7 +351,7 @@ gpf_status view_enter(gpf_filter* v)
     v->has_prev = p->has_prev;
     v->initialized = true;
     if (v->seen_mutations != p->mutations) {                     // the aliased weights changed behind this view's back
-        v->raw_valid = false; v->raw_sum_valid = false; v->raw_has_q = false; v->raw_q_folded = false; v->max_valid = false;
+        v->summary.forget();
         v->seen_mutations = p->mutations;
     }
     return GPF_OK;
@@ -372,7 +377,7 @@ gpf_status view_exit(gpf_filter* v)
     }
     p->epoch = v->epoch;
     p->has_prev = p->has_prev || v->has_prev;
-    p->raw_valid = false; p->raw_sum_valid = false; p->max_valid = false; p->raw_has_q = false; p->raw_q_folded = false;
+    p->summary.forget();                                         // (the view's own transition counted the mutation)
     return GPF_OK;
 }
 
@@ -397,6 +402,15 @@ gpf_status set_obs(gpf_filter* h, const double* obs, int n_obs)
     return GPF_OK;
 }
 
+// the bookkeeping behind a stand-alone move kernel (finish_move, the eager gpf_rejuvenate): it wrote rows[1 - cur]; with a pending resample gather
+// riding on it (fused_gather) the log-weights are all 0 now (resample.jl:195); a reweight move wrote them itself, with their maximum
+static void after_move(gpf_filter* h, bool reweight, bool fused_gather)
+{
+    h->cur ^= 1;
+    if (fused_gather) { h->pending_gather = false; h->pending_fill = false; }
+    if (reweight || fused_gather) weights_written(h, reweight);
+    else mutated(h);                                             // (a plain move: the rows changed, the weights and their summaries stand)
+}
 // a pending lazy move is wanted as a state after all: the stand-alone k_move with the arguments and the epoch of its pf_rejuvenate! call
 gpf_status finish_move(gpf_filter* h)
 {
@@ -411,10 +425,7 @@ gpf_status finish_move(gpf_filter* h)
     });
     if (s) return s;
     HIP_TRY(h, hipGetLastError());
-    h->cur ^= 1;                                                 // (the epoch was consumed at the call)
-    if (fused_gather) { h->pending_gather = false; h->pending_fill = false; h->max_valid = false; }
-    if (h->pm_method == GPF_REJUVENATE_REWEIGHT) { h->raw_valid = false; h->raw_sum_valid = false; h->max_valid = true; }
-    mutated(h);
+    after_move(h, h->pm_method == GPF_REJUVENATE_REWEIGHT, fused_gather);   // (the epoch was consumed at the call)
     return GPF_OK;
 }
 // which models / sizes k_step_search covers: the key-table regime of the search (up to 2.5 M particles)
@@ -716,7 +727,7 @@ gpf_status gpf_step_ess(gpf_handle h, const double* obs, int32_t n_obs, double e
     const double thr = ess_frac * (double)h->n;
     static const bool spec_off = getenv("GPF_STEP_SPECULATE") && !strcmp(getenv("GPF_STEP_SPECULATE"), "0");   // (A/B measurements, tests: the plain sequence)
     const bool fast = !spec_off && !h->parent && !h->hist_on && h->cfg.n_global == h->n && !h->pending_packed && !h->pending_gather && !h->pending_fill &&
-                      !h->pending_search && !h->raw_valid && !h->raw_sum_valid && h->blk_obs_size == 0 && sum_host_ok(h) &&
+                      !h->pending_search && !h->summary.raw_valid && !h->summary.raw_sum_valid && h->blk_obs_size == 0 && sum_host_ok(h) &&
                       n_obs == model_obs_dim(h->cfg.model) && obs != nullptr;
     if (!fast) {
         // the host-decided sequence (sub-states, shards, trajectory stores, a resample still pending, summaries already at hand, ...)
@@ -745,8 +756,9 @@ gpf_status gpf_step_ess(gpf_handle h, const double* obs, int32_t n_obs, double e
     if ((s = sum_host_fold(h, &thr, &go))) return undo(s);
     if (ess_out) {
         uint64_t hi, lo;
-        normalise_Q(h->sum_cache, hi, lo);
-        *ess_out = h->sum_cache.flags ? std::nan("") : ess_from(h->sum_cache.S, hi, lo);
+        const WSum& w = h->summary.sum_cache;
+        normalise_Q(w, hi, lo);
+        *ess_out = w.flags ? std::nan("") : ess_from(w.S, hi, lo);
     }
     if (!go) {
         speculative_step_done(h, true);                          // the speculative propagate WAS the step's pf_update!
@@ -858,11 +870,8 @@ static gpf_status rejuvenate_impl(gpf_handle h, int32_t method, int32_t n_iters,
     });
     if (s) return s;
     HIP_TRY(h, hipGetLastError());
-    h->cur ^= 1;
     h->epoch += 1;
-    if (fused_gather) { h->pending_gather = false; h->pending_fill = false; h->max_valid = false; }   // log-weights are all 0 now (resample.jl:195)
-    if (method == GPF_REJUVENATE_REWEIGHT) { h->raw_valid = false; h->raw_sum_valid = false; h->max_valid = true; }
-    mutated(h);
+    after_move(h, method == GPF_REJUVENATE_REWEIGHT, fused_gather);
     if ((s = view_exit(h))) return s;
     if (n_accepted) {
         if (method == GPF_REJUVENATE_REWEIGHT) *n_accepted = (uint64_t)h->n * (uint64_t)n_iters;     // every particle moves (rejuvenate.jl:81-86)
@@ -945,15 +954,13 @@ gpf_status gpf_set_log_weights(gpf_handle h, const double* lw, int64_t n)
     if (!lw || n != h->n) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad input array");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     if (h->pending_move) { gpf_status s = finish_move(h); if (s) return s; }
-    if (h->parent) { gpf_status s = view_enter(h); if (s) return s; h->parent->raw_valid = false; h->parent->raw_sum_valid = false; h->parent->max_valid = false; }
+    if (h->parent) { gpf_status s = view_enter(h); if (s) return s; h->parent->summary.forget(); }
     { gpf_status s = materialize(h); if (s) return s; }
-    h->max_valid = false;
+    weights_written(h, false);                                   // (before the copy: a failure below leaves nothing cached about half-written weights)
     HIP_TRY(h, hipMemcpyAsync(h->lw, lw, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (h->parent && h->view_step != 1) { gpf_status s = view_exit(h); if (s) return s; }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->raw_valid = false; h->raw_sum_valid = false;
     h->initialized = true;
-    mutated(h);
     return GPF_OK;
 }
 

@@ -84,13 +84,13 @@ gpf_status resample_device_setup(gpf_filter* h)
 // they are current (use_producer_max), else one k_max_partial pass over pv
 gpf_status ensure_max(gpf_filter* h, const PrioView& pv, bool use_producer_max)
 {
-    if (use_producer_max && h->max_valid) return GPF_OK;
+    if (use_producer_max && h->summary.max_valid) return GPF_OK;
     const int gp = (int)std::min<int64_t>(MAX_PARTIALS, (h->n + BLOCK - 1) / BLOCK);
     gpf_status s = timed(h, GPF_K_MAX, [&] {
         GPF_LAUNCH(k_max_partial, dim3(gp), dim3(BLOCK), 0, h->stream, pv, h->n, next_slots(h));
     });
     if (s) return s;
-    h->max_valid = use_producer_max;           // (otherwise the slots describe pv, which may not be the raw log-weights)
+    h->summary.max_produced(use_producer_max);  // (otherwise the slots describe pv, which may not be the raw log-weights)
     return GPF_OK;
 }
 // pv: the weights to summarise into `slot`, as rq asks
@@ -131,14 +131,12 @@ gpf_status ensure_raw(gpf_filter* h, bool want_q, bool* published)
     bool self_published = false; if (published) *published = false;
     gpf_status s = materialize(h);
     if (s) return s;
-    if (h->raw_valid && (!want_q || h->raw_has_q)) return GPF_OK;
+    if (h->summary.raw_valid && (!want_q || h->summary.raw_has_q)) return GPF_OK;
     ScanRequest rq;
     rq.producer_max = true; rq.q = want_q;
     rq.offsets = h->offsets_hint;                                // a resample that follows may reuse this CDF
     if ((s = summarize(h, raw_view(h), &h->sc->raw, rq, &self_published))) return s;
-    h->raw_valid = true;
-    h->raw_has_q = want_q;
-    h->raw_q_folded = self_published;                            // (a publishing scan folds the limbs itself; its partials are tagged words)
+    h->summary.scanned(want_q, self_published);                  // (a publishing scan folds the limbs itself; its partials are tagged words)
     if (published) *published = self_published;
     return GPF_OK;
 }
@@ -174,8 +172,8 @@ gpf_status ensure_raw_summary(gpf_filter* h, bool want_q, bool* done)
     gpf_status s = materialize(h);
     if (s) return s;
     static const bool off = getenv("GPF_SUM_REDUCE") && !strcmp(getenv("GPF_SUM_REDUCE"), "0");          // (A/B: always the scan)
-    if (off || (h->raw_valid && (!want_q || h->raw_has_q))) return GPF_OK;                              // (a scan's summary is there: use it)
-    if (h->raw_sum_valid) { *done = true; return GPF_OK; }
+    if (off || (h->summary.raw_valid && (!want_q || h->summary.raw_has_q))) return GPF_OK;                              // (a scan's summary is there: use it)
+    if (h->summary.raw_sum_valid) { *done = true; return GPF_OK; }
     // GPF_SUM_REDUCE=device: the reduction whose workgroup 0 folds the partials on the device (k_sum_reduce) instead of the host (k_sum_host)
     static const bool device_fold = getenv("GPF_SUM_REDUCE") && !strcmp(getenv("GPF_SUM_REDUCE"), "device");
     const int hgrid = (int)std::max<int64_t>(1, std::min<int64_t>((h->n + SH_TILE - 1) / SH_TILE, (int64_t)h->n_cu));
@@ -204,15 +202,13 @@ gpf_status ensure_raw_summary(gpf_filter* h, bool want_q, bool* done)
     HIP_TRY(h, hipGetLastError());
     WSum w{};
     if ((s = read_published_summary(h, w))) return s;
-    h->sum_cache = w;                                            // (m is not published by this kernel: the log-ML getter reads the device block)
-    h->sum_on_host = false;
-    h->raw_sum_valid = true;
+    h->summary.reduced(w, false);                                // (m is not published by this kernel: the log-ML getter reads the device block)
     *done = true;
     return GPF_OK;
 }
 
 // k_sum_host: the raw weights' {maximum, flags, S, sum q^2} with the HOST as the folder.  sum_host_launch enqueues it, sum_host_fold waits for
-// this launch's lines and leaves the summary in h->sum_cache (sum_on_host, raw_sum_valid).  thr != nullptr (gpf_step_ess): the gated
+// this launch's lines and leaves the summary with the host (WeightSummary::reduced).  thr != nullptr (gpf_step_ess): the gated
 // form -- the last workgroup also folds on the device and leaves the verdict ESS < *thr in sc->gate_go for the launch behind it; the fold
 // then returns that verdict too (after cross-checking it against the host's own).
 bool sum_host_ok(const gpf_filter* h)
@@ -282,9 +278,7 @@ gpf_status sum_host_fold(gpf_filter* h, const double* thr, int* go_out)
     for (int k = 0; k < 4; ++k) w.Ql[k] = t[2 + k];
     const uint64_t mb = flags_m[1] | (flags_m[2] << 32);
     memcpy(&w.m, &mb, sizeof(double));
-    h->sum_cache = w;                                        // (sc->raw on the device is NOT updated: the getters read this copy)
-    h->sum_on_host = true;
-    h->raw_sum_valid = true;
+    h->summary.reduced(w, true);                             // (sc->raw on the device is NOT updated: the getters read this copy)
     if (thr) {
         uint64_t hi, lo;
         normalise_Q(w, hi, lo);
@@ -664,16 +658,17 @@ gpf_status resample_impl(gpf_filter* h, int method, PrioView pv, int sort_partic
     // nothing else of the weight scan -- it converts the weights itself (k_scan_residual2<DIRECT>) and the weight scan is not run
     static const bool no_direct = getenv("GPF_RESIDUAL_DIRECT") && !strcmp(getenv("GPF_RESIDUAL_DIRECT"), "0");
     ResidDirect rdirect{};
-    const bool resid_direct = !no_direct && method == GPF_RESAMPLE_RESIDUAL && pv.mode == 0 && !h->raw_valid && h->raw_sum_valid && h->sum_on_host;
+    const bool resid_direct = !no_direct && method == GPF_RESAMPLE_RESIDUAL && pv.mode == 0 && !h->summary.raw_valid && h->summary.raw_sum_valid && h->summary.sum_on_host;
     int direct_flags = 0;
     if (resid_direct) {
-        rdirect = ResidDirect{h->lw, h->sum_cache.m, h->sum_cache.flags, h->K, h->sum_cache.S, &h->sc->raw, nullptr, 0, 0};
-        direct_flags = h->sum_cache.flags;
+        const WSum& hs = h->summary.sum_cache;
+        rdirect = ResidDirect{h->lw, hs.m, hs.flags, h->K, hs.S, &h->sc->raw, nullptr, 0, 0};
+        direct_flags = hs.flags;
         ws = &h->sc->raw;
     } else
     if (pv.mode == 0) {
         ws = &h->sc->raw;
-        if (!h->raw_valid || sorted || (need_off && !h->ch0_offsets)) {
+        if (!h->summary.raw_valid || sorted || (need_off && !h->ch0_offsets)) {
             rq.producer_max = true; rq.sp = gammas_pending ? &h->sp_job : nullptr;
             if ((s = summarize(h, pv, ws, rq))) return s;
             published = need_sync; gammas_pending = false;
@@ -684,8 +679,7 @@ gpf_status resample_impl(gpf_filter* h, int method, PrioView pv, int sort_partic
         if ((s = summarize(h, pv, ws, rq))) return s;
         published = need_sync; gammas_pending = false;
     }
-    h->raw_valid = false; h->raw_sum_valid = false;                                        // cdf[0] no longer the plain raw CDF / lw about to change
-    h->raw_q_folded = false;
+    h->summary.drop_sums();                                      // cdf[0] no longer the plain raw CDF / lw about to change
     if (need_sync) {
         int flags;
         if (published) {
@@ -773,10 +767,9 @@ gpf_status resample_impl(gpf_filter* h, int method, PrioView pv, int sort_partic
             if ((s = summarize(h, post, &h->sc->post, sums_only))) return s;
             GPF_LAUNCH(k_view_apply_post, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->sc, h->K, h->lws, h->lw, h->n);
         }
-        h->max_valid = false;
+        weights_written(h, false);
         HIP_TRY(h, hipGetLastError());
         h->epoch += 1;
-        mutated(h);
         return view_exit(h);
     }
     if (pv.mode == 0) {
@@ -784,7 +777,6 @@ gpf_status resample_impl(gpf_filter* h, int method, PrioView pv, int sort_partic
         // gather), any other consumer calls materialize().  Log-weights are 0 (resample.jl:195).
         h->pending_gather = true;
         h->pending_fill = local;
-        h->max_valid = false;
     } else {
         // gather + update_weights! with priorities (resample.jl:60,198-200), update_refs! (utils.jl:10-15)
         s = timed(h, GPF_K_GATHER, [&] { launch_gather(h, pv, h->lws); });
@@ -793,11 +785,10 @@ gpf_status resample_impl(gpf_filter* h, int method, PrioView pv, int sort_partic
         PrioView post{h->lws, nullptr, 0.0, 0};
         if ((s = summarize(h, post, &h->sc->post, sums_only))) return s;
         GPF_LAUNCH(k_apply_post, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->sc, h->K, h->logN, h->lws, h->lw, h->n);
-        h->max_valid = false;
     }
+    weights_written(h, false);                                   // (deferred or done: the new weights' maximum is in no slot)
     HIP_TRY(h, hipGetLastError());
     h->epoch += 1;
-    mutated(h);
     return GPF_OK;
 }
 
@@ -828,8 +819,8 @@ gpf_status gpf_resample_local(gpf_handle h, int32_t method, int32_t sort_particl
     struct Scope {                                               // the filter as its own population for the duration of the call
         gpf_filter* h; int K; double logN; int64_t ng;
         explicit Scope(gpf_filter* f) : h(f), K(f->K), logN(f->logN), ng(f->cfg.n_global)
-        { h->K = fix_K(h->n); h->logN = log_((double)h->n); h->cfg.n_global = h->n; h->raw_valid = false; h->raw_sum_valid = false; h->raw_has_q = false; h->raw_q_folded = false; }
-        ~Scope() { h->K = K; h->logN = logN; h->cfg.n_global = ng; h->raw_valid = false; h->raw_sum_valid = false; h->raw_has_q = false; h->raw_q_folded = false; }
+        { h->K = fix_K(h->n); h->logN = log_((double)h->n); h->cfg.n_global = h->n; h->summary.drop_sums(); }
+        ~Scope() { h->K = K; h->logN = logN; h->cfg.n_global = ng; h->summary.drop_sums(); }
     } scope(h);
     return resample_impl(h, method, raw_view(h), sort_particles, check, invalid, true);
 }
@@ -853,7 +844,7 @@ gpf_status gpf_effective_sample_size(gpf_handle h, double* out)
     WSum w{};
     bool reduced = false;
     if ((s = ensure_raw_summary(h, true, &reduced))) return s;
-    if (reduced) w = h->sum_cache;                                // S and sum q^2 from the reduction: no CDF was written
+    if (reduced) w = h->summary.sum_cache;                                // S and sum q^2 from the reduction: no CDF was written
     else {
         bool published = false;
         if ((s = ensure_raw(h, true, &published))) return s;
@@ -861,9 +852,9 @@ gpf_status gpf_effective_sample_size(gpf_handle h, double* out)
             // the scan of this call publishes {flags, S, limbs of sum q^2} itself: wait for its ticket, no publish launch
             if ((s = read_published_summary(h, w))) return s;
         } else {
-            const bool fold = !h->raw_q_folded;                      // the scan blocks' limb partials of sum q^2: folded by the publish kernel
+            const bool fold = !h->summary.raw_q_folded;                      // the scan blocks' limb partials of sum q^2: folded by the publish kernel
             if ((s = fetch_scalars(h, fold))) return s;
-            h->raw_q_folded = true;
+            h->summary.q_folded();
             w = h->h_sc->raw;
         }
     }
@@ -883,7 +874,7 @@ gpf_status gpf_log_ml_estimate(gpf_handle h, double* out)
     if ((s = ensure_raw_summary(h, false, &reduced))) return s;  // (S and the maximum are all it needs: no CDF)
     if (!reduced && (s = ensure_raw(h))) return s;
     if ((s = fetch_scalars(h))) return s;
-    const WSum& w = reduced && h->sum_on_host ? h->sum_cache : h->h_sc->raw;   // (k_sum_host leaves {m, flags, S} with the host, not in the device block)
+    const WSum& w = reduced && h->summary.sum_on_host ? h->summary.sum_cache : h->h_sc->raw;   // (k_sum_host leaves {m, flags, S} with the host, not in the device block)
     double base = h->h_sc->lml_est;
     if (h->parent) {                                             // source.log_ml_est (utils.jl:174-178)
         if ((s = fetch_scalars(h->parent))) { h->err = h->parent->err; return s; }

@@ -66,14 +66,14 @@ static gpf_status shard_max_slots(gpf_handle h, const ShardCall& c)
 {
     gpf_status s;
     if ((s = materialize(h))) return s;
-    if (!h->max_valid || c.view) {                               // (the engine's prioritised resample summarises alpha lw and log_ws too)
+    if (!h->summary.max_valid || c.view) {                              // (the engine's prioritised resample summarises alpha lw and log_ws too)
         const PrioView pv = c.view ? *c.view : raw_view(h);
         const int gp = (int)std::min<int64_t>(MAX_PARTIALS, (h->n + BLOCK - 1) / BLOCK);
         s = timed(h, GPF_K_MAX, [&] {
             GPF_LAUNCH(k_max_partial, dim3(gp), dim3(BLOCK), 0, h->stream, pv, h->n, next_slots(h));
         });
         if (s) return s;
-        h->max_valid = !c.view;
+        h->summary.max_produced(!c.view);
     }
     return GPF_OK;
 }
@@ -135,7 +135,7 @@ static gpf_status shard_weight_scan(gpf_handle h, ShardCall& c, const double* mf
         if ((s = scan_launch_shard(h, 3, in, (int)G, slot, rq, reinterpret_cast<uint64_t*>(out5), mf_all, ex))) return s;
     }
     HIP_TRY(h, hipGetLastError());
-    h->raw_valid = false; h->raw_sum_valid = false;            // sc->raw holds the GLOBAL max but no sum: not the unsharded summary
+    h->summary.drop_sums();                                    // sc->raw holds the GLOBAL max but no sum: not the unsharded summary
     return GPF_OK;
 }
 gpf_status gpf_shard_weight_scan(gpf_handle h, const double* mf_all, int32_t G, int32_t want_q, int64_t* out5) { ShardCall c; gpf_status s = shard_ready(h); return s ? s : shard_weight_scan(h, c, mf_all, G, want_q, out5); }
@@ -176,7 +176,7 @@ static gpf_status shard_residual_scan_direct(gpf_handle h, const ShardCall& c, c
     GPF_LAUNCH(k_export_residual, dim3(1), dim3(64), 0, h->stream, h->sc, out2, mb_begin(h, c.engine, MB_CR), h->shard_counts, (int)(2 * MAX_SHARDS * COUNT_STRIDE));
     HIP_TRY(h, hipGetLastError());
     h->residual_scanned = true;
-    h->raw_valid = false; h->raw_sum_valid = false;
+    h->summary.drop_sums();                                      // (as behind the weight scan this form replaces)
     return GPF_OK;
 }
 
@@ -408,6 +408,21 @@ static gpf_status shard_push(gpf_handle h, const ShardCall& c, int32_t method, c
 gpf_status gpf_shard_push(gpf_handle h, int32_t method, const int64_t* tot_all, const int64_t* cr_all, int32_t G, int32_t me, const int64_t* bounds, int64_t capacity, double* packed_out)
 { gpf_status s = shard_ready(h); return s ? s : shard_push(h, ShardCall{}, method, tot_all, cr_all, G, me, bounds, capacity, packed_out); }
 
+// a sharded resample is over: the phases of the next one start from nothing
+static void shard_phases_done(gpf_filter* h) { h->residual_scanned = false; h->push_counted = false; }
+// Arm the pending commit (shard_commit, shard_commit_ring; the caller has said where the entries sit).  Deferred like the single-GPU gather
+// (DESIGN.md §4.4): the next gpf_update propagates the entries straight out of the exchange buffer / the window into their slots
+// (k_step<PACKED>); any other consumer scatters first (materialize()).  mf_all / tot_all (and the packed buffer) must stay alive and
+// unchanged until then (the caller keeps them until the next commit).
+static void arm_commit(gpf_filter* h, const ShardCall& c, const double* mf_all, const int64_t* tot_all, int G)
+{
+    h->pending_packed = true;
+    h->pend_mf = mf_all; h->pend_tot = tot_all; h->pend_G = G;
+    h->pend_mailbox = h->mb_active && c.engine;
+    h->epoch += 1;
+    shard_phases_done(h);
+    weights_written(h, false);
+}
 static gpf_status shard_commit(gpf_handle h, const ShardCall& c, const double* packed, int64_t m, const double* mf_all, const int64_t* tot_all, int32_t G)
 {
     if (!packed || !mf_all || !tot_all || G < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad arguments");
@@ -415,18 +430,8 @@ static gpf_status shard_commit(gpf_handle h, const ShardCall& c, const double* p
     h->pend_ring = false;
     h->pend_own = c.own; h->pend_m = m;                          // (own-direct engine: m entries from the other shards, the rest through h->anc)
     h->pend_own_range = c.own && c.own_range;
-    // Deferred like the single-GPU gather: the next gpf_update propagates the entries straight out of
-    // the exchange buffer into their slots (k_step<PACKED>); any other consumer scatters first (materialize()).
-    // packed / mf_all / tot_all must stay alive and unchanged until then (the caller keeps them until the next commit).
-    h->pending_packed = true;
-    h->pend_packed = packed; h->pend_mf = mf_all; h->pend_tot = tot_all; h->pend_G = G;
-    h->pend_mailbox = h->mb_active && c.engine;
-    h->epoch += 1;
-    h->raw_valid = false; h->raw_sum_valid = false;
-    h->max_valid = false;
-    h->residual_scanned = false;
-    h->push_counted = false;
-    mutated(h);
+    h->pend_packed = packed;
+    arm_commit(h, c, mf_all, tot_all, G);
     return GPF_OK;
 }
 gpf_status gpf_shard_commit(gpf_handle h, const double* packed, int64_t m, const double* mf_all, const int64_t* tot_all, int32_t G) { gpf_status s = shard_ready(h); return s ? s : shard_commit(h, ShardCall{}, packed, m, mf_all, tot_all, G); }
@@ -1126,8 +1131,7 @@ static gpf_status shard_sorted_plan(gpf_filter* h, const ShardCall& c, int G, in
     // the planner IS the unsharded filter as far as its weights go: same seed, same epoch, same K = fix_K(n_global)
     p->epoch = h->epoch;
     p->pending_gather = false; p->pending_search = false;
-    p->max_valid = false; p->raw_valid = false; p->raw_sum_valid = false;
-    mutated(p);
+    weights_written(p, false);
     s = resample_impl(p, GPF_RESAMPLE_STRATIFIED, raw_view(p), 1, GPF_CHECK_FALSE, nullptr);   // (validity was decided on the gathered flags)
     p->pending_gather = false;                                    // (its ancestors are all this call wants: the planner has no rows worth gathering)
     if (s) return fail(h, s, "planner: " + p->err);
@@ -1160,16 +1164,9 @@ static gpf_status shard_sorted_push(gpf_filter* h, const ShardCall& c, int G, in
 static gpf_status shard_commit_ring(gpf_handle h, const ShardCall& c, const double* mf_all, const int64_t* tot_all, int G)
 {
     h->pend_own = true; h->pend_m = 0; h->pend_own_range = c.own_range;   // (else: the own hits are the slots with anc >= 0, k_search_own)
-    h->pending_packed = true;
-    h->pend_packed = nullptr; h->pend_mf = mf_all; h->pend_tot = tot_all; h->pend_G = G;
-    h->pend_mailbox = h->mb_active && c.engine;
+    h->pend_packed = nullptr;
     h->pend_ring = true; h->pend_ring_seq = h->ring_seq;
-    h->epoch += 1;
-    h->raw_valid = false; h->raw_sum_valid = false;
-    h->max_valid = false;
-    h->residual_scanned = false;
-    h->push_counted = false;
-    mutated(h);
+    arm_commit(h, c, mf_all, tot_all, G);
     return GPF_OK;
 }
 
@@ -1406,8 +1403,8 @@ static gpf_status shard_resample_impl(gpf_handle h, int32_t method, double prior
                mb_wait(h, c.engine, MB_TOT));
     HIP_TRY(h, hipGetLastError());
     h->epoch += 1;
-    h->raw_valid = false; h->raw_sum_valid = false; h->max_valid = false; h->residual_scanned = false; h->push_counted = false;
-    mutated(h);
+    shard_phases_done(h);
+    weights_written(h, false);
     return GPF_OK;
 }
 
@@ -1587,7 +1584,7 @@ gpf_status shard_global_summary_launch(gpf_filter* h, const ShardCall& c, double
     if ((s = shard_sum_launch(h, ss, &ok))) return s;
     if (!ok) return fail(h, GPF_ERR_STATE, "sharded summary: the filter is too large for the reduction's tagged partials");   // (the rounds are begun: no way back to the scan)
     h->cur_mf_all = ss.mf_all; h->cur_tot_all = ss.tot_all;
-    h->raw_valid = false; h->raw_sum_valid = false;              // (sc->raw holds this shard's sums under the GLOBAL maximum: not the unsharded summary)
+    h->summary.drop_sums();                                      // (sc->raw holds this shard's sums under the GLOBAL maximum: not the unsharded summary)
     h->gsum_ok = false; h->gsum_mut = h->mutations; h->gsum_mf_seq = h->mb_cur[MB_MF]; h->gsum_tot_seq = h->mb_cur[MB_TOT];   // (valid once the host has read it)
     *done = true;
     return GPF_OK;
