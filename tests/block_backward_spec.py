@@ -111,8 +111,8 @@ def backward(o, name, P, store, seed, epoch, n_samples, lo=1, hi=None, trans=Tru
 class StoreLoop:
     """initialise -> (resample blocks -> update)* of the plain block-wise filter on the CPU oracle, recorded into a Store"""
 
-    def __init__(self, o, model, n, bs, seed, keep_prev=False):
-        self.L = cs.ConditionalLoop(o, model, n, bs, seed, keep_prev)
+    def __init__(self, o, model, n, bs, seed, keep_prev=False, param_sets=None, assign=None):
+        self.L = cs.ConditionalLoop(o, model, n, bs, seed, keep_prev, param_sets=param_sets, assign=assign)
         self.store = Store(n, bs, model.dim)
         self.d = model.dim
 

@@ -1050,3 +1050,262 @@ def optimal_resize_cases():
 def lse(lw):
     m = np.max(lw)
     return m + math.log(np.exp(lw - m).sum())
+
+
+# ------------------------------------------------------------------------------------------- ancestor sampling, backward simulation, smoothing
+# tests/test_hp_block_smoothing.py (the NumPy restatements on the CPU oracle's filter) and tests/test_gpu_hp_block_smoothing.py (the device) drive
+# these three with plain arrays: the Store of tests/block_backward_spec.py filled from what a caller sees, the seed, the epoch and the outputs
+# of the implementation under test.  Who produced the outputs is unknown here.  Every tolerance is an E bound of tests/hp_weights.py.
+class _Worst:
+    """the worst err / bound per quantity of ONE call of a check, printed when the call ends (profiles/hp_block_smoothing.md)"""
+
+    def __init__(self):
+        self.by = {}
+
+    def add(self, what, got, want: E):
+        if want.e > 0.0 and np.isfinite(got):
+            d, t = hp.differs(got, want)
+            self.by[what] = max(self.by.get(what, 0.0), d / t)
+
+    def show(self, label, left=None):
+        und = "" if left is None else f", undecidable draws {sum(left.values())} (most per block and step {max(left.values(), default=0)})"
+        print(f"{label}: worst err / bound {({k: round(r, 3) for k, r in self.by.items()})}{und}")
+
+
+def _span(n, bs, b):
+    return b * bs, min((b + 1) * bs, n)
+
+
+def smoothing_guard(n, K, e_max):
+    """sum_guard for weights formed from inexact exponents: the counts' N 2^-K as there, plus the relative error expm1(2 e_max) that an absolute
+    error e_max of the exponents (and of their maximum) is of every weight, the same factor 64 for a second moment"""
+    return max(MEDIAN_REL_TOL, 64.0 * (n * 2.0 ** -K + np.expm1(2.0 * e_max)))
+
+
+def check_logtrans(v, refs, bs, blocks, rows, x_ref, obs, got, label):
+    """block_ancestor_log_weights with log_weights = 0 is logtrans itself, up to the terms free of xp that an implementation may drop: over a
+    block's particles the intervals [full_i - got_i +- e_i] must share a point (full: the complete Gen log-density, e_i: the derived bound of
+    Ref.logtrans).  -Inf (line_model: another slope) is exact.  Returns the worst (max lower end - min upper end) / (sum of the two bounds)."""
+    rows, got = np.asarray(rows, np.float64), np.asarray(got, np.float64)
+    worst = 0.0
+    for b in blocks:
+        i0, i1 = _span(len(got), bs, b)
+        lo_i = hi_i = None
+        for i in range(i0, i1):
+            d = len(x_ref[b])
+            full, part = refs[b].logtrans(list(rows[i, :d]), list(x_ref[b]), obs[b], full=True), refs[b].logtrans(list(rows[i, :d]), list(x_ref[b]), obs[b])
+            if full.v == -hp.M.inf:
+                v.exact(f"{label}: logtrans of an impossible transition", i, got[i], -np.inf)
+                continue
+            if not np.isfinite(got[i]):
+                v.bad.append((f"{label}: logtrans", i, float(got[i]), hp.M.nstr(part.v, 20), None, part.e))
+                continue
+            v.tols.append(hp.rel_tol(part))
+            c = full.v - hp.mpf(float(got[i]))
+            if lo_i is None or c - part.e > lo_i[0]:
+                lo_i = (c - part.e, i, part.e)
+            if hi_i is None or c + part.e < hi_i[0]:
+                hi_i = (c + part.e, i, part.e)
+        if lo_i is not None:
+            gap, room = float(lo_i[0] - hi_i[0]), lo_i[2] + hi_i[2]
+            worst = max(worst, gap / room + 1.0 if room > 0.0 else 0.0)     # 0: the two extreme centres coincide, 1: the intervals just touch
+            if gap > 0:
+                v.bad.append((f"{label}: block {b}: no common constant", (lo_i[1], hi_i[1]), float(got[lo_i[1]]), float(got[hi_i[1]]), gap, room))
+    print(f"{label}: worst err / bound {round(worst, 3)}")
+    return worst
+
+
+def check_ancestor(v, refs, bs, blocks, rows, lw, x_ref, obs, seed, epoch, resampled, parents, label):
+    """a_0 of pf_resample_blocks(..., conditional=True, reference=, observations=): rows / lw the state BEFORE the call, parents / resampled after
+    it.  Slot 0 of a block that resampled holds parent a_0 + 1; the decidable draws equal hw.ancestor_draw, a -Inf or flushed candidate is never
+    drawn, invalid ancestor weights give a_0 = 0.  A block that did not resample drew nothing and is left out of the result: the caller asserts
+    which blocks it expects.  Returns {block: undecidable draws}."""
+    rows, lw, left = np.asarray(rows, np.float64), np.asarray(lw, np.float64), {}
+    for b in blocks:
+        if not resampled[b]:
+            continue
+        i0, i1 = _span(len(lw), bs, b)
+        d = len(x_ref[b])
+        got = int(parents[i0]) - 1
+        a, und, sm = hw.ancestor_draw(refs[b], lw[i0:i1], rows[i0:i1, :d], x_ref[b], obs[b], seed, epoch, i0)
+        left[b] = int(und)
+        if sm is hw.FALLBACK:
+            v.exact(f"{label}: a_0 under invalid ancestor weights", b, got, 0)
+            continue
+        if not 0 <= got < i1 - i0 or sm.dead[got]:
+            v.bad.append((f"{label}: a_0 is no candidate of weight", b, got, a, None, 0.0))
+        elif not und:
+            v.exact(f"{label}: a_0", b, got, a)
+    _Worst().show(label, left)
+    assert all(k <= MAX_UNDECIDABLE for k in left.values()), (label, left)
+    return left
+
+
+def check_backward(v, refs, store, blocks, seed, epoch, idx, label):
+    """indices [B, n_samples, T] (1-based, global) of block_backward_trajectories(..., return_indices=True) over all T steps of `store`, the call
+    made under `epoch`: step T against the categorical draw hw.multinomial, every transition against hw.backward_step GIVEN the particle the
+    implementation holds at the step above.  Returns {(block, step): undecidable draws}."""
+    T, bs, n = store.steps, store.bs, store.n
+    idx, left = np.asarray(idx), {}
+    ns = idx.shape[1]
+    lwT = np.asarray(store.lw[T - 1], np.float64)
+    maps = {s: store.step_map(s) for s in range(2, T + 1)}
+    for b in blocks:
+        b0, b1 = _span(n, bs, b)
+        if np.isnan(lwT[b0:b1]).any() or (lwT[b0:b1] == np.inf).any():
+            for j in range(ns):
+                for s in range(T):
+                    v.exact(f"{label}: index of a NaN block", (b, j, s), idx[b, j, s], 0)
+            continue
+        sm = hw.Softmax(lwT[b0:b1])
+        left[(b, T)] = hw.check_ancestors(hw.multinomial(sm, seed, epoch, ns, slot0=b * ns), idx[b, :, T - 1] - 1 - b0, sm, f"{label}: block {b} step T")
+        for s in range(T - 1, 0, -1):                                           # the step being drawn; the held particle is of step s + 1
+            cache, und_s = {}, 0
+            for j in range(ns):
+                p, got = int(idx[b, j, s]) - 1, int(idx[b, j, s - 1]) - 1
+                pm = int(maps[s + 1][p])
+                c0, c1 = _span(n, bs, pm // bs)
+                a, und, sm = hw.backward_step(refs[b], store.lw[s - 1][c0:c1], store.x(s)[c0:c1], store.x(s + 1)[p], store.obs[s][p // bs], seed, epoch + (T - s),
+                                              b * ns + j, sm=cache.get(p))
+                cache[p] = sm
+                if sm is hw.FALLBACK:
+                    v.exact(f"{label}: a held particle no candidate leads to takes its recorded parent", (b, j, s), got, pm)
+                    continue
+                if not c0 <= got < c1 or sm.dead[got - c0]:
+                    v.bad.append((f"{label}: the drawn index is no candidate of weight", (b, j, s), got, c0 + a, None, 0.0))
+                elif und:
+                    und_s += 1
+                else:
+                    v.exact(f"{label}: backward index", (b, j, s), got, c0 + a)
+            left[(b, s)] = und_s
+    _Worst().show(label, left)
+    assert all(k <= MAX_UNDECIDABLE for k in left.values()), (label, left)
+    return left
+
+
+def check_smooth(v, refs, store, blocks, mean, var, weights, lineage, label, lo=None):
+    """mean, var [B, T, d], weights [B, T, bs], lineage [B, T] of block_smoothed_moments(..., return_weights=True, return_blocks=True) over all T
+    steps of `store`: W_T against the block's normalised weights, every step below against hw.smooth_step applied from T downward, mean and variance
+    against hw.mean / hw.var under the reference's W.  `lo`: {block: the lowest step checked} (default 1: all).  Returns the number of (target, step)
+    pairs that took the fallback."""
+    T, bs, n, d = store.steps, store.bs, store.n, store.d
+    lwT, fallbacks, worst = np.asarray(store.lw[T - 1], np.float64), 0, _Worst()
+    for b in blocks:
+        c, (c0, c1) = b, _span(n, bs, b)
+        if np.isnan(lwT[c0:c1]).any() or (lwT[c0:c1] == np.inf).any():
+            assert np.isnan(mean[b]).all() and np.isnan(var[b]).all() and np.isnan(weights[b]).all() and (lineage[b] == 0).all(), (label, b, "a NaN block")
+            continue
+        sm = hw.Softmax(lwT[c0:c1])
+        W, e_max = hw.norm_weights(sm), 0.0
+        for s in range(T, 0, -1):
+            what = f"{label}: W (block {b}, step {s})"
+            assert lineage[b, s - 1] == c + 1, (label, b, s, lineage[b], c + 1)
+            lws = np.asarray(store.lw[s - 1], np.float64)[c0:c1]
+            for i, w in enumerate(W):
+                if lws[i] == -np.inf or (w.v == 0 and w.e == 0.0):
+                    v.exact(what + ", a particle of weight 0", i, weights[b, s - 1, i], 0.0)
+                else:
+                    v.value(what, i, weights[b, s - 1, i], w)
+                    worst.add("W", weights[b, s - 1, i], w)
+            assert np.all(weights[b, s - 1, c1 - c0:] == 0.0), (label, b, s, "beyond a short block")
+            ws, guard = hw.Weighted(W), smoothing_guard(c1 - c0, hw.fix_K(c1 - c0), e_max)
+            for col in range(d):
+                x = store.x(s)[c0:c1, col]
+                for name, got, want in (("mean", mean[b, s - 1, col], hw.mean(ws, x)), ("var", var[b, s - 1, col], hw.var(ws, x))):
+                    v.value(f"{label}: smoothed {name}", (b, s, col), got, want, guard=guard)
+                    worst.add(name, got, want)
+            if s == max(1, (lo or {}).get(b, 1)):
+                break
+            pm = store.step_map(s)[c0:c1]
+            born = pm // bs
+            if born.min() != born.max():                                        # the lineage is undefined from step s - 1 down
+                assert np.isnan(mean[b, :s - 1]).all() and np.isnan(var[b, :s - 1]).all() and np.isnan(weights[b, :s - 1]).all() and (lineage[b, :s - 1] == 0).all()
+                break
+            cp = int(born[0])
+            p0, p1 = _span(n, bs, cp)
+            lwc, xc, xt = store.lw[s - 2][p0:p1], store.x(s - 1)[p0:p1], store.x(s)[c0:c1]
+            W, fell, em = hw.smooth_step(refs[b], W, xt, lwc, xc, store.obs[s - 1][c], pm - p0)
+            fallbacks, e_max = fallbacks + len(fell), max(e_max, em)
+            c, c0, c1 = cp, p0, p1
+    worst.show(label)
+    return fallbacks
+
+
+def _both(x):
+    return set(np.unique(x)) == {0.0, 1.0}
+
+
+def moving_inputs(store, blocks, held=None, travelling=False, label="object_motion"):
+    """object_motion: what a case must hold before anything is compared -- every checked block has both `moving` states among its candidates at
+    some step below T, both appear among the targets / held particles, the covariate obs[1] differs between consecutive steps and between the
+    checked blocks, and the blocks' observation rows differ.  Blocks of five and seven particles rarely keep both states through every resample, so
+    the (block, step) pairs whose candidates hold both are returned and printed: those are where the Bernoulli rows are chosen between.
+    `travelling`: the nested filter, whose rows move between blocks -- two blocks may then hold copies of one row, and more than one checked block,
+    not every one, must hold both states."""
+    T, bs, n = store.steps, store.bs, store.n
+    seen, both = set(), []
+    for b in blocks:
+        b0, b1 = _span(n, bs, b)
+        both += [(b, s) for s in range(1, T) if _both(store.x(s)[b0:b1, 0])]
+        for s in range(1, T):
+            assert store.obs[s - 1][b][1] != store.obs[s][b][1], ("the covariate does not change between steps", b, s)
+        seen |= set(np.unique(store.x(T)[b0:b1, 0] if held is None else held[b]))
+    with_both = {b for b, _ in both}
+    print(f"{label}: candidates of both `moving` states at (block, step) {both}")
+    assert len(with_both) > 1 if travelling else with_both == set(blocks), ("candidates of one `moving` state only", sorted(set(blocks) - with_both))
+    assert seen == {0.0, 1.0}, ("targets of one `moving` state only", seen)
+    if not travelling:
+        for s in range(T):
+            rows = [tuple(store.obs[s][b]) for b in blocks]
+            assert len(set(rows)) == len(rows) and len({r[1] for r in rows}) == len(rows), ("blocks share an observation row or a covariate", s)
+    return both
+
+
+def moving_ancestor_inputs(bs, blocks, calls, label="object_motion"):
+    """the same for ancestor sampling; calls: one (rows before the call, reference [B, d], observations [B, n_obs]) per ancestor resample.  Every
+    checked block has both `moving` states among its candidates in some call (returned and printed: which) and enters with a moving and with a
+    still reference over the calls; the covariates differ between the calls and between the checked blocks, and so do the observation rows."""
+    both = []
+    for b in blocks:
+        for t, (rows, ref, obs) in enumerate(calls):
+            i0, i1 = _span(len(rows), bs, b)
+            if _both(np.asarray(rows)[i0:i1, 0]):
+                both.append((b, t + 1))
+        assert _both([ref[b][0] for _, ref, _ in calls]), ("a block whose reference has one `moving` state only", b)
+        cov = [obs[b][1] for _, _, obs in calls]
+        assert len(set(cov)) == len(cov), ("the covariate does not change between steps", b)
+    print(f"{label}: candidates of both `moving` states at (block, call) {both}")
+    assert {b for b, _ in both} == set(blocks), ("candidates of one `moving` state only", sorted(set(blocks) - {b for b, _ in both}))
+    for _, _, obs in calls:
+        r = [tuple(obs[b]) for b in blocks]
+        assert len(set(r)) == len(r) and len({x[1] for x in r}) == len(r), "blocks share an observation row or a covariate"
+    return both
+
+
+def moving_references(ref):
+    """[B, T, d] reference values of object_motion whose `moving` flag alternates over blocks and steps: every block enters with a moving and with a
+    still reference"""
+    ref = np.array(ref, np.float64)
+    B, T = ref.shape[:2]
+    ref[..., 0] = (np.arange(B)[:, None] + np.arange(T)[None, :]) % 2
+    return ref
+
+
+def case_model(g, name):
+    """the models of these cases: where the defaults make two parameters equal -- bearings4's sp = sv, object_motion's p(moving|still) =
+    1 - p(moving|moving) -- exchanging them would change nothing, so they are set apart; sb as in the block-wise device tests"""
+    if name == "bearings4":
+        return g.models.bearings4(sb=0.5, sp=0.002, sv=0.0005)
+    if name == "object_motion":
+        return g.models.object_motion(p_stay=0.9, p_start=0.3)
+    return g.models.line_model() if name == "line_model" else g.models.by_name(name)
+
+
+def moving_obs(base, seed=8, lo=0.02, hi=0.15):
+    """[B, T, 2] observation rows for object_motion from `base` (any per-block data): the covariate obs[1] -- the velocity a moving object adds --
+    becomes a small value of its own per block and step, so that the measured position does not tell the two `moving` states apart and blocks of
+    seven particles keep both; against sy = 0.01 a covariate of another block or step is still many standard deviations off.  The seed is the
+    first at which moving_inputs holds at every shape of the tests (block sizes 7, 129, 513; 3 and 4 steps), found on the CPU oracle's filter"""
+    ys = np.array(base, np.float64)
+    ys[..., 1] = np.random.default_rng(seed).uniform(lo, hi, ys.shape[:2])
+    return ys

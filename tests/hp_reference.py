@@ -333,6 +333,62 @@ class Ref:
             return normal_logpdf(obs[0], E(obs[1]) * x[0], I["s_out"] if out else I["s_in"], self.sc("s_out" if out else "s_in"))
         raise ValueError(self.name)
 
+    # ---- log f(x_t = x | x_{t-1} = xp): the transition density of the Gen program
+    def logtrans(self, xp, x, obs, full=False):
+        """log f(x | xp) up to terms free of xp (ancestor sampling, backward simulation and smoothing normalise over xp: they cancel): the
+        value of the definition and the bound of a Float64 evaluation that divides the residuals by sigma (one rounding each; lgssm2
+        multiplies by 1 / sq as models.py packs it) and drops the normalising constants of the normals.  object_motion keeps the Bernoulli
+        term of `moving`: it depends on xp.  line_model: the slope persists -- exactly 0, or -Inf where xp holds another slope (the outlier's
+        probability is free of xp).  `full`: the complete Gen log-density, constants included (normal_logpdf, log_bernoulli)."""
+        I = self.info
+        if full:
+            return self._logtrans_full(xp, x, obs)
+        nq = lambda r, sigma: r / E(sigma)                                                      # (x - mean) / sigma
+        if self.name == "lgssm2":
+            A = I["A"]
+            if "inv_sq" not in self._c:
+                self._c["inv_sq"] = 1.0 / E(I["sq"])
+            inv = self._c["inv_sq"]
+            t0 = E(float(A[0][0])) * xp[0] + E(float(A[0][1])) * xp[1]
+            t1 = E(float(A[1][0])) * xp[0] + E(float(A[1][1])) * xp[1]
+            a0, a1 = (E(x[0]) - t0) * inv, (E(x[1]) - t1) * inv
+            return -(a0 * a0 + a1 * a1).scale2(-1)
+        if self.name == "sv1":
+            z = nq(E(x[0]) - (E(I["mu"]) + E(I["phi"]) * (E(xp[0]) - I["mu"])), I["sigma"])
+            return -(z * z).scale2(-1)
+        if self.name == "bearings4":
+            z0, z1 = nq(E(x[0]) - (E(xp[0]) + xp[2]), I["sp"]), nq(E(x[1]) - (E(xp[1]) + xp[3]), I["sp"])
+            z2, z3 = nq(E(x[2]) - xp[2], I["sv"]), nq(E(x[3]) - xp[3], I["sv"])
+            return -((z0 * z0 + z1 * z1) + (z2 * z2 + z3 * z3)).scale2(-1)
+        if self.name == "object_motion":
+            mv = x[0] != 0.0
+            lp = log_bernoulli(I["p_stay"] if xp[0] != 0.0 else I["p_start"], mv)
+            z = nq(E(x[1]) - (E(xp[1]) + (obs[1] if mv else 0.0)), I["sy"])
+            return lp + (-(z * z).scale2(-1))
+        if self.name == "line_model":
+            return E(0.0) if xp[0] == x[0] else E(-M.inf)
+        raise ValueError(self.name)
+
+    def _logtrans_full(self, xp, x, obs):
+        I = self.info
+        if self.name == "lgssm2":
+            mu0, mu1 = self._prior_mean(False, xp)
+            return normal2_logpdf(x[0], x[1], mu0, mu1, I["sq"], self.sc("sq"))
+        if self.name == "sv1":
+            return normal_logpdf(x[0], E(I["mu"]) + E(I["phi"]) * (E(xp[0]) - I["mu"]), I["sigma"], self.sc("sigma"))
+        if self.name == "bearings4":
+            return (normal2_logpdf(x[0], x[1], E(xp[0]) + xp[2], E(xp[1]) + xp[3], I["sp"], self.sc("sp"))
+                    + normal2_logpdf(x[2], x[3], E(xp[2]), E(xp[3]), I["sv"], self.sc("sv")))
+        if self.name == "object_motion":
+            mv = x[0] != 0.0
+            lp = log_bernoulli(I["p_stay"] if xp[0] != 0.0 else I["p_start"], mv)
+            return lp + normal_logpdf(x[1], E(xp[1]) + (obs[1] if mv else 0.0), I["sy"], self.sc("sy"))
+        if self.name == "line_model":                                        # slope: a point mass on xp's; outlier ~ bernoulli(p_out) once a step has happened
+            if xp[0] != x[0]:
+                return E(-M.inf)
+            return log_bernoulli(I["p_out"], x[1] != 0.0) if obs[1] != 0.0 else E(0.0)
+        raise ValueError(self.name)
+
     @staticmethod
     def wrap(r, wraps=None):
         """the bearing residual wrapped to (-pi, pi].  wraps = 1: ONE subtraction / addition of 2 pi, which is what the spec does (enough

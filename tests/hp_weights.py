@@ -32,6 +32,30 @@ documents, per particle, in counts of the fixed-point weight q_i ~ exp(lp_i - m)
 A slot whose target lies within the bound of a CDF boundary of THIS reference is undecidable and is not compared.  No figure here is fitted
 to an output of the oracle or of the device.
 
+Inexact log-weights (Softmax.inexact): the ancestor weights lwa_i = lw_i + logtrans_i of PGAS, backward simulation and smoothing are not
+Float64 inputs but Float64 RESULTS: the device holds l_i with |l_i - a_i| <= e_i, a_i the real value (an E of tests/hp_reference.py).  The
+reference is safe_softmax of the a_i; the device subtracts ITS maximum m = max l_i.  With a* = max a_i and mu = m - a*:
+
+    |mu| <= e_max = max e_i     m = l_k <= a_k + e_k <= a* + e_k for the k that attains it, and m >= l_i* >= a* - e_i* for the real maximiser i*.
+    l_i - m = (a_i - a*) + (l_i - a_i) - mu: the device's count is round(T_i exp(l_i - a_i) (1 + roundings)), T_i = exp(a_i - a*) exp(-mu) 2^K.
+    The factor exp(-mu) is COMMON to all i: the T_i have the normalised weights and the CDF of the definition exactly.  So the bounds above
+    hold with q~_i replaced by T_i <= q~_i exp(e_max) and the absolute error e_i of the exponent entering as a relative error of the count:
+
+    delta_i = 1/2 + q~_i exp(e_max) expm1(e_i + 2 * 2^-52 + ulp(|a_i - a*| + e_i + e_max) / 2 + 2^-53)
+              ((1 + a)(1 + b) <= exp(a + b): the product of the relative factors is inside expm1 of the sum of their exponents)
+    S >= S~ exp(-e_max) - D,  D = sum delta_i
+
+    and |cdf[a] / S - CDF(a)| <= 2 D / S, w_err and lse's relative bound of S follow as before from delta, D and this S_lo.  exp_'s flush:
+    l_i - m < -708 is certain when a_i - a* < -708 - e_i - e_max (`dead`); a flushed count is 0 and T_i < 2^K exp(-708 + 2 e_max) < 1/2: inside
+    delta_i either way.  -Inf is exact (lw = -Inf, or line_model's logtrans): count 0, delta 0.  With every e_i = 0 this is the bound above;
+    Softmax(lp) on Float64 input takes the old statements and returns the old numbers.
+
+ancestor_draw, backward_step and smooth_step restate PGAS' ancestor draw (Lindsten, Jordan & Schoen 2014), one transition of FFBSi (Godsill,
+Doucet & West 2004) and one of FFBSm (Doucet, Godsill & Andrieu 2000) from these: the inverse CDF of w_i f(x' | x_i) / sum at the exact uniform
+with eps = 2 D / S_lo, and W_s^i = sum_j W_{s+1}^j r_ij with r_ij = E(p_i, w_err_i), accumulated by E arithmetic (one multiply and one add per
+term at half an ulp each, W_{s+1}'s own bound carried through the product).  Flagged ancestor weights (NaN, +Inf, all -Inf) are the spec's
+exact fallback -- the recorded parent -- and are reported as such, not bounded.
+
 The rest of the resize family, from src/resize.jl of the reference:
 
   * pf_optimal_resize! (:149-219): w = safe_softmax(lw); find_inv_w_threshold is the ascending loop `A -= 1; B += kappa`, the first kappa with
@@ -92,18 +116,20 @@ def uniform(seed, slot, epoch):
 class Softmax:
     """safe_softmax of a Float64 vector in mpmath, with the per-particle quantisation bound of the module docstring"""
 
-    def __init__(self, lp, K=None):
+    def __init__(self, lp, K=None, real=None, err=None):
+        """`real`, `err`: only through Softmax.inexact"""
         lp = np.ascontiguousarray(lp, np.float64)
         assert lp.size >= 1 and not np.isnan(lp).any() and not (lp == np.inf).any()
         self.lp, self.n = lp, lp.size
         self.K = fix_K(self.n) if K is None else int(K)
         m = float(lp.max())
         self.m, self.invalid = m, m == -np.inf
+        self.e_max = 0.0
         if self.invalid:                                             # utils.jl:123-126: uniform weights
             self.W = [mpf(1)] * self.n
             self.delta = np.zeros(self.n)
             self.St = float(self.n)
-        else:
+        elif real is None:
             mm = mpf(m)
             self.W = [M.exp(mpf(float(x)) - mm) if x != -np.inf else mpf(0) for x in lp]
             with np.errstate(invalid="ignore"):
@@ -112,11 +138,35 @@ class Softmax:
             ulp_d = np.array([math.ulp(x) for x in d])
             self.delta = np.where(lp == -np.inf, 0.0, 0.5 + qt * (4 * U + 0.5 * ulp_d + U))
             self.St = float(M.ldexp(M.fsum(self.W), self.K))
+        else:                                                        # the module docstring, "Inexact log-weights"
+            err = np.where(lp == -np.inf, 0.0, np.asarray(err, np.float64))
+            assert np.isfinite(err).all()
+            mm = max(real)
+            self.e_max = em = float(err[lp != -np.inf].max())
+            self.W = [M.exp(a - mm) if x != -np.inf else mpf(0) for a, x in zip(real, lp)]
+            d = np.array([float(mm - a) if x != -np.inf else 0.0 for a, x in zip(real, lp)])
+            qt = np.array([float(M.ldexp(w, self.K)) for w in self.W])
+            ulp_d = np.array([math.ulp(x) for x in d + err + em])
+            self.delta = np.where(lp == -np.inf, 0.0, 0.5 + qt * math.exp(em) * np.expm1(err + 4 * U + 0.5 * ulp_d + U))
+            self.St = float(M.ldexp(M.fsum(self.W), self.K)) * math.exp(-em)
+            self.margin = err + em
         self.tot = M.fsum(self.W)
         self.D = float(self.delta.sum())
         self.S_lo = self.St - self.D                                 # the integer S is not below this
-        self.dead = (lp - m < -708.0) if not self.invalid else np.zeros(self.n, bool)      # exp_ flushes them; -Inf included
+        if self.invalid:
+            self.dead = np.zeros(self.n, bool)
+        elif real is None:
+            self.dead = lp - m < -708.0                              # exp_ flushes them; -Inf included
+        else:
+            self.dead = (lp == -np.inf) | (-d < -708.0 - self.margin)
         self._p = self._pf = None
+
+    @classmethod
+    def inexact(cls, a, K=None):
+        """`a`: one E per particle -- the real log-weight and the bound of the Float64 the device forms -- or -Inf (float) where it is exactly -Inf"""
+        real = [x.v if isinstance(x, E) else mpf(x) for x in a]
+        err = [x.e if isinstance(x, E) else 0.0 for x in a]
+        return cls([float(r) for r in real], K, real=real, err=err)
 
     @property
     def p(self):
@@ -511,3 +561,94 @@ def coalesce(rows, lw, cols, drop_smallest_of=None):
         sm = Softmax(lw[idx], K)
         weights.append(None if sm.invalid else sm.lse() + ratio)
     return [idx[0] for idx in groups], weights, groups
+
+
+# ------------------------------------------------------------------------------------------- ancestor sampling, backward simulation, smoothing
+FALLBACK = "recorded parent"          # flagged ancestor weights (NaN, +Inf, all -Inf): the spec's exact fallback, not a draw
+
+
+def ancestor_weights(ref, lw, xs, x_next, obs):
+    """lwa_i = lw_i + log f(x_next | xs_i) per candidate: an E (the real value, the bound of the Float64 sum of the two Float64 terms), -Inf
+    where either term is -Inf, or None where the recorded weight is NaN / +Inf.  `ref`: the hp_reference.Ref of the block's parameters."""
+    out = []
+    for w, x in zip(np.asarray(lw, np.float64), np.asarray(xs, np.float64)):
+        if np.isnan(w) or w == np.inf:
+            out.append(None)
+            continue
+        lt = ref.logtrans(list(x), list(x_next), obs)
+        out.append(-np.inf if (w == -np.inf or lt.v == -M.inf) else E(float(w)) + lt)
+    return out
+
+
+def ancestor_softmax(ref, lw, xs, x_next, obs, K=None):
+    """the Softmax over a block's ancestor weights, or FALLBACK"""
+    a = ancestor_weights(ref, lw, xs, x_next, obs)
+    if any(x is None for x in a) or all(not isinstance(x, E) for x in a):
+        return FALLBACK
+    return Softmax.inexact(a, fix_K(len(a)) if K is None else K)
+
+
+def _draw(sm, seed, slot, epoch):
+    """(index, undecidable) of the inverse CDF of sm at the uniform of resample slot `slot`"""
+    anc, und = _inverse_cdf(sm.cdf(), [uniform(seed, slot, epoch)], 2 * sm.D / sm.S_lo)
+    return anc[0], bool(und)
+
+
+def ancestor_draw(ref, lw, xs, x_ref, obs, seed, epoch, slot):
+    """PGAS: a_0 of a block = the inverse CDF of w_i f(x_ref | x_i) / sum over the block's particles (lw, xs: its weights and latents before
+    the call) at the uniform of slot 0's own resample counter `slot` (its global index) of the call's epoch.  Invalid ancestor weights keep the
+    predecessor: (0, False, FALLBACK).  Returns (a_0, undecidable, Softmax)."""
+    sm = ancestor_softmax(ref, lw, xs, x_ref, obs)
+    if sm is FALLBACK:
+        return 0, False, FALLBACK
+    a, und = _draw(sm, seed, slot, epoch)
+    return a, und, sm
+
+
+def backward_step(ref, lw, xs, x_held, obs, seed, epoch, slot, sm=None):
+    """one transition of FFBSi: the local index at step s among the candidates (lw, xs: the recorded weights and latents of the block of the
+    held particle's recorded parent in snapshot s), given the particle held at step s + 1 (x_held; obs: the observation row step s + 1 of ITS
+    block was entered with), at the uniform of resample slot b n_samples + j under the epoch of that step.  `sm`: the ancestor_softmax of the same
+    held particle where a caller has it already (draws that hold one particle share it).  Returns (index | FALLBACK, undecidable, Softmax |
+    FALLBACK)."""
+    sm = ancestor_softmax(ref, lw, xs, x_held, obs) if sm is None else sm
+    if sm is FALLBACK:
+        return FALLBACK, False, FALLBACK
+    a, und = _draw(sm, seed, slot, epoch)
+    return a, und, sm
+
+
+def smooth_step(ref, W_next, x_next, lw, xs, obs, parents):
+    """one transition of FFBSm: W_s^i = sum_j W_{s+1}^j w_s^i f(x_{s+1}^j | x_s^i) / sum_l w_s^l f(x_{s+1}^j | x_s^l), one E per candidate i.
+    W_next: one E per target j; x_next: the targets' latents; lw, xs: the candidates' recorded weights and latents; parents[j]: the local index
+    of target j's recorded parent among the candidates, read only on the fallback.  A target of weight exactly 0 adds nothing, and neither does a
+    candidate that is -Inf or certainly flushed (Softmax.dead: more than 708 plus the bounds below the maximum) -- its W stays E(0, 0), which the
+    check compares exactly.  Returns (W_s,
+    the targets that took the fallback, the largest bound e_max of an ancestor weight met)."""
+    acc, fell, e_max = [E(0.0) for _ in range(len(lw))], [], 0.0
+    for j, Wj in enumerate(W_next):
+        if Wj.v == 0 and Wj.e == 0.0:
+            continue
+        sm = ancestor_softmax(ref, lw, xs, x_next[j], obs)
+        if sm is FALLBACK:
+            acc[parents[j]] = acc[parents[j]] + Wj * E(1.0)
+            fell.append(j)
+            continue
+        p, we, e_max = sm.p, sm.w_err(), max(e_max, sm.e_max)
+        for i in range(len(acc)):
+            if sm.dead[i]:
+                continue                                                       # -Inf, or certainly flushed by exp_: r = 0 EXACTLY, the term is +0.0
+            acc[i] = acc[i] + Wj * E(p[i], we[i])
+    return acc, fell, e_max
+
+
+class Weighted:
+    """weights given as E values, for mean / var below: .p the real weights, .pf their floats, .w_err() their bounds, .n"""
+
+    def __init__(self, W):
+        self.p, self.n = [w.v for w in W], len(W)
+        self.pf = np.array([float(w.v) for w in W])
+        self._e = np.array([w.e for w in W])
+
+    def w_err(self):
+        return self._e

@@ -1,6 +1,6 @@
 """Ancestor sampling for conditional SMC per block (gpf.h gpf_resample_blocks_ancestor, gpf_block_ancestor_log_weights), the parts that need no GPU:
 the two entry points exist in every layer (header with citation, definition and refusals; library; ctypes table; package; Julia glue); the NumPy
-restatement of Model<M>::logtrans -- tests/block_ancestor_spec.py -- against an mpmath restatement of the models' transition densities; the spec
+restatement of Model<M>::logtrans -- tests/block_ancestor_spec.py -- against the mpmath transition densities of tests/hp_reference.py (Ref.logtrans); the spec
 reduces to the plain one where it must; and the invariance experiment of tests/test_gpu_block_ancestor.py run on the CPU through the spec, with the
 negative control that shows the experiment can see a wrong ancestor density."""
 import ctypes
@@ -14,7 +14,6 @@ import pytest
 import block_ancestor_spec as asp
 import block_conditional_spec as cs
 import hp_reference as hp
-from hp_reference import E
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROTOS = {
@@ -92,33 +91,6 @@ def test_julia_glue_calls_the_entry_points():
 
 
 # ----------------------------------------------------------------------------- logtrans against the models' transition densities in mpmath
-def hp_logtrans(m, xp, x, obs):
-    """log f(x | xp) of the model as a Gen program, from the NATURAL parameters (m.info), up to terms free of xp: value and derived Float64 bound.
-    The divisions by sigma are the spec's own (one rounding each); lgssm2 multiplies by 1 / sq as models.py packs it."""
-    I = m.info
-    nq = lambda r, sigma: r / E(sigma)                                                      # (x - mean) / sigma
-    if m.name == "lgssm2":
-        A = I["A"]
-        inv = 1.0 / E(I["sq"])
-        t0 = E(float(A[0][0])) * xp[0] + E(float(A[0][1])) * xp[1]
-        t1 = E(float(A[1][0])) * xp[0] + E(float(A[1][1])) * xp[1]
-        a0, a1 = (E(x[0]) - t0) * inv, (E(x[1]) - t1) * inv
-        return -(a0 * a0 + a1 * a1).scale2(-1)
-    if m.name == "sv1":
-        z = nq(E(x[0]) - (E(I["mu"]) + E(I["phi"]) * (E(xp[0]) - I["mu"])), I["sigma"])
-        return -(z * z).scale2(-1)
-    if m.name == "bearings4":
-        z0, z1 = nq(E(x[0]) - (E(xp[0]) + xp[2]), I["sp"]), nq(E(x[1]) - (E(xp[1]) + xp[3]), I["sp"])
-        z2, z3 = nq(E(x[2]) - xp[2], I["sv"]), nq(E(x[3]) - xp[3], I["sv"])
-        return -((z0 * z0 + z1 * z1) + (z2 * z2 + z3 * z3)).scale2(-1)
-    if m.name == "object_motion":
-        mv = x[0] != 0.0
-        lp = hp.log_bernoulli(I["p_stay"] if xp[0] != 0.0 else I["p_start"], mv)
-        z = nq(E(x[1]) - (E(xp[1]) + (obs[1] if mv else 0.0)), I["sy"])
-        return lp + (-(z * z).scale2(-1))
-    raise ValueError(m.name)
-
-
 def _cases(m, rng, k=12):
     d = m.dim
     xs = rng.standard_normal((k, 3, d))                                                      # (xp_a, xp_b, x)
@@ -132,11 +104,12 @@ def test_logtrans_against_the_mpmath_transition_density(g, name):
     """the difference logtrans(xp_a) - logtrans(xp_b) at a fixed x -- normalising constants drop -- within the bound that first-order error propagation
     through the expression derives (tests/hp_reference.py), per value"""
     m = g.models.by_name(name)
+    ref = hp.Ref(m)
     rng = np.random.default_rng(11)
     obs = np.array([0.3, 0.7, 0.0, 0.0])
     for xa, xb, x in _cases(m, rng):
         got = asp.logtrans(name, m.params, xa, x, obs)[0] - asp.logtrans(name, m.params, xb, x, obs)[0]
-        want = hp_logtrans(m, xa, x, obs) - hp_logtrans(m, xb, x, obs)
+        want = ref.logtrans(xa, x, obs) - ref.logtrans(xb, x, obs)
         err, bound = hp.differs(got, want)
         assert np.isfinite(bound) and bound < 1e-9 * max(1.0, abs(float(want.v))), (name, bound)    # (the bound itself says something)
         assert err <= bound, (name, xa, xb, x, err, bound)

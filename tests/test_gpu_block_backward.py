@@ -43,9 +43,9 @@ class Dev:
     restatement filled from what the state returns.  `epoch`: the epoch-advancing calls so far = the epoch the next call runs under."""
 
     def __init__(self, g, name, bs, *, n=None, keep_prev=False, steps=T, ess_frac=None, across=False, params=None, weights=True, seed=SEED, ys=None,
-                 resample=True, after_update=None, final_resample=False):
+                 resample=True, after_update=None, final_resample=False, model=None):
         self.g, self.bs = g, bs
-        self.m = m = g.models.line_model() if name == "line_model" else model_of(g, name)
+        self.m = m = model if model is not None else g.models.line_model() if name == "line_model" else model_of(g, name)
         self.n = n = n_of(bs) if n is None else n
         self.B = B = (n + bs - 1) // bs
         if ys is None:
