@@ -1188,6 +1188,29 @@ def block_smoothed_weights(state, block_size: int, steps=None):
     return _block_smooth(state, block_size, steps, "block_smoothed_weights", False, False, True, False)[2]
 
 
+def block_smoothed_pair_moments(state, block_size: int, steps=None, return_blocks: bool = False):
+    """pairwise smoothing per block (gpf.h gpf_block_smooth_pairs): the E-step of particle EM.  Beside block_smoothed_moments' mean, the second moments
+    second[b, s] = sum_i W_s^i x_s^i x_s^i' and the lag-one cross moments cross[b, s][a, c] = sum_ij t_ij x_s^i[a] x_{s+1}^j[c] under the pairwise smoothing
+    weights t_ij = W_{s+1}^j w_s^i f(x_{s+1}^j | x_s^i) / sum_l w_s^l f(x_{s+1}^j | x_s^l) -- the particle estimates of E[x_s x_s' | y_1:T] and
+    E[x_s x_{s+1}' | y_1:T].  One launch for all blocks and steps, no block_size x block_size array anywhere; needs pf_initialize_blocks(..., history=T,
+    history_weights=True).  Returns (mean [n_blocks, n_steps, dim], second [n_blocks, n_steps, dim, dim], cross [n_blocks, n_steps - 1, dim, dim]);
+    entry o of cross is the pair of the steps lo + o and lo + o + 1, and a single step has an empty cross.  With return_blocks=True also
+    block_smoothed_moments' blocks.  steps, NaN blocks, undefined lineages (NaN for every pair that touches an undefined step), per-block parameters and
+    effects (none) as in block_smoothed_moments; mean is that call's, bit for bit."""
+    who = "block_smoothed_pair_moments"
+    if not getattr(state, "history_weights", False):
+        raise ErrorException(who + " needs the block-wise trajectory store with its weight records "
+                             "(pf_initialize_blocks(..., history=T, history_weights=True)), which this state does not have")
+    lo, hi = _store_steps(state, steps, who)
+    _, nb = _store_blocks(state, block_size, lo, hi, who)
+    d = state.dim
+    mu, second, cross = np.empty((nb, hi - lo + 1, d)), np.empty((nb, hi - lo + 1, d, d)), np.empty((nb, hi - lo, d, d))
+    blocks = np.empty((nb, hi - lo + 1), np.int64) if return_blocks else None
+    state._check(state._L.gpf_block_smooth_pairs(state._h, int(block_size), lo, hi, _pd(mu), _pd(second), _pd(cross) if hi > lo else None,
+                                                 blocks.ctypes.data_as(C.POINTER(C.c_int64)) if return_blocks else None))
+    return (mu, second, cross) + ((blocks,) if return_blocks else ())
+
+
 # ----------------------------------------------------------------------------- statistics (src/statistics.jl)
 def _addr_values(state, addr) -> np.ndarray:
     """the values at one address over all particles: a column of the current step, or (t, column) for a past choice"""

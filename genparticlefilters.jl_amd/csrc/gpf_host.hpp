@@ -635,6 +635,8 @@ inline void team_dispatch(int64_t block_size, int64_t nblocks, F&& f)
 gpf_status weighted_tree_sum(gpf_filter* h, const double* values, int stride, int col, int pw, const double* center, double match, double* out_dev);
 // ---- defined in libgpf_smooth.hip
 void launch_block_smooth(gpf_filter* h, const SmoothArgs& a, const AncArgs& x);   // k_block_smooth<model, TEAM, ITEMS> by team_dispatch
+// ---- defined in libgpf_pairs.hip
+void launch_block_pairs(gpf_filter* h, const PairArgs& a, const AncArgs& x);      // k_block_smooth_pairs<model, TEAM, ITEMS> by team_dispatch
 // ---- defined in libgpf_shard.hip
 gpf_status shard_device_setup(gpf_filter* h);         // LDS attributes of the push kernels (gpf_create)
 

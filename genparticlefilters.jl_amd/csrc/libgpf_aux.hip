@@ -1757,6 +1757,38 @@ gpf_status gpf_block_smooth(gpf_handle h, int64_t block_size, int32_t step_lo, i
     // (nothing was drawn: the epoch stays)
     return block_out(h, {{d_mean.p, mean_out, b_mom}, {d_var.p, var_out, b_mom}, {d_w.p, weights_out, b_w}, {d_c.p, blocks_out, b_c}});
 }
+// ---- pairwise smoothing per block (gpf.h gpf_block_smooth_pairs): the smoothed mean, second moments and lag-one cross moments of all blocks and steps
+// in one launch; gpf_block_smooth's gate, checks and walk, and like it instantiated in a translation unit of its own (libgpf_pairs.hip)
+gpf_status gpf_block_smooth_pairs(gpf_handle h, int64_t block_size, int32_t step_lo, int32_t step_hi,
+                                  double* mean_out, double* second_out, double* cross_out, int64_t* blocks_out)
+{
+    const char* who = "gpf_block_smooth_pairs";
+    gpf_status s = block_store_gate(h, block_size, who, true);
+    if (s) return s;
+    if (!mean_out && !second_out && !cross_out && !blocks_out) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": all outputs are NULL");
+    StoreSteps r{};
+    if ((s = block_store_steps(h, block_size, step_lo, step_hi, who, r))) return s;
+    if (cross_out && step_lo == step_hi) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": cross_out needs two steps at least (no pair in the range)");
+    const int64_t lim = (int64_t)1 << 31, cells = r.nblocks * r.n_steps, dd = (int64_t)h->d * h->d;   // (nblocks, n_steps, dd < 2^31: as gpf_block_smooth)
+    if (cells >= lim || cells >= (lim + dd - 1) / dd)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": n_blocks * n_steps * dim * dim must stay below 2^31");
+    if ((s = block_store_sizes(h, block_size, r.T, step_lo, who))) return s;
+    const size_t b_mean = (size_t)cells * (size_t)h->d * sizeof(double), b_sec = (size_t)cells * (size_t)dd * sizeof(double),
+                 b_cross = (size_t)(r.nblocks * (r.n_steps - 1)) * (size_t)dd * sizeof(double), b_c = (size_t)cells * sizeof(int64_t);
+    CallScratch d_mean, d_sec, d_cross, d_c;                       // scratch of this call, as gpf_block_smooth; only what was asked for
+    if ((s = block_store_tables(h, true)) || (s = block_store_scratch(h, d_mean, mean_out, b_mean)) || (s = block_store_scratch(h, d_sec, second_out, b_sec)) ||
+        (s = block_store_scratch(h, d_cross, cross_out, b_cross)) || (s = block_store_scratch(h, d_c, blocks_out, b_c))) return s;
+    PairArgs a{};
+    a.maps = h->hist_dev_maps; a.hx = h->hist_dev_x; a.hlw = h->hist_dev_lw; a.hobs = h->hist_dev_obs; a.lw = h->lw;
+    a.T = r.T; a.lo0 = step_lo - 1; a.hi0 = step_hi - 1;
+    a.n = h->n; a.nb = block_size; a.nblocks = r.nblocks;
+    a.mean = static_cast<double*>(d_mean.p); a.second = static_cast<double*>(d_sec.p);
+    a.cross = static_cast<double*>(d_cross.p); a.blocks = static_cast<int64_t*>(d_c.p);
+    launch_block_pairs(h, a, anc_args(h));
+    HIP_TRY(h, hipGetLastError());
+    // (nothing was drawn: the epoch stays)
+    return block_out(h, {{d_mean.p, mean_out, b_mean}, {d_sec.p, second_out, b_sec}, {d_cross.p, cross_out, b_cross}, {d_c.p, blocks_out, b_c}});
+}
 // ---- checkpoint / resume: everything a filter needs to continue bit for bit -- the population, its log-weights and parents, the log-ML
 // estimate, the RNG epoch, the latest observation and strata -- as ONE host blob; loads into a handle created with the same gpf_config
 namespace {

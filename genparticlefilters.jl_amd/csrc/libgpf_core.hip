@@ -3,7 +3,7 @@
 //
 // Host orchestration only: which kernels run for each pf_* operation, on one HIP stream, with all scalars (max, sums, log-ML estimate,
 // residual counts) kept in device memory so that the common path (check = false / :warn without reading the flag) never waits for the GPU.
-// Build: __graft_entry__.build_hip() -- five translation units (this one, libgpf_resample / _aux / _shard / _smooth .hip) linked into libgpf_hip.so.
+// Build: __graft_entry__.build_hip() -- six translation units (this one, libgpf_resample / _aux / _shard / _smooth / _pairs .hip) linked into libgpf_hip.so.
 #include "gpf_host.hpp"
 
 using namespace gpf;

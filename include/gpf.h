@@ -682,6 +682,34 @@ gpf_status gpf_block_backward_sample(gpf_handle h, int64_t block_size, int32_t n
  *             n_blocks * n_steps * block_size >= 2^31, a NULL handle. */
 gpf_status gpf_block_smooth(gpf_handle h, int64_t block_size, int32_t step_lo, int32_t step_hi,
                             double* mean_out, double* var_out, double* weights_out, int64_t* blocks_out);
+/* Pairwise smoothing per block: the E-step of particle EM.  The JOINT smoothed law of two consecutive steps, as lag-one cross moments and second
+ * moments, in the same launch that walks the marginal smoother -- E[x_s x_{s+1}^T | y_1:T] and E[x_s x_s^T | y_1:T] are what re-estimating a linear
+ * model's transition matrix and noise needs, and for object_motion's `moving` flag the cross moment is the expected transition count.  No
+ * block_size x block_size array is stored anywhere: the pairwise weight of (i, j) is the term gpf_block_smooth adds to W_s^i.
+ * Everything not named here is gpf_block_smooth's, word for word: T, the lineage c_s, the step-T weights, targets and candidates, lwa_ij, (m_j, f_j), K,
+ * q_ij, D_j and r_ij, the fallback to the recorded parent, P_b = the FINAL block's CURRENT parameter row, the walk from T with the steps above
+ * step_hi walked and not written, its effects (none: the epoch does not advance) and its refusals.  Needs gpf_history_enable_blocks_weights.
+ *   step s    the walk from step s+1 to step s, per candidate i of block c_s: the targets j are taken in ASCENDING order; a target with
+ *             W_{s+1}^j == 0 is SKIPPED ENTIRELY (0 * x is not +0.0 for every x); for every other target
+ *                 t = W_{s+1}^j * r_ij;    W_s^i = W_s^i + t;    A_i[c] = A_i[c] + t * x_{s+1}^j[c]   for every latent column c,
+ *             W_s^i and A_i[c] from +0.0, one multiply and one add per term (no fused multiply-add).  W_s^i is gpf_block_smooth's bit for bit.
+ *   outputs   HOST, n_steps = step_hi - step_lo + 1, d = the model's latent dimension, tree = the summation tree of gpf_block_moments
+ *             over the index within block c_s, terms beyond a short block +0.0:
+ *               mean_out   [n_blocks][n_steps][d]           gpf_block_smooth's mean_out bit for bit;
+ *               second_out [n_blocks][n_steps][d][d]        second_s[a][c] = tree_i((W_s^i * x_s^i[a]) * x_s^i[c]) for a <= c; second_s[c][a] is the
+ *                                                           same double, mirrored;
+ *               cross_out  [n_blocks][n_steps - 1][d][d]    entry o is the pair (s, s+1), s = step_lo + o: cross_s[a][c] = tree_i(x_s^i[a] * A_i[c]),
+ *                                                           the particle estimate of E[x_s[a] x_{s+1}[c] | y_1:T];
+ *               blocks_out int64 [n_blocks][n_steps]        as in gpf_block_smooth.
+ *             Any may be NULL, not all; what is not asked for is not allocated on the device.
+ *   undefined a block with NaN / +Inf current weights reads NaN everywhere and lineage 0.  A lineage that is undefined from step s down: NaN for mean
+ *             and second of the steps <= s and for every pair whose lower step is <= s.  The other blocks are unaffected.
+ *   refused   nothing written, nothing changed.  Those of gpf_block_smooth (GPF_ERR_STATE: no store, a store without the weight records, a walked step
+ *             entered by a whole-filter call, a clamped block_size > 2048; GPF_ERR_INVALID_ARGUMENT: a bad step range, block_size < 1, a block size other
+ *             than the per-block parameters' or than the one a walked step was entered with, a NULL handle), and GPF_ERR_INVALID_ARGUMENT for all
+ *             outputs NULL, cross_out non-NULL with step_lo == step_hi (no pair in the range), n_blocks * n_steps * d * d >= 2^31. */
+gpf_status gpf_block_smooth_pairs(gpf_handle h, int64_t block_size, int32_t step_lo, int32_t step_hi,
+                                  double* mean_out, double* second_out, double* cross_out, int64_t* blocks_out);
 
 /* ---- shard-level building blocks (multi-GPU) ------------------------------------------------------
  * A filter sharded over G GPUs is G handles created with the same seed / n_global and contiguous

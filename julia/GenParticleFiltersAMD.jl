@@ -672,6 +672,26 @@ function block_smoothed_weights(s::DeviceParticleFilterState, block_size::Int; s
     return w
 end
 
+# Pairwise smoothing per block (gpf.h gpf_block_smooth_pairs): the E-step of particle EM -- block_smoothed_moments' mean (dim, n_steps, n_blocks), the
+# second moments sum_i W_s^i x_s^i x_s^i' and the lag-one cross moments E[x_s x_{s+1}' | y_1:T] under the pairwise smoothing weights, in one launch.
+# The library writes row-major [n_blocks][n_steps][a][c]: second is (dim, dim, n_steps, n_blocks) with second[c, a, s, b] (symmetric), and
+# cross[c, a, o, b] = E[x_s[a] x_{s+1}[c]] for s = first(steps) + o - 1, (dim, dim, n_steps - 1, n_blocks) -- empty for a single step.
+function block_smoothed_pair_moments(s::DeviceParticleFilterState, block_size::Int; steps::Union{Nothing,UnitRange{Int}}=nothing,
+                                     return_blocks::Bool=false)
+    if steps === nothing
+        k = Ref{Cint}(0)
+        _status(s, ccall((:gpf_history_steps, libgpf), Cint, (Ptr{Cvoid}, Ref{Cint}), s.handle, k))
+        steps = 1:Int(k[])
+    end
+    bs = min(block_size, s.n_particles); nb = cld(s.n_particles, bs); d = _latent_dim(s)
+    mu = Array{Float64}(undef, d, length(steps), nb); second = Array{Float64}(undef, d, d, length(steps), nb)
+    cross = Array{Float64}(undef, d, d, length(steps) - 1, nb)
+    blocks = return_blocks ? Array{Int64}(undef, length(steps), nb) : nothing
+    _status(s, ccall((:gpf_block_smooth_pairs, libgpf), Cint, (Ptr{Cvoid}, Int64, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int64}),
+                     s.handle, block_size, first(steps), last(steps), mu, second, length(steps) > 1 ? cross : C_NULL, return_blocks ? blocks : C_NULL))
+    return (mu, second, cross, (return_blocks ? (blocks,) : ())...)
+end
+
 # ---------------------------------------------------------------- multi-GPU: one process per GPU, the exchange inside libgpf
 # A shard of a filter of `n_global` particles: rank r of `world` holds the contiguous global range that starts at gid0 (the
 # first n_global % world ranks hold one particle more).  The communicator is libgpf's own (RCCL); the host only carries the
