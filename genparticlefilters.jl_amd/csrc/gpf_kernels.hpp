@@ -26,4 +26,3 @@
 #include "gpf_k_block_anc.hpp"
 #include "gpf_k_block_back.hpp"
 #include "gpf_k_block_smooth.hpp"
-#include "gpf_k_block_pairs.hpp"

@@ -1578,6 +1578,13 @@ static gpf_status block_store_tables(gpf_handle h, bool with_weights)
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return GPF_OK;
 }
+// the inputs of block_store_walk (SmoothArgs and PairArgs): the tables of block_store_tables(h, true) and the walked steps, 0-based
+static void block_store_walk_args(gpf_handle h, const StoreSteps& r, int32_t step_lo, int32_t step_hi, int64_t block_size, StoreWalkArgs& a)
+{
+    a.maps = h->hist_dev_maps; a.hx = h->hist_dev_x; a.hlw = h->hist_dev_lw; a.hobs = h->hist_dev_obs; a.lw = h->lw;
+    a.T = r.T; a.lo0 = step_lo - 1; a.hi0 = step_hi - 1;
+    a.n = h->n; a.nb = block_size; a.nblocks = r.nblocks;
+}
 // device scratch of one query for an output that was asked for (up to 16 GB of trajectories are nothing to keep on a handle)
 static gpf_status block_store_scratch(gpf_handle h, CallScratch& c, const void* wanted, size_t bytes)
 {
@@ -1747,9 +1754,7 @@ gpf_status gpf_block_smooth(gpf_handle h, int64_t block_size, int32_t step_lo, i
     if ((s = block_store_tables(h, true)) || (s = block_store_scratch(h, d_mean, mean_out, b_mom)) || (s = block_store_scratch(h, d_var, var_out, b_mom)) ||
         (s = block_store_scratch(h, d_w, weights_out, b_w)) || (s = block_store_scratch(h, d_c, blocks_out, b_c))) return s;
     SmoothArgs a{};
-    a.maps = h->hist_dev_maps; a.hx = h->hist_dev_x; a.hlw = h->hist_dev_lw; a.hobs = h->hist_dev_obs; a.lw = h->lw;
-    a.T = r.T; a.lo0 = step_lo - 1; a.hi0 = step_hi - 1;
-    a.n = h->n; a.nb = block_size; a.nblocks = r.nblocks;
+    block_store_walk_args(h, r, step_lo, step_hi, block_size, a);
     a.mean = static_cast<double*>(d_mean.p); a.var = static_cast<double*>(d_var.p);
     a.wout = static_cast<double*>(d_w.p); a.blocks = static_cast<int64_t*>(d_c.p);
     launch_block_smooth(h, a, anc_args(h));
@@ -1779,9 +1784,7 @@ gpf_status gpf_block_smooth_pairs(gpf_handle h, int64_t block_size, int32_t step
     if ((s = block_store_tables(h, true)) || (s = block_store_scratch(h, d_mean, mean_out, b_mean)) || (s = block_store_scratch(h, d_sec, second_out, b_sec)) ||
         (s = block_store_scratch(h, d_cross, cross_out, b_cross)) || (s = block_store_scratch(h, d_c, blocks_out, b_c))) return s;
     PairArgs a{};
-    a.maps = h->hist_dev_maps; a.hx = h->hist_dev_x; a.hlw = h->hist_dev_lw; a.hobs = h->hist_dev_obs; a.lw = h->lw;
-    a.T = r.T; a.lo0 = step_lo - 1; a.hi0 = step_hi - 1;
-    a.n = h->n; a.nb = block_size; a.nblocks = r.nblocks;
+    block_store_walk_args(h, r, step_lo, step_hi, block_size, a);
     a.mean = static_cast<double*>(d_mean.p); a.second = static_cast<double*>(d_sec.p);
     a.cross = static_cast<double*>(d_cross.p); a.blocks = static_cast<int64_t*>(d_c.p);
     launch_block_pairs(h, a, anc_args(h));

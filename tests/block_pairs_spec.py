@@ -1,5 +1,5 @@
 """Pairwise smoothing per block (gpf.h gpf_block_smooth_pairs), restated in NumPy from what a caller sees -- the Store of
-tests/block_backward_spec.py, as tests/block_smooth_spec.py, whose walk this is word for word, with the new statements beside the old one:
+tests/block_backward_spec.py, as tests/block_smooth_spec.py, whose walk this is (block_smooth_spec.walk with pair_sums=True):
 
   pairs       block b, T steps: c = b, W = q / S of the block's current WeightSummary; then for s = T .. lo + 1 the lineage check, and for every target j
               of block c in step s, one at a time in ASCENDING order:  W[j] == 0: the target is skipped entirely.  Otherwise lwa, (m, f), q, D and r as
@@ -18,8 +18,7 @@ import numpy as np
 
 import block_backward_spec as bsp
 import block_conditional_spec as cs
-from block_ancestor_spec import logtrans
-from block_smooth_spec import tree_sum
+from block_smooth_spec import tree_sum, walk
 
 
 def second_of(w, x):
@@ -43,65 +42,23 @@ def cross_of(x, A):
 
 
 def pairs(o, name, P, store, lo=1, hi=None, trans=True, fallback=False, return_A=False):
-    """trans=False: logtrans = 0; fallback=True: every r_ij is the indicator of the recorded parent (as block_smooth_spec.smooth)"""
-    T, bs, n, d, B = store.steps, store.bs, store.n, store.d, store.B
-    hi = T if hi is None else hi
-    assert 1 <= lo <= hi <= T
-    P = np.asarray(P, np.float64)
-    ns = hi - lo + 1
+    """trans, fallback: as block_smooth_spec.walk"""
+    hi = store.steps if hi is None else hi
+    assert 1 <= lo <= hi <= store.steps
+    B, d, ns = store.B, store.d, hi - lo + 1
     mean, second, cross = np.full((B, ns, d), np.nan), np.full((B, ns, d, d), np.nan), np.full((B, ns - 1, d, d), np.nan)
     blocks = np.zeros((B, ns), np.int64)
     As = {}
-    maps = {s: store.step_map(s) for s in range(lo + 1, T + 1)}
-    lwT = np.ascontiguousarray(store.lw[T - 1])
-    for b in range(B):
-        Pb = P[b] if P.ndim == 2 else P
-        c, c0, c1 = b, b * bs, min((b + 1) * bs, n)
-        ws = o.WeightSummary(np.ascontiguousarray(lwT[c0:c1]), c1 - c0)
-        if ws.bad:
-            continue
-        w = ws.q.astype(np.float64) / np.float64(ws.S)
-        for s in range(T, lo - 1, -1):                                        # w: the smoothing weights of block c's particles at step s
-            x = store.x(s)[c0:c1]
-            if s <= hi:
-                with np.errstate(invalid="ignore", over="ignore"):
-                    mean[b, s - lo] = [tree_sum(w * x[:, col]) for col in range(d)]
-                second[b, s - lo] = second_of(w, x)
-                blocks[b, s - lo] = c + 1
-            if s == lo:
-                break
-            pm = maps[s][c0:c1]
-            born = pm // bs
-            if born.min() != born.max():
-                break                                                         # the lineage is undefined from step s - 1 down
-            cp = int(born[0])
-            p0, p1 = cp * bs, min((cp + 1) * bs, n)
-            lwc, xc = store.lw[s - 2][p0:p1], store.x(s - 1)[p0:p1]
-            K = o.fix_K(p1 - p0)
-            acc, A = np.zeros(p1 - p0), np.zeros((p1 - p0, d))
-            for j in range(c1 - c0):
-                if w[j] == 0:
-                    continue                                                  # skipped entirely
-                lwa = lwc.copy()
-                if trans:
-                    with np.errstate(invalid="ignore"):
-                        lwa = lwc + logtrans(name, Pb, xc, x[j], store.obs[s - 1][c])
-                m, f = o.max_flags(np.ascontiguousarray(lwa))
-                if f != 0 or fallback:
-                    r = np.zeros(p1 - p0)
-                    r[pm[j] - p0] = 1.0
-                else:
-                    q = o.fixq(np.ascontiguousarray(lwa), m, K)
-                    r = q.astype(np.float64) / np.float64(int(q.sum(dtype=np.uint64)))
-                with np.errstate(invalid="ignore", over="ignore"):
-                    t = w[j] * r
-                    acc = acc + t
-                    for col in range(d):
-                        A[:, col] = A[:, col] + t * x[j, col]
-            if s <= hi:
-                cross[b, s - 1 - lo] = cross_of(xc, A)
-            As[(b, s - 1)] = A
-            w, c, c0, c1 = acc, cp, p0, p1
+    for b, s, c, w, x, A in walk(o, name, P, store, lo, trans, fallback, pair_sums=True):
+        if A is not None:
+            As[(b, s)] = A                                                    # of the pair (s, s + 1)
+            if s + 1 <= hi:
+                cross[b, s - lo] = cross_of(x, A)
+        if s <= hi:
+            with np.errstate(invalid="ignore", over="ignore"):
+                mean[b, s - lo] = [tree_sum(w * x[:, col]) for col in range(d)]
+            second[b, s - lo] = second_of(w, x)
+            blocks[b, s - lo] = c + 1
     return (mean, second, cross, blocks) + ((As,) if return_A else ())
 
 

@@ -2,12 +2,13 @@
 caller sees -- the Store of tests/block_backward_spec.py (every step's latent columns, log-weights, observation rows and resamples, read back through
 the public interface; nothing from the device's store):
 
-  smooth      block b, T steps: c = b, W = q / S of the block's current WeightSummary; then for s = T .. lo + 1: the targets are the particles of block c
+  walk        block b, T steps: c = b, W = q / S of the block's current WeightSummary; then for s = T .. lo + 1: the targets are the particles of block c
               in step s, pm = g_s[targets] their recorded parents; all in one block cp (else the lineage is undefined: NaN and 0 from step s - 1 down);
               for every target j, one at a time in ascending order: lwa = lw[s-1][block cp] + logtrans(P_b, x[s-1][block cp], x[s][j], obs[s][c])
               (block_ancestor_spec.logtrans), (m, f) = max_flags(lwa), q = fixq(lwa, m, fix_K(particles of cp)), D = the exact integer sum of q,
               r = q / D in float64 -- or the indicator of pm[j] where f != 0 --, acc = acc + W[j] * r (one multiply, one add).  W = acc, c = cp.
-              At every step in [lo, hi]: mean = tree(W x), var = tree(W (x - mean)^2) with the tree of DESIGN.md 3.5, restated as in
+              Written once, for smooth and for tests/block_pairs_spec.py (pair_sums=True: its statements per pair (i, j) beside acc's).
+  smooth      at every step of the walk in [lo, hi]: mean = tree(W x), var = tree(W (x - mean)^2) with the tree of DESIGN.md 3.5, restated as in
               tests/test_block_estimates_host.py.
   Returns mean, var [B, hi - lo + 1, d], weights [B, hi - lo + 1, bs] (0 beyond a short block) and the 1-based lineage blocks [B, hi - lo + 1].  A block
   with NaN / +Inf current weights: NaN everywhere, blocks 0.
@@ -47,16 +48,13 @@ def moments(w, x):
     return mu, s2
 
 
-def smooth(o, name, P, store, lo=1, hi=None, trans=True, fallback=False):
-    """trans=False: logtrans = 0; fallback=True: every r_ij is the indicator of the recorded parent (the two reductions the host tests check)"""
+def walk(o, name, P, store, lo=1, trans=True, fallback=False, pair_sums=False):
+    """the walk of every block, written once for smooth and block_pairs_spec.pairs: yields (b, s, c, w, x, A) for s = T, T - 1, ... down to lo or to the
+    step below which the lineage of final block b is undefined -- c the (0-based) block of the lineage at step s, w the smoothing weights and x the rows of
+    its particles, A the pair sums of the walk from s + 1 to s (pair_sums=True, s < T; else None).  A block with NaN / +Inf current weights yields nothing.
+    trans=False: logtrans = 0; fallback=True: every r_ij is the indicator of the recorded parent (the two reductions the host tests check)"""
     T, bs, n, d, B = store.steps, store.bs, store.n, store.d, store.B
-    hi = T if hi is None else hi
-    assert 1 <= lo <= hi <= T
     P = np.asarray(P, np.float64)
-    ns = hi - lo + 1
-    mean, var = np.full((B, ns, d), np.nan), np.full((B, ns, d), np.nan)
-    weights = np.full((B, ns, bs), np.nan)
-    blocks = np.zeros((B, ns), np.int64)
     maps = {s: store.step_map(s) for s in range(lo + 1, T + 1)}
     lwT = np.ascontiguousarray(store.lw[T - 1])
     for b in range(B):
@@ -65,14 +63,10 @@ def smooth(o, name, P, store, lo=1, hi=None, trans=True, fallback=False):
         ws = o.WeightSummary(np.ascontiguousarray(lwT[c0:c1]), c1 - c0)
         if ws.bad:
             continue
-        w = ws.q.astype(np.float64) / np.float64(ws.S)
+        w, A = ws.q.astype(np.float64) / np.float64(ws.S), None
         for s in range(T, lo - 1, -1):                                        # w: the smoothing weights of block c's particles at step s
             x = store.x(s)[c0:c1]
-            if s <= hi:
-                mean[b, s - lo], var[b, s - lo] = moments(w, x)
-                weights[b, s - lo] = 0.0
-                weights[b, s - lo, :c1 - c0] = w
-                blocks[b, s - lo] = c + 1
+            yield b, s, c, w, x, A
             if s == lo:
                 break
             pm = maps[s][c0:c1]
@@ -83,9 +77,11 @@ def smooth(o, name, P, store, lo=1, hi=None, trans=True, fallback=False):
             p0, p1 = cp * bs, min((cp + 1) * bs, n)
             lwc, xc = store.lw[s - 2][p0:p1], store.x(s - 1)[p0:p1]
             K = o.fix_K(p1 - p0)
-            acc = np.zeros(p1 - p0)
+            acc, A = np.zeros(p1 - p0), np.zeros((p1 - p0, d)) if pair_sums else None
             for j in range(c1 - c0):
-                lwa = lwc.copy()
+                if pair_sums and w[j] == 0:
+                    continue                                                  # the pairwise form skips the target entirely: 0 * x is not +0.0 for every x
+                lwa = lwc.copy()                                              # (for acc alone the skip would change no bit: acc >= +0.0, r finite and >= 0)
                 if trans:
                     with np.errstate(invalid="ignore"):
                         lwa = lwc + logtrans(name, Pb, xc, x[j], store.obs[s - 1][c])
@@ -96,8 +92,29 @@ def smooth(o, name, P, store, lo=1, hi=None, trans=True, fallback=False):
                 else:
                     q = o.fixq(np.ascontiguousarray(lwa), m, K)
                     r = q.astype(np.float64) / np.float64(int(q.sum(dtype=np.uint64)))
-                acc = acc + w[j] * r
+                with np.errstate(invalid="ignore", over="ignore"):
+                    t = w[j] * r
+                    acc = acc + t
+                    if pair_sums:
+                        for col in range(d):
+                            A[:, col] = A[:, col] + t * x[j, col]
             w, c, c0, c1 = acc, cp, p0, p1
+
+
+def smooth(o, name, P, store, lo=1, hi=None, trans=True, fallback=False):
+    """trans, fallback: as walk"""
+    hi = store.steps if hi is None else hi
+    assert 1 <= lo <= hi <= store.steps
+    B, ns = store.B, hi - lo + 1
+    mean, var = np.full((B, ns, store.d), np.nan), np.full((B, ns, store.d), np.nan)
+    weights = np.full((B, ns, store.bs), np.nan)
+    blocks = np.zeros((B, ns), np.int64)
+    for b, s, c, w, x, _ in walk(o, name, P, store, lo, trans, fallback):
+        if s <= hi:
+            mean[b, s - lo], var[b, s - lo] = moments(w, x)
+            weights[b, s - lo] = 0.0
+            weights[b, s - lo, :w.size] = w
+            blocks[b, s - lo] = c + 1
     return mean, var, weights, blocks
 
 

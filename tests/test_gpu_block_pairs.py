@@ -162,8 +162,8 @@ def test_a_whole_filter_resample_leaves_the_scattered_blocks_and_their_pairs_und
     d.close()
 
 
-def test_a_particle_of_weight_zero_at_a_past_step(g, o):
-    bs, B = 7, 64
+@pytest.mark.parametrize("bs,B", [(7, 64), (513, 3)])                        # a wave team; the workgroup team with a ragged lane and wave
+def test_a_particle_of_weight_zero_at_a_past_step(g, o, bs, B):
     dead = np.arange(bs * B) % bs % 2 == 1                                   # local 1, 3, 5 of every block
 
     def kill(d, t):
@@ -180,8 +180,8 @@ def test_a_particle_of_weight_zero_at_a_past_step(g, o):
     d.close()
 
 
-def test_a_target_on_its_fallback(g, o):
-    bs, B = 129, 4
+@pytest.mark.parametrize("bs,B", [(129, 4), (513, 4)])                       # a wave team; the workgroup team with a ragged lane and wave
+def test_a_target_on_its_fallback(g, o, bs, B):
     odd = np.arange(bs * B) % 3 == 0
 
     def foreign_slope(d, t):
@@ -200,8 +200,8 @@ def test_a_target_on_its_fallback(g, o):
     d.close()
 
 
-def test_a_nan_block_reads_nan(g):
-    bs = 7
+@pytest.mark.parametrize("bs", [7, 513])                                      # (n_of: three full blocks and a short fourth)
+def test_a_nan_block_reads_nan(g, bs):
     a, b = Dev(g, "lgssm2", bs), Dev(g, "lgssm2", bs)
     lw = b.st.log_weights
     lw[bs + 3] = np.nan

@@ -155,8 +155,8 @@ def test_a_whole_filter_resample_leaves_the_scattered_blocks_undefined(g, o):
 
 
 # ----------------------------------------------------------------------------- 5. edge weights
-def test_a_particle_of_weight_zero_at_a_past_step_has_smoothing_weight_zero(g, o):
-    bs, B = 7, 64
+@pytest.mark.parametrize("bs,B", [(7, 64), (513, 3)])                        # a wave team; the workgroup team with a ragged lane and wave
+def test_a_particle_of_weight_zero_at_a_past_step_has_smoothing_weight_zero(g, o, bs, B):
     dead = np.arange(bs * B) % bs % 2 == 1                                   # local 1, 3, 5 of every block
 
     def kill(d, t):
@@ -174,8 +174,8 @@ def test_a_particle_of_weight_zero_at_a_past_step_has_smoothing_weight_zero(g, o
     d.close()
 
 
-def test_a_target_no_candidate_leads_to_hands_its_mass_to_its_recorded_parent(g, o):
-    bs, B = 129, 4
+@pytest.mark.parametrize("bs,B", [(129, 4), (513, 4)])                       # a wave team; the workgroup team with a ragged lane and wave
+def test_a_target_no_candidate_leads_to_hands_its_mass_to_its_recorded_parent(g, o, bs, B):
     odd = np.arange(bs * B) % 3 == 0
 
     def foreign_slope(d, t):
@@ -202,8 +202,8 @@ def test_a_target_no_candidate_leads_to_hands_its_mass_to_its_recorded_parent(g,
     d.close()
 
 
-def test_a_nan_block_reads_nan(g):
-    bs = 7
+@pytest.mark.parametrize("bs", [7, 513])                                      # (n_of: three full blocks and a short fourth)
+def test_a_nan_block_reads_nan(g, bs):
     a, b = Dev(g, "lgssm2", bs), Dev(g, "lgssm2", bs)
     lw = b.st.log_weights
     lw[bs + 3] = np.nan
