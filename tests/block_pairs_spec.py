@@ -41,15 +41,15 @@ def cross_of(x, A):
     return out
 
 
-def pairs(o, name, P, store, lo=1, hi=None, trans=True, fallback=False, return_A=False):
-    """trans, fallback: as block_smooth_spec.walk"""
+def pairs(o, name, P, store, lo=1, hi=None, trans=True, fallback=False, return_A=False, skip=True):
+    """trans, fallback, skip: as block_smooth_spec.walk"""
     hi = store.steps if hi is None else hi
     assert 1 <= lo <= hi <= store.steps
     B, d, ns = store.B, store.d, hi - lo + 1
     mean, second, cross = np.full((B, ns, d), np.nan), np.full((B, ns, d, d), np.nan), np.full((B, ns - 1, d, d), np.nan)
     blocks = np.zeros((B, ns), np.int64)
     As = {}
-    for b, s, c, w, x, A in walk(o, name, P, store, lo, trans, fallback, pair_sums=True):
+    for b, s, c, w, x, A in walk(o, name, P, store, lo, trans, fallback, pair_sums=True, skip=skip):
         if A is not None:
             As[(b, s)] = A                                                    # of the pair (s, s + 1)
             if s + 1 <= hi:

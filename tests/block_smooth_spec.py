@@ -48,11 +48,12 @@ def moments(w, x):
     return mu, s2
 
 
-def walk(o, name, P, store, lo=1, trans=True, fallback=False, pair_sums=False):
+def walk(o, name, P, store, lo=1, trans=True, fallback=False, pair_sums=False, skip=True):
     """the walk of every block, written once for smooth and block_pairs_spec.pairs: yields (b, s, c, w, x, A) for s = T, T - 1, ... down to lo or to the
     step below which the lineage of final block b is undefined -- c the (0-based) block of the lineage at step s, w the smoothing weights and x the rows of
     its particles, A the pair sums of the walk from s + 1 to s (pair_sums=True, s < T; else None).  A block with NaN / +Inf current weights yields nothing.
-    trans=False: logtrans = 0; fallback=True: every r_ij is the indicator of the recorded parent (the two reductions the host tests check)"""
+    trans=False: logtrans = 0; fallback=True: every r_ij is the indicator of the recorded parent (the two reductions the host tests check); skip=False:
+    the pairwise form WITHOUT its rule that a target of weight 0 is skipped -- a mistake, for the negative control of tests/test_hp_block_pairs.py"""
     T, bs, n, d, B = store.steps, store.bs, store.n, store.d, store.B
     P = np.asarray(P, np.float64)
     maps = {s: store.step_map(s) for s in range(lo + 1, T + 1)}
@@ -79,7 +80,7 @@ def walk(o, name, P, store, lo=1, trans=True, fallback=False, pair_sums=False):
             K = o.fix_K(p1 - p0)
             acc, A = np.zeros(p1 - p0), np.zeros((p1 - p0, d)) if pair_sums else None
             for j in range(c1 - c0):
-                if pair_sums and w[j] == 0:
+                if pair_sums and skip and w[j] == 0:
                     continue                                                  # the pairwise form skips the target entirely: 0 * x is not +0.0 for every x
                 lwa = lwc.copy()                                              # (for acc alone the skip would change no bit: acc >= +0.0, r finite and >= 0)
                 if trans:

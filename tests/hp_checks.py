@@ -1183,21 +1183,80 @@ def check_backward(v, refs, store, blocks, seed, epoch, idx, label):
     return left
 
 
-def check_smooth(v, refs, store, blocks, mean, var, weights, lineage, label, lo=None):
-    """mean, var [B, T, d], weights [B, T, bs], lineage [B, T] of block_smoothed_moments(..., return_weights=True, return_blocks=True) over all T
-    steps of `store`: W_T against the block's normalised weights, every step below against hw.smooth_step applied from T downward, mean and variance
-    against hw.mean / hw.var under the reference's W.  `lo`: {block: the lowest step checked} (default 1: all).  Returns the number of (target, step)
-    pairs that took the fallback."""
-    T, bs, n, d = store.steps, store.bs, store.n, store.d
-    lwT, fallbacks, worst = np.asarray(store.lw[T - 1], np.float64), 0, _Worst()
+def pairs_guard(n, K, e_max, scale, value):
+    """What the bound of a RAW second or lag-one cross moment sum_i W_i g_i, g = x[a] x[c] (or sum_ij t_ij x_s^i[a] x_{s+1}^j[c]), may not exceed,
+    relative to max(1, |value|) as Violations.value measures it: smoothing_guard's form with the amplification 128 in place of 64, on the entry's
+    own scale m = sqrt(m_aa m_cc), m_aa = sum W x[a]^2 and m_cc = sum W x[c]^2 the raw second moments of the two columns (of steps s and s + 1
+    for a cross moment):
+
+        max(MEDIAN_REL_TOL, 128 (N 2^-K + expm1(2 e_max))) max(1, m) / max(1, |value|).
+
+    Where the 128 comes from.  As in sum_guard every weight is off by up to half a count whatever its size, N 2^-K relative for the numerator
+    and S together, and by expm1(2 e_max) of itself; a weight's error enters the sum times |g_i|.  Under sum_guard's own condition -- no particle
+    further than 8 standard deviations from the weighted mean -- x[a]^2 <= (|mu_a| + 8 sigma_a)^2 <= 2 mu_a^2 + 128 sigma_a^2 <= 128 (mu_a^2 +
+    sigma_a^2) = 128 m_aa, so |g_i| <= sqrt(128 m_aa 128 m_cc) = 128 m: twice sum_guard's 64, because an uncentred moment also carries the mean.
+    The part proportional to the weights needs less: sum W |g| <= m by Cauchy-Schwarz, amplification 1.  On the diagonal m = value and the guard
+    is the plain constant; an off-diagonal or cross entry can be near 0 while its terms are not (a correlation near 0), and a rounding is
+    proportional to the terms, so there the bound is held against m: a mistake of meaning (a transposed, shifted, centred or independent entry)
+    moves an entry by a fraction of m, twelve orders of magnitude above this.  The roundings of the accumulation into A and of the tree, (targets
+    + levels + 4) 2^-53 of sum |terms| <= m, are below N 2^-K for K <= 52 and sit inside the same constant.  Derived, not fitted to any output:
+    a condition on the case, which changes its inputs if its own bounds do not stay below it."""
+    return max(MEDIAN_REL_TOL, 128.0 * (n * 2.0 ** -K + np.expm1(2.0 * e_max))) * max(1.0, scale) / max(1.0, abs(value))
+
+
+def reference_walk(refs, store, blocks, lo=None, stop=1, pairs=False):
+    """The walk of the reference, written once for check_smooth and check_pairs as the kernels share block_store_walk: the list of what the
+    definition says of every checked block b, from step T down to max(stop, lo[b]) --
+        ("nan", b)                                   current weights with NaN / +Inf: everything of the block is NaN, its lineage 0;
+        ("step", b, s, c, c0, c1, W, e_max, A)       step s: the lineage is in block c = particles [c0, c1), W one E per particle (hw.norm_weights
+                                                     at T, hw.smooth_step below), e_max the largest bound of an ancestor weight met so far, A the pair
+                                                     sums of the walk from s + 1 to s (pairs=True and s < T, else None);
+        ("undefined", b, s)                          the particles of step s have their recorded parents in several blocks: no lineage below s;
+        ("fallbacks", k)                             last: the (target, step) pairs that took the fallback.
+    The targets' observation row is that of THEIR block c at step s + 1, the candidates are the block cp of their recorded parents, the parameters
+    the final block b's.  A list, so that two checks of one case share one walk (pairs=True serves both)."""
+    T, bs, n = store.steps, store.bs, store.n
+    lwT, fallbacks, out = np.asarray(store.lw[T - 1], np.float64), 0, []
     for b in blocks:
         c, (c0, c1) = b, _span(n, bs, b)
         if np.isnan(lwT[c0:c1]).any() or (lwT[c0:c1] == np.inf).any():
-            assert np.isnan(mean[b]).all() and np.isnan(var[b]).all() and np.isnan(weights[b]).all() and (lineage[b] == 0).all(), (label, b, "a NaN block")
+            out.append(("nan", b))
             continue
-        sm = hw.Softmax(lwT[c0:c1])
-        W, e_max = hw.norm_weights(sm), 0.0
+        W, e_max, A = hw.norm_weights(hw.Softmax(lwT[c0:c1])), 0.0, None
         for s in range(T, 0, -1):
+            out.append(("step", b, s, c, c0, c1, W, e_max, A))
+            if s == max(1, stop, (lo or {}).get(b, 1)):
+                break
+            pm = store.step_map(s)[c0:c1]
+            born = pm // bs
+            if born.min() != born.max():
+                out.append(("undefined", b, s))
+                break
+            cp = int(born[0])
+            p0, p1 = _span(n, bs, cp)
+            lwc, xc, xt = store.lw[s - 2][p0:p1], store.x(s - 1)[p0:p1], store.x(s)[c0:c1]
+            W, fell, em, *A = hw.smooth_step(refs[b], W, xt, lwc, xc, store.obs[s - 1][c], pm - p0, pairs=pairs)
+            A = A[0] if pairs else None
+            fallbacks, e_max = fallbacks + len(fell), max(e_max, em)
+            c, c0, c1 = cp, p0, p1
+    return out + [("fallbacks", fallbacks)]
+
+
+def check_smooth(v, refs, store, blocks, mean, var, weights, lineage, label, lo=None, walk=None):
+    """mean, var [B, T, d], weights [B, T, bs], lineage [B, T] of block_smoothed_moments(..., return_weights=True, return_blocks=True) over all T
+    steps of `store`: W_T against the block's normalised weights, every step below against hw.smooth_step applied from T downward, mean and variance
+    against hw.mean / hw.var under the reference's W.  `lo`: {block: the lowest step checked} (default 1: all).  `walk`: reference_walk(refs, store,
+    blocks, lo) where the caller has it already.  Returns the number of (target, step) pairs that took the fallback."""
+    d, worst = store.d, _Worst()
+    for ev in reference_walk(refs, store, blocks, lo) if walk is None else walk:
+        if ev[0] == "nan":
+            b = ev[1]
+            assert np.isnan(mean[b]).all() and np.isnan(var[b]).all() and np.isnan(weights[b]).all() and (lineage[b] == 0).all(), (label, b, "a NaN block")
+        elif ev[0] == "undefined":                                              # the lineage is undefined from step s - 1 down
+            b, s = ev[1:]
+            assert np.isnan(mean[b, :s - 1]).all() and np.isnan(var[b, :s - 1]).all() and np.isnan(weights[b, :s - 1]).all() and (lineage[b, :s - 1] == 0).all()
+        elif ev[0] == "step":
+            b, s, c, c0, c1, W, e_max, _ = ev[1:]
             what = f"{label}: W (block {b}, step {s})"
             assert lineage[b, s - 1] == c + 1, (label, b, s, lineage[b], c + 1)
             lws = np.asarray(store.lw[s - 1], np.float64)[c0:c1]
@@ -1214,20 +1273,83 @@ def check_smooth(v, refs, store, blocks, mean, var, weights, lineage, label, lo=
                 for name, got, want in (("mean", mean[b, s - 1, col], hw.mean(ws, x)), ("var", var[b, s - 1, col], hw.var(ws, x))):
                     v.value(f"{label}: smoothed {name}", (b, s, col), got, want, guard=guard)
                     worst.add(name, got, want)
-            if s == max(1, (lo or {}).get(b, 1)):
-                break
-            pm = store.step_map(s)[c0:c1]
-            born = pm // bs
-            if born.min() != born.max():                                        # the lineage is undefined from step s - 1 down
-                assert np.isnan(mean[b, :s - 1]).all() and np.isnan(var[b, :s - 1]).all() and np.isnan(weights[b, :s - 1]).all() and (lineage[b, :s - 1] == 0).all()
-                break
-            cp = int(born[0])
-            p0, p1 = _span(n, bs, cp)
-            lwc, xc, xt = store.lw[s - 2][p0:p1], store.x(s - 1)[p0:p1], store.x(s)[c0:c1]
-            W, fell, em = hw.smooth_step(refs[b], W, xt, lwc, xc, store.obs[s - 1][c], pm - p0)
-            fallbacks, e_max = fallbacks + len(fell), max(e_max, em)
-            c, c0, c1 = cp, p0, p1
+        else:
+            fallbacks = ev[1]
     worst.show(label)
+    return fallbacks
+
+
+def check_pairs(v, refs, store, blocks, mean, second, cross, lineage, label, lo=None, steps=None, walk=None):
+    """mean [B, ns, d], second [B, ns, d, d], cross [B, ns - 1, d, d], lineage [B, ns] of block_smoothed_pair_moments(..., steps=, return_blocks=True)
+    against the definition: the walk of check_smooth (reference_walk, pairs=True) from step T of `store`; at every step of the window
+    the lineage, mean against hw.mean, every entry of second against hw.second and second exactly symmetric; for every pair (s, s + 1) of the window
+    every entry of cross against hw.cross over hw.smooth_step's pair sums.  `steps` = (lo, hi): a windowed call -- walked from T, written for [lo, hi]
+    only, ns = hi - lo + 1 steps and hi - lo pairs (default: all T).  `lo`: {block: the lowest step checked}.  NaN and lineage 0 for a NaN block and
+    below the step where the lineage is undefined, the pair whose lower step is undefined included.  The sums' own bounds must stay below
+    smoothing_guard (mean) and pairs_guard (second, cross).
+
+    A particle of smoothing weight exactly 0 may hold a non-finite latent (it is a target the walk skips entirely).  By the statements of 5.7 the
+    entries of ITS step that multiply that column are NaN -- mean[col], second[col][.] and second[.][col] (0 * Inf), cross_s[col][.] of the pair
+    above it (Inf * A with A = +0.0) -- and are asserted to be; everything else, the pair below it and all lower steps, is finite and compared
+    with the reference, in which the particle contributes nothing.  Returns the fallbacks of the walk."""
+    T, d = store.steps, store.d
+    wlo, whi = (1, T) if steps is None else steps
+    ns = whi - wlo + 1
+    assert mean.shape[1:] == (ns, d) and second.shape[1:] == (ns, d, d) and cross.shape[1:] == (ns - 1, d, d) and lineage.shape[1:] == (ns,), (label, "shapes")
+    worst, diag_above, room = _Worst(), None, {}
+
+    def value(name, at, got, want, guard):
+        """one compared sum: the violation, the worst err / bound, and how much of its guard the reference's own bound takes"""
+        v.value(f"{label}: {name}", at, got, want, guard=guard)
+        key = name.split()[-1]
+        worst.add(key, got, want)
+        room[key] = max(room.get(key, 0.0), hp.rel_tol(want) / guard)
+
+    for ev in reference_walk(refs, store, blocks, lo, stop=wlo, pairs=True) if walk is None else walk:
+        if ev[0] == "nan":
+            b = ev[1]
+            assert np.isnan(mean[b]).all() and np.isnan(second[b]).all() and np.isnan(cross[b]).all() and (lineage[b] == 0).all(), (label, b, "a NaN block")
+        elif ev[0] == "undefined":                                              # steps below s and every pair whose lower step is below s
+            b, k = ev[1], ev[2] - wlo
+            assert np.isnan(mean[b, :k]).all() and np.isnan(second[b, :k]).all() and np.isnan(cross[b, :k]).all() and (lineage[b, :k] == 0).all(), (label, b, ev[2])
+        elif ev[0] == "step":
+            b, s, c, c0, c1, W, e_max, A = ev[1:]
+            ws, x, k = hw.Weighted(W), np.array(store.x(s)[c0:c1], np.float64), s - wlo
+            odd = ~np.isfinite(x)
+            assert all(W[i].v == 0 and W[i].e == 0.0 for i in np.nonzero(odd.any(axis=1))[0]), (label, b, s, "a non-finite row of a particle of weight: not a case")
+            nan_col = odd.any(axis=0)
+            x[odd] = 0.0                                                        # in the definition a particle of weight 0 contributes nothing
+            diag = [float(hw.second(ws, x, a, a).v) for a in range(d)]
+            n_c, K = c1 - c0, hw.fix_K(c1 - c0)
+            if s <= whi:
+                assert lineage[b, k] == c + 1, (label, b, s, lineage[b], c + 1)
+                assert bits_equal_nan(second[b, k], second[b, k].T).all(), (label, b, s, "second is not symmetric")
+                for a in range(d):
+                    if nan_col[a]:
+                        assert np.isnan(mean[b, k, a]) and np.isnan(second[b, k, a]).all(), (label, b, s, a, "0 * Inf")
+                        continue
+                    value("smoothed mean", (b, s, a), mean[b, k, a], hw.mean(ws, x[:, a]), smoothing_guard(n_c, K, e_max))
+                    for col in range(a, d):
+                        if nan_col[col]:
+                            continue
+                        want = hw.second(ws, x, a, col)
+                        guard = pairs_guard(n_c, K, e_max, math.sqrt(diag[a] * diag[col]), float(want.v))
+                        value("second", (b, s, a, col), second[b, k, a, col], want, guard)
+                        value("second", (b, s, col, a), second[b, k, col, a], want, guard)
+            if A is not None and s + 1 <= whi and s >= wlo:                     # the pair (s, s + 1)
+                for a in range(d):
+                    if nan_col[a]:
+                        assert np.isnan(cross[b, k, a]).all(), (label, b, s, a, "Inf * +0.0")
+                        continue
+                    for col in range(d):
+                        want = hw.cross(x, A, a, col)
+                        guard = pairs_guard(n_c, K, e_max, math.sqrt(diag[a] * diag_above[col]), float(want.v))
+                        value("cross", (b, s, a, col), cross[b, k, a, col], want, guard)
+            diag_above = diag
+        else:
+            fallbacks = ev[1]
+    worst.show(label)
+    print(f"{label}: worst bound / guard {({k: float(f'{r:.2g}') for k, r in room.items()})}")
     return fallbacks
 
 

@@ -54,7 +54,9 @@ ancestor_draw, backward_step and smooth_step restate PGAS' ancestor draw (Lindst
 Doucet & West 2004) and one of FFBSm (Doucet, Godsill & Andrieu 2000) from these: the inverse CDF of w_i f(x' | x_i) / sum at the exact uniform
 with eps = 2 D / S_lo, and W_s^i = sum_j W_{s+1}^j r_ij with r_ij = E(p_i, w_err_i), accumulated by E arithmetic (one multiply and one add per
 term at half an ulp each, W_{s+1}'s own bound carried through the product).  Flagged ancestor weights (NaN, +Inf, all -Inf) are the spec's
-exact fallback -- the recorded parent -- and are reported as such, not bounded.
+exact fallback -- the recorded parent -- and are reported as such, not bounded.  The pairwise smoother comes out of the same
+transition: smooth_step(pairs=True) accumulates A_i[c] = sum_j t_ij x_{s+1}^j[c], t_ij = W_{s+1}^j r_ij, beside W_s; `cross` and `second` at the
+end of this module turn A and W into the raw lag-one and second moments, each an E.
 
 The rest of the resize family, from src/resize.jl of the reference:
 
@@ -618,28 +620,46 @@ def backward_step(ref, lw, xs, x_held, obs, seed, epoch, slot, sm=None):
     return a, und, sm
 
 
-def smooth_step(ref, W_next, x_next, lw, xs, obs, parents):
+def smooth_step(ref, W_next, x_next, lw, xs, obs, parents, pairs=False):
     """one transition of FFBSm: W_s^i = sum_j W_{s+1}^j w_s^i f(x_{s+1}^j | x_s^i) / sum_l w_s^l f(x_{s+1}^j | x_s^l), one E per candidate i.
     W_next: one E per target j; x_next: the targets' latents; lw, xs: the candidates' recorded weights and latents; parents[j]: the local index
     of target j's recorded parent among the candidates, read only on the fallback.  A target of weight exactly 0 adds nothing, and neither does a
     candidate that is -Inf or certainly flushed (Softmax.dead: more than 708 plus the bounds below the maximum) -- its W stays E(0, 0), which the
     check compares exactly.  Returns (W_s,
-    the targets that took the fallback, the largest bound e_max of an ancestor weight met)."""
+    the targets that took the fallback, the largest bound e_max of an ancestor weight met).
+
+    pairs=True: the pairwise smoother's sums of the same transition from the SAME loop and the same ancestor softmax, computed once
+    per target: A_i[c] = sum_j t_ij x_{s+1}^j[c] with the pairwise smoothing weight t_ij = W_{s+1}^j p_ij, one E per candidate and latent column,
+    returned as a fourth value.  Value: the real t_ij (the real W_{s+1}^j times the real p_ij) times the Float64 x, summed exactly.  Bound, in E
+    arithmetic, per term: W_{s+1}^j's own bound and p_ij's (w_err: the counts, their sum, two conversions and the division that is r) through the
+    product, one rounding for t = W r, one for t * x (x is a Float64: exact), and one per addition into A in ascending j over the live targets --
+    half an ulp of the largest magnitude the partial sum can have, its real value plus its bound, which the sum of |terms| plus their bounds is
+    never below: the terms are signed and nothing is taken from their cancellation.  A target of weight exactly 0 is skipped before its row is
+    read (its row may hold anything, an infinity included); a dead or certainly flushed candidate keeps A_i = E(0, 0); a target on its fallback
+    gives its whole W_j to the recorded parent: t = W_j for that pair and no other."""
     acc, fell, e_max = [E(0.0) for _ in range(len(lw))], [], 0.0
+    A = [[E(0.0)] * len(x_next[0]) for _ in range(len(lw))] if pairs else None
+
+    def add(i, t, xj):
+        acc[i] = acc[i] + t
+        if pairs:
+            A[i] = [a + t * x for a, x in zip(A[i], xj)]
+
     for j, Wj in enumerate(W_next):
         if Wj.v == 0 and Wj.e == 0.0:
             continue
         sm = ancestor_softmax(ref, lw, xs, x_next[j], obs)
+        xj = [E(float(x)) for x in x_next[j]] if pairs else None
         if sm is FALLBACK:
-            acc[parents[j]] = acc[parents[j]] + Wj * E(1.0)
+            add(parents[j], Wj * E(1.0), xj)
             fell.append(j)
             continue
         p, we, e_max = sm.p, sm.w_err(), max(e_max, sm.e_max)
         for i in range(len(acc)):
             if sm.dead[i]:
                 continue                                                       # -Inf, or certainly flushed by exp_: r = 0 EXACTLY, the term is +0.0
-            acc[i] = acc[i] + Wj * E(p[i], we[i])
-    return acc, fell, e_max
+            add(i, Wj * E(p[i], we[i]), xj)
+    return (acc, fell, e_max, A) if pairs else (acc, fell, e_max)
 
 
 class Weighted:
@@ -652,3 +672,29 @@ class Weighted:
 
     def w_err(self):
         return self._e
+
+
+def second(ws, x, a, c):
+    """sum_i W_i x_i[a] x_i[c] as an E, for the statement (W x[a]) x[c] of DESIGN.md 5.7: each term carries W_i's bound times |x[a] x[c]| and
+    the two products' roundings ((1 + u)^2 - 1 = 2u + u^2 of the largest magnitude the term can have), the tree one rounding per level over
+    sum |terms|.  `x`: [n, d]"""
+    x = np.asarray(x, np.float64)
+    g = [mpf(float(s)) * mpf(float(t)) for s, t in zip(x[:, a], x[:, c])]
+    v = M.fsum([p * t for p, t in zip(ws.p, g)])
+    ag = np.array([abs(float(t)) for t in g])
+    we = ws.w_err()
+    at = float(np.sum(np.abs(ws.pf) * ag))
+    w_part = float(np.sum(ag * we))
+    term_err = w_part + (2 * U + U * U) * (at + w_part)
+    return E(v, term_err + _tree_err(ws.n, at + term_err))
+
+
+def cross(x, A, a, c):
+    """cross_s[a][c] = sum_i x_s^i[a] A_i[c] as an E (A: smooth_step's fourth value, the sums over the targets of step s + 1): A_i[c]'s bound
+    times |x|, one rounding for the product x * A, the tree of DESIGN.md 3.5 one rounding per level over sum |terms| (tree_levels)"""
+    xa = np.asarray(x, np.float64)[:, a]
+    v = M.fsum([mpf(float(t)) * Ai[c].v for t, Ai in zip(xa, A)])
+    at = float(sum(abs(float(t)) * abs(float(Ai[c].v)) for t, Ai in zip(xa, A)))
+    a_part = float(sum(abs(float(t)) * Ai[c].e for t, Ai in zip(xa, A)))
+    term_err = a_part + U * (at + a_part)
+    return E(v, term_err + _tree_err(len(A), at + term_err))
