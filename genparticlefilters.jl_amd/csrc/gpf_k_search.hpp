@@ -1053,7 +1053,11 @@ __global__ __launch_bounds__(MBLOCK, 2) void k_search_strat(SearchArgs a)
                 const Div128 dg = div128_setup(gtot + 1);                               // (as k_sorted_tiles)
                 vlo = div128(gpre, dg); Wt = div128(gpre + gown, dg) - vlo;
             }
-            const uint64_t S = a.ws->S;
+            // the uniform fallback (all -Inf: q_i = 1, S = N) places its targets on the grid of S 2^K and drops the K bits again: on the grid
+            // of S = N one count is a whole particle, the floors of Tlo and Tw would move most slots by one and never reach the last particle
+            // (DESIGN.md §3.6).  Not on a shard: k_sorted_plan forms the same targets and keeps the coarse grid.
+            const int sh = !a.plan && (a.ws->flags & FLAG_ALL_NEGINF) ? a.K : 0;       // kernel-uniform
+            const uint64_t S = a.ws->S << sh;
             const uint64_t Tlo = mulhi64(vlo, S), Tw = mulhi64(vlo + Wt, S) - Tlo;     // the tile's targets lie in [Tlo, Tlo + Tw]
             const double inv_s = 1.0 / (double)st, dTw = (double)Tw;
             const uint64_t off = wex + (inc - run);
@@ -1063,11 +1067,11 @@ __global__ __launch_bounds__(MBLOCK, 2) void k_search_strat(SearchArgs a)
                 const int64_t j = j0 + (int64_t)t0 + k;
                 // (a shard: slots above its served range -- a higher shard's, targets beyond its CDF -- read as padding; the `skip` slots below
                 //  it -- targets below its CDF -- as 0: the targets stay ascending, neither kind is written out)
-                const uint64_t Tg = j < n_out ? sorted_target(off + e[k], inv_s, Tlo, Tw, dTw) : ~0ull;     // resample.jl:59 on the sorted uniform
+                const uint64_t Tg = j < n_out ? sorted_target(off + e[k], inv_s, Tlo, Tw, dTw) >> sh : ~0ull;     // resample.jl:59 on the sorted uniform
                 T[k] = j < n_out ? (j >= skip ? Tg - (uint64_t)t_off : 0) : ~0ull;
             }
-            Lj0 = sorted_target(s_e0, inv_s, Tlo, Tw, dTw);                             // the block's first target ...
-            Lj1 = sorted_target(st - 1 - s_eN, inv_s, Tlo, Tw, dTw) + 1;                // ... and one past its last (real) one
+            Lj0 = sorted_target(s_e0, inv_s, Tlo, Tw, dTw) >> sh;                       // the block's first target ...
+            Lj1 = (sorted_target(st - 1 - s_eN, inv_s, Tlo, Tw, dTw) >> sh) + 1;        // ... and one past its last (real) one
             Lj0 = Lj0 > (uint64_t)t_off ? Lj0 - (uint64_t)t_off : 0;                    // (local; the tile may start below the shard's CDF
             Lj1 -= (uint64_t)t_off;                                                     //  and end above it: a block with a served slot has Lj1 > t_off)
             Lj0s = (int64_t)Lj0;

@@ -61,7 +61,8 @@ typedef enum { GPF_RESAMPLE_MULTINOMIAL = 0, GPF_RESAMPLE_RESIDUAL = 1, GPF_RESA
                 * state.parents comes out non-decreasing instead of as an i.i.d. sequence (src/resample.jl:59), so slot k of the new
                 * population is NOT exchangeable with slot k' any more -- harmless for a filter that treats its particles as a set, visible
                 * to code that cuts the population into views by position.  The ancestor search becomes a streaming merge and the row
-                * gather reads ascending rows.  gpf_resample (and views) only. */
+                * gather reads ascending rows.  gpf_resample (and views) only.  Invalid weights (all -Inf, the uniform fallback): the targets
+                * are placed on the grid of N 2^K, not of S = N, so that every particle is drawn with probability 1 / N. */
                GPF_RESAMPLE_MULTINOMIAL_SORTED = 4 } gpf_resample_method;
 /* method::Symbol of pf_rejuvenate! (src/rejuvenate.jl:18-27) */
 typedef enum { GPF_REJUVENATE_MOVE = 0, GPF_REJUVENATE_REWEIGHT = 1 } gpf_rejuvenate_method;

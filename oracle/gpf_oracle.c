@@ -645,7 +645,9 @@ O_EXPORT void o_targets_stratified(uint64_t seed, uint32_t epoch, int64_t j0, in
  *     e_i   = trunc(neglog(u_i) 2^44),  u_i the 52-bit uniform of resample slot j0 + i, neglog = -log to ~6e-12 (o_neglog_u52);  p_j = sum of the e_i of the tile up to slot j;
  *     s_t   = the tile's sum + 1 (the last tile: + e_N)
  *     Tlo_t = floor(Vlo_t S / 2^64)  (the multinomial target formula on the tile's first uniform),  Tw_t = Tlo_{t+1} - Tlo_t
- *     T_j   = Tlo_t + min(Tw_t, trunc(fl(fl(p_j) fl(1 / fl(s_t))) fl(Tw_t)))      (fl: round to Float64)  */
+ *     T_j   = Tlo_t + min(Tw_t, trunc(fl(fl(p_j) fl(1 / fl(s_t))) fl(Tw_t)))      (fl: round to Float64)
+ * Under the uniform fallback (all -Inf: q_i = 1, S = N) the caller passes S 2^K and drops the K low bits of T_j (oracle.py
+ * ancestors_sorted; k_search_strat<true>): on the grid of S = N a count is a whole particle and the floors above would be visible.  */
 #define O_SP_TILE 2048
 #define O_SP_E 44
 O_EXPORT int32_t o_gamma_E(int64_t ntl)

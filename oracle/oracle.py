@@ -167,6 +167,14 @@ def targets_sorted(seed, epoch, j0, n, S) -> np.ndarray:
     return T
 
 
+def ancestors_sorted(sp, seed, epoch, j0, n) -> np.ndarray:
+    """ancestors of the n slots of "multinomial_sorted" over the weight summary `sp`.  Under the uniform fallback (all -Inf: q_i = 1,
+    S = N) the targets are placed on the grid of S 2^K and the K bits dropped again: on the grid of S = N one count is a whole particle,
+    the floors of Tlo_t and Tw_t would move most slots by one and the last particle would never be drawn"""
+    sh = sp.K if sp.uniform else 0
+    return upper_bound(sp.cdf, targets_sorted(seed, epoch, j0, n, sp.S << sh) >> np.uint64(sh))
+
+
 def targets_stratified(seed, epoch, j0, n, N, S) -> np.ndarray:
     T = np.empty(n, np.uint64)
     lib().o_targets_stratified(seed, epoch, j0, n, N, S, T)
@@ -331,8 +339,7 @@ class OracleFilter:
             T = targets_multinomial(self.seed, epoch, 0, N, sp.S)
             anc = upper_bound(sp.cdf, T)
         elif method == "multinomial_sorted":                        # :59 with the uniforms drawn in sorted order (opt-in)
-            T = targets_sorted(self.seed, epoch, 0, N, sp.S)
-            anc = upper_bound(sp.cdf, T)
+            anc = ancestors_sorted(sp, self.seed, epoch, 0, N)
         elif method == "stratified":                                # :155-170
             if sort_particles:
                 order = argsort_desc(lp)                            # :156-157
@@ -657,7 +664,7 @@ class OracleSubState:
         if method == "multinomial":
             anc = upper_bound(sp.cdf, targets_multinomial(s.seed, epoch, self.start, N, sp.S))
         elif method == "multinomial_sorted":                            # (slot ids start, start + 1, ... like the other streams of a view)
-            anc = upper_bound(sp.cdf, targets_sorted(s.seed, epoch, self.start, N, sp.S))
+            anc = ancestors_sorted(sp, s.seed, epoch, self.start, N)
         elif method == "stratified":
             if sort_particles:
                 order = argsort_desc(lp); cdf, S, _, _ = scan(sp.q[order])

@@ -44,6 +44,12 @@ class OracleAdapter:
     def resample(self, method, alpha=None, sort_particles=True):
         return bool(self.f.resample(method, priority_alpha=alpha, sort_particles=sort_particles, check=False))
 
+    def resample_view(self, sl, method, alpha=None):
+        """pf_resample!(state[sl], method): (the verdict, the view's own 1-based parents)"""
+        v = self.f[sl]
+        invalid = bool(v.resample(method, priority_alpha=alpha, check=False))
+        return invalid, np.array(v.parents)
+
     def resize(self, n_new, method, alpha=None):
         return bool(self.f.resize(n_new, method, priority_alpha=alpha, check=False))
 
@@ -139,10 +145,10 @@ class OracleAdapter:
     def rejuvenate_uncounted(self, method, n_iters):
         self.f.rejuvenate(method, n_iters)
 
-    def step_ess(self, obs, ess_threshold):
+    def step_ess(self, obs, ess_threshold, method="multinomial"):
         go = self.f.effective_sample_size() < ess_threshold * self.f.n
         if go:
-            self.f.resample("multinomial", check=False)
+            self.f.resample(method, check=False)
         self.f.update(obs)
         return bool(go)
 
@@ -183,6 +189,16 @@ class DeviceAdapter:
     def resample(self, method, alpha=None, sort_particles=True):
         kw = {"sort_particles": sort_particles} if method == "stratified" else {}
         return self._invalid(lambda check: self.g.pf_resample(self.st, method, priority_fn=self._prio(alpha), check=check, **kw))
+
+    def resample_view(self, sl, method, alpha=None):
+        """the whole filter as a view is the library's local resample: its parents are the source's (tests/test_sorted_multinomial.py)"""
+        v = self.st[sl]
+        try:
+            invalid = self._invalid(lambda check: self.g.pf_resample(v, method, priority_fn=self._prio(alpha), check=check))
+            whole = v.start == 0 and v.step == 1 and v.n_particles == self.st.n_particles
+            return invalid, (self.st.parents if whole else v.parents)
+        finally:
+            v.close()
 
     check = False
 
@@ -279,8 +295,8 @@ class DeviceAdapter:
         """without `count` the move is left to the pf_update that follows: it runs inside the update kernel"""
         self.g.pf_rejuvenate(self.st, None, (), n_iters, method=method)
 
-    def step_ess(self, obs, ess_threshold):
-        return bool(self.g.pf_step_ess(self.st, (), (), obs, ess_threshold=ess_threshold, method="multinomial", check=False))
+    def step_ess(self, obs, ess_threshold, method="multinomial"):
+        return bool(self.g.pf_step_ess(self.st, (), (), obs, ess_threshold=ess_threshold, method=method, check=False))
 
 
 # ------------------------------------------------------------------------------------------- the checked run
@@ -405,6 +421,8 @@ class Run:
             assert not bad and left_out == 0, f"{label}: residual resampling with undecidable copy counts {bad[:4]} / tail slots {ref.undecidable[:4]}"
         else:
             assert left_out <= MAX_UNDECIDABLE, (label, ref.undecidable)
+        if method == "multinomial_sorted":
+            assert (np.diff(parents0) >= 0).all(), f"{label}: the ancestors of the sorted multinomial are not non-decreasing"
         rows, lw = a.rows, a.lw
         assert rows.shape[0] == n_new and np.array_equal(np.ascontiguousarray(rows).view(np.uint64), np.ascontiguousarray(rows0[parents0]).view(np.uint64)), f"{label}: gathered rows"
         v = Violations()
@@ -427,6 +445,47 @@ class Run:
         rows0, lw0 = self.a.rows, self.a.lw
         invalid = self.a.resample(method, alpha, sort_particles)
         left_out = self._check_resampled(f"resample {method}", method, alpha, sort_particles, rows0, lw0, self.n, invalid)
+        self.epoch += 1
+        return left_out
+
+    def resample_view(self, sl, method="multinomial", alpha=None):
+        """pf_resample!(state[sl], method) for a contiguous or strided slice (view.jl:35-48, resample.jl:185-187, :205-218): the view's
+        weights alone, K from ITS particle count; slot j of the view reads the resample id start + j -- the strata of a stratified
+        resample are local to the view (j of n), their uniforms those of the ids start + j, and a tile total of the sorted multinomial
+        reads id start + first; ancestors local to the view; no log-ML update: the new weights keep the view's total,
+        logsumexp(lw) - log n each, or lw[a] - lp[a] + logsumexp(lw) - logsumexp(lw[a] - lp[a]) under a priority.  Rows and weights
+        outside the view: bit-unchanged.  Returns the number of undecidable slots."""
+        rows0, lw0 = self.a.rows, self.a.lw
+        invalid, parents = self.a.resample_view(sl, method, alpha)
+        idx = np.arange(self.n)[sl]
+        n, label = len(idx), f"resample {method} of the view {sl.start}:{sl.stop}:{sl.step}"
+        lwv = lw0[idx]
+        lp = lwv if alpha is None else np.float64(alpha) * lwv
+        K = hw.fix_K(n)
+        sm, ref, _ = hw.reference_ancestors(lp, method, self.seed, self.epoch, None, True, K, slot0=int(idx[0]))
+        assert invalid is None or invalid == sm.invalid, (label, invalid)
+        parents0 = np.asarray(parents)[:n] - 1
+        left_out = hw.check_ancestors(ref, parents0, sm, label)
+        assert left_out <= MAX_UNDECIDABLE, (label, ref.undecidable)
+        if method == "multinomial_sorted":
+            assert (np.diff(parents0) >= 0).all(), f"{label}: the ancestors of the sorted multinomial are not non-decreasing"
+        rows, lw = self.a.rows, self.a.lw
+        bits = lambda x: np.ascontiguousarray(x).view(np.uint64)
+        assert rows.shape == rows0.shape and np.array_equal(bits(rows[idx]), bits(rows0[idx][parents0])), f"{label}: gathered rows"
+        out = np.ones(self.n, bool)
+        out[idx] = False
+        assert np.array_equal(bits(rows[out]), bits(rows0[out])), f"{label}: rows outside the view changed"
+        assert np.array_equal(bits(lw[out]), bits(lw0[out])), f"{label}: weights outside the view changed"
+        v = Violations()
+        total = hw.Softmax(lwv, K).lse()
+        if alpha is None:
+            want = [total - hw.log_n(n)] * n
+        else:
+            want = hw.weights_after(lwv, lp, parents0, total=total)
+        for j in range(n):
+            v.value("lw of a view after its resample", j, lw[idx[j]], want[j])
+        self._lml_estimate(v, "log_ml_estimate", hw.Softmax(lw))                 # the running estimate is the parent's, untouched
+        self._note(label, v)
         self.epoch += 1
         return left_out
 
@@ -784,12 +843,12 @@ class Run:
         v.finish(f"{self.model.name} move fused into update")
         return len(undecidable)
 
-    def step_ess(self, obs, ess_threshold=0.5, must_decide=False):
+    def step_ess(self, obs, ess_threshold=0.5, must_decide=False, method="multinomial"):
         """pf_step_ess: (resample if ESS < threshold N), update, in one call.  The resampled x_{t-1} is what the new row keeps in its second
         half: an old row, from which the update is predicted; the weights restart from 0 after a multinomial resample."""
         obs = np.ascontiguousarray(obs, np.float64)
         rows0, lw0 = self.a.rows, self.a.lw
-        resampled = self.a.step_ess(obs, ess_threshold)
+        resampled = self.a.step_ess(obs, ess_threshold) if method == "multinomial" else self.a.step_ess(obs, ess_threshold, method)
         rows, lw, v, d = self.a.rows, self.a.lw, Violations(), self.d
         # the verdict ESS < threshold N is the reference's wherever the reference can tell
         sm0 = hw.Softmax(lw0)
@@ -801,8 +860,11 @@ class Run:
         if resampled:
             # the resample of the call, seen through the update that followed it: ancestors, the gathered x_{t-1}, the log-ML estimate
             parents0 = np.asarray(self.a.parents) - 1
-            ref = hw.multinomial(sm0, self.seed, self.epoch)
+            assert method in ("multinomial", "multinomial_sorted"), method       # the forms whose weights restart from 0 with every slot drawn
+            ref = (hw.multinomial if method == "multinomial" else hw.sorted_multinomial)(sm0, self.seed, self.epoch)
             assert hw.check_ancestors(ref, parents0, sm0, "step_ess resample") <= MAX_UNDECIDABLE
+            if method == "multinomial_sorted":
+                assert (np.diff(parents0) >= 0).all(), "step_ess: the ancestors of the sorted multinomial are not non-decreasing"
             assert np.array_equal(np.ascontiguousarray(rows[:, d:2 * d]).view(np.uint64), np.ascontiguousarray(rows0[parents0][:, :d]).view(np.uint64))
             self.lml = self.lml + (sm0.lse() - hw.log_n(self.n))
             self.epoch += 1

@@ -32,6 +32,41 @@ documents, per particle, in counts of the fixed-point weight q_i ~ exp(lp_i - m)
 A slot whose target lies within the bound of a CDF boundary of THIS reference is undecidable and is not compared.  No figure here is fitted
 to an output of the oracle or of the device.
 
+The sorted multinomial (the header comment of o_targets_sorted; this project's own construction, no line of resample.jl behind
+it).  In the reals: e_i = -log((k_i + 1/2) 2^-52), k_i the top 52 bits of the 64-bit word pair of resample slot slot0 + i, i = 0 .. n; tiles of
+2048 consecutive slots; gamma_t the Marsaglia-Tsang variate of shape c_t (c_t + 1 in the last tile) from the blocks 1 + 2k / 2 + 2k of counter
+(slot0 + first, ., epoch, resample tag); V_t = sum_{r<t} gamma_r / sum gamma_r; slot j of tile t at x_j = V_t + (V_{t+1} - V_t) p_j / s_t, p_j the
+tile's spacings up to and including j, s_t the tile's sum (+ e_n in the last tile); the ancestor is the inverse CDF of w at x_j.  The spec
+computes x_j as the integer T_j against the integer CDF.  With S the integer sum of the weights (S >= S_lo), how far T_j / S may sit from x_j:
+
+    gamma         every Float64 operation of gamma_tile carried as an E (d = shape - fl(1/3), c = 1 / sqrt(9 d), Box-Muller's x, v1 = 1 + c x,
+                  v = (v1 v1) v1, d v): |fl(d v) - gamma_t| <= eg_t.  The two DECISIONS, v1 > 0 and log u < ((x^2 / 2 + d) - d v) + d log v, are
+                  decidable when the two sides differ by more than their summed E bounds (the right side's bound carries the cancellation of
+                  (x^2 / 2 + d) - d v at d ~ 2048: half an ulp of 2048 per term, ~7e-13, against |log u - right side| of order 1); asserted
+                  decidable in every case, never skipped.  G_t = trunc(fl(d v) 2^Eg): a_t = eg_t + 2^-Eg, Eg = min(48, 50 - ceil(log2 ntl)),
+                  read only to size the bound.
+    V_t           Gpre_t / Gtot against A / B (A = sum_{r<t} gamma_r, B = sum gamma_r): |dA| <= sum_{r<t} a_r, |dB| <= sum a_r + 2^-Eg (the + 1
+                  of Gtot), so |Gpre_t / Gtot - V_t| <= (|dA| + V_t |dB|) / (B - |dB|) = dV_t; the floor of Vlo_t 2^-64 on top.
+    Tlo_t         floor(Vlo_t S / 2^64): one count of S.  b_t = dV_t + 2^-64 + 1 / S_lo bounds |Tlo_t / S - V_t| (b_0 = 0: Tlo_0 = 0 = V_0
+                  exactly), and |Tw_t / S - (V_{t+1} - V_t)| <= b_t + b_{t+1} = dW_t.
+    p_j / s_t     per spacing c = 1e-11 (neglog_u52's absolute bound, the figure tests/test_hp_math.py pins: passed in, the only imported
+                  constant) + 2^-44 (the truncation): |p_j 2^-44 - P_j| <= (k + 1) c for the k + 1 spacings summed, |s_t 2^-44 - s^_t| <=
+                  m c + 2^-44 for the tile's m spacings and its + 1; the ratio r = p / s against r^ = P / s^:
+                  dr_j = ((k + 1) c + r^ (m c + 2^-44)) / (s^ - m c - 2^-44).
+    the product   fl(fl(fl(p) fl(1 / fl(s))) fl(Tw)): the four roundings of the quotient (two conversions, the reciprocal, the product), the
+                  conversion of Tw (it may exceed 2^53) and the last product, eta = expm1(6 * 2^-53) relative.  The clamp min(Tw, .) costs
+                  nothing: p_j < s_t, the clamp only moves a rounded-up value back towards the real one.
+    the last truncation: one count of S, 1 / S_lo.
+
+    eps_j = 2 D / S_lo                                                     the weight side, as for `multinomial`
+          + b_t + dr_j (W_t + dW_t) + r^_j dW_t + eta (W_t + dW_t) + 1 / S_lo,     W_t = V_{t+1} - V_t
+
+computed per slot; a slot whose x_j lies within eps_j of a CDF boundary of this reference is undecidable.  Under the uniform fallback (all
+-Inf) the spec's weights are q_i = 1 and S = n; it places the targets on the grid of S 2^K and drops the K bits again, so a
+count is 2^-K / n there: S_lo = n 2^K, D = 0.  (On the grid of S = n a count is a whole particle: b_t + dW_t + 1 / S_lo is a few cells wide and
+every slot undecidable by this derivation.  That is how these tests found that the spec had used that grid, had moved 903 of 2049 ancestors
+by one against the construction and could never draw the last particle.)
+
 Inexact log-weights (Softmax.inexact): the ancestor weights lwa_i = lw_i + logtrans_i of PGAS, backward simulation and smoothing are not
 Float64 inputs but Float64 RESULTS: the device holds l_i with |l_i - a_i| <= e_i, a_i the real value (an E of tests/hp_reference.py).  The
 reference is safe_softmax of the a_i; the device subtracts ITS maximum m = max l_i.  With a* = max a_i and mu = m - a*:
@@ -228,9 +263,13 @@ class Ancestors:
 
 
 def _inverse_cdf(cdf, xs, eps):
-    """first a with cdf[a] > x per target; undecidable when x is within eps of the boundary below or above (0 and 1 are exact)"""
+    """first a with cdf[a] > x per target; undecidable when x is within eps of the boundary below or above (0 and 1 are exact).  `eps`: one
+    bound for all targets, or one per target"""
     n, anc, und = len(cdf), [], []
+    per_slot = None if np.isscalar(eps) else eps
     for j, x in enumerate(xs):
+        if per_slot is not None:
+            eps = per_slot[j]
         a = min(bisect.bisect_right(cdf, x), n - 1)
         near = (a > 0 and x - cdf[a - 1] <= eps) or (a < n - 1 and cdf[a] - x <= eps)
         anc.append(a)
@@ -246,16 +285,173 @@ def multinomial(sm, seed, epoch, n_slots=None, slot0=0):
     return Ancestors(anc, und, eps)
 
 
+# ------------------------------------------------------------------------------------------- the sorted multinomial
+SP_TILE = 2048                    # slots per tile
+SP_ATTEMPTS = 8                   # Marsaglia-Tsang attempts per tile total, then the value d
+SP_FRAC = 44                      # a spacing is truncated at 2^-44
+NEGLOG_ABS = 1e-11                # neglog_u52's absolute bound: the figure tests/test_hp_math.py asserts, not measured here
+MUTATIONS = ("attempt_blocks", "accept_words23", "last_shape", "no_e_n", "tile_id_local", "spacing_slot0", "spacing_pair", "d_half",
+             "second_normal", "exclusive", "boundary_next")      # what the negative controls hand the checker; never a truth for the device
+SORTED_MAX = {}                   # largest derived bound per quantity over the calls so far (`python tests/test_hp_sorted_multinomial.py`)
+
+
+def _worst(what, x):
+    SORTED_MAX[what] = max(SORTED_MAX.get(what, 0.0), float(x))
+
+
+def gamma_E(ntl):
+    """Eg = min(48, 50 - ceil(log2 ntl)): read only to size the bound, as fix_K is"""
+    return min(48, 50 - (int(ntl) - 1).bit_length())
+
+
+class GammaTile:
+    """one tile total: .value the E of fl(d v) (its .v the real gamma_t of the construction), .attempt the accepted attempt (SP_ATTEMPTS: none,
+    the value is d), .negative how many attempts had 1 + c x <= 0, .margin the smallest |side - side| - bound over its decisions"""
+
+    def __init__(self, value, attempt, negative, margin):
+        self.value, self.attempt, self.negative, self.margin = value, attempt, negative, margin
+
+
+def gamma_tile(seed, gid, epoch, shape, mutate=None):
+    """Marsaglia & Tsang (2000), Gamma(shape, 1) for an integer shape >= 1, every Float64 operation an E.  Attempt k: x the first Box-Muller
+    normal of block 1 + 2k, u the 52-bit uniform of words (0,1) of block 2 + 2k, both of counter (gid, ., epoch, resample tag); reject when
+    1 + c x <= 0, accept when log u < ((x^2 / 2 + d) - d v) + d log v, v = (1 + c x)^3.  A decision closer than its bounds is an error: the
+    reference cannot say which attempt the spec takes."""
+    d = E(float(shape)) - (E(1.0) / E(2.0 if mutate == "d_half" else 3.0))
+    c = E(1.0) / (E(9.0) * d).sqrt()
+    negative, margin = 0, math.inf
+    for k in range(SP_ATTEMPTS):
+        bx, bu = (1 + k, 2 + k) if mutate == "attempt_blocks" else (1 + 2 * k, 2 + 2 * k)
+        x = hp.box_muller(hp.block(seed, gid, bx, epoch, hp.TAG_RESAMPLE))[1 if mutate == "second_normal" else 0]
+        w = hp.block(seed, gid, bu, epoch, hp.TAG_RESAMPLE)
+        u = hp.u52(w[2], w[3]) if mutate == "accept_words23" else hp.u52(w[0], w[1])
+        v1 = E(1.0) + c * x
+        gap = abs(float(v1.v)) - v1.e
+        assert gap > 0.0, f"gamma_tile(gid {gid}, epoch {epoch}, shape {shape}) attempt {k}: the sign of 1 + c x = {v1} is not decidable"
+        margin = min(margin, gap)
+        if v1.v <= 0:
+            negative += 1
+            continue
+        v = (v1 * v1) * v1
+        lhs = E(u).log()
+        rhs = (((x * x).scale2(-1) + d) - d * v) + d * v.log()
+        gap = abs(float(lhs.v - rhs.v)) - (lhs.e + rhs.e)
+        assert gap > 0.0, f"gamma_tile(gid {gid}, epoch {epoch}, shape {shape}) attempt {k}: log u = {lhs} against {rhs} is not decidable"
+        margin = min(margin, gap)
+        _worst("gamma_tile: bound of the acceptance test's right side", rhs.e)
+        if lhs.v < rhs.v:
+            return GammaTile(d * v, k, negative, margin)
+    return GammaTile(d, SP_ATTEMPTS, negative, margin)
+
+
+def spacing(seed, slot, epoch, mutate=None):
+    """e = -log((k + 1/2) 2^-52), k the top 52 bits of the slot's 64-bit uniform"""
+    if mutate == "spacing_pair":
+        w = hp.block(seed, slot >> 1, 0, epoch, hp.TAG_RESAMPLE)
+        bits = hp.u64(w[0], w[1]) if slot & 1 else hp.u64(w[2], w[3])
+    else:
+        bits = resample_u64(seed, slot, epoch)
+    return -M.log(M.ldexp(mpf(2 * (bits >> 12) + 1), -53))
+
+
+class SortedTargets:
+    """x[j], eps[j] (the target side of the module docstring's eps_j, without 2 D / S_lo) for the slots j of the tiles asked for; .tiles the
+    GammaTile of every tile; .V the tile boundaries"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def sorted_targets(seed, epoch, n, slot0, S_lo, mutate=None, tiles=None):
+    """the construction of DESIGN.md 3.6 in the reals with the bound of the module docstring per slot.  `S_lo`: what the integer sum of the
+    weights is not below (a count of S is at most 1 / S_lo).  `tiles`: the tiles whose slots are placed (None: all); the totals of ALL tiles
+    are drawn either way -- they place every boundary."""
+    assert mutate is None or mutate in MUTATIONS, mutate
+    ntl = (n + SP_TILE - 1) // SP_TILE
+    Eg = gamma_E(ntl)
+    gid0 = 0 if mutate == "tile_id_local" else slot0
+    sp0 = 0 if mutate == "spacing_slot0" else slot0
+    G = []
+    for t in range(ntl):
+        first = t * SP_TILE
+        cnt = min(SP_TILE, n - first)
+        last = t == ntl - 1 and mutate != "last_shape"
+        G.append(gamma_tile(seed, gid0 + first, epoch, cnt + (1 if last else 0), mutate))
+    a = [g.value.e + 2.0 ** -Eg for g in G]
+    B = M.fsum(g.value.v for g in G)
+    dB = sum(a) + 2.0 ** -Eg
+    B_lo = float(B) - dB
+    assert B_lo > 0.0
+    V, b, A, dA = [], [], mpf(0), 0.0
+    for t in range(ntl + 1):
+        Vt = A / B
+        V.append(Vt)
+        # Tlo_0 = 0 and V_0 = 0 exactly; past the last tile nothing is floored twice, but the bound is kept uniform
+        b.append(0.0 if t == 0 else (dA + float(Vt) * dB) / B_lo + 2.0 ** -64 + 1.0 / S_lo)
+        if t < ntl:
+            A += G[t].value.v
+            dA += a[t]
+    for t in range(ntl):
+        _worst("gamma_t: |fl(d v) - gamma| / gamma", G[t].value.e / float(G[t].value.v))
+        _worst("V_t: |Gpre / Gtot - V_t|", b[t] - (2.0 ** -64 + 1.0 / S_lo if t else 0.0))
+    eta = math.expm1(6 * U)
+    c1 = NEGLOG_ABS + 2.0 ** -SP_FRAC
+    x, eps = {}, {}
+    for t in (range(ntl) if tiles is None else tiles):
+        first = t * SP_TILE
+        cnt = min(SP_TILE, n - first)
+        e = [spacing(seed, sp0 + first + k, epoch, mutate) for k in range(cnt)]
+        m = cnt
+        s = M.fsum(e)
+        if t == ntl - 1 and mutate != "no_e_n":
+            s += spacing(seed, sp0 + n, epoch, mutate)
+            m += 1
+        ds = m * c1 + 2.0 ** -SP_FRAC                                        # the tile's spacings and the + 1 of s_t
+        s_lo = float(s) - ds
+        assert s_lo > 0.0
+        lo, hi = (V[t + 1], V[min(t + 2, ntl)]) if mutate == "boundary_next" else (V[t], V[t + 1])
+        W, dW = hi - lo, b[t] + b[t + 1]
+        Wf = float(W)
+        p = mpf(0)
+        for k in range(cnt):
+            pk = p if mutate == "exclusive" else p + e[k]
+            p += e[k]
+            r = pk / s
+            rf = float(r)
+            dr = ((k + 1) * c1 + rf * ds) / s_lo
+            x[first + k] = lo + W * r
+            eps[first + k] = b[t] + dr * (Wf + dW) + rf * dW + eta * (Wf + dW) + 1.0 / S_lo
+            _worst("p_j / s_t: |p / s - P / s^|", dr)
+    return SortedTargets(x=x, eps=eps, tiles=G, V=V, Eg=Eg)
+
+
+def sorted_multinomial(sm, seed, epoch, n_slots=None, slot0=0, mutate=None):
+    """the ancestors of GPF_RESAMPLE_MULTINOMIAL_SORTED: the inverse CDF of w at the x_j of sorted_targets, each slot with its own eps_j.
+    `mutate`: one of MUTATIONS, for the negative controls only.  Beside the fields of Ancestors: .targets (SortedTargets)"""
+    n_slots = sm.n if n_slots is None else n_slots
+    st = sorted_targets(seed, epoch, n_slots, slot0, math.ldexp(sm.n, sm.K) if sm.invalid else sm.S_lo, mutate)
+    weight_side = 0.0 if sm.invalid else 2 * sm.D / sm.S_lo
+    eps = [weight_side + st.eps[j] for j in range(n_slots)]
+    anc, und = _inverse_cdf(sm.cdf(), [st.x[j] for j in range(n_slots)], eps)
+    for e in eps:
+        _worst("eps_j: the slot's whole bound", e)
+    out = Ancestors(anc, und, max(eps))
+    out.targets = st
+    return out
+
+
 def sort_order(lp):
     """sortperm(lp, rev=true) (resample.jl:156-157), stable: ties keep particle order -- the order the oracle uses; the checks accept any"""
     return [int(i) for i in np.argsort(-np.asarray(lp, np.float64), kind="stable")]
 
 
-def stratified(sm, seed, epoch, sort_particles):
+def stratified(sm, seed, epoch, sort_particles, slot0=0):
+    """`slot0`: a view's first particle -- the strata are local to the view (stratum j of n: resample.jl:155-162 on the sub-state's own
+    n_particles), the uniform of stratum j is that of resample slot slot0 + j"""
     n = sm.n
     eps = 0.0 if sm.invalid else (2 * sm.D + 3) / sm.S_lo
     order = sort_order(sm.lp) if sort_particles else None
-    xs = [(j + uniform(seed, j, epoch)) / n for j in range(n)]
+    xs = [(j + uniform(seed, slot0 + j, epoch)) / n for j in range(n)]
     k, und = _inverse_cdf(sm.cdf(order), xs, eps)
     anc = [order[i] for i in k] if order is not None else k
     return Ancestors(anc, und, eps, ties=sm.lp if sort_particles else None)
@@ -295,14 +491,18 @@ def residual(sm, seed, epoch, n_slots=None):
     return Ancestors(anc, und, eps), bad
 
 
-def reference_ancestors(lp, method, seed, epoch, n_slots=None, sort_particles=True, K=None):
-    """(Softmax, Ancestors, undecidable particles) of one resample / resize call"""
+def reference_ancestors(lp, method, seed, epoch, n_slots=None, sort_particles=True, K=None, slot0=0):
+    """(Softmax, Ancestors, undecidable particles) of one resample / resize call; `slot0`: the first particle of a view"""
     sm = Softmax(lp, K)
     if method == "multinomial":
-        return sm, multinomial(sm, seed, epoch, n_slots), []
+        return sm, multinomial(sm, seed, epoch, n_slots, slot0), []
+    if method == "multinomial_sorted":
+        assert n_slots in (None, sm.n)
+        return sm, sorted_multinomial(sm, seed, epoch, slot0=slot0), []
     if method == "stratified":
         assert n_slots in (None, sm.n)
-        return sm, stratified(sm, seed, epoch, sort_particles), []
+        return sm, stratified(sm, seed, epoch, sort_particles, slot0), []
+    assert slot0 == 0
     if method == "residual":
         a, bad = residual(sm, seed, epoch, n_slots)
         return sm, a, bad
@@ -338,9 +538,10 @@ def log_n(n):
     return E(float(n)).log(2.0)
 
 
-def weights_after(lw, lp, parents0, n_new=None):
+def weights_after(lw, lp, parents0, n_new=None, total=None):
     """update_weights! (resample.jl:190-202) under a priority: lw[a] - lp[a] + log N - logsumexp(lw[a] - lp[a]), one E per slot.  The spec
-    sums its own ROUNDED differences: their half ulp enters the logsumexp's bound."""
+    sums its own ROUNDED differences: their half ulp enters the logsumexp's bound.  `total`: the sub-state form (:205-218) -- the
+    logsumexp of the view's weights before the call, as an E, in the place of log N."""
     lw, lp, a = np.asarray(lw), np.asarray(lp), np.asarray(parents0)
     n_new = a.size if n_new is None else n_new
     with np.errstate(invalid="ignore"):
@@ -349,7 +550,7 @@ def weights_after(lw, lp, parents0, n_new=None):
         return None
     sm = Softmax(ws, fix_K(n_new))
     in_err = 0.5 * max(math.ulp(abs(float(x))) for x in ws if np.isfinite(x))
-    shift = log_n(n_new) - sm.lse(in_err)
+    shift = (log_n(n_new) if total is None else total) - sm.lse(in_err)
     return [(E(float(lw[i])) - E(float(lp[i]))) + shift for i in a]
 
 
