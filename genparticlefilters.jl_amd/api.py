@@ -20,6 +20,7 @@ import ctypes as C
 import math
 import os
 import warnings
+from collections import namedtuple
 
 import numpy as np
 
@@ -640,7 +641,7 @@ def block_ancestors(state) -> np.ndarray:
 
 def pf_initialize_blocks(model: NativeModel, model_args: tuple, observations, n_particles: int, block_size: int, *, seed: int = 1,
                          keep_prev: bool = False, device: int = 0, strata=None, layout: str = "contiguous", params=None, history: int = 0,
-                         reference=None, history_weights: bool = False):
+                         reference=None, history_weights: bool = False, forward: bool = False):
     """many small filters in one state, each with its own data: block b (block_size consecutive particles) is initialised with
     observations[b] -- the batched form of per-view initialisation (gpf.h gpf_initialize_blocks).  strata: every block is initialised
     stratified by itself (src/initialize.jl:92-109 per sub-state, gpf.h gpf_initialize_blocks_strata), the same strata for all blocks.
@@ -651,13 +652,17 @@ def pf_initialize_blocks(model: NativeModel, model_args: tuple, observations, n_
     pinned to reference[b] and weighted by log p(y_b | reference[b]); every other particle is what the call without a reference gives.  A
     per-call input (nothing is kept), default proposal only, all values finite; the values of discrete latents are the caller's business.
     history_weights: the store also records every step's log-weights and per-block observations (gpf.h gpf_history_enable_blocks_weights: 8 bytes more
-    per particle and step), which block_backward_trajectories needs; raises without history=T."""
+    per particle and step), which block_backward_trajectories needs; raises without history=T.
+    forward: forward-only smoothing per block (gpf.h gpf_forward_enable_blocks) -- every later block-wise step keeps the additive smoothing statistics
+    that block_forward_moments returns, with a store or without one."""
     if reference is not None and strata is not None:
         raise ValueError("a reference is offered with the default proposal only, not with strata")
     if history_weights and not history:
         raise ValueError("history_weights=True needs the block-wise trajectory store: pass history=T as well")
     state = DeviceParticleFilterState(model, n_particles, seed=seed, keep_prev=keep_prev, device=device, history=history, history_blocks=bool(history),
                                       history_weights=bool(history_weights))
+    if forward:
+        state._check(state._L.gpf_forward_enable_blocks(state._h))
     obs = _block_obs(state, observations, block_size)
     if params is not None:
         set_block_params(state, params, block_size)
@@ -1186,6 +1191,26 @@ def block_smoothed_moments(state, block_size: int, steps=None, return_weights: b
 def block_smoothed_weights(state, block_size: int, steps=None):
     """the smoothing weights of block_smoothed_moments alone: [n_blocks, n_steps, block_size]"""
     return _block_smooth(state, block_size, steps, "block_smoothed_weights", False, False, True, False)[2]
+
+
+BlockForwardMoments = namedtuple("BlockForwardMoments", "sum second cross first first2 last2 n_steps")
+
+
+def block_forward_moments(state, block_size: int) -> BlockForwardMoments:
+    """forward-only smoothing per block (gpf.h gpf_block_forward_moments; needs pf_initialize_blocks(..., forward=True)): after the current step t, per
+    block, sum = sum_s E[x_s | y_1:t] (n_blocks, dim), second = sum_s E[x_s x_s' | y_1:t], cross = sum_s E[x_s x_{s+1}' | y_1:t] (row = the earlier
+    step), first = E[x_1 | y_1:t], first2 = E[x_1 x_1' | y_1:t], last2 = E[x_t x_t' | y_1:t] (n_blocks, dim, dim each) and n_steps = t -- the sums over
+    steps of block_smoothed_pair_moments without a store.  The M-step of a linear model reads second - last2 (steps < t), second - first2 (steps > 1)
+    and cross.  Nothing is drawn and nothing changes; a block with NaN / +Inf weights reads NaN."""
+    bs = max(min(int(block_size), state.n_particles), 1)                     # (the library clamps the size and refuses one below 1)
+    nb = (state.n_particles + bs - 1) // bs
+    d = state.dim
+    vec = lambda: np.empty((nb, d))
+    mat = lambda: np.empty((nb, d, d))
+    out = (vec(), mat(), mat(), vec(), mat(), mat())
+    t = C.c_int32()
+    state._check(state._L.gpf_block_forward_moments(state._h, int(block_size), *[_pd(a) for a in out], C.byref(t)))
+    return BlockForwardMoments(*out, int(t.value))
 
 
 def block_smoothed_pair_moments(state, block_size: int, steps=None, return_blocks: bool = False):

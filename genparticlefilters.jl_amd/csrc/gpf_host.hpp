@@ -154,6 +154,16 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     std::vector<double*> hist_obs;       // [step] the [n_blocks][MAX_OBS] observation rows the step was entered with, in the block order of the snapshot
     std::vector<int64_t> hist_bsize;     // [step] the block size of the block-wise call that entered the step; 0: a whole-filter call (no per-block rows)
     const double** hist_dev_lw = nullptr; const double** hist_dev_obs = nullptr;   // device tables of hist_lw / hist_obs beside hist_dev_x, hist_cap entries each
+    // forward-only smoothing per block (gpf_forward_enable_blocks): ONE generation of records -- the previous step's latent columns,
+    // log-weights and statistics in that step's final order -- and the composed ancestor map of the current step; 8 (2 F + d + 1) n bytes and two maps,
+    // however long the series.  Everything is allocated by the initialising call and overwritten at every close (fwd_begin_step)
+    bool fwd_on = false;
+    int64_t fwd_bsize = 0;               // the (clamped) block size of the initialising call: the mode's; 0 until then
+    int32_t fwd_steps = 0;               // the current step, 1-based; 0: nothing initialised
+    double *fwd_x = nullptr, *fwd_lw = nullptr;   // [n][d], [n] of the step closed last
+    double* fwd_T[2] = {nullptr, nullptr}; int fwd_cur = 0;   // [n][F]: fwd_T[fwd_cur] belongs to the record, the other half is the close's output and the query's scratch
+    int32_t* fwd_map[2] = {nullptr, nullptr}; int fwd_map_cur = 0; bool fwd_map_set = false;   // g_s of the current step in fwd_map[fwd_map_cur] once a resample happened in it
+    int64_t fwd_cap = 0;                 // particles the buffers hold
     // sub-state view (src/view.jl:16-48): this handle aliases particles [view_start, view_start + n) of `parent`
     gpf_filter* parent = nullptr;
     std::vector<gpf_filter*> views;      // the live view handles of THIS filter: gpf_destroy orphans them (a view used after its filter is gone fails loudly)
@@ -315,6 +325,14 @@ inline gpf_status bp_refused(gpf_filter* h, const char* who)
     const gpf_filter* root = (h->parent && !h->orphaned) ? h->parent : h;
     if (root->bp_size > 0)
         return fail(h, GPF_ERR_STATE, std::string(who) + ": per-block model parameters are set (gpf_set_block_params): use the block-wise calls, or clear them first");
+    return GPF_OK;
+}
+
+// gpf_forward_enable_blocks: while the mode is on, the calls that would scatter the blocks' lineages or replace the population are refused
+inline gpf_status fwd_refused(gpf_filter* h, const char* who)
+{
+    if (h->fwd_on)
+        return fail(h, GPF_ERR_STATE, std::string(who) + ": forward smoothing per block is on (gpf_forward_enable_blocks): the statistics follow the block-wise calls only");
     return GPF_OK;
 }
 
@@ -637,6 +655,12 @@ gpf_status weighted_tree_sum(gpf_filter* h, const double* values, int stride, in
 void launch_block_smooth(gpf_filter* h, const SmoothArgs& a, const AncArgs& x);   // k_block_smooth<model, TEAM, ITEMS> by team_dispatch
 // ---- defined in libgpf_pairs.hip
 void launch_block_pairs(gpf_filter* h, const PairArgs& a, const AncArgs& x);      // k_block_smooth_pairs<model, TEAM, ITEMS> by team_dispatch
+// ---- defined in libgpf_forward.hip: the forward-only smoother's records (hist_begin_step / hist_on_resample call the first two) and launches
+gpf_status fwd_begin_step(gpf_filter* h, bool first);             // first: step 1 begins, the statistics are reset; else the step that ends is closed in its final order
+gpf_status fwd_on_resample(gpf_filter* h, int64_t block_size);    // this call's parents into the current step's map (block_size > 0: block-local, h->blk_mask says which)
+gpf_status fwd_form(gpf_filter* h);                               // k_block_forward<model>: the current step's statistics into fwd_T[1 - fwd_cur]; nothing is committed
+void launch_block_forward_reduce(gpf_filter* h, const double* T, double* out);   // k_block_forward_reduce<d, TEAM, ITEMS> by team_dispatch
+void fwd_free(gpf_filter* h);
 // ---- defined in libgpf_shard.hip
 gpf_status shard_device_setup(gpf_filter* h);         // LDS attributes of the push kernels (gpf_create)
 

@@ -26,3 +26,4 @@
 #include "gpf_k_block_anc.hpp"
 #include "gpf_k_block_back.hpp"
 #include "gpf_k_block_smooth.hpp"
+#include "gpf_k_block_forward.hpp"

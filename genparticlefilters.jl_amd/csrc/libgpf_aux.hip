@@ -140,6 +140,7 @@ enum : unsigned {
     GATE_MAX = 128,            // blocks of more than BLK_MAX particles are the work of view handles (below), which a filter with the block-wise store
                                // (gpf_history_enable_blocks) does not have
     GATE_PARAMS = 256,         // the block size of the per-block parameters, where they are set
+    GATE_FWD = 512,            // the block size of forward smoothing per block (gpf_forward_enable_blocks), once its initialising call has set it
     GATE_FILTER = GATE_VIEW | GATE_SHARD | GATE_STORE | GATE_SIZE,
 };
 static gpf_status block_gate(gpf_handle h, int64_t& block_size, const char* who, unsigned steps)
@@ -157,6 +158,9 @@ static gpf_status block_gate(gpf_handle h, int64_t& block_size, const char* who,
     if ((steps & GATE_PARAMS) && h->bp_size > 0 && block_size != h->bp_size)
         return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": block_size " + std::to_string(block_size) + " differs from the " +
                     std::to_string(h->bp_size) + " of the per-block parameters (gpf_set_block_params)");
+    if ((steps & GATE_FWD) && h->fwd_on && h->fwd_steps > 0 && clamped != h->fwd_bsize)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": block_size " + std::to_string(clamped) + " differs from the " +
+                    std::to_string(h->fwd_bsize) + " forward smoothing per block was initialised with (gpf_forward_enable_blocks)");
     return GPF_OK;
 }
 // Blocks of more than BLK_MAX = 2048 particles do not fit the one-workgroup-per-block kernels (gpf_k_block.hpp keeps a block's weights, CDF
@@ -291,7 +295,7 @@ static gpf_status resample_blocks_impl(gpf_handle h, int32_t method, int64_t blo
 {
     const char* const who = anc ? "gpf_resample_blocks_ancestor" : conditional ? "gpf_resample_blocks_conditional" : "gpf_resample_blocks";
     // (the conditional step has no form for blocks that resample through views: "one block" asked for as any size >= n is one block of n particles)
-    gpf_status s = block_gate(h, block_size, who, GATE_FILTER | (conditional ? GATE_CLAMP : GATE_CLAMP_STORE | GATE_MAX) | (anc ? GATE_PARAMS : 0u));
+    gpf_status s = block_gate(h, block_size, who, GATE_FILTER | GATE_FWD | (conditional ? GATE_CLAMP : GATE_CLAMP_STORE | GATE_MAX) | (anc ? GATE_PARAMS : 0u));
     if (s) return s;
     if (conditional && (method == GPF_RESAMPLE_RESIDUAL || method == GPF_RESAMPLE_STRATIFIED))
         return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": multinomial only -- forcing one slot to keep its particle is not a valid conditional scheme "
@@ -568,10 +572,14 @@ static gpf_status set_block_obs(gpf_filter* h, const double* obs, int32_t n_obs,
     return GPF_OK;
 }
 // the gate of the block-wise steps (they index observations by i / block_size: any size, clamped), then the observations
-static gpf_status block_step_checks(gpf_handle h, int64_t& block_size, const char* who, const double* obs = nullptr, int32_t n_obs = 0, bool with_obs = false)
+// initialising: the call sets the block size of forward smoothing per block (at most BLK_MAX, as the store's queries ask); every other step keeps to it
+static gpf_status block_step_checks(gpf_handle h, int64_t& block_size, const char* who, const double* obs = nullptr, int32_t n_obs = 0, bool with_obs = false,
+                                    bool initialising = false)
 {
-    gpf_status s = block_gate(h, block_size, who, GATE_FILTER | GATE_CLAMP | GATE_PARAMS);
+    gpf_status s = block_gate(h, block_size, who, GATE_FILTER | GATE_CLAMP | GATE_PARAMS | (initialising ? 0u : GATE_FWD));
     if (s) return s;
+    if (initialising && h->fwd_on && block_size > BLK_MAX)
+        return fail(h, GPF_ERR_STATE, std::string(who) + ": blocks of more than " + std::to_string(BLK_MAX) + " particles with forward smoothing per block (gpf_forward_enable_blocks)");
     // (callers that change the handle's arguments before set_block_obs -- the strata -- validate the observations first, so that a bad call changes nothing)
     return with_obs ? block_obs_check(h, obs, n_obs) : GPF_OK;
 }
@@ -589,6 +597,7 @@ static gpf_status block_initialize_impl(gpf_handle h, const double* obs, int32_t
 {
     h->generation += 1;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (h->fwd_on) h->fwd_bsize = block_size;                    // (forward smoothing per block: this call's block size is the mode's)
     gpf_status s = hist_begin_step(h, true);                     // (the block-wise store: step 1)
     if (s || (s = set_block_obs(h, obs, n_obs, block_size, ref))) return s;
     if (h->hist_weights) h->hist_bsize.back() = block_size;     // (the step has per-block observation rows for the store to record)
@@ -639,7 +648,7 @@ static gpf_status block_update_impl(gpf_handle h, const double* obs, int32_t n_o
 }
 gpf_status gpf_initialize_blocks(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size)
 {
-    gpf_status s = block_step_checks(h, block_size, "gpf_initialize_blocks", obs, n_obs, true);   // (a refused call leaves the trajectory store alone too)
+    gpf_status s = block_step_checks(h, block_size, "gpf_initialize_blocks", obs, n_obs, true, true);   // (a refused call leaves the trajectory store alone too)
     return s ? s : block_initialize_impl(h, obs, n_obs, block_size, 0);
 }
 gpf_status gpf_update_blocks(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size)
@@ -667,7 +676,7 @@ static gpf_status block_ref_checks(gpf_filter* h, int64_t block_size, const doub
 // conditional SMC: the block-wise pf_initialize / pf_update! with slot 0 of every block pinned to a reference row -- gpf.h
 gpf_status gpf_initialize_blocks_ref(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, const double* ref, int32_t n_ref)
 {
-    gpf_status s = block_step_checks(h, block_size, "gpf_initialize_blocks_ref", obs, n_obs, true);
+    gpf_status s = block_step_checks(h, block_size, "gpf_initialize_blocks_ref", obs, n_obs, true, true);
     if (s || (s = block_ref_checks(h, block_size, ref, n_ref, "gpf_initialize_blocks_ref"))) return s;
     return block_initialize_impl(h, obs, n_obs, block_size, 0, ref);
 }
@@ -687,7 +696,7 @@ static gpf_status block_strata(gpf_handle h, const double* values, int32_t n_str
 }
 gpf_status gpf_initialize_blocks_strata(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, const double* values, int32_t n_strata, int32_t interleaved)
 {
-    gpf_status s = block_step_checks(h, block_size, "gpf_initialize_blocks_strata", obs, n_obs, true);
+    gpf_status s = block_step_checks(h, block_size, "gpf_initialize_blocks_strata", obs, n_obs, true, true);
     if (s || (s = block_strata(h, values, n_strata, interleaved))) return s;
     return block_initialize_impl(h, obs, n_obs, block_size, 2);
 }
@@ -830,7 +839,7 @@ gpf_status gpf_resample_across_blocks(gpf_handle h, int32_t method, int64_t bloc
                                       int32_t* invalid, int32_t* resampled, double* ess_out)
 {
     // (no clamp: the blocks must be congruent, so a size above n is refused below)
-    gpf_status s = block_gate(h, block_size, "gpf_resample_across_blocks", GATE_FILTER | GATE_MAX | GATE_PARAMS);
+    gpf_status s = block_gate(h, block_size, "gpf_resample_across_blocks", GATE_FILTER | GATE_MAX | GATE_PARAMS | GATE_FWD);
     if (s) return s;
     if (h->n % block_size != 0)
         return fail(h, GPF_ERR_INVALID_ARGUMENT, "gpf_resample_across_blocks: " + std::to_string(h->n) + " particles are no whole number of blocks of " +
@@ -1004,6 +1013,7 @@ static gpf_status view_create_impl(gpf_handle parent, int64_t start, int64_t ste
     // the trajectory store keeps ONE ancestor map and one set of columns per time step for the whole filter: a sub-state that
     // resamples or advances only its own particles would leave it describing something else -- refuse instead of going stale
     if (parent->hist_on) return fail(parent, GPF_ERR_STATE, "a filter with a trajectory store has no sub-state views");
+    if (gpf_status b = fwd_refused(parent, "a sub-state view")) return b;   // (the same reason: one record per step for the whole filter)
     if (!index && (start < 0 || count < 1 || start + (count - 1) * step >= parent->n)) return fail(parent, GPF_ERR_INVALID_ARGUMENT, "view range out of bounds");
     gpf_filter* v = new gpf_filter();
     v->cfg = parent->cfg;
@@ -1077,6 +1087,7 @@ static gpf_status view_create_impl(gpf_handle parent, int64_t start, int64_t ste
 static gpf_status resize_ready(gpf_handle h, bool bump = true)
 {
     if (h && bp_refused(h, "resizing")) return GPF_ERR_STATE;   // (the rows are laid out by block: a new particle count breaks the layout)
+    if (h && fwd_refused(h, "resizing")) return GPF_ERR_STATE;  // (the records are laid out by block too)
     gpf_status s = check_ready(h);
     if (s) return s;
     if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, "resizing a sharded filter is not supported");
@@ -1792,6 +1803,60 @@ gpf_status gpf_block_smooth_pairs(gpf_handle h, int64_t block_size, int32_t step
     // (nothing was drawn: the epoch stays)
     return block_out(h, {{d_mean.p, mean_out, b_mean}, {d_sec.p, second_out, b_sec}, {d_cross.p, cross_out, b_cross}, {d_c.p, blocks_out, b_c}});
 }
+// ---- forward-only smoothing per block (gpf.h gpf_forward_enable_blocks / gpf_block_forward_moments): the additive smoothing functionals
+// of particle EM after every step, from one generation of records.  The records, the hooks of the block-wise calls and the kernels' instantiations live in
+// a translation unit of their own (libgpf_forward.hip)
+gpf_status gpf_forward_enable_blocks(gpf_handle h)
+{
+    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+    if (h->parent) return fail(h, GPF_ERR_STATE, "gpf_forward_enable_blocks on a sub-state view: call it on the filter");
+    if (h->cfg.n_global != h->n || h->comm) return fail(h, GPF_ERR_STATE, "forward smoothing per block is not available for sharded filters");
+    if (h->initialized) return fail(h, GPF_ERR_STATE, "enable forward smoothing per block before gpf_initialize_blocks");
+    if (h->hist_on && !h->hist_blocks) return fail(h, GPF_ERR_STATE, "forward smoothing per block follows the block-wise calls: the plain trajectory store refuses them");
+    if (!h->views.empty()) return fail(h, GPF_ERR_STATE, "forward smoothing per block on a filter with sub-state views");
+    h->fwd_on = true; h->fwd_bsize = 0; h->fwd_steps = 0;
+    return GPF_OK;
+}
+gpf_status gpf_block_forward_moments(gpf_handle h, int64_t block_size, double* sum_out, double* second_out, double* cross_out, double* first_out,
+                                     double* first2_out, double* last2_out, int32_t* n_steps_out)
+{
+    const char* who = "gpf_block_forward_moments";
+    if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
+    if (!h->fwd_on) return fail(h, GPF_ERR_STATE, std::string(who) + " needs forward smoothing per block (gpf_forward_enable_blocks before gpf_initialize_blocks)");
+    if (!h->initialized || h->fwd_steps < 1) return fail(h, GPF_ERR_STATE, std::string(who) + ": nothing is initialised (gpf_initialize_blocks)");
+    gpf_status s = block_gate(h, block_size, who, GATE_SIZE | GATE_CLAMP | GATE_FWD | GATE_PARAMS);   // (the rows of the per-block parameters are read by block)
+    if (s) return s;
+    if (!sum_out && !second_out && !cross_out && !first_out && !first2_out && !last2_out && !n_steps_out)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": all outputs are NULL");
+    if ((s = check_ready(h)) || (s = materialize(h))) return s;
+    const int d = h->d, F = fwd_F(d), tri = d * (d + 1) / 2, row = F + d * d;
+    const int64_t nblocks = (h->n + block_size - 1) / block_size;
+    if ((s = block_est_buffer(h, nblocks * row))) return s;
+    // the current step's statistics as a close would form them, into the half of the ping-pong the close writes: nothing is committed, the close recomputes
+    if ((s = fwd_form(h))) return s;
+    launch_block_forward_reduce(h, h->fwd_T[1 - h->fwd_cur], h->blk_est);
+    HIP_TRY(h, hipGetLastError());
+    std::vector<double> host((size_t)(nblocks * row));
+    if ((s = block_out(h, {{h->blk_est, host.data(), host.size() * sizeof(double)}}))) return s;
+    // [sum | second, upper triangle | cross | first | first2, upper triangle | last2] per block -> the caller's arrays, triangles mirrored
+    auto vec = [&](double* out, int off) {
+        if (out) for (int64_t b = 0; b < nblocks; ++b) for (int a = 0; a < d; ++a) out[b * d + a] = host[(size_t)(b * row + off + a)];
+    };
+    auto full = [&](double* out, int off) {
+        if (out) for (int64_t b = 0; b < nblocks; ++b) for (int k = 0; k < d * d; ++k) out[b * d * d + k] = host[(size_t)(b * row + off + k)];
+    };
+    auto mirrored = [&](double* out, int off) {
+        if (!out) return;
+        for (int64_t b = 0; b < nblocks; ++b) {
+            int t = 0;
+            for (int a = 0; a < d; ++a)
+                for (int c = a; c < d; ++c, ++t) out[(b * d + a) * d + c] = out[(b * d + c) * d + a] = host[(size_t)(b * row + off + t)];
+        }
+    };
+    vec(sum_out, 0); mirrored(second_out, d); full(cross_out, d + tri); vec(first_out, d + tri + d * d); mirrored(first2_out, d + tri + d * d + d); full(last2_out, F);
+    if (n_steps_out) *n_steps_out = h->fwd_steps;
+    return GPF_OK;
+}
 // ---- checkpoint / resume: everything a filter needs to continue bit for bit -- the population, its log-weights and parents, the log-ML
 // estimate, the RNG epoch, the latest observation and strata -- as ONE host blob; loads into a handle created with the same gpf_config
 namespace {
@@ -1859,6 +1924,7 @@ gpf_status gpf_checkpoint_load(gpf_handle h, const void* in, int64_t bytes)
     if (!same) return fail(h, GPF_ERR_INVALID_ARGUMENT, "the checkpoint was taken of a filter with another gpf_config (model, parameters, particle counts, gid0, seed, keep_prev)");
     if (bytes != ckpt_bytes(h)) return fail(h, GPF_ERR_INVALID_ARGUMENT, "truncated checkpoint");
     if (h->hist_on) return fail(h, GPF_ERR_STATE, "a filter with a trajectory store cannot load a checkpoint (the store is not part of it)");
+    if (gpf_status b = fwd_refused(h, "gpf_checkpoint_load")) return b;   // (the statistics are not part of a checkpoint either)
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     for (gpf_filter* v : h->blk_views) gpf_destroy(v);
     h->blk_views.clear();

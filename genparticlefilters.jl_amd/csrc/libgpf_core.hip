@@ -257,6 +257,7 @@ gpf_status hist_snapshot(gpf_filter* h)
 // local to the blocks that resampled and stale in the others, h->blk_mask says which (k_hist_compose_blocks)
 gpf_status hist_on_resample(gpf_filter* h, int64_t block_size)
 {
+    if (h->fwd_on) { gpf_status fs = fwd_on_resample(h, block_size); if (fs) return fs; }   // (forward smoothing per block keeps the step's map too, with or without a store)
     if (!h->hist_on || h->hist_step < 0) return GPF_OK;
     int32_t* old = h->hist_map[h->hist_step];
     int32_t* neu = nullptr;
@@ -270,6 +271,8 @@ gpf_status hist_on_resample(gpf_filter* h, int64_t block_size)
 }
 gpf_status hist_begin_step(gpf_filter* h, bool first)
 {
+    // (forward smoothing per block: the step that ends is closed here, in its final order and under the observation rows it was entered with)
+    if (h->fwd_on) { gpf_status fs = fwd_begin_step(h, first); if (fs) return fs; }
     if (!h->hist_on) return GPF_OK;
     if (first) hist_clear(h);
     else { gpf_status s = hist_snapshot(h); if (s) return s; }     // the step that ends now, in its final order
@@ -554,6 +557,7 @@ gpf_status gpf_destroy(gpf_handle h)
     h->views.clear();
     gpf_comm_destroy(h);
     hist_clear(h);
+    fwd_free(h);
     if (h->hist_dev_maps) (void)hipFree(h->hist_dev_maps);
     if (h->hist_dev_x) (void)hipFree(h->hist_dev_x);
     if (h->hist_dev_lw) (void)hipFree(h->hist_dev_lw);
@@ -615,6 +619,7 @@ static gpf_status initialize_impl(gpf_handle h, const double* obs, int32_t n_obs
     if (prop == 3 && !caps.strata_proposal) return fail(h, GPF_ERR_INVALID_ARGUMENT, "stratified initialisation with a native proposal: line_model only");
     if (h->parent) return fail(h, GPF_ERR_STATE, "gpf_initialize on a sub-state view");
     if (gpf_status b = bp_refused(h, "gpf_initialize")) return b;
+    if (gpf_status b = fwd_refused(h, "gpf_initialize")) return b;
     h->generation += 1;
     gpf_status s = set_obs(h, obs, n_obs);
     if (s) return s;
@@ -641,7 +646,7 @@ gpf_status gpf_initialize_proposal(gpf_handle h, const double* obs, int32_t n_ob
 
 static gpf_status update_impl(gpf_handle h, const double* obs, int32_t n_obs, int prop)
 {
-    if (h && bp_refused(h, "gpf_update")) return GPF_ERR_STATE;
+    if (h && (bp_refused(h, "gpf_update") || fwd_refused(h, "gpf_update"))) return GPF_ERR_STATE;
     gpf_status s = check_ready(h, prop == 0);                    // (the plain propagate carries a pending lazy move)
     if (s) return s;
     const ModelCaps caps = model_caps(h);
@@ -712,7 +717,7 @@ extern "C" {
 gpf_status gpf_step_ess(gpf_handle h, const double* obs, int32_t n_obs, double ess_frac, int32_t resample_method, int32_t sort_particles,
                         int32_t check, int32_t rejuvenate_method, int32_t n_iters, int32_t* resampled, int32_t* invalid, double* ess_out)
 {
-    if (h && bp_refused(h, "gpf_step_ess")) return GPF_ERR_STATE;
+    if (h && (bp_refused(h, "gpf_step_ess") || fwd_refused(h, "gpf_step_ess"))) return GPF_ERR_STATE;
     gpf_status s = check_ready(h);
     if (s) return s;
     if (!(ess_frac == ess_frac) || ess_frac < 0.0) return fail(h, GPF_ERR_INVALID_ARGUMENT, "ess_frac must be >= 0");
@@ -792,7 +797,7 @@ gpf_status set_strata(gpf_handle h, const double* values, int32_t n_strata, int3
 extern "C" {
 gpf_status gpf_initialize_strata(gpf_handle h, const double* obs, int32_t n_obs, const double* values, int32_t n_strata, int32_t interleaved)
 {
-    if (h && bp_refused(h, "gpf_initialize_strata")) return GPF_ERR_STATE;   // (before set_strata changes the handle's arguments)
+    if (h && (bp_refused(h, "gpf_initialize_strata") || fwd_refused(h, "gpf_initialize_strata"))) return GPF_ERR_STATE;   // (before set_strata changes the handle's arguments)
     gpf_status s = set_strata(h, values, n_strata, interleaved);
     return s ? s : initialize_impl(h, obs, n_obs, 2);
 }
@@ -800,13 +805,13 @@ gpf_status gpf_initialize_strata_proposal(gpf_handle h, const double* obs, int32
                                           int32_t proposal)
 {
     if ((h && !proposal_valid(h, proposal)) || proposal != GPF_PROPOSAL_LINE_FIXED) return fail(h, GPF_ERR_INVALID_ARGUMENT, "unknown proposal id for this model");
-    if (h && bp_refused(h, "gpf_initialize_strata_proposal")) return GPF_ERR_STATE;
+    if (h && (bp_refused(h, "gpf_initialize_strata_proposal") || fwd_refused(h, "gpf_initialize_strata_proposal"))) return GPF_ERR_STATE;
     gpf_status s = set_strata(h, values, n_strata, interleaved);
     return s ? s : initialize_impl(h, obs, n_obs, 3);
 }
 gpf_status gpf_update_strata(gpf_handle h, const double* obs, int32_t n_obs, const double* values, int32_t n_strata, int32_t interleaved)
 {
-    if (h && bp_refused(h, "gpf_update_strata")) return GPF_ERR_STATE;
+    if (h && (bp_refused(h, "gpf_update_strata") || fwd_refused(h, "gpf_update_strata"))) return GPF_ERR_STATE;
     gpf_status s = set_strata(h, values, n_strata, interleaved);
     return s ? s : update_impl(h, obs, n_obs, 2);
 }

@@ -1,0 +1,100 @@
+// libgpf_forward.hip -- forward-only smoothing per block (gpf_k_block_forward.hpp; gpf.h gpf_forward_enable_blocks / gpf_block_forward_moments, whose
+// entry points are in libgpf_aux.hip): the kernels' instantiations, the mode's one generation of records and the two hooks of the block-wise calls
+// (hist_begin_step, hist_on_resample in libgpf_core.hip).  A translation unit of its own, for the reason libgpf_smooth.hip and libgpf_pairs.hip are:
+// every other unit's device code stays what it was (tools/isa_diff.py; profiles/block_forward.md).
+#include "gpf_host.hpp"
+
+using namespace gpf;
+using namespace gpfh;
+
+namespace gpfh {
+
+void fwd_free(gpf_filter* h)
+{
+    for (void* q : {(void*)h->fwd_x, (void*)h->fwd_lw, (void*)h->fwd_T[0], (void*)h->fwd_T[1], (void*)h->fwd_map[0], (void*)h->fwd_map[1]}) if (q) (void)hipFree(q);
+    h->fwd_x = h->fwd_lw = h->fwd_T[0] = h->fwd_T[1] = nullptr; h->fwd_map[0] = h->fwd_map[1] = nullptr;
+    h->fwd_cap = 0; h->fwd_steps = 0; h->fwd_map_set = false;
+}
+// the records of a filter of n particles: the previous step's columns and log-weights, the two halves of the statistics, the two maps
+static gpf_status fwd_buffers(gpf_filter* h)
+{
+    if (h->fwd_cap == h->n) return GPF_OK;
+    if (h->fwd_cap) { HIP_TRY(h, hipStreamSynchronize(h->stream)); fwd_free(h); }
+    const size_t n = (size_t)h->n, F = (size_t)fwd_F(h->d);
+    HIP_TRY(h, hipMalloc(&h->fwd_x, n * (size_t)h->d * sizeof(double)));
+    HIP_TRY(h, hipMalloc(&h->fwd_lw, n * sizeof(double)));
+    for (int k = 0; k < 2; ++k) {
+        HIP_TRY(h, hipMalloc(&h->fwd_T[k], n * F * sizeof(double)));
+        HIP_TRY(h, hipMalloc(&h->fwd_map[k], n * sizeof(int32_t)));
+    }
+    h->fwd_cap = h->n;
+    return GPF_OK;
+}
+template <int M>
+static void launch_block_forward_model(gpf_filter* h, const ForwardArgs& a, const AncArgs& x)
+{
+    const int64_t waves = a.nblocks * a.wpb;
+    GPF_LAUNCH((k_block_forward<M>), dim3((unsigned)((waves + NWAVES - 1) / NWAVES)), dim3(BLOCK), 0, h->stream, a, x,
+               (const double*)h->fwd_x, (const double*)h->fwd_lw, (const double*)h->fwd_T[h->fwd_cur], h->fwd_T[1 - h->fwd_cur]);
+}
+// the statistics of the CURRENT step from the record of the previous one, as a close forms them (the filter is materialised: the callers see to it)
+gpf_status fwd_form(gpf_filter* h)
+{
+    const int64_t bs = h->fwd_bsize;
+    ForwardArgs a{};
+    a.rows = h->rows[h->cur]; a.W = h->W; a.map = h->fwd_map_set ? h->fwd_map[h->fwd_map_cur] : nullptr; a.obs = h->blk_obs;
+    a.n = h->n; a.nb = bs; a.nblocks = (h->n + bs - 1) / bs; a.wpb = (int)((bs + WAVE - 1) / WAVE); a.first = h->fwd_steps == 1 ? 1 : 0;
+    AncArgs x{};                                                  // (the parameters current now: the filter's, or every block's own row)
+    for (int i = 0; i < MAX_PARAMS; ++i) x.P[i] = h->args.P[i];
+    x.blk_params = h->bp_size > 0 ? h->blk_params : nullptr;
+    x.bp_size = h->bp_size > 0 ? h->bp_size : 1;
+    DISPATCH_MODEL(h, (launch_block_forward_model<MM>(h, a, x)));
+    HIP_TRY(h, hipGetLastError());
+    return GPF_OK;
+}
+gpf_status fwd_begin_step(gpf_filter* h, bool first)
+{
+    if (first) {
+        if (h->fwd_bsize < 1) return fail(h, GPF_ERR_STATE, "forward smoothing per block follows the block-wise calls: begin with gpf_initialize_blocks");
+        if (h->d != 1 && h->d != 2 && h->d != 4) return fail(h, GPF_ERR_STATE, "latent dimension");
+        gpf_status s = fwd_buffers(h);
+        if (s) return s;
+        h->fwd_steps = 1; h->fwd_cur = 0; h->fwd_map_set = false;
+        return GPF_OK;
+    }
+    if (h->fwd_steps < 1) return fail(h, GPF_ERR_STATE, "forward smoothing per block: nothing is initialised");
+    // ---- the close of the step that ends: its statistics, then its columns and log-weights, in its final order
+    gpf_status s = fwd_form(h);
+    if (s) return s;
+    GPF_LAUNCH(k_hist_snapshot, dim3(grid_for(h, h->n * h->d, 8)), dim3(BLOCK), 0, h->stream, h->rows[h->cur], h->W, h->d, h->n, h->fwd_x);
+    GPF_LAUNCH(k_hist_record, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, (const double*)h->lw, h->n, (const double*)nullptr, (int64_t)0, h->fwd_lw, (double*)nullptr);
+    HIP_TRY(h, hipGetLastError());
+    h->fwd_cur ^= 1; h->fwd_steps += 1; h->fwd_map_set = false;
+    return GPF_OK;
+}
+// (two maps used in turn: nothing is allocated, synchronised or freed here -- the kernels of one stream run in order)
+gpf_status fwd_on_resample(gpf_filter* h, int64_t block_size)
+{
+    if (h->fwd_steps < 1) return GPF_OK;
+    const int32_t* old = h->fwd_map_set ? h->fwd_map[h->fwd_map_cur] : nullptr;
+    int32_t* neu = h->fwd_map[1 - h->fwd_map_cur];
+    if (block_size > 0) GPF_LAUNCH(k_hist_compose_blocks, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, (const int32_t*)h->anc, (const int32_t*)h->blk_mask, block_size, old, h->n, neu);
+    else GPF_LAUNCH(k_hist_compose, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, (const int32_t*)h->anc, old, h->n, neu);
+    HIP_TRY(h, hipGetLastError());
+    h->fwd_map_cur ^= 1; h->fwd_map_set = true;
+    return GPF_OK;
+}
+template <int D>
+static void launch_block_forward_reduce_d(gpf_filter* h, const double* T, double* out)
+{
+    const int64_t bs = h->fwd_bsize, nblocks = (h->n + bs - 1) / bs;
+    team_dispatch(bs, nblocks, [&](auto TEAM, auto ITEMS, dim3 grid) {
+        GPF_LAUNCH((k_block_forward_reduce<D, TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, T, (const double*)h->rows[h->cur], h->W, (const double*)h->lw, h->n, bs, nblocks, out);
+    });
+}
+void launch_block_forward_reduce(gpf_filter* h, const double* T, double* out)
+{
+    DISPATCH_D(h, (launch_block_forward_reduce_d<DD>(h, T, out)));
+}
+
+} // namespace gpfh

@@ -800,6 +800,7 @@ extern "C" {
 gpf_status gpf_resample(gpf_handle h, int32_t method, double priority_alpha, int32_t sort_particles, int32_t check,
                         int32_t* invalid)
 {
+    if (h && fwd_refused(h, "gpf_resample")) return GPF_ERR_STATE;
     gpf_status s = check_ready(h);
     if (s) return s;
     PrioView pv = raw_view(h);
@@ -812,6 +813,7 @@ gpf_status gpf_resample(gpf_handle h, int32_t method, double priority_alpha, int
 // every particle keeps the log-weight logsumexp - log n.  The gather stays deferred like gpf_resample's.
 gpf_status gpf_resample_local(gpf_handle h, int32_t method, int32_t sort_particles, int32_t check, int32_t* invalid)
 {
+    if (h && fwd_refused(h, "gpf_resample_local")) return GPF_ERR_STATE;
     gpf_status s = check_ready(h);
     if (s) return s;
     if (h->parent) return fail(h, GPF_ERR_STATE, "gpf_resample_local on a sub-state view: resample the view itself");
@@ -828,6 +830,7 @@ gpf_status gpf_resample_local(gpf_handle h, int32_t method, int32_t sort_particl
 gpf_status gpf_resample_with_priorities(gpf_handle h, int32_t method, const double* log_priorities, int32_t sort_particles,
                                         int32_t check, int32_t* invalid)
 {
+    if (h && fwd_refused(h, "gpf_resample_with_priorities")) return GPF_ERR_STATE;
     gpf_status s = check_ready(h);
     if (s) return s;
     if (!log_priorities) return fail(h, GPF_ERR_INVALID_ARGUMENT, "null log_priorities");

@@ -950,6 +950,7 @@ gpf_status gpf_comm_create(gpf_handle h, const void* id128, int32_t rank, int32_
     if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
     if (world < 1 || world > MAX_SHARDS || rank < 0 || rank >= world) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad rank / world (<= 64 shards)");
     if (h->parent) return fail(h, GPF_ERR_STATE, "a sub-state view has no communicator");
+    if (gpf_status b = fwd_refused(h, "gpf_comm_create")) return b;
     if (h->comm || h->sh_mf) return fail(h, GPF_ERR_STATE, "the handle already has a communicator");
     if (world > 1 && !id128) return fail(h, GPF_ERR_INVALID_ARGUMENT, "null id");
     HIP_TRY(h, hipSetDevice(h->cfg.device));

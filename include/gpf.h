@@ -712,6 +712,53 @@ gpf_status gpf_block_smooth(gpf_handle h, int64_t block_size, int32_t step_lo, i
 gpf_status gpf_block_smooth_pairs(gpf_handle h, int64_t block_size, int32_t step_lo, int32_t step_hi,
                                   double* mean_out, double* second_out, double* cross_out, int64_t* blocks_out);
 
+/* Forward-only smoothing per block: the sums over steps of gpf_block_smooth_pairs' moments -- sum_s E[x_s x_s^T | y_1:t], sum_s E[x_s x_{s+1}^T | y_1:t],
+ * what the M-step of particle EM reads -- after EVERY step, without a store (Del Moral, Doucet & Singh 2010, "Forward smoothing using sequential Monte
+ * Carlo"; Poyiadjis, Doucet & Singh 2011, Biometrika 98; the online EM of Cappe 2011).  Every particle carries a statistic T^j of F = d + d(d+1)/2 + d d +
+ * d + d(d+1)/2 doubles; one O(bs^2) pass per step updates it from the previous step's particles alone, and sum_j w_t^j T_t^j is algebraically the sum
+ * over steps of what gpf_block_smooth_pairs returns.  8 (2 F + d + 1) n bytes and two ancestor maps in all, however long the series.
+ * gpf_forward_enable_blocks: before gpf_initialize_blocks*, on an unsharded filter (GPF_ERR_STATE otherwise); with gpf_history_enable_blocks[_weights] on
+ * the same handle or with no store at all.  The mode follows the store's "recording" conventions:
+ *   step      gpf_initialize_blocks* begins step 1 and resets the statistics; gpf_update_blocks* begins the next step and first CLOSES the step that ends,
+ *             in its final order -- after every resample, gather across blocks and rejuvenation of that step, under the per-block observation rows the
+ *             step was entered with.  A refused block-wise call closes nothing.
+ *   map       g_s, the step's composed ancestor map: gpf_resample_blocks* compose their block-local parents for the blocks that resampled,
+ *             gpf_resample_across_blocks its global parents when it fires; several resamples of one step compose in call order.
+ *   records   of the previous step only, overwritten at every close: its latent columns, its log-weights, the statistics, the step counter.
+ *   size      the clamped block size of the initialising call is the mode's: <= 2048, else GPF_ERR_STATE; a later block-wise step, resample or query with
+ *             another clamped block size returns GPF_ERR_INVALID_ARGUMENT.
+ *   refused   with the mode on (GPF_ERR_STATE, nothing changed): the whole-filter gpf_initialize*, gpf_update*, gpf_step_ess and gpf_resample* (they
+ *             scatter the blocks' lineages), views, gpf_resize / gpf_optimal_resize / gpf_dereplicate / gpf_coalesce / gpf_introduce, gpf_checkpoint_load, a
+ *             communicator.  gpf_checkpoint_save saves what it saves without the mode: the statistics are NOT part of a checkpoint.
+ * The definition.  Everything not named here is gpf_block_smooth's: logtrans, the maximum and its flags, fix_K, exp_fix, the block's normalised weights.
+ * Steps are 1-based, bs = the block size, x = the d latent columns.
+ *     T^j = [ sum (d) | second, upper triangle (d(d+1)/2, a <= c, a outer) | cross (d x d, row a = the EARLIER step) | first (d) | first2, upper triangle ]
+ *   step 1    sum = first = x_1^j;  second = first2 = x_1^j[a] * x_1^j[c];  cross = +0.0.
+ *   step s    >= 2, for every target j of block c = j / bs in the final order of step s:
+ *     lineage   pm_j = g_s[j] (j itself where the step had no resample); the candidates are the particles i of block c' = pm_{c bs} / bs in the previous
+ *               record.  Where the particles of block c do not all have their parent in one block, every entry of every T of block c is NaN.
+ *     weights   lwa_ij = lw_{s-1}[i] + logtrans(P_c, x_{s-1}[i], x_s[j], obs_s[c]); P_c = block c's parameter row CURRENT WHEN THE STEP IS CLOSED
+ *               (gpf_set_block_params; rows travel with their block), else the filter's; obs_s[c] = block c's current observation row.
+ *               (m_j, f_j) = the maximum and flags over i; K = fix_K(count of c'); q_ij = exp_fix(lwa_ij - m_j, K); D_j = sum_i q_ij (u64, exact).
+ *     fallback  f_j != 0 (NaN, +Inf, all -Inf): q_ij = 1 for i = pm_j - c' bs, 0 otherwise, D_j = 1.
+ *     sums      over i in ASCENDING order; a candidate with q_ij == 0 is SKIPPED ENTIRELY (0 * x is not +0.0 for every x, and a dead candidate may
+ *               carry a non-finite statistic):  h_j[f] = h_j[f] + (double)q_ij * T_{s-1}^i[f];   xb_j[a] = xb_j[a] + (double)q_ij * x_{s-1}^i[a];
+ *               both from +0.0, one multiply and one add per term (no fused multiply-add); e_j[f] = h_j[f] / (double)D_j, xbar_j[a] = xb_j[a] / (double)D_j.
+ *     new T     sum[a] = e + x_s^j[a];  second[a,c] = e + x_s^j[a] * x_s^j[c];  cross[a][c] = e + xbar_j[a] * x_s^j[c];  first = e;  first2 = e
+ *               (e = the entry's own e_j[f]).
+ * gpf_block_forward_moments: HOST outputs [n_blocks][d] (sum, first) or [n_blocks][d][d] (second, cross, first2, last2; triangles mirrored); any may be
+ * NULL, not all.  It materialises anything deferred, forms the statistics of the CURRENT step as a close would (into scratch: nothing is committed, the
+ * close inside the next gpf_update_blocks* recomputes them) and returns
+ *     out[b][f] = tree_j(W^j * T^j[f]),      last2_out[b][a][c] = tree_j((W^j * x^j[a]) * x^j[c])   (gpf_block_smooth_pairs' second at the last step)
+ * with W^j = (double)q_j / (double)S of the block's current weights and the summation tree of gpf_block_moments over the index within
+ * the block.  *n_steps_out = the current step.  The M-step sums follow as second - last2 (steps < t), second - first2 (steps > 1) and cross.
+ * A block whose current weights hold NaN / +Inf reads NaN everywhere; the others are unaffected.  No effects: no uniform is read, and epoch, rows, weights,
+ * parents and records stay as they are; the stream is synchronised.  Refused: GPF_ERR_STATE -- the mode is off, nothing is initialised;
+ * GPF_ERR_INVALID_ARGUMENT -- block_size < 1 or another clamped block size than the mode's, all outputs NULL, a NULL handle. */
+gpf_status gpf_forward_enable_blocks(gpf_handle h);   /* before gpf_initialize_blocks */
+gpf_status gpf_block_forward_moments(gpf_handle h, int64_t block_size, double* sum_out, double* second_out, double* cross_out, double* first_out,
+                                     double* first2_out, double* last2_out, int32_t* n_steps_out);
+
 /* ---- shard-level building blocks (multi-GPU) ------------------------------------------------------
  * A filter sharded over G GPUs is G handles created with the same seed / n_global and contiguous
  * [gid0, gid0 + n_particles) ranges.  gpf_initialize / gpf_update / gpf_rejuvenate work per shard as they
@@ -898,7 +945,8 @@ void    gpf_host_math(int32_t which, const double* a, const double* b, int64_t n
  * shard) as ONE host blob: population, log-weights, parents, log-ML estimate, RNG epoch, the latest observation and strata.  gpf_checkpoint_save first
  * turns everything deferred (lazy move, lazy search, un-gathered resample, un-scattered sharded commit) into state; gpf_checkpoint_load takes a handle
  * created with the SAME gpf_config (model, parameters, particle counts, gid0, seed, keep_prev -- else GPF_ERR_INVALID_ARGUMENT) and continues bit for bit
- * where the saved filter stood.  Not part of a blob: the trajectory store (a filter that records one refuses to load), per-block observations, views. */
+ * where the saved filter stood.  Not part of a blob: the trajectory store (a filter that records one refuses to load), per-block observations, views, the
+ * statistics of forward smoothing per block (gpf_forward_enable_blocks: such a filter saves what it would save without the mode and refuses to load). */
 gpf_status gpf_checkpoint_size(gpf_handle h, int64_t* bytes);
 gpf_status gpf_checkpoint_save(gpf_handle h, void* out, int64_t bytes);
 gpf_status gpf_checkpoint_load(gpf_handle h, const void* in, int64_t bytes);

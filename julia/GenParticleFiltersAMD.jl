@@ -41,9 +41,10 @@ mutable struct DeviceParticleFilterState
     n_particles::Int
     # history = T: the trajectory store for T time steps (gpf.h gpf_history_enable); history_blocks: the block-wise store, which the block-wise
     # calls feed too (gpf_history_enable_blocks); history_weights: that store with every step's log-weights and per-block observations, which
-    # block_backward_trajectories needs (gpf_history_enable_blocks_weights)
+    # block_backward_trajectories needs (gpf_history_enable_blocks_weights); forward: forward-only smoothing per block (gpf_forward_enable_blocks), with
+    # the block-wise store or without a store
     function DeviceParticleFilterState(model::NativeModel, n::Int; seed::Integer=1, keep_prev::Bool=false, device::Integer=0, history::Integer=0,
-                                       history_blocks::Bool=false, history_weights::Bool=false)
+                                       history_blocks::Bool=false, history_weights::Bool=false, forward::Bool=false)
         history_weights && !(history > 0 && history_blocks) && error("history_weights needs the block-wise trajectory store (history = T)")
         h = Ref{Ptr{Cvoid}}(C_NULL)
         GC.@preserve model begin
@@ -58,6 +59,10 @@ mutable struct DeviceParticleFilterState
             st = history_weights ? ccall((:gpf_history_enable_blocks_weights, libgpf), Cint, (Ptr{Cvoid}, Cint), h[], history) :
                  history_blocks ? ccall((:gpf_history_enable_blocks, libgpf), Cint, (Ptr{Cvoid}, Cint), h[], history) :
                                   ccall((:gpf_history_enable, libgpf), Cint, (Ptr{Cvoid}, Cint), h[], history)
+            st == 0 || error(unsafe_string(ccall((:gpf_last_error, libgpf), Cstring, (Ptr{Cvoid},), h[])))
+        end
+        if forward
+            st = ccall((:gpf_forward_enable_blocks, libgpf), Cint, (Ptr{Cvoid},), h[])
             st == 0 || error(unsafe_string(ccall((:gpf_last_error, libgpf), Cstring, (Ptr{Cvoid},), h[])))
         end
         return state
@@ -690,6 +695,21 @@ function block_smoothed_pair_moments(s::DeviceParticleFilterState, block_size::I
     _status(s, ccall((:gpf_block_smooth_pairs, libgpf), Cint, (Ptr{Cvoid}, Int64, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int64}),
                      s.handle, block_size, first(steps), last(steps), mu, second, length(steps) > 1 ? cross : C_NULL, return_blocks ? blocks : C_NULL))
     return (mu, second, cross, (return_blocks ? (blocks,) : ())...)
+end
+
+# Forward-only smoothing per block (gpf.h gpf_block_forward_moments; needs pf_initialize_blocks(...; forward=true)): after the current step t, the sums
+# over steps of block_smoothed_pair_moments without a store -- sum = sum_s E[x_s | y_1:t] and first = E[x_1 | y_1:t] as (dim, n_blocks); second =
+# sum_s E[x_s x_s' | y_1:t], first2, last2 = E[x_t x_t' | y_1:t] (symmetric) and cross as (dim, dim, n_blocks) with cross[c, a, b] = sum_s E[x_s[a]
+# x_{s+1}[c] | y_1:t] (the library writes row-major [n_blocks][a][c]) -- and t.  The M-step reads second - last2, second - first2 and cross.
+function block_forward_moments(s::DeviceParticleFilterState, block_size::Int)
+    bs = min(block_size, s.n_particles); nb = cld(s.n_particles, bs); d = _latent_dim(s)
+    sum_ = Array{Float64}(undef, d, nb); first_ = Array{Float64}(undef, d, nb)
+    second = Array{Float64}(undef, d, d, nb); cross = Array{Float64}(undef, d, d, nb)
+    first2 = Array{Float64}(undef, d, d, nb); last2 = Array{Float64}(undef, d, d, nb)
+    t = Ref{Cint}(0)
+    _status(s, ccall((:gpf_block_forward_moments, libgpf), Cint, (Ptr{Cvoid}, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cint}),
+                     s.handle, block_size, sum_, second, cross, first_, first2, last2, t))
+    return (sum=sum_, second=second, cross=cross, first=first_, first2=first2, last2=last2, n_steps=Int(t[]))
 end
 
 # ---------------------------------------------------------------- multi-GPU: one process per GPU, the exchange inside libgpf
