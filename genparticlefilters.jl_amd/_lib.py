@@ -110,6 +110,7 @@ SYMBOLS = [
     ("gpf_block_backward_sample", C.c_int, [_H, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _pd, _pi64]),
     ("gpf_block_smooth", C.c_int, [_H, C.c_int64, C.c_int32, C.c_int32, _pd, _pd, _pd, _pi64]),
     ("gpf_block_smooth_pairs", C.c_int, [_H, C.c_int64, C.c_int32, C.c_int32, _pd, _pd, _pd, _pi64]),
+    ("gpf_block_map_path", C.c_int, [_H, C.c_int64, C.c_int32, C.c_int32, _pd, _pi64, _pd]),
     ("gpf_forward_enable_blocks", C.c_int, [_H]),
     ("gpf_block_forward_moments", C.c_int, [_H, C.c_int64, _pd, _pd, _pd, _pd, _pd, _pd, C.POINTER(C.c_int32)]),
     # shard-level building blocks: device pointers are passed as integers (tensor.data_ptr())

@@ -1236,6 +1236,32 @@ def block_smoothed_pair_moments(state, block_size: int, steps=None, return_block
     return (mu, second, cross) + ((blocks,) if return_blocks else ())
 
 
+def block_map_trajectories(state, block_size: int, steps=None, return_indices: bool = False, return_log_density: bool = False):
+    """the most probable path per block (particle Viterbi; gpf.h gpf_block_map_path, Godsill, Doucet & West 2001): over the sequences that take one
+    particle of the block's lineage at every recorded step, the maximiser of log mu(x_1) + sum_s log f(x_s | x_{s-1}) + sum_s log g(y_s | x_s), by
+    max-plus dynamic programming -- what block_proportionmap's per-step modes do not give, because marginal modes need not form a likely path.  One launch
+    for all blocks and steps, O(block_size^2) per block and step; needs pf_initialize_blocks(..., history=T, history_weights=True).  Returns the paths
+    [n_blocks, n_steps, dim]; with return_indices=True also the [n_blocks, n_steps] int64 indices (1-based, GLOBAL, in the final order of their step) of
+    the path's particles; with return_log_density=True also [n_blocks], the maximum -- comparable between paths of one block, not a normalised density
+    (the constants of the transition and the initial law are omitted).  steps as in block_backward_trajectories; the recursion always runs over all
+    steps.  A block whose lineage is undefined at any step (a whole-filter resample) or that has no path of positive density reads NaN paths and
+    indices 0.  Under set_block_params every step uses the final block's CURRENT parameter row.  Nothing is drawn: the RNG epoch and the filter are
+    left untouched."""
+    who = "block_map_trajectories"
+    if not getattr(state, "history_weights", False):
+        raise ErrorException(who + " needs the block-wise trajectory store with its weight records "
+                             "(pf_initialize_blocks(..., history=T, history_weights=True)), which this state does not have")
+    lo, hi = _store_steps(state, steps, who)
+    _, nb = _store_blocks(state, block_size, lo, hi, who)
+    path = np.empty((nb, hi - lo + 1, state.dim))
+    idx = np.empty((nb, hi - lo + 1), np.int64) if return_indices else None
+    logp = np.empty(nb) if return_log_density else None
+    state._check(state._L.gpf_block_map_path(state._h, int(block_size), lo, hi, _pd(path), idx.ctypes.data_as(C.POINTER(C.c_int64)) if return_indices else None,
+                                             _pd(logp) if return_log_density else None))
+    out = (path,) + ((idx,) if return_indices else ()) + ((logp,) if return_log_density else ())
+    return out if len(out) > 1 else path
+
+
 # ----------------------------------------------------------------------------- statistics (src/statistics.jl)
 def _addr_values(state, addr) -> np.ndarray:
     """the values at one address over all particles: a column of the current step, or (t, column) for a past choice"""

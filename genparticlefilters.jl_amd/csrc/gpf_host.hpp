@@ -655,6 +655,8 @@ gpf_status weighted_tree_sum(gpf_filter* h, const double* values, int stride, in
 void launch_block_smooth(gpf_filter* h, const SmoothArgs& a, const AncArgs& x);   // k_block_smooth<model, TEAM, ITEMS> by team_dispatch
 // ---- defined in libgpf_pairs.hip
 void launch_block_pairs(gpf_filter* h, const PairArgs& a, const AncArgs& x);      // k_block_smooth_pairs<model, TEAM, ITEMS> by team_dispatch
+// ---- defined in libgpf_map.hip
+void launch_block_map(gpf_filter* h, const MapArgs& a, const AncArgs& x);         // k_block_map<model, TEAM, ITEMS> by team_dispatch
 // ---- defined in libgpf_forward.hip: the forward-only smoother's records (hist_begin_step / hist_on_resample call the first two) and launches
 gpf_status fwd_begin_step(gpf_filter* h, bool first);             // first: step 1 begins, the statistics are reset; else the step that ends is closed in its final order
 gpf_status fwd_on_resample(gpf_filter* h, int64_t block_size);    // this call's parents into the current step's map (block_size > 0: block-local, h->blk_mask says which)

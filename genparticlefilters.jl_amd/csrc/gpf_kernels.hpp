@@ -27,3 +27,4 @@
 #include "gpf_k_block_back.hpp"
 #include "gpf_k_block_smooth.hpp"
 #include "gpf_k_block_forward.hpp"
+#include "gpf_k_block_map.hpp"

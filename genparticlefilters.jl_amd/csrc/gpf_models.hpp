@@ -7,6 +7,9 @@
 //   loglik(P, x, obs) -> log p(y_t | x_t)               the weight increment of the constrained obs
 //   logtrans(P, xp, x, obs) -> log f(x_t = x | x_{t-1} = xp) MINUS the terms that do not depend on xp (normalising constants cancel wherever
 //                                                       it is used: ancestor sampling, backward simulation) -- + - * / only, no log_
+//   transrest(P, x, obs) -> the part of log f(x_t = x | x_{t-1}) that is free of x_{t-1} but NOT of x (what logtrans leaves out and a maximisation over
+//                                                       x needs: gpf_block_map_path); HAS_TRANS_REST = false: there is none, and the member is absent
+//   logprior(P, x, obs) -> log mu(x_1 = x), the law sample(first = true) draws from, MINUS the terms that do not depend on x -- + - * / only
 // Parameter vectors P (incl. derived constants such as log sigma) are built on the host
 // (models.py) so the CPU oracle and the kernels receive bit-identical inputs.
 // Operation order inside each expression is part of the spec.
@@ -147,6 +150,13 @@ template <> struct Model<MODEL_LGSSM2> {
         const double a0 = (x[0] - t0) * P[12], a1 = (x[1] - t1) * P[12];
         return -0.5 * (a0 * a0 + a1 * a1);
     }
+    static constexpr bool HAS_TRANS_REST = false;
+    // the quadratic of `lt` in proposal_weight (o = 14, mu = 0)
+    static GPF_HD double logprior(const double* P, const double* x, const double*)
+    {
+        const double a0 = x[0] * P[18], a1 = x[1] * P[18];
+        return -0.5 * (a0 * a0 + a1 * a1);
+    }
 };
 
 // bearings-only tracking, x = (px, py, vx, vy)   (BASELINE config 4)
@@ -188,6 +198,13 @@ template <> struct Model<MODEL_BEARINGS4> {
         const double z2 = (x[2] - xp[2]) / P[9], z3 = (x[3] - xp[3]) / P[9];
         return -0.5 * ((z0 * z0 + z1 * z1) + (z2 * z2 + z3 * z3));
     }
+    static constexpr bool HAS_TRANS_REST = false;
+    static GPF_HD double logprior(const double* P, const double* x, const double*)
+    {
+        const double z0 = (x[0] - P[0]) / P[4], z1 = (x[1] - P[1]) / P[5];
+        const double z2 = (x[2] - P[2]) / P[6], z3 = (x[3] - P[3]) / P[7];
+        return -0.5 * ((z0 * z0 + z1 * z1) + (z2 * z2 + z3 * z3));
+    }
 };
 
 // stochastic volatility, x = h   (BASELINE config 5)
@@ -215,6 +232,13 @@ template <> struct Model<MODEL_SV1> {
     {
         const double mean = P[0] + P[1] * (xp[0] - P[0]);
         const double z = (x[0] - mean) / P[2];
+        return -0.5 * (z * z);
+    }
+    static constexpr bool HAS_TRANS_REST = false;
+    // the stationary law sample(first) draws from
+    static GPF_HD double logprior(const double* P, const double* x, const double*)
+    {
+        const double z = (x[0] - P[0]) / P[3];
         return -0.5 * (z * z);
     }
 };
@@ -273,6 +297,13 @@ template <> struct Model<MODEL_OBJECT_MOTION> {
         const double z = (x[1] - (xp[1] + vel)) / P[2];
         return lp + (-0.5 * (z * z));
     }
+    static constexpr bool HAS_TRANS_REST = false;
+    // the first step is a transition from (still, 0), as sample(first) has it
+    static GPF_HD double logprior(const double* P, const double* x, const double* obs)
+    {
+        const double x0[2] = {0.0, 0.0};
+        return logtrans(P, x0, x, obs);
+    }
 };
 
 // line_model, the fixture model of the reference's own tests (reference test/runtests.jl:3-16):
@@ -304,6 +335,17 @@ template <> struct Model<MODEL_LINE> {
     static GPF_HD double logtrans(const double*, const double* xp, const double* x, const double*)
     {
         return xp[0] == x[0] ? 0.0 : -__builtin_huge_val();
+    }
+    // ... and is what logtrans leaves out: log p(outlier) of a step that has one (model args (0,): no outlier choice)
+    static constexpr bool HAS_TRANS_REST = true;
+    static GPF_HD double transrest(const double* P, const double* x, const double* obs)
+    {
+        return obs[1] != 0.0 ? (x[1] != 0.0 ? P[5] : P[6]) : 0.0;
+    }
+    // log p(slope) = -log(n_slopes), and the first step's outlier under the same rule
+    static GPF_HD double logprior(const double* P, const double* x, const double* obs)
+    {
+        return obs[1] != 0.0 ? P[7] + (x[1] != 0.0 ? P[5] : P[6]) : P[7];
     }
     // The custom proposals of the reference's tests as ONE native proposal (test/initialize.jl:16-19, test/update.jl:42-43):
     // slope ~ uniform_discrete(0, 0) at the first step, outlier ~ bernoulli(0.0) at every step.  Both are deterministic

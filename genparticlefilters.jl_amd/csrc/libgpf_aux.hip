@@ -1803,6 +1803,39 @@ gpf_status gpf_block_smooth_pairs(gpf_handle h, int64_t block_size, int32_t step
     // (nothing was drawn: the epoch stays)
     return block_out(h, {{d_mean.p, mean_out, b_mean}, {d_sec.p, second_out, b_sec}, {d_cross.p, cross_out, b_cross}, {d_c.p, blocks_out, b_c}});
 }
+// ---- the most probable path per block (gpf.h gpf_block_map_path): max-plus dynamic programming over the store's grid and the trace, all
+// blocks and steps in one launch; gpf_block_smooth's gate and checks, and like it instantiated in a translation unit of its own (libgpf_map.hip).  The DP
+// always walks T .. 1 whatever the range written, so every step -- step 1 too, whose observation row the node score and the prior term read -- must have
+// been entered by a block-wise call of this block size
+gpf_status gpf_block_map_path(gpf_handle h, int64_t block_size, int32_t step_lo, int32_t step_hi, double* path_out, int64_t* idx_out, double* logp_out)
+{
+    const char* who = "gpf_block_map_path";
+    gpf_status s = block_store_gate(h, block_size, who, true);
+    if (s) return s;
+    if (!path_out && !idx_out && !logp_out) return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": all outputs are NULL");
+    StoreSteps r{};
+    if ((s = block_store_steps(h, block_size, step_lo, step_hi, who, r))) return s;
+    const int64_t lim = (int64_t)1 << 31, cells = r.nblocks * r.n_steps;   // (nblocks, n_steps, d < 2^31: as gpf_block_smooth)
+    if (cells >= lim || cells >= (lim + h->d - 1) / h->d)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": n_blocks * n_steps * dim must stay below 2^31");
+    if ((s = block_store_sizes(h, block_size, r.T, 0, who))) return s;
+    const size_t b_path = (size_t)cells * (size_t)h->d * sizeof(double), b_idx = (size_t)cells * sizeof(int64_t), b_lp = (size_t)r.nblocks * sizeof(double);
+    // the back-pointers (2 bytes per particle and step, rows padded to 16 bytes) and the lineage blocks: scratch of this call like the outputs' device
+    // copies -- 198 MB at 10^4 blocks of 100 and T = 100 are nothing to keep on a handle; hipFree on return waits for the launch
+    const int64_t bsp = (block_size + 7) / 8 * 8;
+    const size_t b_ptr = (size_t)std::max(r.T - 1, 1) * (size_t)r.nblocks * (size_t)bsp * sizeof(uint16_t), b_lin = (size_t)r.nblocks * (size_t)r.T * sizeof(int32_t);
+    CallScratch d_path, d_idx, d_lp, d_ptr, d_lin;
+    if ((s = block_store_tables(h, true)) || (s = block_store_scratch(h, d_path, path_out, b_path)) || (s = block_store_scratch(h, d_idx, idx_out, b_idx)) ||
+        (s = block_store_scratch(h, d_lp, logp_out, b_lp)) || (s = block_store_scratch(h, d_ptr, h, b_ptr)) || (s = block_store_scratch(h, d_lin, h, b_lin))) return s;
+    MapArgs a{};
+    block_store_walk_args(h, r, step_lo, step_hi, block_size, a);
+    a.path = static_cast<double*>(d_path.p); a.idx = static_cast<int64_t*>(d_idx.p); a.logp = static_cast<double*>(d_lp.p);
+    a.ptr = static_cast<uint16_t*>(d_ptr.p); a.lin = static_cast<int32_t*>(d_lin.p); a.bsp = bsp;
+    launch_block_map(h, a, anc_args(h));
+    HIP_TRY(h, hipGetLastError());
+    // (nothing was drawn: the epoch stays)
+    return block_out(h, {{d_path.p, path_out, b_path}, {d_idx.p, idx_out, b_idx}, {d_lp.p, logp_out, b_lp}});
+}
 // ---- forward-only smoothing per block (gpf.h gpf_forward_enable_blocks / gpf_block_forward_moments): the additive smoothing functionals
 // of particle EM after every step, from one generation of records.  The records, the hooks of the block-wise calls and the kernels' instantiations live in
 // a translation unit of their own (libgpf_forward.hip)

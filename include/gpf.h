@@ -712,6 +712,42 @@ gpf_status gpf_block_smooth(gpf_handle h, int64_t block_size, int32_t step_lo, i
 gpf_status gpf_block_smooth_pairs(gpf_handle h, int64_t block_size, int32_t step_lo, int32_t step_hi,
                                   double* mean_out, double* second_out, double* cross_out, int64_t* blocks_out);
 
+/* The most probable path per block over the grid the block-wise trajectory store holds: the MAP sequence estimator of Godsill, Doucet & West 2001
+ * ("Maximum a posteriori sequence estimation using Monte Carlo particle filters", Ann. Inst. Statist. Math. 53) -- particle Viterbi.  For every final
+ * block b, over the bs^T sequences that take one particle of the lineage's block at every step 1 .. T (T = gpf_history_steps, bs the clamped block
+ * size), the maximiser of
+ *     log mu(x_1) + sum_s log f(x_s | x_{s-1}) + sum_s log g(y_s | x_s)
+ * by dynamic programming in max-plus form, all blocks and steps in ONE launch, O(T bs^2) logtrans evaluations per block.  The gate, the clamped block
+ * size, P_b = the FINAL block's CURRENT parameter row, the step range, materialising deferred work and synchronising the stream are gpf_block_smooth's.
+ * Needs gpf_history_enable_blocks_weights: the observation rows are recorded only then (no weight is read).
+ *   lineage   c_T = b; c_s = the block ALL recorded parents of the particles of block c_{s+1} sit in (gpf_block_smooth's check).  Where it is undefined
+ *             at ANY step, the whole block reads NaN paths, index 0 and logp NaN -- not gpf_block_smooth's rule, on purpose: a recursion that cannot
+ *             reach step 1 has no prior term.
+ *   node      n_s^i = loglik(P_b, x_s^i, obs_s[c_s]); for s >= 2 and a model with HAS_TRANS_REST: n_s^i = loglik + transrest(P_b, x_s^i, obs_s[c_s])
+ *             (one add) -- the part of log f that logtrans drops because it is free of x_{s-1}, but not of x_s (line_model: the outlier's Bernoulli term).
+ *   recursion v_T^j = n_T^j.  For s = T-1 .. 1 and every candidate i of block c_s: best = -Inf, ptr = 0; over the targets j of block c_{s+1} in ASCENDING j:
+ *                 val = logtrans(P_b, x_s^i, x_{s+1}^j, obs_{s+1}[c_{s+1}]) + v_{s+1}^j;     if (val > best) { best = val; ptr = j; }
+ *             so a NaN never wins and the smallest j wins a tie.  v_s^i = n_s^i + best;  ptr_s[i] = ptr.  One add each; no fused multiply-add anywhere.
+ *   step 1    tot_i = logprior(P_b, x_1^i, obs_1[c_1]) + v_1^i; i* = the smallest i attaining the maximum of the non-NaN totals, logp[b] = that maximum.
+ *             The maximum -Inf (no sequence of positive density on the grid), or every total NaN (then logp = NaN): NaN paths, indices 0.
+ *   trace     p_1 = i*, p_{s+1} = ptr_s[p_s].
+ *   outputs   HOST, n_steps = step_hi - step_lo + 1, d = the model's latent dimension; the recursion always runs over 1 .. T, the range selects what is written:
+ *               path_out [n_blocks][n_steps][d]         path[b][s - step_lo] = the latent columns of particle c_s bs + p_s of snapshot s;
+ *               idx_out  int64 [n_blocks][n_steps]      c_s bs + p_s + 1: 1-based, GLOBAL, in the final order of its step (as gpf_block_backward_sample);
+ *               logp_out [n_blocks]                     the maximum.
+ *             Any may be NULL, not all.
+ *   logp      comparable between the paths of ONE block under one parameter row; NOT a normalised log density.  It holds loglik in full, and of log f and
+ *             log mu only what depends on the path: the Gaussian normalising constants of the transition and the initial law (T log(sqrt(2 pi) sigma)
+ *             terms) and every other term free of x are omitted, as in logtrans.  Because rounded addition is monotone, logp is bit for bit the maximum
+ *             over all bs^T sequences of the right-nested total logprior + (n_1 + (lt_12 + (n_2 + (lt_23 + ... + n_T)))).
+ *   effects   none: no uniform is read; the epoch does not advance; rows, weights, parents and the store are untouched.  The back-pointers (16-bit, 2 bytes per
+ *             particle and step) are device scratch of the call.
+ *   refused   nothing written, nothing changed: those of gpf_block_smooth (GPF_ERR_STATE: no store, a store without the weight records, a step entered by a
+ *             whole-filter call, a clamped block_size > 2048; GPF_ERR_INVALID_ARGUMENT: a bad step range, block_size < 1, a block size other than the
+ *             per-block parameters' or than the one a step was entered with, a NULL handle, all outputs NULL, n_blocks * n_steps * d >= 2^31) -- with every
+ *             step 1 .. T a walked step, whatever the range.  Custom proposals: the path is the MAP under the MODEL's densities whatever proposed the grid. */
+gpf_status gpf_block_map_path(gpf_handle h, int64_t block_size, int32_t step_lo, int32_t step_hi, double* path_out, int64_t* idx_out, double* logp_out);
+
 /* Forward-only smoothing per block: the sums over steps of gpf_block_smooth_pairs' moments -- sum_s E[x_s x_s^T | y_1:t], sum_s E[x_s x_{s+1}^T | y_1:t],
  * what the M-step of particle EM reads -- after EVERY step, without a store (Del Moral, Doucet & Singh 2010, "Forward smoothing using sequential Monte
  * Carlo"; Poyiadjis, Doucet & Singh 2011, Biometrika 98; the online EM of Cappe 2011).  Every particle carries a statistic T^j of F = d + d(d+1)/2 + d d +

@@ -697,6 +697,26 @@ function block_smoothed_pair_moments(s::DeviceParticleFilterState, block_size::I
     return (mu, second, cross, (return_blocks ? (blocks,) : ())...)
 end
 
+# The most probable path per block (gpf.h gpf_block_map_path; particle Viterbi, Godsill, Doucet & West 2001): max-plus dynamic programming over the
+# particles of the block's lineage at every recorded step -- one launch, nothing drawn, the epoch stays.  Needs pf_initialize_blocks(...; history=T,
+# history_weights=true).  Returns the paths (dim, n_steps, n_blocks), then on request the (n_steps, n_blocks) 1-based GLOBAL indices of their particles and
+# the (n_blocks) maxima (comparable within a block, not a normalised density).  NaN and 0 where a lineage is undefined or no path has positive density.
+function block_map_trajectories(s::DeviceParticleFilterState, block_size::Int; steps::Union{Nothing,UnitRange{Int}}=nothing,
+                                return_indices::Bool=false, return_log_density::Bool=false)
+    if steps === nothing
+        k = Ref{Cint}(0)
+        _status(s, ccall((:gpf_history_steps, libgpf), Cint, (Ptr{Cvoid}, Ref{Cint}), s.handle, k))
+        steps = 1:Int(k[])
+    end
+    bs = min(block_size, s.n_particles); nb = cld(s.n_particles, bs); d = _latent_dim(s)
+    path = Array{Float64}(undef, d, length(steps), nb)
+    idx = return_indices ? Array{Int64}(undef, length(steps), nb) : nothing
+    logp = return_log_density ? Array{Float64}(undef, nb) : nothing
+    _status(s, ccall((:gpf_block_map_path, libgpf), Cint, (Ptr{Cvoid}, Int64, Cint, Cint, Ptr{Cdouble}, Ptr{Int64}, Ptr{Cdouble}),
+                     s.handle, block_size, first(steps), last(steps), path, return_indices ? idx : C_NULL, return_log_density ? logp : C_NULL))
+    return (return_indices || return_log_density) ? (path, (return_indices ? (idx,) : ())..., (return_log_density ? (logp,) : ())...) : path
+end
+
 # Forward-only smoothing per block (gpf.h gpf_block_forward_moments; needs pf_initialize_blocks(...; forward=true)): after the current step t, the sums
 # over steps of block_smoothed_pair_moments without a store -- sum = sum_s E[x_s | y_1:t] and first = E[x_1 | y_1:t] as (dim, n_blocks); second =
 # sum_s E[x_s x_s' | y_1:t], first2, last2 = E[x_t x_t' | y_1:t] (symmetric) and cross as (dim, dim, n_blocks) with cross[c, a, b] = sum_s E[x_s[a]

@@ -1,6 +1,6 @@
 """Register / scratch / LDS / occupancy table of every kernel of libgpf (compile-time, no GPU):
     python3 tools/kernel_resources.py > profiles/rNN_kernel_resources.txt
-Compiles the seven translation units with -Rpass-analysis=kernel-resource-usage and prints one line per kernel."""
+Compiles the eight translation units with -Rpass-analysis=kernel-resource-usage and prints one line per kernel."""
 import os
 import re
 import subprocess
@@ -14,7 +14,7 @@ with tempfile.TemporaryDirectory() as td:
     procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden",
                                "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"), "-Rpass-analysis=kernel-resource-usage", *sys.argv[1:],
                                "-c", os.path.join(csrc, u), "-o", os.path.join(td, u + ".o")], stderr=subprocess.PIPE, text=True)
-             for u in ("libgpf_core.hip", "libgpf_resample.hip", "libgpf_aux.hip", "libgpf_shard.hip", "libgpf_smooth.hip", "libgpf_pairs.hip", "libgpf_forward.hip")]
+             for u in ("libgpf_core.hip", "libgpf_resample.hip", "libgpf_aux.hip", "libgpf_shard.hip", "libgpf_smooth.hip", "libgpf_pairs.hip", "libgpf_forward.hip", "libgpf_map.hip")]
     for q in procs:
         err += q.communicate()[1]
 class _P: stderr = err
