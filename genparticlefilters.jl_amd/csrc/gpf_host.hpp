@@ -74,17 +74,35 @@ struct WeightSummary {
     void reduced(const WSum& w, bool on_host) { sum_cache = w; sum_on_host = on_host; raw_sum_valid = true; }   // k_sum_reduce / k_sum_host
 };
 
-} // namespace gpfh
+// ------------------------------------------------------------------ owned memory
+// `count` elements of T on the device (Dev<T>) or in pinned host memory (Pinned<T>), freed by the destructor.  Every allocation a handle owns, and every
+// scratch buffer of one call, is one of these -- apart from the per-particle set (Bufs below, which is swapped whole and aliased by views) and the memory
+// other processes map (the shard mailboxes and windows).  Move-only; reads as its pointer, but a kernel launch takes its arguments by value and so has
+// to name the pointer (.p) -- passing the owner there does not compile.
+template <class T, bool PINNED>
+struct Owned {
+    T* p = nullptr;
+    size_t count = 0;                  // elements held
+    Owned() = default;
+    Owned(Owned&& o) noexcept : p(o.p), count(o.count) { o.p = nullptr; o.count = 0; }
+    Owned& operator=(Owned&& o) noexcept { if (this != &o) { reset(); p = o.p; count = o.count; o.p = nullptr; o.count = 0; } return *this; }
+    ~Owned() { reset(); }
+    void reset()
+    {
+        if (p) { if (PINNED) (void)hipHostFree(p); else (void)hipFree(p); }
+        p = nullptr; count = 0;
+    }
+    gpf_status alloc(gpf_filter* h, size_t n);                        // exactly n elements into an empty owner
+    gpf_status grow(gpf_filter* h, size_t n, bool* fresh = nullptr);   // at least n: nothing, or (drain the stream, free, allocate exactly n) with *fresh = true
+    operator T*() const { return p; }
+    T* operator->() const { return p; }
+};
+template <class T> using Dev = Owned<T, false>;
+template <class T> using Pinned = Owned<T, true>;
 
-struct __attribute__((visibility("hidden"))) gpf_filter {
-    gpf_config cfg{};
-    ModelArgs args{};
-    int d = 0, W = 0, K = 0;
-    double logN = 0.0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int n_cu = 256;
-    int64_t n = 0, ntiles = 0;
+// ------------------------------------------------------------------ per-N device buffers
+struct Bufs {                        // everything whose size depends on the particle count: the base of the handle, and a detached set while resizing.  Plain
+    int64_t n = 0, ntiles = 0;       // pointers (free_bufs frees a set): views alias their filter's rows / lw / anc, the resize family swaps whole sets
     double* rows[2] = {nullptr, nullptr};
     int cur = 0;
     double *lw = nullptr, *lws = nullptr, *lp = nullptr, *dtmp = nullptr;
@@ -92,29 +110,43 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     uint64_t* t16[3] = {nullptr, nullptr, nullptr};     // coarser levels written by the scan (gpf_kernels.hpp ScanOut)
     uint64_t* t256[3] = {nullptr, nullptr, nullptr};
     uint64_t* desc[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};   // [channel][ping-pong]: agg | prefix
-    int dcur[3] = {0, 0, 0};
-    const uint64_t* table[3] = {nullptr, nullptr, nullptr};   // per-tile inclusive prefixes of the last scan per channel
     int32_t *anc = nullptr, *order = nullptr, *idx_in = nullptr;
     uint64_t *keys = nullptr, *keys_out = nullptr;
     void* sort_tmp = nullptr;
+};
+
+} // namespace gpfh
+
+struct __attribute__((visibility("hidden"))) gpf_filter : gpfh::Bufs {
+    template <class T> using Dev = gpfh::Dev<T>;
+    template <class T> using Pinned = gpfh::Pinned<T>;
+    gpf_config cfg{};
+    ModelArgs args{};
+    int d = 0, W = 0, K = 0;
+    double logN = 0.0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    int n_cu = 256;
+    int dcur[3] = {0, 0, 0};
+    const uint64_t* table[3] = {nullptr, nullptr, nullptr};   // per-tile inclusive prefixes of the last scan per channel
     size_t sort_tmp_bytes = 0;
     int sort_ws_cur = 0;
-    int64_t* h_sort_flag = nullptr; int64_t sort_ticket = 0;   // pinned {a run too long for k_sort_finish, ticket}
-    unsigned long long* mslots[2] = {nullptr, nullptr};   // MaxSlots (gpf_k_common.hpp): maximum + flags of the log-weights, two alternating arrays
+    Pinned<int64_t> h_sort_flag; int64_t sort_ticket = 0;   // pinned {a run too long for k_sort_finish, ticket}
+    Dev<unsigned long long> mslots[2];                    // MaxSlots (gpf_k_common.hpp): maximum + flags of the log-weights, two alternating arrays
     int mcur = 0;                                         // mslots[mcur]: written by the latest producer
-    uint64_t* blockQ = nullptr;
-    double *partial = nullptr, *dscal = nullptr;
-    unsigned long long* acc_part = nullptr;   // [MAX_PARTIALS] accepted moves per workgroup of the last move-accept kernel
-    double* tree_buf = nullptr; int64_t tree_cap = 0;   // partials of the weighted tree sums (statistics)
-    Scalars* sc = nullptr;
-    Scalars* h_sc = nullptr;       // pinned mirror
-    long long* h_sc_ticket = nullptr; long long sc_ticket = 0;   // k_publish_scalars -> host polling (fetch_scalars)
+    Dev<uint64_t> blockQ;
+    Dev<double> partial, dscal;
+    Dev<unsigned long long> acc_part;         // [MAX_PARTIALS] accepted moves per workgroup of the last move-accept kernel
+    Dev<double> tree_buf;                     // partials of the weighted tree sums (statistics)
+    Dev<Scalars> sc;
+    Pinned<Scalars> h_sc;          // pinned mirror
+    Pinned<long long> h_sc_ticket; long long sc_ticket = 0;   // k_publish_scalars -> host polling (fetch_scalars)
     uint32_t epoch = 0;
     bool initialized = false, has_prev = false, residual_scanned = false;
     gpfh::WeightSummary summary;   // the cached summaries of the current log-weights
-    uint64_t* sum_part = nullptr;  // [6][workgroups] tagged partials of k_sum_reduce
-    int64_t* h_spart = nullptr;    // pinned: [n_cu][8] tagged partials of k_sum_host, folded by the host
-    uint64_t* gate_part = nullptr; int gate_cur = 0; int64_t* h_gate = nullptr;   // gpf_step_ess: two sets of k_sum_host<GATE>'s accumulator lines (gate_verdict), pinned {ticket << 1 | verdict} of the launch that read them
+    Dev<uint64_t> sum_part;        // [6][workgroups] tagged partials of k_sum_reduce
+    Pinned<int64_t> h_spart;       // pinned: [n_cu][8] tagged partials of k_sum_host, folded by the host
+    Dev<uint64_t> gate_part; int gate_cur = 0; Pinned<int64_t> h_gate;   // gpf_step_ess: two sets of k_sum_host<GATE>'s accumulator lines (gate_verdict), pinned {ticket << 1 | verdict} of the launch that read them
     bool pending_gather = false;   // a resample left (rows[cur], anc) un-gathered; log-weights are 0
     bool pending_fill = false;     // ... or, after gpf_resample_local, the constant sc->lw_fill
     // "lazy search" (gpf_k_fused.hpp): pf_resample!(:multinomial) enqueued only the weight scan; the ancestors (h->anc) and the log-ML
@@ -142,36 +174,35 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     bool hist_on = false;
     bool hist_blocks = false;            // gpf_history_enable_blocks: the block-wise calls feed the store too (the plain store refuses them)
     int hist_cap = 0;
-    std::vector<double*> hist_x;         // [step] n*d doubles (nullptr until snapshotted)
-    std::vector<int32_t*> hist_map;      // [step] n int32 or nullptr
+    std::vector<Dev<double>> hist_x;     // [step] n*d doubles (empty until snapshotted)
+    std::vector<Dev<int32_t>> hist_map;  // [step] n int32 or empty
     int hist_step = -1;                  // index of the current step (0 = after gpf_initialize)
-    const int32_t** hist_dev_maps = nullptr;
-    const double** hist_dev_x = nullptr;   // device table of the snapshots hist_x[s], hist_cap entries (gpf_block_sample_trajectories walks all steps in one launch)
+    Dev<const int32_t*> hist_dev_maps;
+    Dev<const double*> hist_dev_x;         // device table of the snapshots hist_x[s], hist_cap entries (gpf_block_sample_trajectories walks all steps in one launch)
     // gpf_history_enable_blocks_weights: what a backward pass needs of every step, taken wherever hist_snapshot takes hist_x (none of it exists otherwise)
     bool hist_weights = false;
     // (both live behind the step's columns in the allocation of hist_x[step]: nothing of their own to free)
     std::vector<double*> hist_lw;        // [step] the n log-weights in the step's final order (nullptr until snapshotted)
     std::vector<double*> hist_obs;       // [step] the [n_blocks][MAX_OBS] observation rows the step was entered with, in the block order of the snapshot
     std::vector<int64_t> hist_bsize;     // [step] the block size of the block-wise call that entered the step; 0: a whole-filter call (no per-block rows)
-    const double** hist_dev_lw = nullptr; const double** hist_dev_obs = nullptr;   // device tables of hist_lw / hist_obs beside hist_dev_x, hist_cap entries each
+    Dev<const double*> hist_dev_lw, hist_dev_obs;   // device tables of hist_lw / hist_obs beside hist_dev_x, hist_cap entries each
     // forward-only smoothing per block (gpf_forward_enable_blocks): ONE generation of records -- the previous step's latent columns,
     // log-weights and statistics in that step's final order -- and the composed ancestor map of the current step; 8 (2 F + d + 1) n bytes and two maps,
     // however long the series.  Everything is allocated by the initialising call and overwritten at every close (fwd_begin_step)
     bool fwd_on = false;
     int64_t fwd_bsize = 0;               // the (clamped) block size of the initialising call: the mode's; 0 until then
     int32_t fwd_steps = 0;               // the current step, 1-based; 0: nothing initialised
-    double *fwd_x = nullptr, *fwd_lw = nullptr;   // [n][d], [n] of the step closed last
-    double* fwd_T[2] = {nullptr, nullptr}; int fwd_cur = 0;   // [n][F]: fwd_T[fwd_cur] belongs to the record, the other half is the close's output and the query's scratch
-    int32_t* fwd_map[2] = {nullptr, nullptr}; int fwd_map_cur = 0; bool fwd_map_set = false;   // g_s of the current step in fwd_map[fwd_map_cur] once a resample happened in it
-    int64_t fwd_cap = 0;                 // particles the buffers hold
+    Dev<double> fwd_x, fwd_lw;           // [n][d], [n] of the step closed last: fwd_lw.count = the particles the records hold
+    Dev<double> fwd_T[2]; int fwd_cur = 0;   // [n][F]: fwd_T[fwd_cur] belongs to the record, the other half is the close's output and the query's scratch
+    Dev<int32_t> fwd_map[2]; int fwd_map_cur = 0; bool fwd_map_set = false;   // g_s of the current step in fwd_map[fwd_map_cur] once a resample happened in it
     // sub-state view (src/view.jl:16-48): this handle aliases particles [view_start, view_start + n) of `parent`
     gpf_filter* parent = nullptr;
     std::vector<gpf_filter*> views;      // the live view handles of THIS filter: gpf_destroy orphans them (a view used after its filter is gone fails loudly)
     bool orphaned = false;               // view: its filter was destroyed -- parent dangles and is never followed, the stream is gone with it
     int64_t view_start = 0;
     int64_t view_step = 1;               // > 1: strided view (state[start:step:stop]); works on the compact copies below
-    double* vrows[2] = {nullptr, nullptr}; double* vlw = nullptr; int32_t* vanc = nullptr;
-    int32_t* vidx = nullptr; int32_t* vgid = nullptr;   // view over an index vector (view_step == 0): the particles' indices in the parent, and idx - idx[0] (ModelArgs::gid_map)
+    Dev<double> vrows[2], vlw; Dev<int32_t> vanc;
+    Dev<int32_t> vidx, vgid;             // view over an index vector (view_step == 0): the particles' indices in the parent, and idx - idx[0] (ModelArgs::gid_map)
     uint64_t generation = 0;             // bumped when the per-particle buffers are reallocated (views check it)
     uint64_t parent_generation = 0;
     uint64_t mutations = 0;              // bumped by every change of the rows / log-weights of this filter (through any handle)
@@ -180,7 +211,7 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 1;
     double *sh_mf = nullptr, *sh_mf_all = nullptr; int64_t *sh_tot = nullptr, *sh_tot_all = nullptr, *sh_cr = nullptr, *sh_cr_all = nullptr;
-    double *sh_send = nullptr, *sh_recv = nullptr; int64_t sh_send_cap = 0, sh_recv_cap = 0;
+    Dev<double> sh_send, sh_recv;        // the exchange buffers: released with the communicator (gpf_comm_destroy)
     // shard mailboxes (gpf_k_common.hpp): the three small summaries of a sharded resample travel as peer stores from the
     // producing kernel into every rank's mailbox instead of RCCL all-gathers
     uint64_t* mbox = nullptr;            // this rank's mailbox (device memory, exported through hipIpc)
@@ -207,64 +238,62 @@ struct __attribute__((visibility("hidden"))) gpf_filter {
     const double* cur_mf_all = nullptr; const int64_t* cur_tot_all = nullptr; const int64_t* cur_cr_all = nullptr;   // the gathered summaries of the current round
     uint64_t mb_seq[MB_KINDS] = {0, 0, 0, 0};   // rounds so far per kind: the same on every rank (SPMD call order)
     uint64_t mb_cur[MB_KINDS] = {0, 0, 0, 0};   // the round whose entries the current gathered pointers name
-    int32_t* h_timeout = nullptr;        // pinned: set by a scan whose bounded inter-workgroup wait gave up (checked on the host)
+    Pinned<int32_t> h_timeout;           // pinned: set by a scan whose bounded inter-workgroup wait gave up (checked on the host)
     int scan_blocks_per_cu = 2;          // resident scan workgroups per CU the launch may rely on (occupancy query)
     int wscan_blocks_per_cu = 2;         // ... of the weight scans k_scan<InFixQ, *> alone (fewer registers than the residual scan)
-    int64_t* shard_counts = nullptr;     // [2 * MAX_SHARDS] exchange counters of the current resample (device) + pinned mirror
-    int64_t* h_shard_counts = nullptr;
+    Dev<int64_t> shard_counts;           // [2 * MAX_SHARDS] exchange counters of the current resample (device) + pinned mirror
+    Pinned<int64_t> h_shard_counts;
     // block-wise resampling (gpf_resample_blocks): {flags, count} words, the per-block mask, per-block statistics
-    int64_t* h_qpub = nullptr; int64_t q_ticket = 0;   // the ESS getter's scan publishes {flags, S, limbs of sum q^2} itself (ScanExtras::q_host)
-    int32_t* blk_words = nullptr; int32_t* blk_mask = nullptr; double* blk_stats = nullptr; int64_t blk_cap = 0, blk_last = 0;
-    double* blk_est = nullptr; int64_t blk_est_cap = 0;         // per-block estimates (gpf_block_moments / gpf_block_proportion): blk_est_cap doubles
+    Pinned<int64_t> h_qpub; int64_t q_ticket = 0;   // the ESS getter's scan publishes {flags, S, limbs of sum q^2} itself (ScanExtras::q_host)
+    Dev<int32_t> blk_words, blk_mask; Dev<double> blk_stats; int64_t blk_last = 0;   // (mask and statistics grow together: [n_blocks], [n_blocks][2])
+    Dev<double> blk_est;                                        // per-block estimates (gpf_block_moments / gpf_block_proportion)
     // blocks of more than BLK_MAX particles: gpf_resample_blocks / gpf_block_stats run the loop over sub-states themselves, through view
     // handles kept on the filter (one per block; rebuilt when the block size or the particle buffers change)
     std::vector<gpf_filter*> blk_views; int64_t blk_views_size = 0; uint64_t blk_views_gen = 0;
-    double* blk_obs = nullptr; int64_t blk_obs_cap = 0;                                // per-block observations [n_blocks][MAX_OBS] on the device
+    Dev<double> blk_obs;                                                               // per-block observations [n_blocks][MAX_OBS] on the device
     static constexpr int BLK_STAGE = 4;                                                // pinned staging buffers, used in turn (no stream sync per step)
-    double* h_blk_obs[BLK_STAGE] = {nullptr, nullptr, nullptr, nullptr};
+    Pinned<double> h_blk_obs[BLK_STAGE];
     int64_t blk_stage_next = 0;                                                        // staging copies issued so far (ticket of the next one - 1)
-    int64_t* h_blk_done = nullptr; unsigned int* blk_stage_counter = nullptr;          // pinned: ticket of the last finished staging copy; device: its workgroup counter
+    Pinned<int64_t> h_blk_done; Dev<unsigned int> blk_stage_counter;                   // pinned: ticket of the last finished staging copy; device: its workgroup counter
     int64_t blk_obs_size = 0;                                                          // > 0: the latest observations are per block, blocks of this size
     // conditional SMC (gpf_initialize_blocks_ref / gpf_update_blocks_ref): the reference rows of the CURRENT call, [n_blocks][MAX_DIM] on the device
     // (ModelArgs::blk_ref for the one launch).  They are staged behind the observations in the same pinned buffer (h_blk_obs holds MAX_OBS + MAX_DIM
     // words per block) and copied by the same launch; nothing of them is kept between calls
-    double* blk_ref = nullptr; int64_t blk_ref_cap = 0;
+    Dev<double> blk_ref;
     // ancestor sampling (gpf_resample_blocks_ancestor / gpf_block_ancestor_log_weights): the data vectors and reference values of the step being ENTERED,
     // [n_blocks][MAX_OBS] then [n_blocks][MAX_DIM] on the device -- scratch of the one call, apart from blk_obs (a rejuvenation before the update still
     // sees the previous step's observation).  h_anc_in: the pinned buffer the copy kernel reads; anc_ev: recorded behind that kernel, waited for before
     // the buffer is filled again
-    double* anc_in = nullptr; double* h_anc_in = nullptr; int64_t anc_in_cap = 0; hipEvent_t anc_ev = nullptr; bool anc_ev_pending = false;
+    Dev<double> anc_in; Pinned<double> h_anc_in; hipEvent_t anc_ev = nullptr; bool anc_ev_pending = false;
     // gpf_set_block_params: every block's own model parameters, [n_blocks][MAX_PARAMS] on the device (ModelArgs::blk_params), uploaded once;
     // bp_size > 0: the rows are in force for blocks of this (clamped) size -- the block-wise steps run their BP kernels, everything that would
     // read cfg.params is refused (bp_refused)
-    double* blk_params = nullptr; int64_t blk_params_cap = 0, bp_size = 0;
+    Dev<double> blk_params; int64_t bp_size = 0;
     // gpf_resample_across_blocks: the planner filter of n_blocks particles whose log-weights are the blocks' log-ML estimates (its ancestors name the
     // source block of every block; it runs on this filter's stream), the second buffers the per-block rows are gathered into (swapped with
     // blk_params / blk_obs), and the 1-based block ancestors of the last call that fired with the buffers they refer to (gpf_block_ancestors)
     gpf_filter* xb_planner = nullptr;
-    double* blk_params_alt = nullptr; int64_t blk_params_alt_cap = 0;
-    double* blk_obs_alt = nullptr; int64_t blk_obs_alt_cap = 0;
+    Dev<double> blk_params_alt, blk_obs_alt;
     std::vector<int64_t> xb_anc; uint64_t xb_anc_gen = 0; int64_t xb_anc_n = 0;
     // the pull plan (gpf_comm_set_plan): request lists [G][n], their counters, the dense / gathered request matrix and its pinned mirror
     int shard_plan_kind = 0;
-    ulonglong2* pull_req = nullptr; int64_t pull_req_cap = 0;
-    int64_t* pull_counts = nullptr; int64_t* pull_pc = nullptr; int64_t* pull_pc_all = nullptr; int64_t* h_pull_pc_all = nullptr;
-    int64_t* h_flags = nullptr;          // pinned {validity flags, ticket} published by the weight scan of a checked resample
+    Dev<ulonglong2> pull_req;
+    Dev<int64_t> pull_counts, pull_pc, pull_pc_all; Pinned<int64_t> h_pull_pc_all;
+    Pinned<int64_t> h_flags;             // pinned {validity flags, ticket} published by the weight scan of a checked resample
     int64_t flag_ticket = 0;
     int64_t push_ticket = 0;             // bumped by every gpf_shard_push launch; k_push publishes it with the counts
     bool counts_published = false;
     // GPF_RESAMPLE_MULTINOMIAL_SORTED: gamma totals of the tiles of SP_TILE slots (k_sorted_gammas) and, for many tiles, their starting points (k_sorted_tiles)
-    uint64_t* sp_g = nullptr; uint64_t* sp_vlo = nullptr; int64_t sp_cap = 0;
+    Dev<uint64_t> sp_g, sp_vlo;          // (grown together)
     SortedGammaJob sp_job{};             // the latest job that draws them (sorted_job_prepare): a weight scan of the same call carries it (ScanRequest::sp), else k_sorted_gammas
-    ulonglong2* push_stage = nullptr;    // push exchange: staged hits, one 16-byte entry per global output slot at most
+    Dev<ulonglong2> push_stage;          // push exchange: staged hits, one 16-byte entry per global output slot at most
     // sharded stratified resampling with sort_particles = true (gpf_shard_resample_sorted; gpf_k_shard.hpp AncPlan): the planner filter of n_global particles
     // every rank sorts / scans / searches the gathered log-weights with, the all-gather staging of unequal shards, the pack cursors
     gpf_filter* planner = nullptr;
-    double* sorted_src = nullptr; double* sorted_gath = nullptr; int64_t sorted_per = 0;
-    unsigned long long* anc_cursors = nullptr;
-    ShardPlan* shard_plan = nullptr;     // sharded stratified / sorted multinomial resampling: the slot range this shard serves (k_strat_plan, k_sorted_plan)
-    int64_t* splan_F = nullptr; unsigned int* splan_arrive = nullptr;   // k_sorted_plan: boundary scratch [MAX_SHARDS + 1], arrival counter (zero between launches)
-    int64_t push_cap = 0;
+    Dev<double> sorted_src, sorted_gath;
+    Dev<unsigned long long> anc_cursors;
+    Dev<ShardPlan> shard_plan;           // sharded stratified / sorted multinomial resampling: the slot range this shard serves (k_strat_plan, k_sorted_plan)
+    Dev<int64_t> splan_F; Dev<unsigned int> splan_arrive;   // k_sorted_plan: boundary scratch [MAX_SHARDS + 1], arrival counter (zero between launches)
     bool push_counted = false;
     // exchange volume of the sharded resamples so far (gpf_comm_traffic): calls, entries sent to / received from OTHER ranks, bytes of one entry of the latest call
     int64_t tr_calls = 0, tr_sent = 0, tr_recv = 0, tr_entry_bytes = 0;
@@ -296,6 +325,24 @@ inline gpf_status fail(gpf_handle h, gpf_status s, const std::string& msg)
 // Poll pinned memory that a kernel on h->stream publishes into, until ready() holds.  A failed kernel never publishes: any stream status other than
 // "not ready" is terminal (ready() once more, then report), so a faulting kernel cannot hang the host -- or, in a multi-rank job, its peers in the
 // next collective.  The failure text: [what: ] + `drained` when the stream is idle and nothing came, else the stream's own error.
+// (see Owned above) a failed allocation leaves the owner empty and the HIP error in h->err; the next call tries again
+template <class T, bool PINNED>
+gpf_status Owned<T, PINNED>::alloc(gpf_filter* h, size_t n)
+{
+    if (PINNED) HIP_TRY(h, hipHostMalloc(&p, n * sizeof(T))); else HIP_TRY(h, hipMalloc(&p, n * sizeof(T)));
+    count = n;
+    return GPF_OK;
+}
+// grow-only: kernels enqueued earlier may still read the old buffer, so the stream drains before it is freed.  No geometric growth
+template <class T, bool PINNED>
+gpf_status Owned<T, PINNED>::grow(gpf_filter* h, size_t n, bool* fresh)
+{
+    if (count >= n) return GPF_OK;
+    if (p) { HIP_TRY(h, hipStreamSynchronize(h->stream)); reset(); }
+    if (fresh) *fresh = true;
+    return alloc(h, n);
+}
+
 template <class Ready>
 gpf_status poll_published(gpf_filter* h, Ready&& ready, const char* what, const char* drained)
 {
@@ -313,9 +360,9 @@ gpf_status poll_published(gpf_filter* h, Ready&& ready, const char* what, const 
 inline gpf_status wait_ticket(gpf_filter* h, volatile int64_t* tk, int64_t want, const char* what)
 { return poll_published(h, [&] { return __atomic_load_n(tk, __ATOMIC_ACQUIRE) == want; }, what, "the stream drained without the ticket being published"); }
 // a lazily allocated block of n pinned words a kernel publishes into (flags, tickets, summaries), zeroed
-inline gpf_status pinned_words(gpf_filter* h, int64_t*& words, int n)
+inline gpf_status pinned_words(gpf_filter* h, Pinned<int64_t>& words, int n)
 {
-    if (!words) { HIP_TRY(h, hipHostMalloc(&words, (size_t)n * sizeof(int64_t))); std::fill(words, words + n, (int64_t)0); }
+    if (!words) { if (gpf_status s = words.alloc(h, (size_t)n)) return s; std::fill(words.p, words.p + n, (int64_t)0); }
     return GPF_OK;
 }
 
@@ -459,18 +506,6 @@ inline const void* mb_gathered(const gpf_filter* h, int kind)
     return h->mbox + mb_payload_off(kind, (int)(h->mb_cur[kind] & (MB_SLOTS - 1)));
 }
 
-// ------------------------------------------------------------------ per-N device buffers
-struct Bufs {                        // everything whose size depends on the particle count (detached copy, for resizing)
-    int64_t n = 0, ntiles = 0;
-    double* rows[2] = {nullptr, nullptr};
-    int cur = 0;
-    double *lw = nullptr, *lws = nullptr, *lp = nullptr, *dtmp = nullptr;
-    uint64_t *cdf[3] = {}, *t16[3] = {}, *t256[3] = {}, *desc[3][2] = {};
-    int32_t *anc = nullptr, *order = nullptr, *idx_in = nullptr;
-    uint64_t *keys = nullptr, *keys_out = nullptr;
-    void* sort_tmp = nullptr;
-};
-
 #ifndef STEP_BLOCKS_PER_CU
 #define STEP_BLOCKS_PER_CU 4
 #endif
@@ -586,7 +621,8 @@ inline void normalise_Q(const WSum& w, uint64_t& hi, uint64_t& lo)
 // ---- defined in libgpf_core.hip
 Bufs take_particle_buffers(gpf_filter* h);
 void free_bufs(Bufs& b);
-gpf_status alloc_particle_buffers(gpf_filter* h);
+gpf_status alloc_particle_buffers(gpf_filter* h, bool scratch_only = false);
+gpf_status alloc_fixed_buffers(gpf_filter* h);
 void launch_gather_ex(gpf_filter* h, const int32_t* anc, const double* in, double* out, const PrioView& pv, double* lw_out, int64_t n);
 void launch_gather(gpf_filter* h, const PrioView& pv, double* lw_out);
 void launch_gather_rows_lw(gpf_filter* h, const int32_t* anc, const double* rows_in, const double* lw_in, double* rows_out, double* lw_out, int64_t n);

@@ -1,5 +1,7 @@
 // libgpf_aux.hip -- what widened around the hot path: block-wise operations on many small filters, weighted statistics,
 // sub-state views (src/view.jl), the resize family with coalesce / introduce (src/resize.jl), the trajectory store.
+// Buffers: what these calls keep on the handle (per-block masks, statistics, observation / reference / parameter rows, staging, the store's snapshots
+// and tables) are Dev<T> / Pinned<T> members (gpf_host.hpp Owned) that only grow, through grow(); the scratch of one call is a local Dev<T>.
 #include "gpf_host.hpp"
 #include "gpf_k_coalesce.hpp"
 
@@ -33,7 +35,7 @@ void launch_move_blk(gpf_filter* h, int grid, int n_iters)
     constexpr int Wc = row_width(Model<M>::D, true);
     GPF_LAUNCH((k_move<M, Wc, RW, false, false, true, BP>), dim3(grid), dim3(BLOCK), 0, h->stream, h->args, h->cfg.seed, h->epoch,
                        h->cfg.gid0, h->n, (int)h->has_prev, n_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw,
-                       h->acc_part, RW ? next_slots(h) : MaxSlots{nullptr, nullptr});
+                       h->acc_part.p, RW ? next_slots(h) : MaxSlots{nullptr, nullptr});
 }
 // METHOD_COND: the conditional multinomial step (slot 0 of every resampling block keeps itself), PRIO = false only
 template <int METHOD, int Wc, bool PRIO>
@@ -73,24 +75,12 @@ extern "C" {
 // ------------------------------------------------------------------ block-wise resampling: many small filters in one launch (K11)
 static gpf_status block_buffers(gpf_filter* h, int64_t nblocks)
 {
-    if (!h->blk_words) HIP_TRY(h, hipMalloc(&h->blk_words, 2 * sizeof(int32_t)));
-    if (h->blk_cap < nblocks) {
-        if (h->blk_mask) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->blk_mask); (void)hipFree(h->blk_stats); h->blk_mask = nullptr; h->blk_stats = nullptr; h->blk_cap = 0; }
-        h->blk_last = 0;                                         // the new mask is uninitialised: no block resample to refer to
-        HIP_TRY(h, hipMalloc(&h->blk_mask, (size_t)nblocks * sizeof(int32_t)));
-        HIP_TRY(h, hipMalloc(&h->blk_stats, (size_t)nblocks * 2 * sizeof(double)));
-        h->blk_cap = nblocks;
-    }
-    return GPF_OK;
-}
-// a device array of doubles that only ever grows: at least cap * width of them (kernels enqueued earlier may read the old one: the stream drains first)
-static gpf_status grow_doubles(gpf_filter* h, double*& p, int64_t& have, int64_t cap, int width = 1)
-{
-    if (have >= cap) return GPF_OK;
-    if (p) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(p); p = nullptr; have = 0; }
-    HIP_TRY(h, hipMalloc(&p, (size_t)cap * width * sizeof(double)));
-    have = cap;
-    return GPF_OK;
+    gpf_status s;
+    if (!h->blk_words && (s = h->blk_words.alloc(h, 2))) return s;
+    bool fresh = false;
+    s = h->blk_mask.grow(h, (size_t)nblocks, &fresh);
+    if (fresh) h->blk_last = 0;                                  // the new mask is uninitialised: no block resample to refer to
+    return s ? s : h->blk_stats.grow(h, (size_t)nblocks * 2);
 }
 // the results of a call from the device to the host, each where the caller wants it (nullptr: not asked for), then the one synchronisation
 struct OutCopy { const void* dev; void* host; size_t bytes; };
@@ -212,23 +202,17 @@ static gpf_status stage_ancestor_in(gpf_filter* h, int64_t nblocks, const Ancest
 {
     constexpr int ROW = MAX_OBS + MAX_DIM;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (h->anc_in_cap < nblocks) {
-        if (h->anc_in) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            (void)hipFree(h->anc_in); (void)hipHostFree(h->h_anc_in);
-            h->anc_in = nullptr; h->h_anc_in = nullptr; h->anc_in_cap = 0; h->anc_ev_pending = false;
-        }
-        HIP_TRY(h, hipMalloc(&h->anc_in, (size_t)nblocks * ROW * sizeof(double)));
-        HIP_TRY(h, hipHostMalloc(&h->h_anc_in, (size_t)nblocks * ROW * sizeof(double)));
-        if (!h->anc_ev) HIP_TRY(h, hipEventCreateWithFlags(&h->anc_ev, hipEventDisableTiming));
-        h->anc_in_cap = nblocks;
-    }
+    bool fresh = false;
+    gpf_status s = h->anc_in.grow(h, (size_t)nblocks * ROW, &fresh);
+    if (fresh) h->anc_ev_pending = false;                        // (the stream drained before the old buffers went: nothing reads them any more)
+    if (s || (s = h->h_anc_in.grow(h, (size_t)nblocks * ROW))) return s;
+    if (!h->anc_ev) HIP_TRY(h, hipEventCreateWithFlags(&h->anc_ev, hipEventDisableTiming));
     if (h->anc_ev_pending) { HIP_TRY(h, hipEventSynchronize(h->anc_ev)); h->anc_ev_pending = false; }   // (the copy that last read the pinned buffer)
     pack4(h->h_anc_in, in.obs, nblocks, in.n_obs);               // (n_obs, dim >= 1: checked)
     pack4(h->h_anc_in + nblocks * MAX_OBS, in.ref, nblocks, model_dim(h->cfg.model));
     const int64_t n_words = nblocks * ROW;
     GPF_LAUNCH(k_stage_words, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(64, (n_words + BLOCK - 1) / BLOCK))), dim3(BLOCK), 0, h->stream,
-               (const double*)h->h_anc_in, h->anc_in, n_words);
+               (const double*)h->h_anc_in.p, h->anc_in.p, n_words);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipEventRecord(h->anc_ev, h->stream));
     h->anc_ev_pending = true;
@@ -339,7 +323,7 @@ static gpf_status resample_blocks_impl(gpf_handle h, int32_t method, int64_t blo
     if ((s = hist_on_resample(h, block_size))) return s;
     if (check != GPF_CHECK_FALSE || invalid || n_resampled) {
         int32_t words[2] = {0, 0};
-        GPF_LAUNCH(k_block_summary, dim3(1), dim3(BLOCK), 0, h->stream, h->blk_mask, nblocks, h->blk_words);
+        GPF_LAUNCH(k_block_summary, dim3(1), dim3(BLOCK), 0, h->stream, h->blk_mask.p, nblocks, h->blk_words.p);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipMemcpyAsync(words, h->blk_words, sizeof(words), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -385,7 +369,7 @@ static gpf_status launch_block_stats(gpf_filter* h, int64_t block_size, int64_t 
     gpf_status s = block_buffers(h, nblocks);
     if (s) return s;
     team_dispatch(block_size, nblocks, [&](auto TEAM, auto ITEMS, dim3 grid) {
-        GPF_LAUNCH((k_block_stats<TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, h->lw, h->n, block_size, nblocks, &h->sc->lml_est, h->blk_stats, h->blk_stats + nblocks);
+        GPF_LAUNCH((k_block_stats<TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, h->lw, h->n, block_size, nblocks, &h->sc->lml_est, h->blk_stats.p, h->blk_stats.p + nblocks);
     });
     HIP_TRY(h, hipGetLastError());
     return GPF_OK;
@@ -416,7 +400,7 @@ void launch_block_moments_w(gpf_filter* h, int64_t nb, int64_t nblocks, int want
     });
 }
 // the device buffer of the per-block estimates: at least `need` doubles
-static gpf_status block_est_buffer(gpf_filter* h, int64_t need) { return grow_doubles(h, h->blk_est, h->blk_est_cap, need); }
+static gpf_status block_est_buffer(gpf_filter* h, int64_t need) { return h->blk_est.grow(h, (size_t)need); }
 // the gate of the per-block estimates: a filter that can have sub-state views
 constexpr unsigned GATE_EST = GATE_FILTER | GATE_STORE_VIEWS | GATE_CLAMP_STORE | GATE_MAX;
 // the view of one big block (big_block_views) brought up to date, its weight summary on the host: *bad = NaN / +Inf weights
@@ -495,7 +479,7 @@ gpf_status gpf_block_proportion(gpf_handle h, int64_t block_size, int32_t column
     const BlockMatch mv = make_block_match(values, n_values);
     const double* rows = h->rows[h->cur];
     team_dispatch(block_size, nblocks, [&](auto TEAM, auto ITEMS, dim3 grid) {
-        GPF_LAUNCH((k_block_proportion<TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, rows, h->W, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
+        GPF_LAUNCH((k_block_proportion<TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, rows, h->W, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est.p);
     });
     HIP_TRY(h, hipGetLastError());
     return block_out(h, {{h->blk_est, out, cells * sizeof(double)}});
@@ -527,30 +511,24 @@ static gpf_status set_block_obs(gpf_filter* h, const double* obs, int32_t n_obs,
     gpf_status s = block_obs_check(h, obs, n_obs);
     if (s) return s;
     const int64_t nblocks = (h->n + block_size - 1) / block_size;
-    if (h->blk_obs_cap < nblocks) {
-        if (h->blk_obs) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            (void)hipFree(h->blk_obs); h->blk_obs = nullptr; h->blk_obs_cap = 0;
-            for (int k = 0; k < gpf_filter::BLK_STAGE; ++k) { (void)hipHostFree(h->h_blk_obs[k]); h->h_blk_obs[k] = nullptr; }
-        }
-        HIP_TRY(h, hipMalloc(&h->blk_obs, (size_t)nblocks * MAX_OBS * sizeof(double)));
-        // (MAX_DIM more words per block: the reference rows of a pinned step.  blk_obs_cap is also the capacity of these buffers: they are only ever
-        //  reallocated here, together with blk_obs, and gpf_resample_across_blocks swaps in a second buffer of at least this capacity)
-        for (int k = 0; k < gpf_filter::BLK_STAGE; ++k) HIP_TRY(h, hipHostMalloc(&h->h_blk_obs[k], (size_t)nblocks * (MAX_OBS + MAX_DIM) * sizeof(double)));
-        if (!h->h_blk_done) {
-            HIP_TRY(h, hipHostMalloc(&h->h_blk_done, sizeof(int64_t))); *h->h_blk_done = 0;
-            HIP_TRY(h, hipMalloc(&h->blk_stage_counter, sizeof(unsigned int)));
-            HIP_TRY(h, hipMemsetAsync(h->blk_stage_counter, 0, sizeof(unsigned int), h->stream));
-        }
-        h->blk_obs_cap = nblocks;
+    if ((s = h->blk_obs.grow(h, (size_t)nblocks * MAX_OBS))) return s;
+    // (MAX_DIM more words per block: the reference rows of a pinned step.  The staging buffers grow with blk_obs and only here;
+    //  gpf_resample_across_blocks swaps in a second buffer of at least blk_obs' capacity)
+    for (int k = 0; k < gpf_filter::BLK_STAGE; ++k)
+        if ((s = h->h_blk_obs[k].grow(h, (size_t)nblocks * (MAX_OBS + MAX_DIM)))) return s;
+    if (!h->h_blk_done) {
+        if (!h->blk_stage_counter && (s = h->blk_stage_counter.alloc(h, 1))) return s;
+        HIP_TRY(h, hipMemsetAsync(h->blk_stage_counter, 0, sizeof(unsigned int), h->stream));
+        if ((s = h->h_blk_done.alloc(h, 1))) return s;
+        *h->h_blk_done = 0;
     }
-    if (ref && (s = grow_doubles(h, h->blk_ref, h->blk_ref_cap, nblocks, MAX_DIM))) return s;
+    if (ref && (s = h->blk_ref.grow(h, (size_t)nblocks * MAX_DIM))) return s;
     // the staging buffers are used in turn: wait only until the copy that last read THIS buffer (four calls ago) has finished -- its
     // kernel publishes a ticket to pinned memory -- not for the stream
     const int k = (int)(h->blk_stage_next % gpf_filter::BLK_STAGE);
     if (h->blk_stage_next >= gpf_filter::BLK_STAGE) {
         const int64_t need = h->blk_stage_next - gpf_filter::BLK_STAGE + 1;
-        const gpf_status ws = poll_published(h, [&] { return __atomic_load_n(h->h_blk_done, __ATOMIC_ACQUIRE) >= need; }, nullptr,
+        const gpf_status ws = poll_published(h, [&] { return __atomic_load_n(h->h_blk_done.p, __ATOMIC_ACQUIRE) >= need; }, nullptr,
                                              "observation staging: the stream drained without the copy's ticket");
         if (ws) return ws;
     }
@@ -562,10 +540,10 @@ static gpf_status set_block_obs(gpf_filter* h, const double* obs, int32_t n_obs,
         pack4(stage + n_words, ref, nblocks, model_dim(h->cfg.model));
         const int64_t n_ref_words = nblocks * MAX_DIM;
         GPF_LAUNCH(k_stage_obs_ref, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(64, (n_words + n_ref_words + BLOCK - 1) / BLOCK))), dim3(BLOCK), 0, h->stream,
-                   stage, h->blk_obs, n_words, h->blk_ref, n_ref_words, h->blk_stage_counter, h->h_blk_done, h->blk_stage_next);
+                   stage, h->blk_obs.p, n_words, h->blk_ref.p, n_ref_words, h->blk_stage_counter.p, h->h_blk_done.p, h->blk_stage_next);
     } else
     GPF_LAUNCH(k_stage_obs, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(64, (n_words + BLOCK - 1) / BLOCK))), dim3(BLOCK), 0, h->stream,
-               stage, h->blk_obs, n_words, h->blk_stage_counter, h->h_blk_done, h->blk_stage_next);
+               stage, h->blk_obs.p, n_words, h->blk_stage_counter.p, h->h_blk_done.p, h->blk_stage_next);
     HIP_TRY(h, hipGetLastError());
     h->args.blk_obs = h->blk_obs; h->args.blk_mask = nullptr; h->args.blk_size = (int32_t)block_size;
     h->blk_obs_size = block_size;
@@ -750,7 +728,7 @@ gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, 
         if (method == GPF_REJUVENATE_REWEIGHT && !only_resampled) *n_accepted = (uint64_t)h->n * (uint64_t)n_iters;
         else if (method == GPF_REJUVENATE_REWEIGHT) {
             int64_t nres = 0;
-            GPF_LAUNCH(k_block_summary, dim3(1), dim3(BLOCK), 0, h->stream, h->blk_mask, h->blk_last, h->blk_words);
+            GPF_LAUNCH(k_block_summary, dim3(1), dim3(BLOCK), 0, h->stream, h->blk_mask.p, h->blk_last, h->blk_words.p);
             int32_t words[2] = {0, 0};
             HIP_TRY(h, hipMemcpyAsync(words, h->blk_words, sizeof(words), hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -761,7 +739,7 @@ gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, 
             HIP_TRY(h, hipMemcpy(&last_word, h->blk_mask + (h->blk_last - 1), sizeof(int32_t), hipMemcpyDeviceToHost));
             *n_accepted = (uint64_t)((nres - (last_word & 1)) * bs + (last_word & 1) * last) * (uint64_t)n_iters;
         } else {
-            GPF_LAUNCH(k_sum_accepts, dim3(1), dim3(BLOCK), 0, h->stream, h->acc_part, grid, reinterpret_cast<unsigned long long*>(&h->sc->n_accept));
+            GPF_LAUNCH(k_sum_accepts, dim3(1), dim3(BLOCK), 0, h->stream, h->acc_part.p, grid, reinterpret_cast<unsigned long long*>(&h->sc->n_accept));
             HIP_TRY(h, hipGetLastError());
             if ((s = fetch_scalars(h))) return s;
             *n_accepted = h->h_sc->n_accept;
@@ -788,11 +766,8 @@ gpf_status gpf_set_block_params(gpf_handle h, const double* params, int32_t n_pa
         for (int i = 0; i < n_params; ++i) rows[(size_t)b * MAX_PARAMS + i] = params[b * n_params + i];
     // (kernels enqueued earlier may still read the old rows: the stream drains before the buffer is replaced or overwritten)
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h->blk_params_cap < nblocks) {
-        if (h->blk_params) { (void)hipFree(h->blk_params); h->blk_params = nullptr; h->blk_params_cap = 0; h->bp_size = 0; h->args.blk_params = nullptr; }
-        HIP_TRY(h, hipMalloc(&h->blk_params, rows.size() * sizeof(double)));
-        h->blk_params_cap = nblocks;
-    }
+    if (h->blk_params.count < rows.size()) { h->bp_size = 0; h->args.blk_params = nullptr; }   // (the rows in force go with their buffer)
+    if (gpf_status s = h->blk_params.grow(h, rows.size())) return s;
     HIP_TRY(h, hipMemcpyAsync(h->blk_params, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));                 // (the host rows go out of scope)
     h->args.blk_params = h->blk_params;
@@ -891,8 +866,8 @@ gpf_status gpf_resample_across_blocks(gpf_handle h, int32_t method, int64_t bloc
         if (s) return fail(h, s, "planner: " + p->err);
         const bool with_par = h->bp_size > 0, with_obs = h->blk_obs_size > 0;
         // (the second buffer of a per-block row array, at least as large as the first)
-        if (with_par && (s = grow_doubles(h, h->blk_params_alt, h->blk_params_alt_cap, h->blk_params_cap, MAX_PARAMS))) return s;
-        if (with_obs && (s = grow_doubles(h, h->blk_obs_alt, h->blk_obs_alt_cap, h->blk_obs_cap, MAX_OBS))) return s;
+        if (with_par && (s = h->blk_params_alt.grow(h, h->blk_params.count))) return s;
+        if (with_obs && (s = h->blk_obs_alt.grow(h, h->blk_obs.count))) return s;
         // 4. whole blocks: rows, log-weights + (M - L[a]), parents, per-block rows -- one launch
         BlockGatherArgs a{};
         a.rows_in = h->rows[h->cur]; a.rows_out = h->rows[1 - h->cur]; a.lw_in = h->lw; a.lw_out = h->lws; a.anc_out = h->anc;
@@ -913,8 +888,8 @@ gpf_status gpf_resample_across_blocks(gpf_handle h, int32_t method, int64_t bloc
         h->xb_anc_gen = h->generation; h->xb_anc_n = h->n;
         h->cur ^= 1;                                             // update_refs! (utils.jl:10-15)
         std::swap(h->lw, h->lws);
-        if (with_par) { std::swap(h->blk_params, h->blk_params_alt); std::swap(h->blk_params_cap, h->blk_params_alt_cap); h->args.blk_params = h->blk_params; }
-        if (with_obs) { std::swap(h->blk_obs, h->blk_obs_alt); std::swap(h->blk_obs_cap, h->blk_obs_alt_cap); h->args.blk_obs = h->blk_obs; }
+        if (with_par) { std::swap(h->blk_params, h->blk_params_alt); h->args.blk_params = h->blk_params; }
+        if (with_obs) { std::swap(h->blk_obs, h->blk_obs_alt); h->args.blk_obs = h->blk_obs; }
         h->blk_last = 0;                                         // only_resampled refers to a gpf_resample_blocks of the CURRENT block layout
         weights_written(h, false);
     }
@@ -942,11 +917,7 @@ gpf_status weighted_tree_sum(gpf_filter* h, const double* values, int stride, in
 {
     const int64_t nb = (h->n + TREE_CHUNK - 1) / TREE_CHUNK;
     const int64_t need = nb + (nb + TREE_CHUNK - 1) / TREE_CHUNK + 1;
-    if (h->tree_cap < need) {
-        if (h->tree_buf) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->tree_buf); h->tree_buf = nullptr; h->tree_cap = 0; }
-        HIP_TRY(h, hipMalloc(&h->tree_buf, (size_t)need * sizeof(double)));
-        h->tree_cap = need;
-    }
+    if (gpf_status s = h->tree_buf.grow(h, (size_t)need)) return s;
     double *in = h->tree_buf, *out = h->tree_buf + nb;
     GPF_LAUNCH(k_wsum_tree, dim3((unsigned)nb), dim3(BLOCK), 0, h->stream, h->lw, &h->sc->raw, h->K, values, stride, col, h->n, pw, center, match, in);
     for (int64_t np = nb; np > 1;) {
@@ -1027,52 +998,20 @@ static gpf_status view_create_impl(gpf_handle parent, int64_t start, int64_t ste
     auto body = [&]() -> gpf_status {
         HIP_TRY(v, hipSetDevice(v->cfg.device));
         // scratch of its own (weight levels, descriptors, partials, scalars); rows / lw / anc alias the parent
-        v->ntiles = (v->n + TILE - 1) / TILE;
-        v->K = fix_K(count);
-        v->logN = log_((double)count);
+        gpf_status s;
+        if ((s = alloc_particle_buffers(v, true)) || (s = alloc_fixed_buffers(v))) return s;
         const size_t n = (size_t)count;
         if (index) {                                             // the particles' indices in the parent; their ids relative to the first
             std::vector<int32_t> ix((size_t)count), rel((size_t)count);
             for (int64_t i = 0; i < count; ++i) { ix[i] = (int32_t)index[i]; rel[i] = (int32_t)(index[i] - index[0]); }
-            HIP_TRY(v, hipMalloc(&v->vidx, n * sizeof(int32_t)));
-            HIP_TRY(v, hipMalloc(&v->vgid, n * sizeof(int32_t)));
+            if ((s = v->vidx.alloc(v, n)) || (s = v->vgid.alloc(v, n))) return s;
             HIP_TRY(v, hipMemcpy(v->vidx, ix.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
             HIP_TRY(v, hipMemcpy(v->vgid, rel.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
             v->args.gid_map = v->vgid;
         }
-        if (step != 1) {
-            HIP_TRY(v, hipMalloc(&v->vrows[0], n * (size_t)v->W * sizeof(double)));
-            HIP_TRY(v, hipMalloc(&v->vrows[1], n * (size_t)v->W * sizeof(double)));
-            HIP_TRY(v, hipMalloc(&v->vlw, n * sizeof(double)));
-            HIP_TRY(v, hipMalloc(&v->vanc, n * sizeof(int32_t)));
-        }
-        HIP_TRY(v, hipMalloc(&v->lws, n * sizeof(double)));
-        HIP_TRY(v, hipMalloc(&v->lp, n * sizeof(double)));
-        HIP_TRY(v, hipMalloc(&v->dtmp, n * sizeof(double)));
-        HIP_TRY(v, hipMalloc(&v->cdf[0], (size_t)v->ntiles * TILE * sizeof(uint64_t)));
-        HIP_TRY(v, hipMalloc(&v->t16[0], (size_t)v->ntiles * (TILE / 16) * sizeof(uint64_t)));
-        HIP_TRY(v, hipMalloc(&v->t256[0], t256_bytes(v->ntiles)));
-        const size_t db = (((size_t)2 * v->ntiles * sizeof(uint64_t)) + 15) & ~(size_t)15;
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 2; ++j) {
-                HIP_TRY(v, hipMalloc(&v->desc[i][j], db));
-                HIP_TRY(v, hipMemsetAsync(v->desc[i][j], 0, db, v->stream));
-            }
-        for (int b = 0; b < 2; ++b) {
-            HIP_TRY(v, hipMalloc(&v->mslots[b], (size_t)MAX_SLOTS * SLOT_WORDS * sizeof(unsigned long long)));
-            HIP_TRY(v, hipMemsetAsync(v->mslots[b], 0, (size_t)MAX_SLOTS * SLOT_WORDS * sizeof(unsigned long long), v->stream));
-        }
-        HIP_TRY(v, hipMalloc(&v->blockQ, (size_t)4 * 8 * v->n_cu * sizeof(uint64_t) + 64));
-        HIP_TRY(v, hipMemsetAsync(v->blockQ, 0, (size_t)4 * 8 * v->n_cu * sizeof(uint64_t) + 64, v->stream));
-        HIP_TRY(v, hipMalloc(&v->partial, MAX_PARTIALS * sizeof(double)));
-        HIP_TRY(v, hipMalloc(&v->acc_part, MAX_PARTIALS * sizeof(unsigned long long)));
-        HIP_TRY(v, hipMalloc(&v->dscal, 4 * sizeof(double)));
-        HIP_TRY(v, hipMalloc(&v->sc, sizeof(Scalars)));
-        HIP_TRY(v, hipHostMalloc(&v->h_sc, sizeof(Scalars)));
-        HIP_TRY(v, hipHostMalloc(&v->h_timeout, sizeof(int32_t)));
-        *v->h_timeout = 0;
+        if (step != 1 && ((s = v->vrows[0].alloc(v, n * (size_t)v->W)) || (s = v->vrows[1].alloc(v, n * (size_t)v->W)) ||
+                          (s = v->vlw.alloc(v, n)) || (s = v->vanc.alloc(v, n)))) return s;
         v->scan_blocks_per_cu = parent->scan_blocks_per_cu; v->wscan_blocks_per_cu = parent->wscan_blocks_per_cu;
-        HIP_TRY(v, hipMemsetAsync(v->sc, 0, sizeof(Scalars), v->stream));
         return GPF_OK;
     };
     gpf_status st = body();
@@ -1132,8 +1071,8 @@ static gpf_status resize_optimal(gpf_handle h, int64_t n_new, int32_t check, int
     rq.order = h->order; rq.max_ready = true;
     if ((s = summarize(h, pv, ws, rq))) return s;
     HIP_TRY(h, hipMemsetAsync(&h->sc->opt_d, 0xff, sizeof(long long), h->stream));
-    GPF_LAUNCH(k_opt_threshold, dim3(grid_for(h, n_new, 8)), dim3(BLOCK), 0, h->stream, h->cdf[0], ws, n_new, n_old, h->sc);
-    GPF_LAUNCH(k_opt_params, dim3(1), dim3(1), 0, h->stream, h->cdf[0], ws, n_new, h->sc);
+    GPF_LAUNCH(k_opt_threshold, dim3(grid_for(h, n_new, 8)), dim3(BLOCK), 0, h->stream, h->cdf[0], ws, n_new, n_old, h->sc.p);
+    GPF_LAUNCH(k_opt_params, dim3(1), dim3(1), 0, h->stream, h->cdf[0], ws, n_new, h->sc.p);
     // keep flags -> compaction offsets (channel 1); weights of the others -> their CDF (channel 2)
     InOptimal ik{h->lw, ws, h->sc, h->K, 0}, iw{h->lw, ws, h->sc, h->K, 1};
     if ((s = scan_launch_optimal(h, 1, ik, &h->sc->Ctot))) return s;
@@ -1174,7 +1113,7 @@ static gpf_status resize_optimal(gpf_handle h, int64_t n_new, int32_t check, int
     // new_traces .= view(traces, parents); log_weights (resize.jl:189-197)
     launch_gather_rows_lw(h, h->anc, old.rows[old.cur], old.lw, h->rows[0], h->lw, n_new);
     const double ratio = log_((double)n_new) - log_((double)n_old);
-    GPF_LAUNCH(k_opt_weights, dim3(grid_for(h, n_new, 8)), dim3(BLOCK), 0, h->stream, h->lw, n_new, h->sc, ws, K, ratio);
+    GPF_LAUNCH(k_opt_weights, dim3(grid_for(h, n_new, 8)), dim3(BLOCK), 0, h->stream, h->lw, n_new, h->sc.p, ws, K, ratio);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     free_bufs(old);
     HIP_TRY(h, hipGetLastError());
@@ -1236,7 +1175,7 @@ gpf_status gpf_resize(gpf_handle h, int64_t n_new, int32_t method, double priori
         PrioView post{h->lws, nullptr, 0.0, 0};
         rq.cdf = false;
         if ((s = summarize(h, post, &h->sc->post, rq))) { free_bufs(old); return s; }
-        GPF_LAUNCH(k_apply_post, dim3(grid_for(h, n_new, 8)), dim3(BLOCK), 0, h->stream, h->sc, h->K, h->logN, h->lws, h->lw, n_new);      // (the slots describe log_ws: ensure_max said so)
+        GPF_LAUNCH(k_apply_post, dim3(grid_for(h, n_new, 8)), dim3(BLOCK), 0, h->stream, h->sc.p, h->K, h->logN, h->lws, h->lw, n_new);      // (the slots describe log_ws: ensure_max said so)
     }
     (void)Kp;
     HIP_TRY(h, hipStreamSynchronize(h->stream));                 // the old buffers are read by the kernels above
@@ -1294,12 +1233,8 @@ gpf_status gpf_dereplicate(gpf_handle h, int32_t n_replicates, int32_t interleav
 // pf_coalesce! (resize.jl:309-334) -- gpf.h gpf_coalesce.  Four passes (gpf_k_coalesce.hpp) and one host read of the group count.
 } // extern "C"
 namespace gpfh {
-// device scratch of ONE call (hash table, slots, tile counts / the observation history): freed on every return path -- hipFree waits
-// for the device, so no kernel of the call still reads it -- and never kept on the handle (46 MB at n = 10^6)
-struct CallScratch {
-    void* p = nullptr;
-    ~CallScratch() { if (p) (void)hipFree(p); }
-};
+// device scratch of ONE call (hash table, slots, tile counts / the observation history) is a local Dev<T>: freed on every return path -- hipFree
+// waits for the device, so no kernel of the call still reads it -- and never kept on the handle (46 MB at n = 10^6)
 static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 template <int W>
 void launch_coal(gpf_filter* h, const CoalArgs& a, int stage, double log_ratio = 0.0)
@@ -1342,9 +1277,9 @@ gpf_status gpf_coalesce(gpf_handle h, uint64_t key_mask, int64_t* n_out)
     while (T < 2 * (uint64_t)n) T <<= 1;
     const int64_t ntl = (n + COAL_TILE - 1) / COAL_TILE;
     const size_t b_claim = align256(T * 4), b_gm = align256(T * 16), b_slot = align256((size_t)n * 4), b_tile = align256((size_t)ntl * 4);
-    CallScratch scr;
-    HIP_TRY(h, hipMalloc(&scr.p, b_claim + b_gm + b_slot + 2 * b_tile + 256));
-    char* p = static_cast<char*>(scr.p);
+    Dev<char> scr;
+    if ((s = scr.alloc(h, b_claim + b_gm + b_slot + 2 * b_tile + 256))) return s;
+    char* p = scr;
     CoalArgs a{};
     a.rows = h->rows[h->cur]; a.lw = h->lw; a.n = n; a.mask = (uint32_t)(key_mask ? key_mask : all);
     a.claim = reinterpret_cast<uint32_t*>(p); p += b_claim;
@@ -1394,9 +1329,9 @@ gpf_status gpf_introduce(gpf_handle h, const double* obs, int32_t n_obs, int32_t
     std::vector<double> hobs((size_t)n_steps * MAX_OBS, 0.0);
     for (int32_t e = 0; e < n_steps; ++e)
         for (int k = 0; k < n_obs; ++k) hobs[(size_t)e * MAX_OBS + k] = obs[(size_t)e * n_obs + k];
-    CallScratch scr;
-    HIP_TRY(h, hipMalloc(&scr.p, hobs.size() * sizeof(double)));
-    double* dobs = static_cast<double*>(scr.p);
+    Dev<double> scr;
+    if ((s = scr.alloc(h, hobs.size()))) return s;
+    double* dobs = scr;
     HIP_TRY(h, hipMemcpyAsync(dobs, hobs.data(), hobs.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     const uint64_t seed = intro_seed(h->cfg.seed, h->epoch);
     Bufs old = take_particle_buffers(h);
@@ -1404,8 +1339,8 @@ gpf_status gpf_introduce(gpf_handle h, const double* obs, int32_t n_obs, int32_t
     if ((s = alloc_particle_buffers(h))) { free_bufs(old); return s; }
     HIP_TRY(h, hipMemcpyAsync(h->rows[0], old.rows[old.cur], (size_t)n_old * h->W * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->anc, old.anc, (size_t)n_old * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
-    GPF_LAUNCH(k_intro_old, dim3(grid_for(h, n_old, 8)), dim3(BLOCK), 0, h->stream, old.lw, h->sc, n_old, h->lw);
-    HIP_TRY(h, hipMemsetAsync(reinterpret_cast<char*>(h->sc) + offsetof(Scalars, lml_est), 0, sizeof(double), h->stream));   // log_ml_est = 0
+    GPF_LAUNCH(k_intro_old, dim3(grid_for(h, n_old, 8)), dim3(BLOCK), 0, h->stream, old.lw, h->sc.p, n_old, h->lw);
+    HIP_TRY(h, hipMemsetAsync(reinterpret_cast<char*>(h->sc.p) + offsetof(Scalars, lml_est), 0, sizeof(double), h->stream));   // log_ml_est = 0
     bool_dispatch(h->cfg.keep_prev != 0, proposal != 0, [&](auto KEEP, auto PROP) {
         DISPATCH_MODEL(h, (launch_introduce<MM, KEEP, PROP>(h, seed, dobs, n_steps, n_old, n_particles)));
     });
@@ -1424,11 +1359,9 @@ gpf_status gpf_history_enable(gpf_handle h, int32_t max_steps)
     if (h->cfg.n_global != h->n) return fail(h, GPF_ERR_STATE, "the trajectory store is not available for sharded filters");
     if (h->initialized) return fail(h, GPF_ERR_STATE, "enable the trajectory store before gpf_initialize");
     h->hist_on = true; h->hist_blocks = false; h->hist_weights = false; h->hist_cap = max_steps;
-    if (h->hist_dev_maps) (void)hipFree(h->hist_dev_maps);
-    HIP_TRY(h, hipMalloc(&h->hist_dev_maps, (size_t)max_steps * sizeof(int32_t*)));
-    if (h->hist_dev_x) { (void)hipFree(h->hist_dev_x); h->hist_dev_x = nullptr; }
-    HIP_TRY(h, hipMalloc(&h->hist_dev_x, (size_t)max_steps * sizeof(double*)));
-    return GPF_OK;
+    h->hist_dev_maps.reset(); h->hist_dev_x.reset();
+    gpf_status s = h->hist_dev_maps.alloc(h, (size_t)max_steps);
+    return s ? s : h->hist_dev_x.alloc(h, (size_t)max_steps);
 }
 
 // the block-wise store: the same store, fed by the block-wise calls as well (gpf.h)
@@ -1445,10 +1378,8 @@ gpf_status gpf_history_enable_blocks_weights(gpf_handle h, int32_t max_steps)
 {
     gpf_status s = gpf_history_enable_blocks(h, max_steps);
     if (s) return s;
-    for (const double*** t : {&h->hist_dev_lw, &h->hist_dev_obs}) {
-        if (*t) { (void)hipFree(*t); *t = nullptr; }
-        HIP_TRY(h, hipMalloc(t, (size_t)max_steps * sizeof(double*)));
-    }
+    h->hist_dev_lw.reset(); h->hist_dev_obs.reset();
+    if ((s = h->hist_dev_lw.alloc(h, (size_t)max_steps)) || (s = h->hist_dev_obs.alloc(h, (size_t)max_steps))) return s;
     h->hist_weights = true;
     return GPF_OK;
 }
@@ -1475,8 +1406,8 @@ static gpf_status history_values(gpf_handle h, int32_t step, int32_t column)
     if (!maps.empty())
         HIP_TRY(h, hipMemcpyAsync(h->hist_dev_maps, maps.data(), maps.size() * sizeof(int32_t*), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));                   // `maps` is a host temporary
-    GPF_LAUNCH(k_hist_column, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->hist_dev_maps, (int)maps.size(),
-                       h->hist_x[step - 1], h->d, (int)column, h->n, h->dtmp);
+    GPF_LAUNCH(k_hist_column, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->hist_dev_maps.p, (int)maps.size(),
+                       h->hist_x[step - 1].p, h->d, (int)column, h->n, h->dtmp);
     HIP_TRY(h, hipGetLastError());
     return GPF_OK;
 }
@@ -1597,10 +1528,10 @@ static void block_store_walk_args(gpf_handle h, const StoreSteps& r, int32_t ste
     a.n = h->n; a.nb = block_size; a.nblocks = r.nblocks;
 }
 // device scratch of one query for an output that was asked for (up to 16 GB of trajectories are nothing to keep on a handle)
-static gpf_status block_store_scratch(gpf_handle h, CallScratch& c, const void* wanted, size_t bytes)
+template <class T>
+static gpf_status block_store_scratch(gpf_handle h, Dev<T>& c, const void* wanted, size_t bytes)
 {
-    if (wanted) HIP_TRY(h, hipMalloc(&c.p, bytes));
-    return GPF_OK;
+    return wanted ? c.alloc(h, bytes / sizeof(T)) : GPF_OK;
 }
 // what both estimate queries do once the gate and their own arguments have passed: the current step is snapshotted and the maps of the steps
 // T, T-1, ..., step+1 go to h->hist_dev_maps (as history_values): *n_maps of them
@@ -1623,7 +1554,7 @@ template <int D>
 void launch_block_hist_moments(gpf_filter* h, int n_maps, const double* hx, int64_t nb, int64_t nblocks, int want_var, double* mean, double* var)
 {
     team_dispatch(nb, nblocks, [&](auto TEAM, auto ITEMS, dim3 grid) {
-        GPF_LAUNCH((k_block_hist_moments<D, TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, h->hist_dev_maps, n_maps, hx, h->lw, h->n, nb, nblocks, want_var, mean, var);
+        GPF_LAUNCH((k_block_hist_moments<D, TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, h->hist_dev_maps.p, n_maps, hx, h->lw, h->n, nb, nblocks, want_var, mean, var);
     });
 }
 } // namespace gpfh
@@ -1662,7 +1593,7 @@ gpf_status gpf_block_history_proportion(gpf_handle h, int32_t step, int64_t bloc
     const BlockMatch mv = make_block_match(values, n_values);
     const double* hx = h->hist_x[step - 1];
     team_dispatch(block_size, nblocks, [&](auto TEAM, auto ITEMS, dim3 grid) {
-        GPF_LAUNCH((k_block_hist_proportion<TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, h->hist_dev_maps, n_maps, hx, h->d, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est);
+        GPF_LAUNCH((k_block_hist_proportion<TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, h->hist_dev_maps.p, n_maps, hx, h->d, (int)column, h->lw, h->n, block_size, nblocks, mv, h->blk_est.p);
     });
     HIP_TRY(h, hipGetLastError());
     return block_out(h, {{h->blk_est, out, cells * sizeof(double)}});
@@ -1675,7 +1606,7 @@ template <int D>
 void launch_block_sample_traj(gpf_filter* h, const TrajLaunch& a)
 {
     team_dispatch(a.nb, a.nblocks, [&](auto TEAM, auto ITEMS, dim3 grid) {
-        GPF_LAUNCH((k_block_sample_traj<D, TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, h->hist_dev_maps, h->hist_dev_x, a.T, a.lo0, a.hi0, h->lw, h->n, a.nb, a.nblocks,
+        GPF_LAUNCH((k_block_sample_traj<D, TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, h->hist_dev_maps.p, h->hist_dev_x.p, a.T, a.lo0, a.hi0, h->lw, h->n, a.nb, a.nblocks,
                    a.n_samples, h->cfg.seed, h->epoch, a.traj, a.idx);
     });
 }
@@ -1694,9 +1625,9 @@ gpf_status gpf_block_sample_trajectories(gpf_handle h, int64_t block_size, int32
     int64_t draws = 0;
     if ((s = block_store_steps(h, block_size, step_lo, step_hi, who, r)) || (s = block_store_draws(h, r, n_samples, who, &draws))) return s;
     const size_t b_traj = (size_t)draws * (size_t)r.n_steps * (size_t)h->d * sizeof(double), b_idx = (size_t)draws * sizeof(int64_t);
-    CallScratch d_traj, d_idx;                                     // scratch of this call: freed before it returns
+    Dev<double> d_traj; Dev<int64_t> d_idx;                                    // scratch of this call: freed before it returns
     if ((s = block_store_tables(h, false)) || (s = block_store_scratch(h, d_traj, traj_out, b_traj)) || (s = block_store_scratch(h, d_idx, idx_out, b_idx))) return s;
-    const TrajLaunch a{r.T, step_lo - 1, step_hi - 1, block_size, r.nblocks, (int)n_samples, static_cast<double*>(d_traj.p), static_cast<int64_t*>(d_idx.p)};
+    const TrajLaunch a{r.T, step_lo - 1, step_hi - 1, block_size, r.nblocks, (int)n_samples, d_traj, d_idx};
     DISPATCH_D(h, (launch_block_sample_traj<DD>(h, a)));
     HIP_TRY(h, hipGetLastError());
     if ((s = block_out(h, {{d_traj.p, traj_out, b_traj}, {d_idx.p, idx_out, b_idx}}))) return s;
@@ -1730,13 +1661,13 @@ gpf_status gpf_block_backward_sample(gpf_handle h, int64_t block_size, int32_t n
     if ((s = block_store_steps(h, block_size, step_lo, step_hi, who, r)) || (s = block_store_draws(h, r, n_samples, who, &draws)) ||
         (s = block_store_sizes(h, block_size, r.T, step_lo, who))) return s;
     const size_t b_traj = (size_t)draws * (size_t)r.n_steps * (size_t)h->d * sizeof(double), b_idx = (size_t)draws * (size_t)r.n_steps * sizeof(int64_t);
-    CallScratch d_traj, d_idx;                                     // scratch of this call, as gpf_block_sample_trajectories
+    Dev<double> d_traj; Dev<int64_t> d_idx;                                    // scratch of this call, as gpf_block_sample_trajectories
     if ((s = block_store_tables(h, true)) || (s = block_store_scratch(h, d_traj, traj_out, b_traj)) || (s = block_store_scratch(h, d_idx, idx_out, b_idx))) return s;
     BackArgs a{};
     a.maps = h->hist_dev_maps; a.hx = h->hist_dev_x; a.hlw = h->hist_dev_lw; a.hobs = h->hist_dev_obs; a.lw = h->lw;
     a.T = r.T; a.lo0 = step_lo - 1; a.hi0 = step_hi - 1; a.n_samples = (int)n_samples;
     a.n = h->n; a.nb = block_size; a.nblocks = r.nblocks; a.seed = h->cfg.seed; a.epoch = h->epoch;
-    a.traj = static_cast<double*>(d_traj.p); a.idx = static_cast<int64_t*>(d_idx.p);
+    a.traj = d_traj; a.idx = d_idx;
     const AncArgs x = anc_args(h);
     DISPATCH_MODEL(h, (launch_block_backward<MM>(h, a, x)));
     HIP_TRY(h, hipGetLastError());
@@ -1761,13 +1692,13 @@ gpf_status gpf_block_smooth(gpf_handle h, int64_t block_size, int32_t step_lo, i
         return fail(h, GPF_ERR_INVALID_ARGUMENT, std::string(who) + ": n_blocks * n_steps * dim and n_blocks * n_steps * block_size must stay below 2^31");
     if ((s = block_store_sizes(h, block_size, r.T, step_lo, who))) return s;
     const size_t b_mom = (size_t)cells * (size_t)h->d * sizeof(double), b_w = (size_t)cells * (size_t)block_size * sizeof(double), b_c = (size_t)cells * sizeof(int64_t);
-    CallScratch d_mean, d_var, d_w, d_c;                           // scratch of this call, as gpf_block_backward_sample; only what was asked for
+    Dev<double> d_mean, d_var, d_w; Dev<int64_t> d_c;                          // scratch of this call, as gpf_block_backward_sample; only what was asked for
     if ((s = block_store_tables(h, true)) || (s = block_store_scratch(h, d_mean, mean_out, b_mom)) || (s = block_store_scratch(h, d_var, var_out, b_mom)) ||
         (s = block_store_scratch(h, d_w, weights_out, b_w)) || (s = block_store_scratch(h, d_c, blocks_out, b_c))) return s;
     SmoothArgs a{};
     block_store_walk_args(h, r, step_lo, step_hi, block_size, a);
-    a.mean = static_cast<double*>(d_mean.p); a.var = static_cast<double*>(d_var.p);
-    a.wout = static_cast<double*>(d_w.p); a.blocks = static_cast<int64_t*>(d_c.p);
+    a.mean = d_mean; a.var = d_var;
+    a.wout = d_w; a.blocks = d_c;
     launch_block_smooth(h, a, anc_args(h));
     HIP_TRY(h, hipGetLastError());
     // (nothing was drawn: the epoch stays)
@@ -1791,13 +1722,13 @@ gpf_status gpf_block_smooth_pairs(gpf_handle h, int64_t block_size, int32_t step
     if ((s = block_store_sizes(h, block_size, r.T, step_lo, who))) return s;
     const size_t b_mean = (size_t)cells * (size_t)h->d * sizeof(double), b_sec = (size_t)cells * (size_t)dd * sizeof(double),
                  b_cross = (size_t)(r.nblocks * (r.n_steps - 1)) * (size_t)dd * sizeof(double), b_c = (size_t)cells * sizeof(int64_t);
-    CallScratch d_mean, d_sec, d_cross, d_c;                       // scratch of this call, as gpf_block_smooth; only what was asked for
+    Dev<double> d_mean, d_sec, d_cross; Dev<int64_t> d_c;                      // scratch of this call, as gpf_block_smooth; only what was asked for
     if ((s = block_store_tables(h, true)) || (s = block_store_scratch(h, d_mean, mean_out, b_mean)) || (s = block_store_scratch(h, d_sec, second_out, b_sec)) ||
         (s = block_store_scratch(h, d_cross, cross_out, b_cross)) || (s = block_store_scratch(h, d_c, blocks_out, b_c))) return s;
     PairArgs a{};
     block_store_walk_args(h, r, step_lo, step_hi, block_size, a);
-    a.mean = static_cast<double*>(d_mean.p); a.second = static_cast<double*>(d_sec.p);
-    a.cross = static_cast<double*>(d_cross.p); a.blocks = static_cast<int64_t*>(d_c.p);
+    a.mean = d_mean; a.second = d_sec;
+    a.cross = d_cross; a.blocks = d_c;
     launch_block_pairs(h, a, anc_args(h));
     HIP_TRY(h, hipGetLastError());
     // (nothing was drawn: the epoch stays)
@@ -1824,13 +1755,13 @@ gpf_status gpf_block_map_path(gpf_handle h, int64_t block_size, int32_t step_lo,
     // copies -- 198 MB at 10^4 blocks of 100 and T = 100 are nothing to keep on a handle; hipFree on return waits for the launch
     const int64_t bsp = (block_size + 7) / 8 * 8;
     const size_t b_ptr = (size_t)std::max(r.T - 1, 1) * (size_t)r.nblocks * (size_t)bsp * sizeof(uint16_t), b_lin = (size_t)r.nblocks * (size_t)r.T * sizeof(int32_t);
-    CallScratch d_path, d_idx, d_lp, d_ptr, d_lin;
+    Dev<double> d_path, d_lp; Dev<int64_t> d_idx; Dev<uint16_t> d_ptr; Dev<int32_t> d_lin;
     if ((s = block_store_tables(h, true)) || (s = block_store_scratch(h, d_path, path_out, b_path)) || (s = block_store_scratch(h, d_idx, idx_out, b_idx)) ||
         (s = block_store_scratch(h, d_lp, logp_out, b_lp)) || (s = block_store_scratch(h, d_ptr, h, b_ptr)) || (s = block_store_scratch(h, d_lin, h, b_lin))) return s;
     MapArgs a{};
     block_store_walk_args(h, r, step_lo, step_hi, block_size, a);
-    a.path = static_cast<double*>(d_path.p); a.idx = static_cast<int64_t*>(d_idx.p); a.logp = static_cast<double*>(d_lp.p);
-    a.ptr = static_cast<uint16_t*>(d_ptr.p); a.lin = static_cast<int32_t*>(d_lin.p); a.bsp = bsp;
+    a.path = d_path; a.idx = d_idx; a.logp = d_lp;
+    a.ptr = d_ptr; a.lin = d_lin; a.bsp = bsp;
     launch_block_map(h, a, anc_args(h));
     HIP_TRY(h, hipGetLastError());
     // (nothing was drawn: the epoch stays)
@@ -1934,7 +1865,7 @@ gpf_status gpf_checkpoint_save(gpf_handle h, void* out, int64_t bytes)
     for (int i = 0; i < 4; ++i) hd.q[i] = h->args.q[i];
     char* o = static_cast<char*>(out) + sizeof(CkptHeader);
     const size_t rb = (size_t)h->n * h->W * 8, wb = (size_t)h->n * 8, ab = (size_t)h->n * 4;
-    HIP_TRY(h, hipMemcpyAsync(&hd.lml_est, reinterpret_cast<const char*>(h->sc) + offsetof(Scalars, lml_est), sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&hd.lml_est, reinterpret_cast<const char*>(h->sc.p) + offsetof(Scalars, lml_est), sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(o, h->rows[h->cur], rb, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(o + rb, h->lw, wb, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(o + rb + wb, h->anc, ab, hipMemcpyDeviceToHost, h->stream));
@@ -1969,7 +1900,7 @@ gpf_status gpf_checkpoint_load(gpf_handle h, const void* in, int64_t bytes)
     HIP_TRY(h, hipMemcpyAsync(h->rows[h->cur], o, rb, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->lw, o + rb, wb, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->anc, o + rb + wb, ab, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(reinterpret_cast<char*>(h->sc) + offsetof(Scalars, lml_est), &hd.lml_est, sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(reinterpret_cast<char*>(h->sc.p) + offsetof(Scalars, lml_est), &hd.lml_est, sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->epoch = hd.epoch; h->has_prev = hd.has_prev != 0; h->initialized = true;
     h->args.n_strata = hd.n_strata; h->args.interleaved = hd.interleaved; h->args.logK = hd.logK;

@@ -13,18 +13,11 @@ namespace gpfh {
 
 Bufs take_particle_buffers(gpf_filter* h)
 {
-    Bufs b;
-    b.n = h->n; b.ntiles = h->ntiles; b.cur = h->cur;
-    b.rows[0] = h->rows[0]; b.rows[1] = h->rows[1]; h->rows[0] = h->rows[1] = nullptr;
-    b.lw = h->lw; b.lws = h->lws; b.lp = h->lp; b.dtmp = h->dtmp; h->lw = h->lws = h->lp = h->dtmp = nullptr;
-    for (int i = 0; i < 3; ++i) {
-        b.cdf[i] = h->cdf[i]; b.t16[i] = h->t16[i]; b.t256[i] = h->t256[i]; h->cdf[i] = h->t16[i] = h->t256[i] = nullptr;
-        for (int j = 0; j < 2; ++j) { b.desc[i][j] = h->desc[i][j]; h->desc[i][j] = nullptr; }
-        h->table[i] = nullptr; h->dcur[i] = 0;
-    }
-    b.anc = h->anc; b.order = h->order; b.idx_in = h->idx_in; h->anc = h->order = h->idx_in = nullptr;
-    b.keys = h->keys; b.keys_out = h->keys_out; b.sort_tmp = h->sort_tmp;
-    h->keys = h->keys_out = nullptr; h->sort_tmp = nullptr; h->sort_tmp_bytes = 0;
+    const Bufs b = *h;                                           // (the handle's base: slices the set off)
+    static_cast<Bufs&>(*h) = Bufs();
+    h->n = b.n; h->ntiles = b.ntiles; h->cur = b.cur;            // the counts stand until the caller sets new ones
+    for (int i = 0; i < 3; ++i) { h->table[i] = nullptr; h->dcur[i] = 0; }
+    h->sort_tmp_bytes = 0;
     return b;
 }
 
@@ -37,17 +30,20 @@ void free_bufs(Bufs& b)
     b = Bufs();
 }
 
-// allocate the per-N buffers for h->n particles (fields must be null); sets ntiles, K, logN
-gpf_status alloc_particle_buffers(gpf_filter* h)
+// allocate the per-N buffers for h->n particles (fields must be null); sets ntiles, K, logN.  scratch_only: a view's set -- rows / lw / anc alias its filter's
+gpf_status alloc_particle_buffers(gpf_filter* h, bool scratch_only)
 {
     h->ntiles = (h->n + TILE - 1) / TILE;
     h->K = fix_K(h->cfg.n_global);
     h->logN = log_((double)h->cfg.n_global);
     h->cur = 0;
     const size_t n = (size_t)h->n, rb = n * (size_t)h->W * sizeof(double);
-    HIP_TRY(h, hipMalloc(&h->rows[0], rb));
-    HIP_TRY(h, hipMalloc(&h->rows[1], rb));
-    HIP_TRY(h, hipMalloc(&h->lw, n * sizeof(double)));
+    if (!scratch_only) {
+        HIP_TRY(h, hipMalloc(&h->rows[0], rb));
+        HIP_TRY(h, hipMalloc(&h->rows[1], rb));
+        HIP_TRY(h, hipMalloc(&h->lw, n * sizeof(double)));
+        HIP_TRY(h, hipMalloc(&h->anc, n * sizeof(int32_t)));
+    }
     HIP_TRY(h, hipMalloc(&h->lws, n * sizeof(double)));
     HIP_TRY(h, hipMalloc(&h->lp, n * sizeof(double)));
     HIP_TRY(h, hipMalloc(&h->dtmp, n * sizeof(double)));
@@ -60,7 +56,23 @@ gpf_status alloc_particle_buffers(gpf_filter* h)
             HIP_TRY(h, hipMalloc(&h->desc[i][j], db));
             HIP_TRY(h, hipMemsetAsync(h->desc[i][j], 0, db, h->stream));     // descriptors start invalid; kernels keep them so
         }
-    HIP_TRY(h, hipMalloc(&h->anc, n * sizeof(int32_t)));
+    return GPF_OK;
+}
+// the buffers every handle has, whatever its size (a filter and a view alike): maximum slots, partials, the scalar block and its pinned mirror
+gpf_status alloc_fixed_buffers(gpf_filter* h)
+{
+    gpf_status s;
+    for (int b = 0; b < 2; ++b) {
+        if ((s = h->mslots[b].alloc(h, (size_t)MAX_SLOTS * SLOT_WORDS))) return s;
+        HIP_TRY(h, hipMemsetAsync(h->mslots[b], 0, (size_t)MAX_SLOTS * SLOT_WORDS * sizeof(unsigned long long), h->stream));
+    }
+    if ((s = h->blockQ.alloc(h, (size_t)4 * 8 * h->n_cu + 8))) return s;   // (4 limbs per scan workgroup, <= 8 workgroups per CU)
+    // (zeroed: the ESS scan recognises this launch's partials by a tag in their top bits -- recycled memory may hold another filter's)
+    HIP_TRY(h, hipMemsetAsync(h->blockQ, 0, h->blockQ.count * sizeof(uint64_t), h->stream));
+    if ((s = h->partial.alloc(h, MAX_PARTIALS)) || (s = h->acc_part.alloc(h, MAX_PARTIALS)) || (s = h->dscal.alloc(h, 4)) ||
+        (s = h->sc.alloc(h, 1)) || (s = h->h_sc.alloc(h, 1)) || (s = h->h_timeout.alloc(h, 1))) return s;
+    *h->h_timeout = 0;
+    HIP_TRY(h, hipMemsetAsync(h->sc, 0, sizeof(Scalars), h->stream));
     return GPF_OK;
 }
 
@@ -140,7 +152,7 @@ void launch_move_t(gpf_filter* h, int grid, int n_iters, const ModelArgs& args, 
     else bool_dispatch(h->pending_gather, [&](auto GATHER) {
         GPF_LAUNCH((k_move<M, Wc, RW, GATHER, PROP>), dim3(grid), dim3(BLOCK), 0, h->stream, args, h->cfg.seed, epoch,
                    h->cfg.gid0, h->n, (int)h->has_prev, n_iters, h->anc, h->rows[h->cur], h->rows[1 - h->cur], h->lw,
-                   h->acc_part, RW ? next_slots(h) : MaxSlots{nullptr, nullptr});
+                   h->acc_part.p, RW ? next_slots(h) : MaxSlots{nullptr, nullptr});
     });
 }
 // the pending move inside the propagate (k_move_step): old observation + the move's epoch, new observation (h->args) + the update's epoch
@@ -203,9 +215,9 @@ gpf_status materialize(gpf_filter* h)
             // (ascending targets: few slots outside the own range -- a small grid; i.i.d. targets: (G-1)/G of all slots sit in the window)
             const int gr = h->pend_own_range ? grid_for(h, std::min<int64_t>(h->n, (int64_t)1 << 16), 8) : grid_for(h, h->n, 8);
             const int64_t* own_rng_ring = h->pend_own_range ? h->shard_plan->own_range : nullptr;
-            DISPATCH_W(h, GPF_LAUNCH((k_commit_ring<WW>), dim3(gr), dim3(BLOCK), 0, h->stream, rin, h->n, own_rng_ring, out, h->anc, h->lw, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, h->sc, (int)h->pend_mailbox));
+            DISPATCH_W(h, GPF_LAUNCH((k_commit_ring<WW>), dim3(gr), dim3(BLOCK), 0, h->stream, rin, h->n, own_rng_ring, out, h->anc, h->lw, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, h->sc.p, (int)h->pend_mailbox));
         } else {
-            DISPATCH_W(h, GPF_LAUNCH((k_commit_packed<WW>), dim3(grid), dim3(BLOCK), 0, h->stream, h->pend_packed, m, out, h->anc, h->lw, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, h->sc, (int)h->pend_mailbox));
+            DISPATCH_W(h, GPF_LAUNCH((k_commit_packed<WW>), dim3(grid), dim3(BLOCK), 0, h->stream, h->pend_packed, m, out, h->anc, h->lw, h->pend_mf, h->pend_tot, h->pend_G, h->K, h->logN, h->sc.p, (int)h->pend_mailbox));
         }
         HIP_TRY(h, hipGetLastError());
         h->cur ^= 1;
@@ -228,8 +240,6 @@ gpf_status materialize(gpf_filter* h)
 // ------------------------------------------------------------------ trajectory store
 void hist_clear(gpf_filter* h)
 {
-    for (double* p : h->hist_x) if (p) (void)hipFree(p);
-    for (int32_t* p : h->hist_map) if (p) (void)hipFree(p);
     h->hist_x.clear(); h->hist_map.clear(); h->hist_lw.clear(); h->hist_obs.clear(); h->hist_bsize.clear(); h->hist_step = -1;
 }
 // snapshot the latent columns of the CURRENT step (final order: called when the step is over, or at query time)
@@ -238,17 +248,17 @@ gpf_status hist_snapshot(gpf_filter* h)
     if (!h->hist_on || h->hist_step < 0) return GPF_OK;
     gpf_status s = materialize(h);
     if (s) return s;
-    double*& dst = h->hist_x[h->hist_step];
+    Dev<double>& dst = h->hist_x[h->hist_step];
     // (the weights mode: the step's log-weights and observation rows live behind its columns, in the same allocation -- one hipMalloc per step as before)
     const int64_t bs = h->hist_weights ? h->hist_bsize[h->hist_step] : 0;
     const int64_t n_obs_words = bs > 0 ? (h->n + bs - 1) / bs * MAX_OBS : 0;
-    if (!dst) HIP_TRY(h, hipMalloc(&dst, (size_t)(h->n * h->d + (h->hist_weights ? h->n + n_obs_words : 0)) * sizeof(double)));
-    GPF_LAUNCH(k_hist_snapshot, dim3(grid_for(h, h->n * h->d, 8)), dim3(BLOCK), 0, h->stream, h->rows[h->cur], h->W, h->d, h->n, dst);
+    if (!dst && (s = dst.alloc(h, (size_t)(h->n * h->d + (h->hist_weights ? h->n + n_obs_words : 0))))) return s;
+    GPF_LAUNCH(k_hist_snapshot, dim3(grid_for(h, h->n * h->d, 8)), dim3(BLOCK), 0, h->stream, h->rows[h->cur], h->W, h->d, h->n, dst.p);
     HIP_TRY(h, hipGetLastError());
     if (h->hist_weights) {                                         // the same moment, the same order: the step's log-weights and per-block observation rows
         double* const dlw = h->hist_lw[h->hist_step] = dst + h->n * h->d;
         double* const dob = h->hist_obs[h->hist_step] = n_obs_words ? dlw + h->n : nullptr;
-        GPF_LAUNCH(k_hist_record, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, (const double*)h->lw, h->n, (const double*)h->blk_obs, n_obs_words, dlw, dob);
+        GPF_LAUNCH(k_hist_record, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, (const double*)h->lw, h->n, (const double*)h->blk_obs.p, n_obs_words, dlw, dob);
         HIP_TRY(h, hipGetLastError());
     }
     return GPF_OK;
@@ -259,14 +269,14 @@ gpf_status hist_on_resample(gpf_filter* h, int64_t block_size)
 {
     if (h->fwd_on) { gpf_status fs = fwd_on_resample(h, block_size); if (fs) return fs; }   // (forward smoothing per block keeps the step's map too, with or without a store)
     if (!h->hist_on || h->hist_step < 0) return GPF_OK;
-    int32_t* old = h->hist_map[h->hist_step];
-    int32_t* neu = nullptr;
-    HIP_TRY(h, hipMalloc(&neu, (size_t)h->n * sizeof(int32_t)));
-    if (block_size > 0) GPF_LAUNCH(k_hist_compose_blocks, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->anc, h->blk_mask, block_size, old, h->n, neu);
-    else GPF_LAUNCH(k_hist_compose, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->anc, old, h->n, neu);
+    Dev<int32_t>& old = h->hist_map[h->hist_step];
+    Dev<int32_t> neu;
+    if (gpf_status s = neu.alloc(h, (size_t)h->n)) return s;
+    if (block_size > 0) GPF_LAUNCH(k_hist_compose_blocks, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->anc, h->blk_mask.p, block_size, old.p, h->n, neu.p);
+    else GPF_LAUNCH(k_hist_compose, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->anc, old.p, h->n, neu.p);
     HIP_TRY(h, hipGetLastError());
-    if (old) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(old); }
-    h->hist_map[h->hist_step] = neu;
+    if (old) HIP_TRY(h, hipStreamSynchronize(h->stream));        // (the launch above read it)
+    old = std::move(neu);
     return GPF_OK;
 }
 gpf_status hist_begin_step(gpf_filter* h, bool first)
@@ -277,7 +287,7 @@ gpf_status hist_begin_step(gpf_filter* h, bool first)
     if (first) hist_clear(h);
     else { gpf_status s = hist_snapshot(h); if (s) return s; }     // the step that ends now, in its final order
     if ((int)h->hist_x.size() >= h->hist_cap) return fail(h, GPF_ERR_STATE, "trajectory store full: raise max_steps of gpf_history_enable");
-    h->hist_x.push_back(nullptr); h->hist_map.push_back(nullptr);
+    h->hist_x.emplace_back(); h->hist_map.emplace_back();
     if (h->hist_weights) { h->hist_lw.push_back(nullptr); h->hist_obs.push_back(nullptr); h->hist_bsize.push_back(0); }   // (a block-wise call sets its block size)
     h->hist_step = (int)h->hist_x.size() - 1;
     return GPF_OK;
@@ -343,10 +353,10 @@ gpf_status view_enter(gpf_filter* v)
         v->rows[0] = v->vrows[0]; v->rows[1] = v->vrows[1]; v->lw = v->vlw; v->anc = v->vanc;
         if (v->view_step == 0)                                   // state[idxs]: an arbitrary index vector
             GPF_LAUNCH(k_view_index_copy, dim3(grid_for(v, v->n * (v->W / 2), 8)), dim3(BLOCK), 0, v->stream, p->rows[p->cur], p->lw, p->anc,
-                       v->vrows[0], v->vlw, v->vanc, v->W, v->vidx, v->n, 1);
+                       v->vrows[0].p, v->vlw.p, v->vanc.p, v->W, v->vidx.p, v->n, 1);
         else
         GPF_LAUNCH(k_view_strided_copy, dim3(grid_for(v, v->n * (v->W / 2), 8)), dim3(BLOCK), 0, v->stream, p->rows[p->cur] + o * v->W, p->lw + o, p->anc + o,
-                   v->vrows[0], v->vlw, v->vanc, v->W, v->view_step, v->n, 1);
+                   v->vrows[0].p, v->vlw.p, v->vanc.p, v->W, v->view_step, v->n, 1);
         HIP_TRY(v, hipGetLastError());
     }
     v->cur = 0;
@@ -368,10 +378,10 @@ gpf_status view_exit(gpf_filter* v)
         const int64_t o = v->view_start;
         if (v->view_step == 0)
             GPF_LAUNCH(k_view_index_copy, dim3(grid_for(v, v->n * (v->W / 2), 8)), dim3(BLOCK), 0, v->stream, p->rows[p->cur], p->lw, p->anc,
-                       v->rows[v->cur], v->vlw, v->vanc, v->W, v->vidx, v->n, 0);
+                       v->rows[v->cur], v->vlw.p, v->vanc.p, v->W, v->vidx.p, v->n, 0);
         else
         GPF_LAUNCH(k_view_strided_copy, dim3(grid_for(v, v->n * (v->W / 2), 8)), dim3(BLOCK), 0, v->stream, p->rows[p->cur] + o * v->W, p->lw + o, p->anc + o,
-                   v->rows[v->cur], v->vlw, v->vanc, v->W, v->view_step, v->n, 0);
+                   v->rows[v->cur], v->vlw.p, v->vanc.p, v->W, v->view_step, v->n, 0);
         HIP_TRY(v, hipGetLastError());
         v->cur = 0;
     } else if (v->cur == 1) {
@@ -495,23 +505,9 @@ gpf_status gpf_create(const gpf_config* cfg, gpf_handle* out)
         }
         { gpf_status a_ = alloc_particle_buffers(h); if (a_) return a_; }
         const size_t n = (size_t)h->n, rb = n * (size_t)h->W * sizeof(double);
-        for (int b = 0; b < 2; ++b) {
-            HIP_TRY(h, hipMalloc(&h->mslots[b], (size_t)MAX_SLOTS * SLOT_WORDS * sizeof(unsigned long long)));
-            HIP_TRY(h, hipMemsetAsync(h->mslots[b], 0, (size_t)MAX_SLOTS * SLOT_WORDS * sizeof(unsigned long long), h->stream));
-        }
-        HIP_TRY(h, hipMalloc(&h->blockQ, (size_t)4 * 8 * h->n_cu * sizeof(uint64_t) + 64));   // (4 limbs per scan workgroup, <= 8 workgroups per CU)
-        // (zeroed: the ESS scan recognises this launch's partials by a tag in their top bits -- recycled memory may hold another filter's)
-        HIP_TRY(h, hipMemsetAsync(h->blockQ, 0, (size_t)4 * 8 * h->n_cu * sizeof(uint64_t) + 64, h->stream));
-        HIP_TRY(h, hipMalloc(&h->partial, MAX_PARTIALS * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&h->acc_part, MAX_PARTIALS * sizeof(unsigned long long)));
-        HIP_TRY(h, hipMalloc(&h->dscal, 4 * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&h->sc, sizeof(Scalars)));
-        HIP_TRY(h, hipHostMalloc(&h->h_sc, sizeof(Scalars)));
-        HIP_TRY(h, hipHostMalloc(&h->h_timeout, sizeof(int32_t)));
-        *h->h_timeout = 0;
+        { gpf_status a_ = alloc_fixed_buffers(h); if (a_) return a_; }
         { gpf_status su = resample_device_setup(h); if (su) return su; }
         { gpf_status su = shard_device_setup(h); if (su) return su; }
-        HIP_TRY(h, hipMemsetAsync(h->sc, 0, sizeof(Scalars), h->stream));
         HIP_TRY(h, hipMemsetAsync(h->lw, 0, n * sizeof(double), h->stream));
         HIP_TRY(h, hipMemsetAsync(h->rows[0], 0, rb, h->stream));
         GPF_LAUNCH(k_iota, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->anc, h->n);   // parents = 1:N
@@ -548,45 +544,18 @@ gpf_status gpf_destroy(gpf_handle h)
     h->pending_packed = false;                                   // the filter goes away: nothing to scatter a deferred commit into
     if (h->planner) { gpf_destroy(h->planner); h->planner = nullptr; }
     if (h->xb_planner) { gpf_destroy(h->xb_planner); h->xb_planner = nullptr; }
-    for (void* q : {(void*)h->blk_params_alt, (void*)h->blk_obs_alt}) if (q) (void)hipFree(q);
-    for (void* q : {(void*)h->sorted_src, (void*)h->sorted_gath, (void*)h->anc_cursors}) if (q) (void)hipFree(q);
     { const std::vector<gpf_filter*> own = h->blk_views; h->blk_views.clear(); for (gpf_filter* v : own) gpf_destroy(v); }
     // view handles the host still holds outlive this filter as orphans: every later call on them fails ("stale view"), their own gpf_destroy frees
     // what they own -- the aliased buffers and the stream (drained above) are never touched through them again
     for (gpf_filter* v : h->views) { v->orphaned = true; v->stream = nullptr; v->rows[0] = v->rows[1] = nullptr; v->lw = nullptr; v->anc = nullptr; }
     h->views.clear();
     gpf_comm_destroy(h);
-    hist_clear(h);
-    fwd_free(h);
-    if (h->hist_dev_maps) (void)hipFree(h->hist_dev_maps);
-    if (h->hist_dev_x) (void)hipFree(h->hist_dev_x);
-    if (h->hist_dev_lw) (void)hipFree(h->hist_dev_lw);
-    if (h->hist_dev_obs) (void)hipFree(h->hist_dev_obs);
     if (h->parent) { h->rows[0] = h->rows[1] = nullptr; h->lw = nullptr; h->anc = nullptr; }   // aliases of the parent's buffers (or of the compact copies below)
-    for (void* q : {(void*)h->vrows[0], (void*)h->vrows[1], (void*)h->vlw, (void*)h->vanc, (void*)h->vidx, (void*)h->vgid}) if (q) (void)hipFree(q);
     { Bufs b = take_particle_buffers(h); free_bufs(b); }
-    void* bufs[] = {h->mslots[0], h->mslots[1], h->blockQ, h->partial, h->dscal, h->sc, h->push_stage, h->shard_counts, h->shard_plan, h->tree_buf, h->acc_part,
-                    h->pull_req, h->pull_counts, h->pull_pc, h->pull_pc_all, h->blk_words, h->blk_mask, h->blk_stats, h->blk_obs, h->blk_params, h->blk_est, h->blk_ref, h->anc_in};
-    for (void* b : bufs) if (b) hipFree(b);
-    if (h->h_anc_in) hipHostFree(h->h_anc_in);
     if (h->anc_ev) (void)hipEventDestroy(h->anc_ev);
-    if (h->h_sc) hipHostFree(h->h_sc);
-    if (h->h_sc_ticket) hipHostFree(h->h_sc_ticket);
-    if (h->h_shard_counts) hipHostFree(h->h_shard_counts);
-    if (h->h_pull_pc_all) hipHostFree(h->h_pull_pc_all);
-    if (h->h_qpub) hipHostFree(h->h_qpub);
-    if (h->h_spart) hipHostFree(h->h_spart);
-    if (h->sp_g) { (void)hipFree(h->sp_g); (void)hipFree(h->sp_vlo); }
-    if (h->splan_F) { (void)hipFree(h->splan_F); (void)hipFree(h->splan_arrive); }
-    if (h->gate_part) { (void)hipFree(h->gate_part); hipHostFree(h->h_gate); }
-    if (h->sum_part) (void)hipFree(h->sum_part);
-    for (int k = 0; k < gpf_filter::BLK_STAGE; ++k) if (h->h_blk_obs[k]) hipHostFree(h->h_blk_obs[k]);
-    if (h->h_blk_done) hipHostFree(h->h_blk_done);
-    if (h->blk_stage_counter) (void)hipFree(h->blk_stage_counter);
-    if (h->h_flags) hipHostFree(h->h_flags);
-    if (h->h_sort_flag) hipHostFree(h->h_sort_flag);
-    if (h->h_timeout) hipHostFree(h->h_timeout);
     if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
+    // every other allocation is an owner on the handle (gpf_host.hpp Owned) and is freed here, behind the stream: the stream was drained and the device
+    // selected at the top, which is all the frees need
     delete h;
     return GPF_OK;
 }
@@ -881,7 +850,7 @@ static gpf_status rejuvenate_impl(gpf_handle h, int32_t method, int32_t n_iters,
     if (n_accepted) {
         if (method == GPF_REJUVENATE_REWEIGHT) *n_accepted = (uint64_t)h->n * (uint64_t)n_iters;     // every particle moves (rejuvenate.jl:81-86)
         else {
-            GPF_LAUNCH(k_sum_accepts, dim3(1), dim3(BLOCK), 0, h->stream, h->acc_part, grid, reinterpret_cast<unsigned long long*>(&h->sc->n_accept));
+            GPF_LAUNCH(k_sum_accepts, dim3(1), dim3(BLOCK), 0, h->stream, h->acc_part.p, grid, reinterpret_cast<unsigned long long*>(&h->sc->n_accept));
             HIP_TRY(h, hipGetLastError());
             if ((s = fetch_scalars(h))) return s;
             *n_accepted = h->h_sc->n_accept;
@@ -998,19 +967,18 @@ gpf_status gpf_debug_math(gpf_handle h, int32_t which, const double* a, const do
 {
     if (!h) return fail(nullptr, GPF_ERR_INVALID_ARGUMENT, "null handle");
     if (!a || !out || n < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, "bad arrays");
-    double *da = nullptr, *db = nullptr, *d1 = nullptr, *d2 = nullptr;
+    Dev<double> da, db, d1, d2;
     const size_t bytes = (size_t)n * sizeof(double);
-    HIP_TRY(h, hipMalloc(&da, bytes)); HIP_TRY(h, hipMalloc(&db, bytes));
-    HIP_TRY(h, hipMalloc(&d1, bytes)); HIP_TRY(h, hipMalloc(&d2, bytes));
+    gpf_status s;
+    if ((s = da.alloc(h, (size_t)n)) || (s = db.alloc(h, (size_t)n)) || (s = d1.alloc(h, (size_t)n)) || (s = d2.alloc(h, (size_t)n))) return s;
     HIP_TRY(h, hipMemcpyAsync(da, a, bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(db, b ? b : a, bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemsetAsync(d2, 0, bytes, h->stream));
-    GPF_LAUNCH(k_debug_math, dim3(grid_for(h, n, 8)), dim3(BLOCK), 0, h->stream, which, da, db, n, h->cfg.seed, h->epoch,
-                       (uint32_t)TAG_UPDATE, d1, d2);
+    GPF_LAUNCH(k_debug_math, dim3(grid_for(h, n, 8)), dim3(BLOCK), 0, h->stream, which, da.p, db.p, n, h->cfg.seed, h->epoch,
+                       (uint32_t)TAG_UPDATE, d1.p, d2.p);
     HIP_TRY(h, hipMemcpyAsync(out, d1, bytes, hipMemcpyDeviceToHost, h->stream));
     if (out2) HIP_TRY(h, hipMemcpyAsync(out2, d2, bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    hipFree(da); hipFree(db); hipFree(d1); hipFree(d2);
     return GPF_OK;
 }
 

@@ -11,31 +11,28 @@ namespace gpfh {
 
 void fwd_free(gpf_filter* h)
 {
-    for (void* q : {(void*)h->fwd_x, (void*)h->fwd_lw, (void*)h->fwd_T[0], (void*)h->fwd_T[1], (void*)h->fwd_map[0], (void*)h->fwd_map[1]}) if (q) (void)hipFree(q);
-    h->fwd_x = h->fwd_lw = h->fwd_T[0] = h->fwd_T[1] = nullptr; h->fwd_map[0] = h->fwd_map[1] = nullptr;
-    h->fwd_cap = 0; h->fwd_steps = 0; h->fwd_map_set = false;
+    h->fwd_x.reset(); h->fwd_lw.reset();
+    for (int k = 0; k < 2; ++k) { h->fwd_T[k].reset(); h->fwd_map[k].reset(); }
+    h->fwd_steps = 0; h->fwd_map_set = false;
 }
 // the records of a filter of n particles: the previous step's columns and log-weights, the two halves of the statistics, the two maps
 static gpf_status fwd_buffers(gpf_filter* h)
 {
-    if (h->fwd_cap == h->n) return GPF_OK;
-    if (h->fwd_cap) { HIP_TRY(h, hipStreamSynchronize(h->stream)); fwd_free(h); }
     const size_t n = (size_t)h->n, F = (size_t)fwd_F(h->d);
-    HIP_TRY(h, hipMalloc(&h->fwd_x, n * (size_t)h->d * sizeof(double)));
-    HIP_TRY(h, hipMalloc(&h->fwd_lw, n * sizeof(double)));
-    for (int k = 0; k < 2; ++k) {
-        HIP_TRY(h, hipMalloc(&h->fwd_T[k], n * F * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&h->fwd_map[k], n * sizeof(int32_t)));
-    }
-    h->fwd_cap = h->n;
-    return GPF_OK;
+    if (h->fwd_lw.count == n) return GPF_OK;
+    if (h->fwd_x) { HIP_TRY(h, hipStreamSynchronize(h->stream)); fwd_free(h); }   // (another particle count, or an allocation that failed half-way)
+    gpf_status s;
+    if ((s = h->fwd_x.alloc(h, n * (size_t)h->d))) return s;
+    for (int k = 0; k < 2; ++k)
+        if ((s = h->fwd_T[k].alloc(h, n * F)) || (s = h->fwd_map[k].alloc(h, n))) return s;
+    return h->fwd_lw.alloc(h, n);                                 // (last: its count says the records are complete)
 }
 template <int M>
 static void launch_block_forward_model(gpf_filter* h, const ForwardArgs& a, const AncArgs& x)
 {
     const int64_t waves = a.nblocks * a.wpb;
     GPF_LAUNCH((k_block_forward<M>), dim3((unsigned)((waves + NWAVES - 1) / NWAVES)), dim3(BLOCK), 0, h->stream, a, x,
-               (const double*)h->fwd_x, (const double*)h->fwd_lw, (const double*)h->fwd_T[h->fwd_cur], h->fwd_T[1 - h->fwd_cur]);
+               (const double*)h->fwd_x.p, (const double*)h->fwd_lw.p, (const double*)h->fwd_T[h->fwd_cur].p, h->fwd_T[1 - h->fwd_cur].p);
 }
 // the statistics of the CURRENT step from the record of the previous one, as a close forms them (the filter is materialised: the callers see to it)
 gpf_status fwd_form(gpf_filter* h)
@@ -66,8 +63,8 @@ gpf_status fwd_begin_step(gpf_filter* h, bool first)
     // ---- the close of the step that ends: its statistics, then its columns and log-weights, in its final order
     gpf_status s = fwd_form(h);
     if (s) return s;
-    GPF_LAUNCH(k_hist_snapshot, dim3(grid_for(h, h->n * h->d, 8)), dim3(BLOCK), 0, h->stream, h->rows[h->cur], h->W, h->d, h->n, h->fwd_x);
-    GPF_LAUNCH(k_hist_record, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, (const double*)h->lw, h->n, (const double*)nullptr, (int64_t)0, h->fwd_lw, (double*)nullptr);
+    GPF_LAUNCH(k_hist_snapshot, dim3(grid_for(h, h->n * h->d, 8)), dim3(BLOCK), 0, h->stream, h->rows[h->cur], h->W, h->d, h->n, h->fwd_x.p);
+    GPF_LAUNCH(k_hist_record, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, (const double*)h->lw, h->n, (const double*)nullptr, (int64_t)0, h->fwd_lw.p, (double*)nullptr);
     HIP_TRY(h, hipGetLastError());
     h->fwd_cur ^= 1; h->fwd_steps += 1; h->fwd_map_set = false;
     return GPF_OK;
@@ -78,7 +75,7 @@ gpf_status fwd_on_resample(gpf_filter* h, int64_t block_size)
     if (h->fwd_steps < 1) return GPF_OK;
     const int32_t* old = h->fwd_map_set ? h->fwd_map[h->fwd_map_cur] : nullptr;
     int32_t* neu = h->fwd_map[1 - h->fwd_map_cur];
-    if (block_size > 0) GPF_LAUNCH(k_hist_compose_blocks, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, (const int32_t*)h->anc, (const int32_t*)h->blk_mask, block_size, old, h->n, neu);
+    if (block_size > 0) GPF_LAUNCH(k_hist_compose_blocks, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, (const int32_t*)h->anc, (const int32_t*)h->blk_mask.p, block_size, old, h->n, neu);
     else GPF_LAUNCH(k_hist_compose, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, (const int32_t*)h->anc, old, h->n, neu);
     HIP_TRY(h, hipGetLastError());
     h->fwd_map_cur ^= 1; h->fwd_map_set = true;

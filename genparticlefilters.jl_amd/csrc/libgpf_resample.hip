@@ -23,8 +23,8 @@ gpf_status scan_launch(gpf_filter* h, int ch, const In& in, int np, WSum* slot, 
     if (ch == 0 && rq.cdf) h->ch0_offsets = offsets && so.off16 != nullptr;
     const ChainScope chain(h);                                   // (several filters on this device: their chained kernels take turns, gpf_host.hpp)
     gpf_status s = timed(h, GPF_K_SCAN, [&] {
-        GPF_LAUNCH((k_scan<In, FIXQ>), dim3(g_launch), dim3(SCAN_BLOCK), 0, h->stream, in, h->n, h->ntiles, mf_all, h->mslots[h->mcur], np, slot,
-                           so, dc, dn, total_out, h->blockQ, h->h_timeout, ex);
+        GPF_LAUNCH((k_scan<In, FIXQ>), dim3(g_launch), dim3(SCAN_BLOCK), 0, h->stream, in, h->n, h->ntiles, mf_all, h->mslots[h->mcur].p, np, slot,
+                           so, dc, dn, total_out, h->blockQ.p, h->h_timeout.p, ex);
     });
     if (s) return s;
     h->table[ch] = dc + h->ntiles;
@@ -187,7 +187,7 @@ gpf_status ensure_raw_summary(gpf_filter* h, bool want_q, bool* done)
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(h->ntiles, (int64_t)h->n_cu * 4));
     if ((h->ntiles + grid - 1) / grid > Q_TAG_MAX_TILES) return GPF_OK;
     if (!h->sum_part) {
-        HIP_TRY(h, hipMalloc(&h->sum_part, (size_t)6 * 4 * h->n_cu * sizeof(uint64_t)));
+        if (gpf_status a_ = h->sum_part.alloc(h, (size_t)6 * 4 * h->n_cu)) return a_;
         HIP_TRY(h, hipMemsetAsync(h->sum_part, 0, (size_t)6 * 4 * h->n_cu * sizeof(uint64_t), h->stream));
     }
     if ((s = pinned_words(h, h->h_qpub, 8))) return s;
@@ -195,8 +195,8 @@ gpf_status ensure_raw_summary(gpf_filter* h, bool want_q, bool* done)
     h->q_ticket += 1;
     InFixQ in{raw_view(h), nullptr, nullptr, h->K, 0.0, 0};
     s = timed(h, GPF_K_SCAN, [&] {
-        GPF_LAUNCH(k_sum_reduce<false>, dim3(grid), dim3(SCAN_BLOCK), 0, h->stream, in, h->n, h->ntiles, h->mslots[h->mcur], &h->sc->raw, h->sum_part, h->h_qpub,
-                   h->q_ticket, h->h_timeout, ShardSum{});
+        GPF_LAUNCH(k_sum_reduce<false>, dim3(grid), dim3(SCAN_BLOCK), 0, h->stream, in, h->n, h->ntiles, h->mslots[h->mcur].p, &h->sc->raw, h->sum_part.p, h->h_qpub.p,
+                   h->q_ticket, h->h_timeout.p, ShardSum{});
     });
     if (s) return s;
     HIP_TRY(h, hipGetLastError());
@@ -222,9 +222,10 @@ bool sum_host_ok(const gpf_filter* h)
 gpf_status ensure_gate_buffers(gpf_filter* h)
 {
     if (h->gate_part) return GPF_OK;
-    HIP_TRY(h, hipMalloc(&h->gate_part, (size_t)(2 * GATE_WORDS + 8) * sizeof(uint64_t)));
+    gpf_status s;
+    if ((s = h->gate_part.alloc(h, (size_t)(2 * GATE_WORDS + 8)))) return s;
     HIP_TRY(h, hipMemsetAsync(h->gate_part, 0, (size_t)(2 * GATE_WORDS + 8) * sizeof(uint64_t), h->stream));
-    HIP_TRY(h, hipHostMalloc(&h->h_gate, sizeof(int64_t)));
+    if ((s = h->h_gate.alloc(h, 1))) return s;
     *h->h_gate = 0;
     h->gate_cur = 0;
     return GPF_OK;
@@ -234,7 +235,7 @@ gpf_status sum_host_launch(gpf_filter* h, const double* thr)
     gpf_status s;
     const int hgrid = (int)std::max<int64_t>(1, std::min<int64_t>((h->n + SH_TILE - 1) / SH_TILE, (int64_t)h->n_cu));
     if (!h->h_spart) {
-        HIP_TRY(h, hipHostMalloc(&h->h_spart, (size_t)8 * h->n_cu * sizeof(int64_t)));
+        if ((s = h->h_spart.alloc(h, (size_t)8 * h->n_cu))) return s;
         memset(h->h_spart, 0, (size_t)8 * h->n_cu * sizeof(int64_t));
     }
     if (thr && (s = ensure_gate_buffers(h))) return s;
@@ -243,8 +244,8 @@ gpf_status sum_host_launch(gpf_filter* h, const double* thr)
     h->q_ticket += 1;
     InFixQ in{raw_view(h), nullptr, nullptr, h->K, 0.0, 0};
     s = timed(h, GPF_K_SCAN, [&] {
-        if (thr) GPF_LAUNCH(k_sum_host<true>, dim3(hgrid), dim3(SH_BLOCK), 0, h->stream, in, h->n, h->mslots[h->mcur], h->h_spart, h->q_ticket, SumGate{h->gate_part + h->gate_cur * GATE_WORDS, h->gate_part + (1 - h->gate_cur) * GATE_WORDS});
-        else     GPF_LAUNCH(k_sum_host<false>, dim3(hgrid), dim3(SH_BLOCK), 0, h->stream, in, h->n, h->mslots[h->mcur], h->h_spart, h->q_ticket, SumGate{nullptr, nullptr});
+        if (thr) GPF_LAUNCH(k_sum_host<true>, dim3(hgrid), dim3(SH_BLOCK), 0, h->stream, in, h->n, h->mslots[h->mcur].p, h->h_spart.p, h->q_ticket, SumGate{h->gate_part.p + h->gate_cur * GATE_WORDS, h->gate_part.p + (1 - h->gate_cur) * GATE_WORDS});
+        else     GPF_LAUNCH(k_sum_host<false>, dim3(hgrid), dim3(SH_BLOCK), 0, h->stream, in, h->n, h->mslots[h->mcur].p, h->h_spart.p, h->q_ticket, SumGate{nullptr, nullptr});
     });
     if (s) return s;
     HIP_TRY(h, hipGetLastError());
@@ -293,7 +294,7 @@ gpf_status sum_host_fold(gpf_filter* h, const double* thr, int* go_out)
 gpf_status sum_gate_check(gpf_filter* h, int host_go, int64_t ticket)
 {
     int64_t gv;
-    gpf_status s = poll_published(h, [&] { return ((gv = __atomic_load_n(h->h_gate, __ATOMIC_ACQUIRE)) >> 1) == ticket; }, nullptr,
+    gpf_status s = poll_published(h, [&] { return ((gv = __atomic_load_n(h->h_gate.p, __ATOMIC_ACQUIRE)) >> 1) == ticket; }, nullptr,
                                   "ESS gate: the stream drained without the verdict being published");
     if (s || (s = check_scan_timeout(h))) return s;
     if (host_go != (int)(gv & 1)) return fail(h, GPF_ERR_HIP, "ESS gate: the device's verdict differs from the host's (state may be inconsistent)");
@@ -316,7 +317,7 @@ gpf_status shard_sum_launch(gpf_filter* h, const ShardSum& ss, bool* ok)
         const int hgrid = (int)std::max<int64_t>(1, std::min<int64_t>((h->n + SH_TILE - 1) / SH_TILE, (int64_t)h->n_cu));
         InFixQ in0{raw_view(h), nullptr, nullptr, h->K, 0.0, 0};
         const ShardAcc sa{h->gate_part + h->gate_cur * GATE_WORDS, h->gate_part + (1 - h->gate_cur) * GATE_WORDS, reinterpret_cast<unsigned int*>(h->gate_part + 2 * GATE_WORDS)};
-        s0 = timed(h, GPF_K_SCAN, [&] { GPF_LAUNCH(k_sum_shard, dim3(hgrid), dim3(SH_BLOCK), 0, h->stream, in0, h->n, &h->sc->raw, h->h_qpub, h->q_ticket, sa, ss); });
+        s0 = timed(h, GPF_K_SCAN, [&] { GPF_LAUNCH(k_sum_shard, dim3(hgrid), dim3(SH_BLOCK), 0, h->stream, in0, h->n, &h->sc->raw, h->h_qpub.p, h->q_ticket, sa, ss); });
         if (s0) return s0;
         HIP_TRY(h, hipGetLastError());
         *ok = true;
@@ -325,7 +326,7 @@ gpf_status shard_sum_launch(gpf_filter* h, const ShardSum& ss, bool* ok)
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(h->ntiles, (int64_t)h->n_cu * 4));
     if ((h->ntiles + grid - 1) / grid > Q_TAG_MAX_TILES) return GPF_OK;
     if (!h->sum_part) {
-        HIP_TRY(h, hipMalloc(&h->sum_part, (size_t)6 * 4 * h->n_cu * sizeof(uint64_t)));
+        if (gpf_status a_ = h->sum_part.alloc(h, (size_t)6 * 4 * h->n_cu)) return a_;
         HIP_TRY(h, hipMemsetAsync(h->sum_part, 0, (size_t)6 * 4 * h->n_cu * sizeof(uint64_t), h->stream));
     }
     gpf_status s = pinned_words(h, h->h_qpub, 8);
@@ -333,8 +334,8 @@ gpf_status shard_sum_launch(gpf_filter* h, const ShardSum& ss, bool* ok)
     h->q_ticket += 1;
     InFixQ in{raw_view(h), nullptr, nullptr, h->K, 0.0, 0};
     s = timed(h, GPF_K_SCAN, [&] {
-        GPF_LAUNCH(k_sum_reduce<true>, dim3(grid), dim3(SCAN_BLOCK), 0, h->stream, in, h->n, h->ntiles, h->mslots[h->mcur], &h->sc->raw, h->sum_part, h->h_qpub,
-                   h->q_ticket, h->h_timeout, ss);
+        GPF_LAUNCH(k_sum_reduce<true>, dim3(grid), dim3(SCAN_BLOCK), 0, h->stream, in, h->n, h->ntiles, h->mslots[h->mcur].p, &h->sc->raw, h->sum_part.p, h->h_qpub.p,
+                   h->q_ticket, h->h_timeout.p, ss);
     });
     if (s) return s;
     HIP_TRY(h, hipGetLastError());
@@ -345,23 +346,23 @@ gpf_status shard_sum_launch(gpf_filter* h, const ShardSum& ss, bool* ok)
 // a scan whose bounded inter-workgroup wait gave up leaves garbage prefixes behind: fail loudly at the next host touch point
 gpf_status check_scan_timeout(gpf_filter* h)
 {
-    if (h->h_timeout && __atomic_load_n(h->h_timeout, __ATOMIC_ACQUIRE) == 2)
+    if (h->h_timeout && __atomic_load_n(h->h_timeout.p, __ATOMIC_ACQUIRE) == 2)
         return fail(h, GPF_ERR_HIP, "sharded resample: a peer's summary did not arrive in its mailbox in time (a rank is down or far behind); results are invalid");
-    if (h->h_timeout && __atomic_load_n(h->h_timeout, __ATOMIC_ACQUIRE) == 3)
+    if (h->h_timeout && __atomic_load_n(h->h_timeout.p, __ATOMIC_ACQUIRE) == 3)
         return fail(h, GPF_ERR_HIP, "sharded resample: a peer's rows did not arrive in the receive window in time (a rank is down or far behind); results are invalid");
-    if (h->h_timeout && __atomic_load_n(h->h_timeout, __ATOMIC_ACQUIRE) != 0)
+    if (h->h_timeout && __atomic_load_n(h->h_timeout.p, __ATOMIC_ACQUIRE) != 0)
         return fail(h, GPF_ERR_HIP, "scan kernel: bounded inter-workgroup wait timed out (workgroups not co-resident?); results are invalid");
     return GPF_OK;
 }
 
 gpf_status fetch_scalars(gpf_filter* h, bool fold_raw_q)
 {
-    if (!h->h_sc_ticket) { HIP_TRY(h, hipHostMalloc(&h->h_sc_ticket, sizeof(long long))); *h->h_sc_ticket = 0; }
+    if (!h->h_sc_ticket) { if (gpf_status a_ = h->h_sc_ticket.alloc(h, 1)) return a_; *h->h_sc_ticket = 0; }
     h->sc_ticket += 1;
-    GPF_LAUNCH(k_publish_scalars, dim3(1), dim3(WAVE), 0, h->stream, h->sc, h->h_sc, h->h_sc_ticket, h->sc_ticket,
-               fold_raw_q ? h->blockQ : nullptr, fold_raw_q ? wscan_grid(h) : 0);
+    GPF_LAUNCH(k_publish_scalars, dim3(1), dim3(WAVE), 0, h->stream, h->sc.p, h->h_sc.p, h->h_sc_ticket.p, h->sc_ticket,
+               fold_raw_q ? h->blockQ.p : nullptr, fold_raw_q ? wscan_grid(h) : 0);
     HIP_TRY(h, hipGetLastError());
-    { gpf_status w = wait_ticket(h, reinterpret_cast<volatile int64_t*>(h->h_sc_ticket), (int64_t)h->sc_ticket, "scalar block"); if (w) return w; }
+    { gpf_status w = wait_ticket(h, reinterpret_cast<volatile int64_t*>(h->h_sc_ticket.p), (int64_t)h->sc_ticket, "scalar block"); if (w) return w; }
     return check_scan_timeout(h);
 }
 
@@ -417,10 +418,10 @@ gpf_status sort_passes(gpf_filter* h, const PrioView& pv, int64_t n, bool coarse
         const int64_t kf_grid = std::max<int64_t>(1, std::min<int64_t>((n + 4 * KF_BLOCK - 1) / (4 * KF_BLOCK), h->n_cu));
         if (sort_buckets_wide(n)) {
             GPF_LAUNCH(k_sort_keys_fine<SORT_FINE_BITS_WIDE>, dim3((unsigned)kf_grid), dim3(KF_BLOCK), 0, h->stream, pv, n, h->keys, fine, reinterpret_cast<uint4*>(other), clear16, slots, m_ptr);
-            GPF_LAUNCH((k_sort_pass<2, SORT_BINS_WIDE, SORT_FINE_BITS_WIDE>), dim3((unsigned)nt), dim3(SORT_BLOCK), 0, h->stream, h->keys, nullptr, h->keys_out, h->idx_in, n, 0, hist, ticket, desc, h->h_timeout, m_ptr, fine, bbase);
+            GPF_LAUNCH((k_sort_pass<2, SORT_BINS_WIDE, SORT_FINE_BITS_WIDE>), dim3((unsigned)nt), dim3(SORT_BLOCK), 0, h->stream, h->keys, nullptr, h->keys_out, h->idx_in, n, 0, hist, ticket, desc, h->h_timeout.p, m_ptr, fine, bbase);
         } else {
             GPF_LAUNCH(k_sort_keys_fine<SORT_FINE_BITS>, dim3((unsigned)kf_grid), dim3(KF_BLOCK), 0, h->stream, pv, n, h->keys, fine, reinterpret_cast<uint4*>(other), clear16, slots, m_ptr);
-            GPF_LAUNCH(k_sort_pass<2>, dim3((unsigned)nt), dim3(SORT_BLOCK), 0, h->stream, h->keys, nullptr, h->keys_out, h->idx_in, n, 0, hist, ticket, desc, h->h_timeout, m_ptr, fine, bbase);
+            GPF_LAUNCH(k_sort_pass<2>, dim3((unsigned)nt), dim3(SORT_BLOCK), 0, h->stream, h->keys, nullptr, h->keys_out, h->idx_in, n, 0, hist, ticket, desc, h->h_timeout.p, m_ptr, fine, bbase);
         }
         HIP_TRY(h, hipGetLastError());
         return GPF_OK;
@@ -433,8 +434,8 @@ gpf_status sort_passes(gpf_filter* h, const PrioView& pv, int64_t n, bool coarse
         uint64_t* kout = (p & 1) ? h->keys : h->keys_out;
         const int32_t* vin = p == 0 ? nullptr : ((p & 1) ? h->idx_in : h->order);
         int32_t* vout = (p & 1) ? h->order : h->idx_in;
-        if (coarse) GPF_LAUNCH(k_sort_pass<1>, dim3((unsigned)nt), dim3(SORT_BLOCK), 0, h->stream, kin, vin, kout, vout, n, p, hist, ticket, desc, h->h_timeout, m_ptr, nullptr, nullptr);
-        else        GPF_LAUNCH(k_sort_pass<0>, dim3((unsigned)nt), dim3(SORT_BLOCK), 0, h->stream, kin, vin, kout, vout, n, p, hist, ticket, desc, h->h_timeout, m_ptr, nullptr, nullptr);
+        if (coarse) GPF_LAUNCH(k_sort_pass<1>, dim3((unsigned)nt), dim3(SORT_BLOCK), 0, h->stream, kin, vin, kout, vout, n, p, hist, ticket, desc, h->h_timeout.p, m_ptr, nullptr, nullptr);
+        else        GPF_LAUNCH(k_sort_pass<0>, dim3((unsigned)nt), dim3(SORT_BLOCK), 0, h->stream, kin, vin, kout, vout, n, p, hist, ticket, desc, h->h_timeout.p, m_ptr, nullptr, nullptr);
     }
     HIP_TRY(h, hipGetLastError());
     return GPF_OK;
@@ -466,12 +467,12 @@ gpf_status sort_desc_begin(gpf_filter* h, const PrioView& pv, int64_t n, bool* p
         // every bucket is ordered in place (the dead keys' bucket is left as the partition wrote it): the partition's output buffers
         // become the sorted keys / the permutation
         GPF_LAUNCH(k_sort_buckets, dim3(sort_buckets_wide(n) ? SORT_BINS_WIDE : SORT_BINS), dim3(BK_BLOCK), 0, h->stream, h->keys_out, h->idx_in, n, bbase,
-                   done, h->h_sort_flag, h->sort_ticket, m_ptr);
+                   done, h->h_sort_flag.p, h->sort_ticket, m_ptr);
         std::swap(h->keys, h->keys_out);
         std::swap(h->order, h->idx_in);
     } else {
         GPF_LAUNCH(k_sort_finish, dim3((unsigned)((n + FIN_TILE - 1) / FIN_TILE)), dim3(FIN_BLOCK), 0, h->stream, h->keys_out, h->idx_in, h->keys, h->order, n,
-                   done, h->h_sort_flag, h->sort_ticket, m_ptr);
+                   done, h->h_sort_flag.p, h->sort_ticket, m_ptr);
     }
     HIP_TRY(h, hipGetLastError());
     *pending = true;
@@ -539,8 +540,8 @@ gpf_status residual_scans(gpf_filter* h, const WSum* ws, int64_t n_slots_global,
     const int gs = scan_grid(h);
     const ChainScope chain(h);
     s = timed(h, GPF_K_SCAN, [&] {
-        if (direct) GPF_LAUNCH(k_scan_residual2<true>, dim3(gs), dim3(SCAN_BLOCK), 0, h->stream, h->cdf[0], ws, n_slots_global, h->n, h->ntiles, ch[0], ch[1], h->h_timeout, head_anc, &h->sc->giants, h->epoch & 0xffffffu, *direct);
-        else        GPF_LAUNCH(k_scan_residual2<false>, dim3(gs), dim3(SCAN_BLOCK), 0, h->stream, h->cdf[0], ws, n_slots_global, h->n, h->ntiles, ch[0], ch[1], h->h_timeout, head_anc, &h->sc->giants, h->epoch & 0xffffffu, ResidDirect{});
+        if (direct) GPF_LAUNCH(k_scan_residual2<true>, dim3(gs), dim3(SCAN_BLOCK), 0, h->stream, h->cdf[0], ws, n_slots_global, h->n, h->ntiles, ch[0], ch[1], h->h_timeout.p, head_anc, &h->sc->giants, h->epoch & 0xffffffu, *direct);
+        else        GPF_LAUNCH(k_scan_residual2<false>, dim3(gs), dim3(SCAN_BLOCK), 0, h->stream, h->cdf[0], ws, n_slots_global, h->n, h->ntiles, ch[0], ch[1], h->h_timeout.p, head_anc, &h->sc->giants, h->epoch & 0xffffffu, ResidDirect{});
     });
     if (s) return s;
     HIP_TRY(h, hipGetLastError());
@@ -579,12 +580,8 @@ void launch_search_strat(gpf_filter* h, const SearchArgs& sa, int64_t n_slots, b
 gpf_status sorted_job_prepare(gpf_filter* h, int64_t gid0, int64_t n_slots)
 {
     const int64_t ntl = (n_slots + SP_TILE - 1) / SP_TILE;
-    if (h->sp_cap < ntl + 1) {
-        if (h->sp_g) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->sp_g); (void)hipFree(h->sp_vlo); h->sp_g = h->sp_vlo = nullptr; h->sp_cap = 0; }
-        HIP_TRY(h, hipMalloc(&h->sp_g, (size_t)(ntl + 1) * sizeof(uint64_t)));
-        HIP_TRY(h, hipMalloc(&h->sp_vlo, (size_t)(ntl + 1) * sizeof(uint64_t)));
-        h->sp_cap = ntl + 1;
-    }
+    gpf_status s;
+    if ((s = h->sp_g.grow(h, (size_t)(ntl + 1))) || (s = h->sp_vlo.grow(h, (size_t)(ntl + 1)))) return s;
     h->sp_job = SortedGammaJob{h->cfg.seed, h->sp_g, gid0, n_slots, ntl, h->epoch, gamma_E(ntl), 0};
     return GPF_OK;
 }
@@ -593,7 +590,7 @@ gpf_status sorted_gammas_finish(gpf_filter* h, bool with_tiles, bool gammas_pend
 {
     const int64_t ntl = h->sp_job.ntl;
     if (gammas_pending) GPF_LAUNCH(k_sorted_gammas, dim3((unsigned)((ntl + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, h->stream, h->sp_job);
-    if (with_tiles) GPF_LAUNCH(k_sorted_tiles, dim3(1), dim3(STILES_BLOCK), 0, h->stream, h->sp_g, ntl, h->sp_vlo);
+    if (with_tiles) GPF_LAUNCH(k_sorted_tiles, dim3(1), dim3(STILES_BLOCK), 0, h->stream, h->sp_g.p, ntl, h->sp_vlo.p);
     HIP_TRY(h, hipGetLastError());
     return GPF_OK;
 }
@@ -765,7 +762,7 @@ gpf_status resample_impl(gpf_filter* h, int method, PrioView pv, int sort_partic
         } else {
             PrioView post{h->lws, nullptr, 0.0, 0};
             if ((s = summarize(h, post, &h->sc->post, sums_only))) return s;
-            GPF_LAUNCH(k_view_apply_post, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->sc, h->K, h->lws, h->lw, h->n);
+            GPF_LAUNCH(k_view_apply_post, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->sc.p, h->K, h->lws, h->lw, h->n);
         }
         weights_written(h, false);
         HIP_TRY(h, hipGetLastError());
@@ -784,7 +781,7 @@ gpf_status resample_impl(gpf_filter* h, int method, PrioView pv, int sort_partic
         h->cur ^= 1;
         PrioView post{h->lws, nullptr, 0.0, 0};
         if ((s = summarize(h, post, &h->sc->post, sums_only))) return s;
-        GPF_LAUNCH(k_apply_post, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->sc, h->K, h->logN, h->lws, h->lw, h->n);
+        GPF_LAUNCH(k_apply_post, dim3(grid_for(h, h->n, 8)), dim3(BLOCK), 0, h->stream, h->sc.p, h->K, h->logN, h->lws, h->lw, h->n);
     }
     weights_written(h, false);                                   // (deferred or done: the new weights' maximum is in no slot)
     HIP_TRY(h, hipGetLastError());
@@ -911,9 +908,8 @@ gpf_status gpf_sample_unweighted(gpf_handle h, int64_t n_samples, double* rows_o
     if ((s = ensure_raw(h))) return s;                            // CDF of state.log_weights in cdf[0]
     if ((s = fetch_scalars(h))) return s;
     if (h->h_sc->raw.flags & (FLAG_NAN | FLAG_POSINF)) return fail(h, GPF_ERR_INVALID_WEIGHTS, "Invalid weights (NaN).");
-    int32_t* anc = nullptr; double* rows = nullptr; int64_t* idx64 = nullptr;
-    HIP_TRY(h, hipMalloc(&anc, (size_t)n_samples * sizeof(int32_t)));
-    HIP_TRY(h, hipMalloc(&rows, (size_t)n_samples * h->W * sizeof(double)));
+    Dev<int32_t> anc; Dev<double> rows; Dev<int64_t> idx64;
+    if ((s = anc.alloc(h, (size_t)n_samples)) || (s = rows.alloc(h, (size_t)n_samples * h->W))) return s;
     SearchArgs sa{};
     sa.w = levels(h, 0); sa.c = levels(h, 0); sa.ntiles = h->ntiles; sa.order = nullptr; sa.sc = h->sc; sa.ws = &h->sc->raw;
     sa.raw = &h->sc->raw; sa.n = n_samples; sa.n_cells = h->n; sa.n_global = n_samples; sa.gid0 = h->cfg.gid0; sa.seed = h->cfg.seed;
@@ -922,12 +918,11 @@ gpf_status gpf_sample_unweighted(gpf_handle h, int64_t n_samples, double* rows_o
     launch_gather_rows_lw(h, anc, h->rows[h->cur], h->lw, rows, nullptr, n_samples);
     HIP_TRY(h, hipMemcpyAsync(rows_out, rows, (size_t)n_samples * h->W * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (idx_out) {
-        HIP_TRY(h, hipMalloc(&idx64, (size_t)n_samples * sizeof(int64_t)));
-        GPF_LAUNCH(k_parents, dim3(grid_for(h, n_samples, 8)), dim3(BLOCK), 0, h->stream, anc, n_samples, idx64);
+        if ((s = idx64.alloc(h, (size_t)n_samples))) return s;
+        GPF_LAUNCH(k_parents, dim3(grid_for(h, n_samples, 8)), dim3(BLOCK), 0, h->stream, anc.p, n_samples, idx64.p);
         HIP_TRY(h, hipMemcpyAsync(idx_out, idx64, (size_t)n_samples * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    (void)hipFree(anc); (void)hipFree(rows); if (idx64) (void)hipFree(idx64);
     h->epoch += 1;
     if (h->parent) h->parent->epoch = h->epoch;
     return GPF_OK;

@@ -50,12 +50,22 @@ static gpf_status shard_ready(gpf_handle h)
     return GPF_OK;
 }
 
+// k_sorted_plan: its boundary scratch and its arrival counter (zero between launches)
+static gpf_status sorted_plan_scratch(gpf_handle h)
+{
+    if (h->splan_arrive) return GPF_OK;
+    gpf_status s;
+    if ((!h->splan_F && (s = h->splan_F.alloc(h, MAX_SHARDS + 1))) || (s = h->splan_arrive.alloc(h, 1))) return s;
+    HIP_TRY(h, hipMemsetAsync(h->splan_arrive, 0, sizeof(unsigned int), h->stream));
+    return GPF_OK;
+}
 static gpf_status ensure_shard_counts(gpf_handle h)
 {
     if (h->shard_counts) return GPF_OK;
-    HIP_TRY(h, hipMalloc(&h->shard_counts, (size_t)2 * MAX_SHARDS * COUNT_STRIDE * sizeof(int64_t)));
+    gpf_status s;
+    if ((s = h->shard_counts.alloc(h, (size_t)2 * MAX_SHARDS * COUNT_STRIDE))) return s;
     HIP_TRY(h, hipMemsetAsync(h->shard_counts, 0, (size_t)2 * MAX_SHARDS * COUNT_STRIDE * sizeof(int64_t), h->stream));
-    HIP_TRY(h, hipHostMalloc(&h->h_shard_counts, (size_t)(2 * MAX_SHARDS + 1) * sizeof(int64_t)));
+    if ((s = h->h_shard_counts.alloc(h, (size_t)(2 * MAX_SHARDS + 1)))) return s;
     h->h_shard_counts[2 * MAX_SHARDS] = 0;
     return GPF_OK;
 }
@@ -82,7 +92,7 @@ static gpf_status shard_weight_max(gpf_handle h, const ShardCall& c, double* out
     if (!out2) return fail(h, GPF_ERR_INVALID_ARGUMENT, "null out");
     gpf_status s = shard_max_slots(h, c);
     if (s) return s;
-    GPF_LAUNCH(k_pack_mflags, dim3(1), dim3(BLOCK), 0, h->stream, h->mslots[h->mcur], out2, mb_begin(h, c.engine, MB_MF));
+    GPF_LAUNCH(k_pack_mflags, dim3(1), dim3(BLOCK), 0, h->stream, h->mslots[h->mcur].p, out2, mb_begin(h, c.engine, MB_MF));
     HIP_TRY(h, hipGetLastError());
     return GPF_OK;
 }
@@ -119,7 +129,7 @@ static gpf_status shard_weight_scan(gpf_handle h, ShardCall& c, const double* mf
     if (c.plan_in_scan && !splan_off && !want_q && h->mb_active && c.engine && (int)G == h->comm_world) {
         // a stratified resample: the plan needs nothing but the G shard totals of THIS round, and the scan's workgroup that ends up with this shard's total
         // pushes the last one of them -- it derives the plan right there (no k_strat_plan launch, no gap in front of the merge kernel)
-        if (!h->shard_plan) HIP_TRY(h, hipMalloc(&h->shard_plan, sizeof(ShardPlan)));
+        if (!h->shard_plan && (s = h->shard_plan.alloc(h, 1))) return s;
         h->push_ticket += 1;
         int64_t* const host_counts = ((c.own && G == 1) || c.ring) ? nullptr : h->h_shard_counts;   // (as the push count)
         ex.splan = StratPlanJob{h->shard_plan, h->cfg.seed, h->epoch, (int)G, h->comm_rank, h->cfg.n_global, static_cast<const int64_t*>(mb_gathered(h, MB_TOT)), mb_wait(h, c.engine, MB_TOT),
@@ -129,7 +139,7 @@ static gpf_status shard_weight_scan(gpf_handle h, ShardCall& c, const double* mf
     }
     if (want_q) {
         if ((s = scan_launch_shard(h, 4, in, (int)G, slot, rq, reinterpret_cast<uint64_t*>(out5), mf_all, ex))) return s;
-        GPF_LAUNCH(k_export_q, dim3(1), dim3(BLOCK), 0, h->stream, h->blockQ, gs, out5, tot_push);
+        GPF_LAUNCH(k_export_q, dim3(1), dim3(BLOCK), 0, h->stream, h->blockQ.p, gs, out5, tot_push);
     } else {
         ex.push = tot_push;
         if ((s = scan_launch_shard(h, 3, in, (int)G, slot, rq, reinterpret_cast<uint64_t*>(out5), mf_all, ex))) return s;
@@ -157,7 +167,7 @@ static gpf_status shard_residual_scan(gpf_handle h, const ShardCall& c, const in
     GPF_LAUNCH(k_set_global, dim3(1), dim3(64), 0, h->stream, tot_all, (int)G, &h->sc->prio, mb_wait(h, c.engine, MB_TOT));
     gpf_status s = residual_scans(h, &h->sc->prio, h->cfg.n_global);
     if (s) return s;
-    GPF_LAUNCH(k_export_residual, dim3(1), dim3(64), 0, h->stream, h->sc, out2, mb_begin(h, c.engine, MB_CR), nullptr, 0);
+    GPF_LAUNCH(k_export_residual, dim3(1), dim3(64), 0, h->stream, h->sc.p, out2, mb_begin(h, c.engine, MB_CR), nullptr, 0);
     HIP_TRY(h, hipGetLastError());
     h->residual_scanned = true;
     return GPF_OK;
@@ -173,7 +183,7 @@ static gpf_status shard_residual_scan_direct(gpf_handle h, const ShardCall& c, c
     if ((s = materialize(h))) return s;
     const ResidDirect rd{h->lw, 0.0, 0, h->K, S_global, &h->sc->prio, mf_all, G, (int32_t)(h->mb_active && c.engine)};
     if ((s = residual_scans(h, &h->sc->prio, h->cfg.n_global, nullptr, &rd))) return s;
-    GPF_LAUNCH(k_export_residual, dim3(1), dim3(64), 0, h->stream, h->sc, out2, mb_begin(h, c.engine, MB_CR), h->shard_counts, (int)(2 * MAX_SHARDS * COUNT_STRIDE));
+    GPF_LAUNCH(k_export_residual, dim3(1), dim3(64), 0, h->stream, h->sc.p, out2, mb_begin(h, c.engine, MB_CR), h->shard_counts.p, (int)(2 * MAX_SHARDS * COUNT_STRIDE));
     HIP_TRY(h, hipGetLastError());
     h->residual_scanned = true;
     h->summary.drop_sums();                                      // (as behind the weight scan this form replaces)
@@ -197,12 +207,7 @@ static gpf_status push_args(gpf_handle h, const ShardCall& c, int32_t method, co
         nch += (bounds[g + 1] - bounds[g] + PUSH_CHUNK - 1) / PUSH_CHUNK;
     }
     a.bounds[G] = bounds[G]; a.chunk0[G] = nch; a.nchunks = nch;
-    if (h->cfg.n_global > h->push_cap) {                       // staging list: one 16-byte entry per GLOBAL output slot at most
-        if (h->push_stage) (void)hipFree(h->push_stage);
-        h->push_stage = nullptr; h->push_cap = 0;
-        HIP_TRY(h, hipMalloc(&h->push_stage, (size_t)h->cfg.n_global * sizeof(ulonglong2)));
-        h->push_cap = h->cfg.n_global;
-    }
+    if (gpf_status s = h->push_stage.grow(h, (size_t)h->cfg.n_global)) return s;   // staging list: one 16-byte entry per GLOBAL output slot at most
     a.extra = c.extra; a.pv = c.extra_pv; a.skip_own = 0;
     a.wait_tot = mb_wait(h, c.engine, MB_TOT);
     a.wait_cr = method == GPF_RESAMPLE_RESIDUAL ? mb_wait(h, c.engine, MB_CR) : MboxWait{};
@@ -223,14 +228,10 @@ static gpf_status shard_push_count(gpf_handle h, ShardCall& c, int32_t method, c
     if (method == GPF_RESAMPLE_MULTINOMIAL_SORTED) {
         // sorted uniforms: ascending targets, so the plan is again ONE served slot range per shard (k_sorted_plan); every shard draws ALL tile
         // totals itself -- with its weight scan when the library engine prepared the job (ShardCall::gammas_pending, carried since), else now
-        if (!h->shard_plan) HIP_TRY(h, hipMalloc(&h->shard_plan, sizeof(ShardPlan)));
-        if (!h->splan_F) {
-            HIP_TRY(h, hipMalloc(&h->splan_F, (MAX_SHARDS + 1) * sizeof(int64_t)));
-            HIP_TRY(h, hipMalloc(&h->splan_arrive, sizeof(unsigned int)));
-            HIP_TRY(h, hipMemsetAsync(h->splan_arrive, 0, sizeof(unsigned int), h->stream));
-        }
+        if (!h->shard_plan && (s = h->shard_plan.alloc(h, 1))) return s;
+        if ((s = sorted_plan_scratch(h))) return s;
         const int64_t ntl = (h->cfg.n_global + SP_TILE - 1) / SP_TILE;
-        if (!(h->sp_cap >= ntl + 1 && h->sp_job.g == h->sp_g && h->sp_job.epoch == h->epoch && h->sp_job.n == h->cfg.n_global && h->sp_job.gid0 == 0 && h->sp_job.ntl == ntl)) {
+        if (!(h->sp_g.count >= (size_t)(ntl + 1) && h->sp_job.g == h->sp_g && h->sp_job.epoch == h->epoch && h->sp_job.n == h->cfg.n_global && h->sp_job.gid0 == 0 && h->sp_job.ntl == ntl)) {
             if ((s = sorted_job_prepare(h, 0, h->cfg.n_global))) return s;
             c.gammas_pending = true;
         }
@@ -239,7 +240,7 @@ static gpf_status shard_push_count(gpf_handle h, ShardCall& c, int32_t method, c
         a.ticket = h->push_ticket;
         if (no_host_counts) a.host_counts = nullptr;
         const SortedPlanJob job{h->sp_g, h->sp_vlo, ntl, ntl > SP_DIRECT_TILES ? 1 : 0, h->splan_F, h->splan_arrive};
-        s = timed(h, GPF_K_SEARCH, [&] { GPF_LAUNCH(k_sorted_plan, dim3((unsigned)(G > 1 ? G - 1 : 1)), dim3(MBLOCK), 0, h->stream, a, h->shard_plan, job); });
+        s = timed(h, GPF_K_SEARCH, [&] { GPF_LAUNCH(k_sorted_plan, dim3((unsigned)(G > 1 ? G - 1 : 1)), dim3(MBLOCK), 0, h->stream, a, h->shard_plan.p, job); });
         if (s) return s;
         HIP_TRY(h, hipGetLastError());
         h->counts_published = a.host_counts != nullptr;         // (else gpf_shard_counts copies them from the device)
@@ -256,11 +257,11 @@ static gpf_status shard_push_count(gpf_handle h, ShardCall& c, int32_t method, c
     if (method == GPF_RESAMPLE_STRATIFIED) {
         // contiguous strata x contiguous shard ranges: the plan (served slot range, exchange counts) is closed-form; the
         // counts go to the host right away
-        if (!h->shard_plan) HIP_TRY(h, hipMalloc(&h->shard_plan, sizeof(ShardPlan)));
+        if (!h->shard_plan && (s = h->shard_plan.alloc(h, 1))) return s;
         h->push_ticket += 1;
         a.ticket = h->push_ticket;
         if (no_host_counts) a.host_counts = nullptr;
-        s = timed(h, GPF_K_SEARCH, [&] { GPF_LAUNCH(k_strat_plan, dim3(1), dim3(128), 0, h->stream, a, h->shard_plan); });
+        s = timed(h, GPF_K_SEARCH, [&] { GPF_LAUNCH(k_strat_plan, dim3(1), dim3(128), 0, h->stream, a, h->shard_plan.p); });
         if (s) return s;
         HIP_TRY(h, hipGetLastError());
         h->counts_published = a.host_counts != nullptr;         // (else gpf_shard_counts copies them from the device)
@@ -642,9 +643,9 @@ gpf_status host_all_gather(gpf_filter* h, const void* src, void* dst_host, size_
 {
     const int G = h->comm_world;
     if (G == 1) { memcpy(dst_host, src, each); return GPF_OK; }
-    char *dsrc = nullptr, *ddst = nullptr;
-    struct Bufs { char*& a; char*& b; ~Bufs() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); } } bufs{dsrc, ddst};
-    HIP_TRY(h, hipMalloc(&dsrc, each)); HIP_TRY(h, hipMalloc(&ddst, each * G));
+    Dev<char> dsrc, ddst;
+    gpf_status s;
+    if ((s = dsrc.alloc(h, each)) || (s = ddst.alloc(h, each * G))) return s;
     HIP_TRY(h, hipMemcpyAsync(dsrc, src, each, hipMemcpyHostToDevice, h->stream));
     NCCL_TRY(h, g_rccl.AllGather(dsrc, ddst, each, ncclInt8, h->comm, h->stream));
     HIP_TRY(h, hipMemcpyAsync(dst_host, ddst, each * G, hipMemcpyDeviceToHost, h->stream));
@@ -706,11 +707,11 @@ gpf_status ring_setup(gpf_filter* h)
         for (int d = 1; d < G; ++d) {
             h->ring_seq += 1;
             if (pass) {
-                GPF_LAUNCH(k_ring_selftest, dim3(1), dim3(WAVE), 0, h->stream, h->ring_peers, h->ring, G, me, d, h->ring_parity_words, h->ring_seq, h->W, h->h_timeout, bad);
+                GPF_LAUNCH(k_ring_selftest, dim3(1), dim3(WAVE), 0, h->stream, h->ring_peers, h->ring, G, me, d, h->ring_parity_words, h->ring_seq, h->W, h->h_timeout.p, bad);
                 int32_t hb = 0;
                 if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&hb, bad, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
                     hipStreamSynchronize(h->stream) != hipSuccess || hb != 0) { (void)hipGetLastError(); pass = 0; }
-                if (__atomic_load_n(h->h_timeout, __ATOMIC_ACQUIRE) != 0) { __atomic_store_n(h->h_timeout, 0, __ATOMIC_RELEASE); pass = 0; }
+                if (__atomic_load_n(h->h_timeout.p, __ATOMIC_ACQUIRE) != 0) { __atomic_store_n(h->h_timeout.p, 0, __ATOMIC_RELEASE); pass = 0; }
             }
             if (selftest_mode() == 3 && me == 0) pass = 0;         // (tests: "this rank's test failed")
             if ((s = host_all_gather(h, &pass, oks.data(), sizeof(int64_t)))) { if (bad) (void)hipFree(bad); ring_teardown(h); return s; }
@@ -785,9 +786,9 @@ gpf_status mailbox_setup(gpf_filter* h)
     // for all G entries.  A rank whose wait gives up votes "no"; one "no" and every rank keeps the RCCL all-gathers.  GPF_SHARD_SELFTEST=0 skips it.
     if (G > 1 && selftest_mode() != 0) {
         int64_t pass = 1;
-        GPF_LAUNCH(k_mbox_rounds, dim3(1), dim3(WAVE), 0, h->stream, h->mb_peers, h->mbox, G, me, h->mb_seq[MB_CAL], 4, h->h_timeout);
+        GPF_LAUNCH(k_mbox_rounds, dim3(1), dim3(WAVE), 0, h->stream, h->mb_peers, h->mbox, G, me, h->mb_seq[MB_CAL], 4, h->h_timeout.p);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) { (void)hipGetLastError(); pass = 0; }
-        if (__atomic_load_n(h->h_timeout, __ATOMIC_ACQUIRE) != 0) { __atomic_store_n(h->h_timeout, 0, __ATOMIC_RELEASE); pass = 0; }
+        if (__atomic_load_n(h->h_timeout.p, __ATOMIC_ACQUIRE) != 0) { __atomic_store_n(h->h_timeout.p, 0, __ATOMIC_RELEASE); pass = 0; }
         if (selftest_mode() == 2 && me == 0) pass = 0;            // (tests: "this rank's test failed")
         h->mb_seq[MB_CAL] += 4;
         if ((s = gather(&pass, oks.data(), sizeof(int64_t)))) { mailbox_teardown(h); return s; }
@@ -846,13 +847,13 @@ gpf_status gpf_comm_calibrate(gpf_handle h, int64_t entries, int32_t reps, doubl
     struct Ev { hipEvent_t a, b; ~Ev() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } evs{e0, e1};
     if (G > 1 && h->comm) {
         const int64_t E = h->W + 1;
-        double *sb = nullptr, *rb = nullptr;
+        Dev<double> sb, rb;                                       // scratch of this call
         const size_t bytes = (size_t)entries * E * G * sizeof(double);
         // (allocation failures are local: decide together before the first collective)
-        int64_t ok = hipMalloc(&sb, bytes) == hipSuccess && hipMalloc(&rb, bytes) == hipSuccess ? 1 : 0;
+        int64_t ok = !sb.alloc(h, bytes / sizeof(double)) && !rb.alloc(h, bytes / sizeof(double)) ? 1 : 0;
         if (!ok) (void)hipGetLastError();
         std::vector<int64_t> oks((size_t)G, 0);
-        if ((s = host_all_gather(h, &ok, oks.data(), sizeof(int64_t)))) { if (sb) (void)hipFree(sb); if (rb) (void)hipFree(rb); return s; }
+        if ((s = host_all_gather(h, &ok, oks.data(), sizeof(int64_t)))) return s;
         bool all_ok = true;
         for (int r = 0; r < G; ++r) all_ok = all_ok && oks[r] != 0;
         if (all_ok) {
@@ -871,20 +872,18 @@ gpf_status gpf_comm_calibrate(gpf_handle h, int64_t entries, int32_t reps, doubl
             }
             HIP_TRY(h, hipEventRecord(e1, h->stream));
             HIP_TRY(h, hipStreamSynchronize(h->stream));
-            if (first != ncclSuccess) { (void)hipFree(sb); (void)hipFree(rb); return fail(h, GPF_ERR_HIP, std::string("calibration exchange: ") + g_rccl.GetErrorString(first)); }
+            if (first != ncclSuccess) return fail(h, GPF_ERR_HIP, std::string("calibration exchange: ") + g_rccl.GetErrorString(first));
             float ms = 0.f;
             HIP_TRY(h, hipEventElapsedTime(&ms, e0, e1));
             out4[0] = 1e3 * (double)ms / reps;
             out4[1] = out4[0] > 0.0 ? (double)(entries * E * (int64_t)sizeof(double)) / (out4[0] * 1e-6) / 1e9 : 0.0;
         }
-        if (sb) (void)hipFree(sb);
-        if (rb) (void)hipFree(rb);
     }
     if (h->mb_active && h->h_timeout) {
         for (int pass = 0; pass < 2; ++pass) {
             const int n = pass == 0 ? reps : 0;
             HIP_TRY(h, hipEventRecord(e0, h->stream));
-            GPF_LAUNCH(k_mbox_rounds, dim3(1), dim3(WAVE), 0, h->stream, h->mb_peers, h->mbox, G, me, h->mb_seq[MB_CAL], n, h->h_timeout);
+            GPF_LAUNCH(k_mbox_rounds, dim3(1), dim3(WAVE), 0, h->stream, h->mb_peers, h->mbox, G, me, h->mb_seq[MB_CAL], n, h->h_timeout.p);
             HIP_TRY(h, hipEventRecord(e1, h->stream));
             HIP_TRY(h, hipGetLastError());
             h->mb_seq[MB_CAL] += (uint64_t)n;
@@ -990,10 +989,10 @@ gpf_status gpf_comm_destroy(gpf_handle h)
     if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
     h->comm = nullptr; h->comm_world = 1; h->comm_rank = 0;
     void* bufs[] = {h->sh_mf, h->sh_mf_all != h->sh_mf ? h->sh_mf_all : nullptr, h->sh_tot, h->sh_tot_all != h->sh_tot ? h->sh_tot_all : nullptr,
-                    h->sh_cr, h->sh_cr_all != h->sh_cr ? h->sh_cr_all : nullptr, h->sh_send, h->sh_recv};
+                    h->sh_cr, h->sh_cr_all != h->sh_cr ? h->sh_cr_all : nullptr};   // (for one rank the gathered arrays ARE the local ones)
     for (void* b : bufs) if (b) (void)hipFree(b);
     h->sh_mf = h->sh_mf_all = nullptr; h->sh_tot = h->sh_tot_all = h->sh_cr = h->sh_cr_all = nullptr;
-    h->sh_send = h->sh_recv = nullptr; h->sh_send_cap = h->sh_recv_cap = 0;
+    h->sh_send.reset(); h->sh_recv.reset();                      // (the exchange buffers go with the communicator, not with the filter)
     return ms;
 }
 
@@ -1003,19 +1002,11 @@ gpf_status gpf_comm_destroy(gpf_handle h)
 // entries to serve per shard, counts[G..2G) = entries to receive.  Buffers are allocated by pull_buffers before any collective.
 static gpf_status pull_buffers(gpf_filter* h, int G)
 {
-    if (!h->pull_counts) {
-        HIP_TRY(h, hipMalloc(&h->pull_counts, (size_t)MAX_SHARDS * COUNT_STRIDE * sizeof(int64_t)));
-        HIP_TRY(h, hipMalloc(&h->pull_pc, (size_t)MAX_SHARDS * sizeof(int64_t)));
-        HIP_TRY(h, hipMalloc(&h->pull_pc_all, (size_t)MAX_SHARDS * MAX_SHARDS * sizeof(int64_t)));
-        HIP_TRY(h, hipHostMalloc(&h->h_pull_pc_all, (size_t)MAX_SHARDS * MAX_SHARDS * sizeof(int64_t)));
-    }
-    const int64_t want = (int64_t)G * std::max<int64_t>(h->n, 1);
-    if (h->pull_req_cap < want) {
-        if (h->pull_req) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->pull_req); h->pull_req = nullptr; h->pull_req_cap = 0; }
-        HIP_TRY(h, hipMalloc(&h->pull_req, (size_t)want * sizeof(ulonglong2)));
-        h->pull_req_cap = want;
-    }
-    return GPF_OK;
+    gpf_status s;
+    if ((!h->pull_counts && (s = h->pull_counts.alloc(h, (size_t)MAX_SHARDS * COUNT_STRIDE))) || (!h->pull_pc && (s = h->pull_pc.alloc(h, MAX_SHARDS))) ||
+        (!h->pull_pc_all && (s = h->pull_pc_all.alloc(h, (size_t)MAX_SHARDS * MAX_SHARDS))) ||
+        (!h->h_pull_pc_all && (s = h->h_pull_pc_all.alloc(h, (size_t)MAX_SHARDS * MAX_SHARDS)))) return s;
+    return h->pull_req.grow(h, (size_t)G * (size_t)std::max<int64_t>(h->n, 1));
 }
 static gpf_status pull_requests(gpf_filter* h, const ShardCall& c, int32_t method, const int64_t* tot_all, const int64_t* cr_all, int G, int me, const int64_t* bounds,
                                 bool exchange, bool force_self, std::vector<int64_t>& counts)
@@ -1028,11 +1019,11 @@ static gpf_status pull_requests(gpf_filter* h, const ShardCall& c, int32_t metho
     const int64_t nch = (n + PUSH_CHUNK - 1) / PUSH_CHUNK;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(nch, (int64_t)h->n_cu * PUSH_SCAN_BLOCKS_PER_CU));
     s = timed(h, GPF_K_SEARCH, [&] {
-        if (method == GPF_RESAMPLE_MULTINOMIAL) GPF_LAUNCH((k_pull_scan<0>), dim3(grid), dim3(PUSH_SCAN_BLOCK), 0, h->stream, a, h->pull_req, n, h->pull_counts);
-        else                                    GPF_LAUNCH((k_pull_scan<1>), dim3(grid), dim3(PUSH_SCAN_BLOCK), 0, h->stream, a, h->pull_req, n, h->pull_counts);
+        if (method == GPF_RESAMPLE_MULTINOMIAL) GPF_LAUNCH((k_pull_scan<0>), dim3(grid), dim3(PUSH_SCAN_BLOCK), 0, h->stream, a, h->pull_req.p, n, h->pull_counts.p);
+        else                                    GPF_LAUNCH((k_pull_scan<1>), dim3(grid), dim3(PUSH_SCAN_BLOCK), 0, h->stream, a, h->pull_req.p, n, h->pull_counts.p);
     });
     if (s) return s;
-    GPF_LAUNCH(k_pull_counts, dim3(1), dim3(WAVE), 0, h->stream, h->pull_counts, G, h->pull_pc);
+    GPF_LAUNCH(k_pull_counts, dim3(1), dim3(WAVE), 0, h->stream, h->pull_counts.p, G, h->pull_pc.p);
     HIP_TRY(h, hipGetLastError());
     if ((s = shard_all_gather(h, h->pull_pc, h->pull_pc_all, (size_t)G, ncclInt64, sizeof(int64_t)))) return s;
     HIP_TRY(h, hipMemcpyAsync(h->h_pull_pc_all, h->pull_pc_all, (size_t)G * G * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
@@ -1064,7 +1055,7 @@ static gpf_status pull_requests(gpf_filter* h, const ShardCall& c, int32_t metho
         const hipError_t ce = hipMemcpyAsync(h->push_stage + bounds[me], h->pull_req + (size_t)me * n, (size_t)counts[me] * sizeof(ulonglong2), hipMemcpyDeviceToDevice, h->stream);
         if (ce != hipSuccess) remember(fail(h, GPF_ERR_HIP, std::string("self copy: ") + hipGetErrorString(ce)));
     }
-    GPF_LAUNCH(k_pull_set_counts, dim3(1), dim3(WAVE), 0, h->stream, h->pull_pc_all, G, me, h->shard_counts);
+    GPF_LAUNCH(k_pull_set_counts, dim3(1), dim3(WAVE), 0, h->stream, h->pull_pc_all.p, G, me, h->shard_counts.p);
     if (hipGetLastError() != hipSuccess) remember(fail(h, GPF_ERR_HIP, "k_pull_set_counts launch"));
     if (late) { h->err = late_msg; return late; }
     h->counts_published = false;
@@ -1098,15 +1089,13 @@ static gpf_status shard_sorted_buffers(gpf_filter* h, int G)
         }
     }
     if ((s = ensure_shard_counts(h))) return s;
-    if (!h->anc_cursors) HIP_TRY(h, hipMalloc(&h->anc_cursors, MAX_SHARDS * sizeof(unsigned long long)));
+    if (!h->anc_cursors && (s = h->anc_cursors.alloc(h, MAX_SHARDS))) return s;
     const int64_t N = h->cfg.n_global, per = N / G + (N % G ? 1 : 0);
-    if (N % G && h->sorted_per != per) {
-        for (void* q : {(void*)h->sorted_src, (void*)h->sorted_gath}) if (q) (void)hipFree(q);
-        h->sorted_src = h->sorted_gath = nullptr; h->sorted_per = 0;
-        HIP_TRY(h, hipMalloc(&h->sorted_src, (size_t)per * sizeof(double)));
+    if (N % G && h->sorted_gath.count != (size_t)per * G) {       // (unequal shards: the all-gather's staging, `per` values per rank)
+        h->sorted_src.reset(); h->sorted_gath.reset();
+        if ((s = h->sorted_src.alloc(h, (size_t)per))) return s;
         HIP_TRY(h, hipMemsetAsync(h->sorted_src, 0, (size_t)per * sizeof(double), h->stream));
-        HIP_TRY(h, hipMalloc(&h->sorted_gath, (size_t)per * G * sizeof(double)));
-        h->sorted_per = per;
+        if ((s = h->sorted_gath.alloc(h, (size_t)per * G))) return s;
     }
     return GPF_OK;
 }
@@ -1118,8 +1107,8 @@ static gpf_status shard_sorted_gather(gpf_filter* h, int G, int me)
     const int64_t N = h->cfg.n_global;
     if (N % G == 0) return shard_all_gather(h, h->lw, p->lw, (size_t)h->n, ncclDouble, sizeof(double));
     HIP_TRY(h, hipMemcpyAsync(h->sorted_src, h->lw, (size_t)h->n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    if ((s = shard_all_gather(h, h->sorted_src, h->sorted_gath, (size_t)h->sorted_per, ncclDouble, sizeof(double)))) return s;
-    GPF_LAUNCH(k_anc_compact, dim3(grid_for(h, N, 8)), dim3(BLOCK), 0, h->stream, anc_plan(h, G, me), h->sorted_gath, h->sorted_per, p->lw);
+    if ((s = shard_all_gather(h, h->sorted_src, h->sorted_gath, h->sorted_src.count, ncclDouble, sizeof(double)))) return s;
+    GPF_LAUNCH(k_anc_compact, dim3(grid_for(h, N, 8)), dim3(BLOCK), 0, h->stream, anc_plan(h, G, me), h->sorted_gath.p, (int64_t)h->sorted_src.count, p->lw);
     HIP_TRY(h, hipGetLastError());
     return GPF_OK;
 }
@@ -1138,7 +1127,7 @@ static gpf_status shard_sorted_plan(gpf_filter* h, const ShardCall& c, int G, in
     if (s) return fail(h, s, "planner: " + p->err);
     HIP_TRY(h, hipMemsetAsync(h->shard_counts, 0, (size_t)2 * MAX_SHARDS * COUNT_STRIDE * sizeof(int64_t), h->stream));
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((N + ANC_CHUNK - 1) / ANC_CHUNK, (int64_t)h->n_cu * 4));
-    s = timed(h, GPF_K_SEARCH, [&] { GPF_LAUNCH(k_anc_count, dim3(grid), dim3(ANC_BLOCK), 0, h->stream, anc_plan(h, G, me), c.own ? 1 : 0, h->anc, h->shard_counts); });
+    s = timed(h, GPF_K_SEARCH, [&] { GPF_LAUNCH(k_anc_count, dim3(grid), dim3(ANC_BLOCK), 0, h->stream, anc_plan(h, G, me), c.own ? 1 : 0, h->anc, h->shard_counts.p); });
     if (s) return s;
     HIP_TRY(h, hipGetLastError());
     h->counts_published = false;                                  // (gpf_shard_counts copies them from the device)
@@ -1154,7 +1143,7 @@ static gpf_status shard_sorted_push(gpf_filter* h, const ShardCall& c, int G, in
     const AncPlan ap = anc_plan(h, G, me);
     const double* rows = h->rows[h->cur];
     gpf_status s = timed(h, GPF_K_GATHER, [&] {
-        DISPATCH_W(h, GPF_LAUNCH((k_anc_pack<WW>), dim3(grid), dim3(ANC_BLOCK), 0, h->stream, ap, c.own ? 1 : 0, rows, h->shard_counts, h->anc_cursors, capacity, packed_out));
+        DISPATCH_W(h, GPF_LAUNCH((k_anc_pack<WW>), dim3(grid), dim3(ANC_BLOCK), 0, h->stream, ap, c.own ? 1 : 0, rows, h->shard_counts.p, h->anc_cursors.p, capacity, packed_out));
     });
     if (s) return s;
     HIP_TRY(h, hipGetLastError());
@@ -1205,23 +1194,19 @@ static gpf_status shard_resample_impl(gpf_handle h, int32_t method, double prior
     // rank that returned early would leave its peers blocked in a collective it never joins.  The send buffer holds a balanced
     // exchange with slack -- or, when that is cheap against the HBM at hand (<= 1/16 of the free memory), one entry per GLOBAL slot,
     // the most any shard can ever serve, so that the overflow re-push below never has to allocate.
-    auto ensure = [&](double*& buf, int64_t& cap, int64_t want) -> gpf_status {
-        if (cap >= want) return GPF_OK;
-        if (buf) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(buf); buf = nullptr; cap = 0; }
-        HIP_TRY(h, hipMalloc(&buf, (size_t)want * (h->W + 2) * sizeof(double)));   // (room for the widest entry: a prioritised resample's [row | meta | log_ws])
-        cap = want;
-        return GPF_OK;
-    };
+    const size_t entry = (size_t)h->W + 2;                        // (doubles of the widest entry: a prioritised resample's [row | meta | log_ws])
+    auto entries = [&](const Dev<double>& buf) { return (int64_t)(buf.count / entry); };
+    auto ensure = [&](Dev<double>& buf, int64_t want) { return buf.grow(h, (size_t)want * entry); };
     int64_t cap = std::min<int64_t>(h->cfg.n_global, 2 * n + 65536);
-    if (h->sh_send_cap < h->cfg.n_global) {
+    if (entries(h->sh_send) < h->cfg.n_global) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (size_t)h->cfg.n_global * (h->W + 2) * sizeof(double) <= free_b / 16) cap = h->cfg.n_global;
     } else cap = h->cfg.n_global;
     if (const char* e = getenv("GPF_PUSH_CAPACITY")) cap = atoll(e);                                  // tests: force the overflow path
-    if ((s = ensure(h->sh_send, h->sh_send_cap, std::max<int64_t>(cap, 1)))) return s;
+    if ((s = ensure(h->sh_send, std::max<int64_t>(cap, 1)))) return s;
     static const bool force = getenv("GPF_SHARD_FORCE_COLLECTIVES") && !strcmp(getenv("GPF_SHARD_FORCE_COLLECTIVES"), "1");
     const bool exchange = G > 1 || (force && h->comm);            // one shard: what it "sends" is what it "receives"
-    if (exchange && (s = ensure(h->sh_recv, h->sh_recv_cap, n))) return s;
+    if (exchange && (s = ensure(h->sh_recv, n))) return s;
     const bool pull = h->shard_plan_kind == GPF_SHARD_PLAN_PULL && !ranged && !sorted;
     if (pull && (s = pull_buffers(h, G))) return s;
     if (sorted && ((s = materialize(h)) || (s = shard_sorted_buffers(h, G)))) return s;
@@ -1249,12 +1234,8 @@ static gpf_status shard_resample_impl(gpf_handle h, int32_t method, double prior
         if ((s = materialize(h))) return s;
         if ((s = sorted_job_prepare(h, 0, h->cfg.n_global))) return s;
         c.gammas_pending = true;
-        if (!h->shard_plan) HIP_TRY(h, hipMalloc(&h->shard_plan, sizeof(ShardPlan)));
-        if (!h->splan_F) {
-            HIP_TRY(h, hipMalloc(&h->splan_F, (MAX_SHARDS + 1) * sizeof(int64_t)));
-            HIP_TRY(h, hipMalloc(&h->splan_arrive, sizeof(unsigned int)));
-            HIP_TRY(h, hipMemsetAsync(h->splan_arrive, 0, sizeof(unsigned int), h->stream));
-        }
+        if (!h->shard_plan && (s = h->shard_plan.alloc(h, 1))) return s;
+        if ((s = sorted_plan_scratch(h))) return s;
     }
 
     const double* raw_mf = nullptr; const int64_t* raw_tot = nullptr;
@@ -1308,14 +1289,14 @@ static gpf_status shard_resample_impl(gpf_handle h, int32_t method, double prior
         return shard_commit_ring(h, c, h->cur_mf_all, tot_all, G);   // deferred: the next propagate reads window and own hits in ONE launch
     }
     std::vector<int64_t> counts(2 * (size_t)G);
-    int64_t pushed_cap = std::min(cap, h->sh_send_cap);
+    int64_t pushed_cap = std::min(cap, entries(h->sh_send));
     int64_t n_send = 0, n_recv = 0;
     if (pull) {
         // phase 3 of the pull plan: requests out, counts known on the host BEFORE pass 2 is enqueued (no speculative capacity)
         if ((s = pull_requests(h, c, method, tot_all, cr_all, G, me, bounds.data(), exchange, force && G == 1, counts))) return s;
         phase_mark(h, GPF_PHASE_PLAN);
         for (int g = 0; g < G; ++g) { n_send += counts[g]; n_recv += counts[G + g]; }
-        pushed_cap = std::min(n_send, h->sh_send_cap);
+        pushed_cap = std::min(n_send, entries(h->sh_send));
         if ((s = push(pushed_cap, h->sh_send))) return s;
         phase_mark(h, GPF_PHASE_PACK);
     } else {
@@ -1349,8 +1330,8 @@ static gpf_status shard_resample_impl(gpf_handle h, int32_t method, double prior
     std::string late_msg;
     auto remember = [&](gpf_status st) { if (st && !late) { late = st; late_msg = h->err; } };
     if (n_recv != n) remember(fail(h, GPF_ERR_STATE, "exchange counts do not add up to the shard's slots"));
-    if (n_send > h->sh_send_cap) {                                // skewed weights: this shard serves more than its buffer held
-        gpf_status es = ensure(h->sh_send, h->sh_send_cap, n_send);
+    if (n_send > entries(h->sh_send)) {                                // skewed weights: this shard serves more than its buffer held
+        gpf_status es = ensure(h->sh_send, n_send);
         if (es) {                                                 // cannot hold what the peers expect: nothing sane can be sent
             if (exchange) remember(fail(h, GPF_ERR_HIP, "send buffer for a skewed exchange could not be allocated; the communicator is poisoned (peers are waiting)"));
             return es;
@@ -1366,7 +1347,7 @@ static gpf_status shard_resample_impl(gpf_handle h, int32_t method, double prior
         ncclResult_t first = ncclSuccess;
         const char* where = "";
         auto note = [&](ncclResult_t r, const char* w) { if (r != ncclSuccess && first == ncclSuccess) { first = r; where = w; } };
-        const bool recv_fits = n_recv <= h->sh_recv_cap;
+        const bool recv_fits = n_recv <= entries(h->sh_recv);
         int64_t so = 0, ro = 0, self_so = -1, self_ro = -1;
         note(g_rccl.GroupStart(), "ncclGroupStart");
         for (int g = 0; g < G; ++g) {
@@ -1394,7 +1375,7 @@ static gpf_status shard_resample_impl(gpf_handle h, int32_t method, double prior
         const int grid = grid_for(h, n, 8);
         double* out = h->rows[1 - h->cur];
         const int mbx = (int)h->mb_active;
-        DISPATCH_W(h, GPF_LAUNCH((k_commit_packed_ws<WW>), dim3(grid), dim3(BLOCK), 0, h->stream, commit_from, n, out, h->anc, h->lws, raw_mf, raw_tot, G, h->K, h->logN, h->sc, mbx));
+        DISPATCH_W(h, GPF_LAUNCH((k_commit_packed_ws<WW>), dim3(grid), dim3(BLOCK), 0, h->stream, commit_from, n, out, h->anc, h->lws, raw_mf, raw_tot, G, h->K, h->logN, h->sc.p, mbx));
         HIP_TRY(h, hipGetLastError());
         h->cur ^= 1;
     }

@@ -1,6 +1,7 @@
 """which code path does not give its device memory back (development aid)"""
 import os, sys, gc
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
+import numpy as np
 import torch
 import gpf_amd as g
 from gpf_amd import sharded
@@ -24,6 +25,14 @@ def e():
 def f():
     sh = sharded.pf_initialize(model, (1,), ys[0], 200_000, seed=3)
     sharded.pf_resample(sh, "multinomial", check=False); sharded.pf_update(sh, (2,), (None,), ys[1]); sharded.get_lml_est(sh); sh.local.close()
+def bw():   # every block-wise call once: 100 000 blocks of 2, store with weight records, forward smoothing
+    m = g.models.lgssm2(); nb = 100_000; o = [np.tile(y, (nb, 1)) for y in g.models.simulate(m, 3)]; r = np.zeros((nb, m.dim))
+    st = g.pf_initialize_blocks(m, (1,), o[0], 2 * nb, 2, seed=3, keep_prev=True, history=4, history_weights=True, forward=True)
+    g.pf_resample_blocks(st, 2, check=False); g.pf_update_blocks(st, (2,), (None,), o[1], 2)
+    g.pf_resample_blocks(st, 2, check=False, conditional=True, reference=r, observations=o[2]); g.pf_update_blocks(st, (3,), (None,), o[2], 2, reference=r)
+    g.set_block_params(st, np.tile(np.asarray(m.params, float), (nb, 1)), 2); g.pf_resample_across_blocks(st, 2, check=False); g.block_moments(st, 2)
+    g.block_sample_trajectories(st, 2); g.block_backward_trajectories(st, 2); g.block_smoothed_moments(st, 2); g.block_map_trajectories(st, 2)
+    g.block_forward_moments(st, 2); st.close()
 def z():
     st = g.pf_initialize(model, (1,), ys[0], 200_000, seed=3); st.close()
 
@@ -36,7 +45,7 @@ def f2():
     b = sh.backend; mf = b.weight_max(); b.weight_scan(mf.unsqueeze(0).contiguous(), False); sh.local.close()
 def f3():
     x = torch.empty((465_536, 5), dtype=torch.float64, device="cuda"); del x
-for name, fn in (("sh-init", f0), ("stream", f1), ("sh-scan", f2), ("tensor", f3), ("plain", z), ("history", a), ("sort+mh", b), ("residual", c), ("view", d), ("resize", e), ("sharded", f)):
+for name, fn in (("sh-init", f0), ("stream", f1), ("sh-scan", f2), ("tensor", f3), ("plain", z), ("history", a), ("sort+mh", b), ("residual", c), ("view", d), ("resize", e), ("sharded", f), ("blockwise", bw)):
     for _ in range(3): fn()
     gc.collect(); torch.cuda.synchronize(); torch.cuda.empty_cache(); f0, _ = torch.cuda.mem_get_info()
     for _ in range(20): fn()
