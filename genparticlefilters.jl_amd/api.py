@@ -1121,6 +1121,18 @@ def _store_blocks(state, block_size, lo, hi, who, n_samples=None):
     return bs, (state.n_particles + bs - 1) // bs
 
 
+def _store_weights(state, who):
+    """the queries that walk the store's weight records (a backward pass): refuse a state without them"""
+    if not getattr(state, "history_weights", False):
+        raise ErrorException(who + " needs the block-wise trajectory store with its weight records "
+                             "(pf_initialize_blocks(..., history=T, history_weights=True)), which this state does not have")
+
+
+def _pi64(a):
+    """an optional int64 output: None (not asked for) stays None"""
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
 def block_sample_trajectories(state, block_size: int, n_samples: int = 1, steps=None, return_indices: bool = False):
     """for b in blocks; sample_unweighted_traces(state[b], n_samples); end (src/utils.jl:7,189-194 on sub-states, src/view.jl:35-48): the reference's
     traces are persistent, so every draw is a whole path of block b.  One launch for all blocks (gpf.h gpf_block_sample_trajectories); needs the
@@ -1134,8 +1146,7 @@ def block_sample_trajectories(state, block_size: int, n_samples: int = 1, steps=
     _, nb = _store_blocks(state, block_size, lo, hi, "block_sample_trajectories", n_samples)
     traj = np.empty((nb, int(n_samples), hi - lo + 1, state.dim))
     idx = np.empty((nb, int(n_samples)), np.int64) if return_indices else None
-    state._check(state._L.gpf_block_sample_trajectories(state._h, int(block_size), int(n_samples), lo, hi, _pd(traj),
-                                                        idx.ctypes.data_as(C.POINTER(C.c_int64)) if return_indices else None))
+    state._check(state._L.gpf_block_sample_trajectories(state._h, int(block_size), int(n_samples), lo, hi, _pd(traj), _pi64(idx)))
     return (traj, idx) if return_indices else traj
 
 
@@ -1148,22 +1159,17 @@ def block_backward_trajectories(state, block_size: int, n_samples: int = 1, step
     final order of their step) of the held particles.  steps as in block_sample_trajectories; the walk always starts at the last step.  A block with
     NaN / +Inf weights gets indices 0 and NaN paths.  Under set_block_params every step uses the drawing block's CURRENT parameter row.  Advances the
     RNG epoch by T - lo + 1; the filter is left untouched."""
-    if not getattr(state, "history_weights", False):
-        raise ErrorException("block_backward_trajectories needs the block-wise trajectory store with its weight records "
-                             "(pf_initialize_blocks(..., history=T, history_weights=True)), which this state does not have")
+    _store_weights(state, "block_backward_trajectories")
     lo, hi = _store_steps(state, steps, "block_backward_trajectories")
     _, nb = _store_blocks(state, block_size, lo, hi, "block_backward_trajectories", n_samples)
     traj = np.empty((nb, int(n_samples), hi - lo + 1, state.dim))
     idx = np.empty((nb, int(n_samples), hi - lo + 1), np.int64) if return_indices else None
-    state._check(state._L.gpf_block_backward_sample(state._h, int(block_size), int(n_samples), lo, hi, _pd(traj),
-                                                    idx.ctypes.data_as(C.POINTER(C.c_int64)) if return_indices else None))
+    state._check(state._L.gpf_block_backward_sample(state._h, int(block_size), int(n_samples), lo, hi, _pd(traj), _pi64(idx)))
     return (traj, idx) if return_indices else traj
 
 
 def _block_smooth(state, block_size, steps, who, want_mean, want_var, want_weights, want_blocks):
-    if not getattr(state, "history_weights", False):
-        raise ErrorException(who + " needs the block-wise trajectory store with its weight records "
-                             "(pf_initialize_blocks(..., history=T, history_weights=True)), which this state does not have")
+    _store_weights(state, who)
     lo, hi = _store_steps(state, steps, who)
     bs, nb = _store_blocks(state, block_size, lo, hi, who)
     mu = np.empty((nb, hi - lo + 1, state.dim)) if want_mean else None
@@ -1171,7 +1177,7 @@ def _block_smooth(state, block_size, steps, who, want_mean, want_var, want_weigh
     w = np.empty((nb, hi - lo + 1, bs)) if want_weights else None
     blocks = np.empty((nb, hi - lo + 1), np.int64) if want_blocks else None
     state._check(state._L.gpf_block_smooth(state._h, int(block_size), lo, hi, _pd(mu) if want_mean else None, _pd(s2) if want_var else None,
-                                           _pd(w) if want_weights else None, blocks.ctypes.data_as(C.POINTER(C.c_int64)) if want_blocks else None))
+                                           _pd(w) if want_weights else None, _pi64(blocks)))
     return mu, s2, w, blocks
 
 
@@ -1223,16 +1229,13 @@ def block_smoothed_pair_moments(state, block_size: int, steps=None, return_block
     block_smoothed_moments' blocks.  steps, NaN blocks, undefined lineages (NaN for every pair that touches an undefined step), per-block parameters and
     effects (none) as in block_smoothed_moments; mean is that call's, bit for bit."""
     who = "block_smoothed_pair_moments"
-    if not getattr(state, "history_weights", False):
-        raise ErrorException(who + " needs the block-wise trajectory store with its weight records "
-                             "(pf_initialize_blocks(..., history=T, history_weights=True)), which this state does not have")
+    _store_weights(state, who)
     lo, hi = _store_steps(state, steps, who)
     _, nb = _store_blocks(state, block_size, lo, hi, who)
     d = state.dim
     mu, second, cross = np.empty((nb, hi - lo + 1, d)), np.empty((nb, hi - lo + 1, d, d)), np.empty((nb, hi - lo, d, d))
     blocks = np.empty((nb, hi - lo + 1), np.int64) if return_blocks else None
-    state._check(state._L.gpf_block_smooth_pairs(state._h, int(block_size), lo, hi, _pd(mu), _pd(second), _pd(cross) if hi > lo else None,
-                                                 blocks.ctypes.data_as(C.POINTER(C.c_int64)) if return_blocks else None))
+    state._check(state._L.gpf_block_smooth_pairs(state._h, int(block_size), lo, hi, _pd(mu), _pd(second), _pd(cross) if hi > lo else None, _pi64(blocks)))
     return (mu, second, cross) + ((blocks,) if return_blocks else ())
 
 
@@ -1248,15 +1251,13 @@ def block_map_trajectories(state, block_size: int, steps=None, return_indices: b
     indices 0.  Under set_block_params every step uses the final block's CURRENT parameter row.  Nothing is drawn: the RNG epoch and the filter are
     left untouched."""
     who = "block_map_trajectories"
-    if not getattr(state, "history_weights", False):
-        raise ErrorException(who + " needs the block-wise trajectory store with its weight records "
-                             "(pf_initialize_blocks(..., history=T, history_weights=True)), which this state does not have")
+    _store_weights(state, who)
     lo, hi = _store_steps(state, steps, who)
     _, nb = _store_blocks(state, block_size, lo, hi, who)
     path = np.empty((nb, hi - lo + 1, state.dim))
     idx = np.empty((nb, hi - lo + 1), np.int64) if return_indices else None
     logp = np.empty(nb) if return_log_density else None
-    state._check(state._L.gpf_block_map_path(state._h, int(block_size), lo, hi, _pd(path), idx.ctypes.data_as(C.POINTER(C.c_int64)) if return_indices else None,
+    state._check(state._L.gpf_block_map_path(state._h, int(block_size), lo, hi, _pd(path), _pi64(idx),
                                              _pd(logp) if return_log_density else None))
     out = (path,) + ((idx,) if return_indices else ()) + ((logp,) if return_log_density else ())
     return out if len(out) > 1 else path

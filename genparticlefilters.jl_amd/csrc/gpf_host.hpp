@@ -1,4 +1,4 @@
-// gpf_host.hpp -- host-side internals shared by the translation units of libgpf_hip.so (libgpf_core / _resample / _aux / _shard .hip):
+// gpf_host.hpp -- host-side internals shared by the translation units of libgpf_hip.so (libgpf_core / _resample / _aux / _blocks / _store / _shard ... .hip):
 // the filter handle, the launch / error macros and the declarations of the helpers one unit defines and another calls.  Nothing here is
 // part of the C ABI (include/gpf.h); everything lives in namespace gpfh and is built with hidden visibility.
 #pragma once
@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -687,6 +688,39 @@ inline void team_dispatch(int64_t block_size, int64_t nblocks, F&& f)
 }
 // ---- defined in libgpf_aux.hip
 gpf_status weighted_tree_sum(gpf_filter* h, const double* values, int stride, int col, int pw, const double* center, double match, double* out_dev);
+// the per-particle kernels of the block-wise initialise / propagate / move (called from libgpf_blocks.hip): k_init / k_step / k_move<model, ...> by the
+// handle's keep_prev and per-block parameters; mode 0 | 2 | MODE_REF, the propagate 4 as well
+void launch_init_blk(gpf_filter* h, int grid, int mode);
+void launch_step_blk(gpf_filter* h, int grid, int mode);
+void launch_move_blk(gpf_filter* h, int grid, int n_iters, bool reweight);
+// ---- defined in libgpf_blocks.hip: what the block-wise filter shares with the store's queries (libgpf_store.hip) and the forward smoother (libgpf_forward.hip)
+// The preconditions of a block-wise call, in ONE order for every entry point ("the gate of the block-wise calls"); `steps` names the ones
+// the entry point has.  Nothing here touches the handle -- check_ready, which brings a lazy move or a view up to date, comes after the gate and after the
+// entry point's own checks -- so a refused call changes nothing.  The null handle is refused always.
+enum : unsigned {
+    GATE_VIEW = 1, GATE_SHARD = 2,
+    GATE_STORE = 4,            // a filter with the plain trajectory store (gpf_history_enable) takes no block-wise call
+    GATE_STORE_VIEWS = 8,      //   ... and says why: the estimates of big blocks are the work of sub-state views, which it does not have
+    GATE_SIZE = 16,            // block_size < 1
+    GATE_CLAMP = 32,           // block_size comes back clamped to the particle count: "one block" may be asked for as any size >= n, 2^32 included (the
+                               // step kernels divide by it as a 32-bit number, ModelArgs::blk_size, and n < 2^31)
+    GATE_CLAMP_STORE = 64,     //   ... only on a filter with the block-wise store (elsewhere a size >= n stays what it is: above BLK_MAX the work of a view)
+    GATE_MAX = 128,            // blocks of more than BLK_MAX particles are the work of view handles (big_block_views), which a filter with the block-wise store
+                               // (gpf_history_enable_blocks) does not have
+    GATE_PARAMS = 256,         // the block size of the per-block parameters, where they are set
+    GATE_FWD = 512,            // the block size of forward smoothing per block (gpf_forward_enable_blocks), once its initialising call has set it
+    GATE_FILTER = GATE_VIEW | GATE_SHARD | GATE_STORE | GATE_SIZE,
+};
+gpf_status block_gate(gpf_handle h, int64_t& block_size, const char* who, unsigned steps);
+// the results of a call from the device to the host, each where the caller wants it (nullptr: not asked for), then the one synchronisation
+struct OutCopy { const void* dev; void* host; size_t bytes; };
+gpf_status block_out(gpf_filter* h, std::initializer_list<OutCopy> outs);
+// the parameters a transition density is evaluated with: the filter's own, and the per-block rows where they are set
+AncArgs anc_args(const gpf_filter* h);
+// the device buffer of the per-block estimates (h->blk_est): at least `need` doubles
+gpf_status block_est_buffer(gpf_filter* h, int64_t need);
+// the match values of a proportion kernel, padded with the last one (the kernels take them two at a time)
+BlockMatch make_block_match(const double* values, int32_t n_values);
 // ---- defined in libgpf_smooth.hip
 void launch_block_smooth(gpf_filter* h, const SmoothArgs& a, const AncArgs& x);   // k_block_smooth<model, TEAM, ITEMS> by team_dispatch
 // ---- defined in libgpf_pairs.hip

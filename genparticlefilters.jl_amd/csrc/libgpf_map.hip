@@ -1,4 +1,4 @@
-// libgpf_map.hip -- the kernels of the most probable path per block (gpf_k_block_map.hpp; gpf.h gpf_block_map_path, whose host side is in libgpf_aux.hip).
+// libgpf_map.hip -- the kernels of the most probable path per block (gpf_k_block_map.hpp; gpf.h gpf_block_map_path, whose host side is in libgpf_store.hip).
 // A translation unit of their own, for the reason libgpf_smooth.hip is one: fifteen more instantiations beside the other block kernels would change their
 // register allocation; here every other unit's device code stays what it was (tools/isa_diff.py).
 #include "gpf_host.hpp"

@@ -1,5 +1,5 @@
 // libgpf_pairs.hip -- the kernels of the pairwise smoother per block (gpf_k_block_smooth.hpp, the walk it shares with k_block_smooth; gpf.h
-// gpf_block_smooth_pairs, whose host side is in libgpf_aux.hip).  A translation unit of their own, for the reason libgpf_smooth.hip is one: fifteen more
+// gpf_block_smooth_pairs, whose host side is in libgpf_store.hip).  A translation unit of their own, for the reason libgpf_smooth.hip is one: fifteen more
 // instantiations of the block family's one compute-heavy walk, and every other unit's device code stays what it was (tools/isa_diff.py;
 // profiles/block_pairs.md).
 #include "gpf_host.hpp"

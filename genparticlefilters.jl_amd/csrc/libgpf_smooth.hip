@@ -1,4 +1,4 @@
-// libgpf_smooth.hip -- the kernels of the marginal smoother per block (gpf_k_block_smooth.hpp; gpf.h gpf_block_smooth, whose host side is in libgpf_aux.hip).
+// libgpf_smooth.hip -- the kernels of the marginal smoother per block (gpf_k_block_smooth.hpp; gpf.h gpf_block_smooth, whose host side is in libgpf_store.hip).
 // A translation unit of their own: k_block_smooth is the one compute-heavy kernel of the block family (fifteen instantiations of 150-256 registers), and
 // instantiated beside the other block kernels it changed their register allocation; here every other unit's device code stays what it was.
 #include "gpf_host.hpp"

@@ -1,5 +1,5 @@
 # usage: bash tools/build_variant.sh NAME -DFLAG=VALUE ...   -> genparticlefilters.jl_amd/libgpf_NAME.so (kernel experiments only;
-# run with GPF_LIB_OVERRIDE=$PWD/genparticlefilters.jl_amd/libgpf_NAME.so).  Same six translation units as the product build
+# run with GPF_LIB_OVERRIDE=$PWD/genparticlefilters.jl_amd/libgpf_NAME.so).  Same translation units as the product build
 # (__graft_entry__.build_hip), objects under build/obj_libgpf_NAME/.
 NAME=$1; shift
 R=$(cd "$(dirname "$0")/.." && pwd)

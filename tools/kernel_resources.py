@@ -1,6 +1,6 @@
 """Register / scratch / LDS / occupancy table of every kernel of libgpf (compile-time, no GPU):
     python3 tools/kernel_resources.py > profiles/rNN_kernel_resources.txt
-Compiles the eight translation units with -Rpass-analysis=kernel-resource-usage and prints one line per kernel."""
+Compiles the translation units (HIP_UNITS of __graft_entry__.py) with -Rpass-analysis=kernel-resource-usage and prints one line per kernel."""
 import os
 import re
 import subprocess
@@ -8,13 +8,16 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from __graft_entry__ import HIP_UNITS
+
 csrc = os.path.join(ROOT, "genparticlefilters.jl_amd", "csrc")
 err = ""
 with tempfile.TemporaryDirectory() as td:
     procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden",
                                "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"), "-Rpass-analysis=kernel-resource-usage", *sys.argv[1:],
                                "-c", os.path.join(csrc, u), "-o", os.path.join(td, u + ".o")], stderr=subprocess.PIPE, text=True)
-             for u in ("libgpf_core.hip", "libgpf_resample.hip", "libgpf_aux.hip", "libgpf_shard.hip", "libgpf_smooth.hip", "libgpf_pairs.hip", "libgpf_forward.hip", "libgpf_map.hip")]
+             for u in HIP_UNITS]
     for q in procs:
         err += q.communicate()[1]
 class _P: stderr = err
