@@ -61,6 +61,7 @@ SYMBOLS = [
     ("gpf_update_blocks_strata", C.c_int, [_H, _pd, C.c_int32, C.c_int64, _pd, C.c_int32, C.c_int32]),
     ("gpf_update_blocks_proposal", C.c_int, [_H, _pd, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int32]),
     ("gpf_rejuvenate_blocks", C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]),
+    ("gpf_run_blocks", C.c_int, [_H, _pd, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_double, _pd, _pd, _pi32, _pi32]),
     ("gpf_set_block_params", C.c_int, [_H, _pd, C.c_int32, C.c_int64]),
     ("gpf_get_block_params", C.c_int, [_H, _pd, C.c_int32, C.c_int64]),
     ("gpf_resample_across_blocks", C.c_int, [_H, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32, _pi32, _pi32, _pd]),

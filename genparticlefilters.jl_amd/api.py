@@ -714,6 +714,49 @@ def pf_update_blocks(state, new_args: tuple, argdiffs: tuple, observations, bloc
     return state
 
 
+BlockRun = namedtuple("BlockRun", ["lml", "ess", "resampled"])
+
+
+def pf_run_blocks(state, observations, block_size: int, method: str = "multinomial", *, ess_frac=0.5, sort_particles: bool = True) -> BlockRun:
+    """A whole series per block in ONE launch (gpf.h gpf_run_blocks) -- bit for bit the loop
+
+        for t in range(T):
+            pf_resample_blocks(state, block_size, method, ess_frac=ess_frac, sort_particles=sort_particles, check=False)
+            pf_update_blocks(state, (t,), (None,), observations[:, t], block_size)
+
+    on an initialised state: rows, log-weights, parents, the RNG epoch (+ 2 T) and the per-block observations are what the loop leaves, so
+    every later call continues identically and runs of T1 and T2 steps compose to one of T1 + T2.  observations: (n_blocks, T, n_obs), or
+    (T, n_obs) -- one series shared by all blocks, the SMC^2 / particle-marginal MH case (the blocks differ by set_block_params).
+    ess_frac=None: every block resamples at every step.  Default proposals only; no rejuvenation, store or reference path inside the run.
+    Returns BlockRun(lml, ess, resampled), each (n_blocks, T): log_ml_estimate(state[b]) and effective_sample_size(state[b]) after step t's
+    update (block_stats) and whether block b resampled at step t (block_resampled).  Blocks with NaN / +Inf weights are left alone by the
+    resample and propagated anyway; the call then raises "Invalid weights (NaN)." after the whole run."""
+    if method not in ("multinomial", "residual", "stratified"):
+        raise ErrorException(f"Resampling method {method} not recognized.")
+    if isinstance(state, DeviceParticleFilterSubState):
+        raise ErrorException("pf_run_blocks works on the whole filter")
+    if int(block_size) < 1:
+        raise ErrorException("block_size < 1")
+    nb = (state.n_particles + min(int(block_size), max(state.n_particles, 1)) - 1) // min(int(block_size), max(state.n_particles, 1))
+    obs = np.ascontiguousarray(observations, np.float64)
+    if obs.ndim == 3 and obs.shape[0] == nb and obs.shape[1] >= 1:
+        shared = False
+    elif obs.ndim == 2 and obs.shape[0] >= 1:
+        shared = True
+    else:
+        raise ErrorException(f"observations of shape ({nb}, T, n_obs), or (T, n_obs) for one series shared by all blocks, expected: got {obs.shape}")
+    T = obs.shape[0] if shared else obs.shape[1]
+    ess, lml, res = np.empty((T, nb)), np.empty((T, nb)), np.zeros((T, nb), np.int32)
+    inv = C.c_int32(0)
+    st = state._L.gpf_run_blocks(state._h, _pd(obs), obs.shape[-1], T, int(shared), int(block_size), RESAMPLE_METHODS[method], int(sort_particles),
+                                 float("nan") if ess_frac is None else float(ess_frac), _pd(ess), _pd(lml),
+                                 res.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(inv))
+    if st != _lib.OK:
+        raise ErrorException(state._L.gpf_last_error(state._h).decode())
+    state._n_blocks_last = 0                                     # (no pf_resample_blocks for block_resampled to refer to, as after the loop's last update)
+    return BlockRun(lml.T, ess.T, (res & 1).astype(bool).T)      # (views of the library's [T][n_blocks] arrays: no transposed copies)
+
+
 def pf_rejuvenate_blocks(state, kern=None, kern_args: tuple = (), n_iters: int = 1, *, method: str = "move", only_resampled: bool = False,
                          count: bool = False):
     """for b in blocks: pf_rejuvenate!(state[b], ...) with the block's own latest observation; only_resampled: only the blocks the last

@@ -270,6 +270,10 @@ struct __attribute__((visibility("hidden"))) gpf_filter : gpfh::Bufs {
     // bp_size > 0: the rows are in force for blocks of this (clamped) size -- the block-wise steps run their BP kernels, everything that would
     // read cfg.params is refused (bp_refused)
     Dev<double> blk_params; int64_t bp_size = 0;
+    // gpf_run_blocks: the call's device input [MAX_PARAMS parameters | n_steps x (n_blocks | 1) x MAX_OBS observations] with the pinned buffer it is
+    // packed into, and its outputs [ess | lml] x [n_steps][n_blocks], [n_steps][n_blocks] resample words.  Scratch of one call (it ends with a
+    // synchronisation), kept for the next
+    Dev<double> run_in, run_stats; Pinned<double> h_run_in; Dev<int32_t> run_words;
     // gpf_resample_across_blocks: the planner filter of n_blocks particles whose log-weights are the blocks' log-ML estimates (its ancestors name the
     // source block of every block; it runs on this filter's stream), the second buffers the per-block rows are gathered into (swapped with
     // blk_params / blk_obs), and the 1-based block ancestors of the last call that fired with the buffers they refer to (gpf_block_ancestors)
@@ -727,6 +731,8 @@ void launch_block_smooth(gpf_filter* h, const SmoothArgs& a, const AncArgs& x); 
 void launch_block_pairs(gpf_filter* h, const PairArgs& a, const AncArgs& x);      // k_block_smooth_pairs<model, TEAM, ITEMS> by team_dispatch
 // ---- defined in libgpf_map.hip
 void launch_block_map(gpf_filter* h, const MapArgs& a, const AncArgs& x);         // k_block_map<model, TEAM, ITEMS> by team_dispatch
+// ---- defined in libgpf_run.hip
+void launch_block_run(gpf_filter* h, const RunArgs& a, int method);               // k_block_run<model, W, method, TEAM, ITEMS> by team_dispatch; method 0 | 1 | 2
 // ---- defined in libgpf_forward.hip: the forward-only smoother's records (hist_begin_step / hist_on_resample call the first two) and launches
 gpf_status fwd_begin_step(gpf_filter* h, bool first);             // first: step 1 begins, the statistics are reset; else the step that ends is closed in its final order
 gpf_status fwd_on_resample(gpf_filter* h, int64_t block_size);    // this call's parents into the current step's map (block_size > 0: block-local, h->blk_mask says which)

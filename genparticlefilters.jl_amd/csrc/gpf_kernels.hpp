@@ -28,3 +28,4 @@
 #include "gpf_k_block_smooth.hpp"
 #include "gpf_k_block_forward.hpp"
 #include "gpf_k_block_map.hpp"
+#include "gpf_k_block_run.hpp"

@@ -646,6 +646,82 @@ gpf_status gpf_update_blocks_proposal(gpf_handle h, const double* obs, int32_t n
     if (!proposal_valid(h, proposal) || !model_caps(h).proposal) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no such native proposal");
     return block_update_impl(h, obs, n_obs, block_size, 4, use_proposal);
 }
+// for t in 1:n_steps; gpf_resample_blocks(check = false); gpf_update_blocks(obs[:, t]); end in one launch (k_block_run, libgpf_run.hip) -- gpf.h.
+// Everything up to the input's upload is a check or scratch of the call: a refused call changes nothing
+gpf_status gpf_run_blocks(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs, int64_t block_size, int32_t method,
+                          int32_t sort_particles, double ess_frac, double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid)
+{
+    const std::string who = "gpf_run_blocks";
+    gpf_status s = block_gate(h, block_size, who.c_str(), GATE_VIEW | GATE_SHARD | GATE_SIZE | GATE_CLAMP | GATE_MAX | GATE_PARAMS | GATE_FWD);
+    if (s) return s;
+    if (h->hist_on) return fail(h, GPF_ERR_STATE, who + " on a filter with a trajectory store: recording a step is host bookkeeping per step (run the loop of gpf_resample_blocks / gpf_update_blocks)");
+    if (h->fwd_on) return fail(h, GPF_ERR_STATE, who + ": forward smoothing per block is on (gpf_forward_enable_blocks): its statistics are closed by a call per step");
+    if (h->cfg.keep_prev) return fail(h, GPF_ERR_STATE, who + " on a keep_prev filter: x_{t-1} serves only the rejuvenation moves, and the run has none");
+    if (block_size > BLK_MAX) return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": blocks of more than " + std::to_string(BLK_MAX) + " particles are not the work of one team");
+    if (h->args.n_strata > 0) return fail(h, GPF_ERR_STATE, who + ": strata are set on this filter; the run extends every block with the default proposal only");
+    if (n_steps < 1 || n_steps > 4096) return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": need 1 <= n_steps <= 4096 (longer series: call it in chunks, they compose)");
+    const int64_t nblocks = (h->n + block_size - 1) / block_size, obs_blocks = shared_obs ? 1 : nblocks;
+    if (method != GPF_RESAMPLE_MULTINOMIAL && method != GPF_RESAMPLE_RESIDUAL && method != GPF_RESAMPLE_STRATIFIED)
+        return fail(h, GPF_ERR_UNKNOWN_METHOD, "Resampling method not recognized.");          // resample.jl:28
+    if ((s = block_obs_check(h, obs, n_obs))) return s;          // (as gpf_update_blocks refuses them: every step's rows have the one width)
+    const int64_t obs_words = (int64_t)n_steps * obs_blocks * n_obs;
+    if (obs_words > ((int64_t)1 << 31)) return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": the observations of the call exceed 2^31 words on the device: fewer steps per call");
+    // ---- the call's input [MAX_PARAMS parameters | the observations in the caller's layout] into the pinned buffer: ONE pass over the observations,
+    //      which is also their check (the exponent fields, branch-free as in block_ref_checks; the offender is looked for only when there is one).
+    //      Scratch: a call refused here or below has changed nothing
+    const size_t in_words = (size_t)MAX_PARAMS + (size_t)obs_words, cells = (size_t)n_steps * (size_t)nblocks;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if ((s = h->h_run_in.grow(h, in_words))) return s;
+    {
+        double* const dst = h->h_run_in + MAX_PARAMS;
+        uint64_t bad = 0;
+        for (int64_t k = 0; k < obs_words; ++k) { uint64_t u; memcpy(&u, obs + k, sizeof(u)); bad |= (uint64_t)(((u >> 52) & 0x7ffu) == 0x7ffu); memcpy(dst + k, &u, sizeof(u)); }
+        if (bad)
+            for (int64_t k = 0; k < obs_words; ++k)
+                if (!(obs[k] - obs[k] == 0.0)) {
+                    const int64_t row = k / n_obs;
+                    return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": the observation of step " + std::to_string(row % n_steps + 1) +
+                                (shared_obs ? std::string() : ", block " + std::to_string(row / n_steps)) + " is not finite");
+                }
+    }
+    if (h->W != 2 && h->W != 4) return fail(h, GPF_ERR_STATE, "row width");
+    if ((s = check_ready(h)) || (s = materialize(h))) return s;
+    // ---- device scratch: the input, the outputs, the words of the summary
+    if ((s = block_buffers(h, nblocks)) || (s = h->run_in.grow(h, in_words)) || (s = h->run_stats.grow(h, 2 * cells)) || (s = h->run_words.grow(h, cells)) ||
+        (s = h->blk_obs.grow(h, (size_t)nblocks * MAX_OBS))) return s;
+    for (int i = 0; i < MAX_PARAMS; ++i) h->h_run_in[i] = h->args.P[i];
+    HIP_TRY(h, hipMemcpyAsync(h->run_in, h->h_run_in, in_words * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    RunArgs a{};
+    a.rows[0] = h->rows[h->cur]; a.rows[1] = h->rows[1 - h->cur]; a.lw = h->lw; a.anc = h->anc;
+    a.n = h->n; a.nb = block_size; a.nblocks = nblocks; a.gid0 = h->cfg.gid0; a.seed = h->cfg.seed; a.epoch = h->epoch; a.n_steps = n_steps;
+    a.sorted = method == GPF_RESAMPLE_STRATIFIED && sort_particles ? 1 : 0;
+    a.ess_frac = ess_frac == ess_frac ? ess_frac : -1.0;
+    a.P = h->run_in; a.blk_params = h->bp_size > 0 ? h->blk_params.p : nullptr;
+    a.obs = h->run_in + MAX_PARAMS; a.obs_blocks = obs_blocks; a.n_obs = n_obs;
+    a.lml_est = &h->sc->lml_est;
+    a.ess_out = h->run_stats; a.lml_out = h->run_stats + cells; a.res_out = h->run_words; a.flags_out = h->blk_mask; a.blk_obs = h->blk_obs;
+    const int m_id = method == GPF_RESAMPLE_MULTINOMIAL ? 0 : (method == GPF_RESAMPLE_RESIDUAL ? 1 : 2);
+    s = timed(h, GPF_K_STEP, [&] { launch_block_run(h, a, m_id); });
+    if (s) return s;
+    HIP_TRY(h, hipGetLastError());
+    // ---- what the loop's 2 n_steps calls leave: two row-buffer flips per iteration (cur as it was), one epoch each, the last step's observation rows
+    h->epoch += 2u * (uint32_t)n_steps;
+    h->has_prev = true;
+    h->pending_gather = false; h->pending_fill = false;
+    h->args.blk_obs = h->blk_obs; h->args.blk_mask = nullptr; h->args.blk_size = (int32_t)block_size;
+    h->blk_obs_size = block_size;
+    h->blk_last = 0;                                             // (blk_mask holds the flag words of the summary below, not a resample's mask)
+    weights_written(h, false);
+    GPF_LAUNCH(k_block_summary, dim3(1), dim3(BLOCK), 0, h->stream, h->blk_mask.p, nblocks, h->blk_words.p);
+    HIP_TRY(h, hipGetLastError());
+    int32_t words[2] = {0, 0};
+    const size_t bytes = cells * sizeof(double);
+    if ((s = block_out(h, {{h->run_stats, ess_out, bytes}, {h->run_stats + cells, lml_out, bytes}, {h->run_words, resampled_out, cells * sizeof(int32_t)},
+                           {h->blk_words, words, sizeof(words)}}))) return s;
+    if (invalid) *invalid = words[0] != 0;
+    if (words[0] & (FLAG_NAN | FLAG_POSINF)) return fail(h, GPF_ERR_INVALID_WEIGHTS, "Invalid weights (NaN).");
+    return GPF_OK;
+}
 gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, int32_t only_resampled, uint64_t* n_accepted)
 {
     gpf_status s = check_ready(h);

@@ -277,6 +277,40 @@ gpf_status gpf_update_blocks_proposal(gpf_handle h, const double* obs, int32_t n
 gpf_status gpf_initialize_blocks_strata(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, const double* values, int32_t n_strata, int32_t interleaved);
 gpf_status gpf_update_blocks_strata(gpf_handle h, const double* obs, int32_t n_obs, int64_t block_size, const double* values, int32_t n_strata, int32_t interleaved);
 gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, int32_t only_resampled, uint64_t* n_accepted);
+/* A whole series per block in ONE launch: the filter loop of README.md:60-79 run per block (the block-wise resampling of test/resample.jl:130-162
+ * followed by the per-view update),
+ *     for t in 1:n_steps
+ *         gpf_resample_blocks(h, method, block_size, NaN, sort_particles, ess_frac, GPF_CHECK_FALSE, NULL, NULL);      epoch E + 2(t-1)
+ *         gpf_update_blocks(h, obs[:, t], n_obs, block_size);                                                          epoch E + 2(t-1) + 1
+ *     end
+ * for the callers that filter y_1:T again and again under new parameters (SMC^2 rejuvenation, parallel particle-marginal MH, a likelihood surface over
+ * a theta grid: gpf_set_block_params, gpf_resample_across_blocks, gpf_block_stats).  The blocks do not interact inside this loop, so one team -- a wave
+ * up to 512 particles per block, a workgroup up to 2048 -- runs all steps of its block with no launch in between.
+ *   contract  on an initialised filter at epoch E the call leaves EXACTLY what the loop leaves after n_steps iterations: rows, log-weights, parents
+ *             (block-local, written only when a block resamples, the last write stands), the epoch E + 2 n_steps, the per-block observation rows of
+ *             the last step, the block size, "no gpf_resample_blocks to refer to" (gpf_block_resampled, only_resampled) -- bit for bit, so every
+ *             later call continues identically and two calls of T1 and T2 steps equal one of T1 + T2.  Resample slot gid0 + b block_size + j draws
+ *             under epoch E + 2(t-1), the propagate of particle gid under E + 2(t-1) + 1, exactly as the two calls do.  Per-block parameters
+ *             (gpf_set_block_params) are used as gpf_update_blocks uses them.
+ *   obs       HOST, [n_blocks][n_steps][n_obs]: block b's series, step-major inside the block; shared_obs != 0: [n_steps][n_obs], ONE series for all
+ *             blocks.  All values finite, n_obs the model's.  Copied to the device once per call.
+ *   outputs   HOST, each may be NULL: ess_out, lml_out [n_steps][n_blocks] -- what gpf_block_stats returns after step t's update, bit for bit;
+ *             resampled_out [n_steps][n_blocks] -- the word of step t's resample: bit 0 = the block resampled (gpf_block_resampled), bits 8.. = the
+ *             validity flags it reported (1 NaN, 2 +Inf, 4 all -Inf); *invalid = 1 if any flag was reported at any step.
+ *   ess_frac  as in gpf_resample_blocks; NaN: every block resamples at every step.
+ *   weights   a block whose weights hold a NaN or +Inf is skipped by the resample and propagated anyway, at every step; after the whole run the call
+ *             returns GPF_ERR_INVALID_WEIGHTS ("Invalid weights (NaN)."), the state being what the loop leaves when every iteration's error is
+ *             ignored.  An all -Inf block resamples with uniform weights where its gate lets it (safe_softmax's fallback) and sets *invalid.
+ *   timing    the launch is booked under GPF_K_STEP (gpf_kernel_timing).
+ *   refused   nothing changed, epoch included.  GPF_ERR_STATE: a sub-state view, a shard, a trajectory store of either kind (recording a step is host
+ *             bookkeeping per step), forward smoothing per block, a keep_prev filter (x_{t-1} serves only the moves), strata set on the filter;
+ *             GPF_ERR_INVALID_ARGUMENT: block_size < 1, a clamped block_size > 2048 or other than the per-block parameters', n_steps < 1 or > 4096
+ *             (chunks compose), more than 2^31 observation words on the device, obs NULL, n_obs not the model's, a non-finite observation;
+ *             GPF_ERR_UNKNOWN_METHOD.  Not offered inside the run (the loop of calls has them): rejuvenation, proposals, a reference path, tempering,
+ *             the initial step (gpf_initialize_blocks stays a call of its own). */
+gpf_status gpf_run_blocks(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs,
+                          int64_t block_size, int32_t method, int32_t sort_particles, double ess_frac,
+                          double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid);
 /* Conditional SMC, the propagation half: gpf_initialize_blocks / gpf_update_blocks with ONE PARTICLE PER BLOCK PINNED to a given value -- the
  * conditional filter of Andrieu, Doucet & Holenstein (2010), section 4.3 (step (a) / (b): "set X_n^{B_n} = the retained path, sample the other
  * N - 1 particles"), on the reference's per-view loop

@@ -397,6 +397,24 @@ function pf_rejuvenate_blocks!(s::DeviceParticleFilterState, kern=nothing, kern_
     m = method == :move ? 0 : method == :reweight ? 1 : error("Method $method not recognized.")
     _status(s, ccall((:gpf_rejuvenate_blocks, libgpf), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{UInt64}), s.handle, m, n_iters, only_resampled ? 1 : 0, C_NULL)); s
 end
+# A whole series per block in ONE launch (gpf.h gpf_run_blocks): bit for bit the loop
+#     for t in 1:T; pf_resample_blocks!(s, block_size, method; ess_frac, sort_particles, check=false); pf_update_blocks!(s, (t,), (nothing,), observations[:, t, :], block_size); end
+# observations: (n_obs, T, n_blocks) -- block b's series in observations[:, :, b] -- or a (n_obs, T) Matrix, ONE series shared by all blocks (the
+# SMC^2 / particle-marginal MH case: the blocks differ by set_block_params!).  ess_frac = nothing: every block resamples at every step.  Returns
+# (lml, ess, resampled), each (n_blocks, T): block_stats after step t's update and whether block b resampled at step t.
+function pf_run_blocks!(s::DeviceParticleFilterState, observations::Union{Array{Float64,3},Matrix{Float64}}, block_size::Int, method::Symbol=:multinomial;
+                        ess_frac=0.5, sort_particles::Bool=true)
+    m = method == :multinomial ? 0 : method == :residual ? 1 : method == :stratified ? 2 : error("Resampling method $method not recognized.")
+    nb = cld(s.n_particles, min(block_size, s.n_particles)); T = size(observations, 2)
+    shared = ndims(observations) == 2
+    shared || size(observations, 3) == nb || error("one series per block expected: observations of size (n_obs, T, $nb)")
+    ess = Matrix{Float64}(undef, nb, T); lml = Matrix{Float64}(undef, nb, T); words = Matrix{Int32}(undef, nb, T)
+    invalid = Ref{Cint}(0)
+    _status(s, ccall((:gpf_run_blocks, libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Cint, Int64, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}),
+                     s.handle, observations, size(observations, 1), T, shared ? 1 : 0, block_size, m, sort_particles ? 1 : 0,
+                     ess_frac === nothing ? NaN : Float64(ess_frac), ess, lml, words, invalid))
+    return lml, ess, (words .& Int32(1)) .!= 0
+end
 # for b in blocks: the model arguments of state[b] (src/update.jl:12-25 on a sub-state with new_args_b) -- gpf.h gpf_set_block_params.  params: a
 # (n_params, n_blocks) Matrix, column b = block b's parameter vector in the layout of csrc/gpf_models.hpp (derived constants included), or a
 # Vector of NativeModel descriptors of the state's model; `nothing` clears them.  While set, the block-wise calls use column b for block b (this
