@@ -757,6 +757,56 @@ def pf_run_blocks(state, observations, block_size: int, method: str = "multinomi
     return BlockRun(lml.T, ess.T, (res & 1).astype(bool).T)      # (views of the library's [T][n_blocks] arrays: no transposed copies)
 
 
+BlockSweep = namedtuple("BlockSweep", ["path", "index", "lml", "ess", "resampled"])
+
+
+def pf_sweep_blocks(state, observations, reference, block_size: int, *, ancestor_sampling: bool = True, ess_frac=0.5) -> BlockSweep:
+    """One conditional SMC sweep per block in ONE launch (gpf.h gpf_sweep_blocks) -- bit for bit the loop
+
+        for t in range(T):
+            pf_resample_blocks(state, block_size, "multinomial", conditional=True, ess_frac=ess_frac, check=False,
+                               reference=reference[:, t], observations=observations[:, t])        # ancestor_sampling=False: without these two
+            pf_update_blocks(state, (), (), observations[:, t], block_size, reference=reference[:, t])
+        path, index = block_sample_trajectories(state, block_size, 1, return_indices=True)
+
+    on a state initialised with pf_initialize_blocks(..., reference=x_1) -- and WITHOUT a trajectory store: the sweep keeps its genealogy in scratch of
+    the call.  Rows, log-weights, parents, the RNG epoch (+ 2 T + 1) and the per-block observations are what the loop leaves on a twin made with
+    history=T + 1, so every later call continues identically and sweeps of T1 and T2 steps compose.  observations: (n_blocks, T, n_obs), or (T, n_obs)
+    -- one series shared by all blocks; reference: (n_blocks, T, dim), the retained path's values at the T steps being entered, all finite.
+    ess_frac=None: every block resamples at every step.
+    Returns BlockSweep(path, index, lml, ess, resampled): path (n_blocks, T + 1, dim) -- one drawn path per block, the step the state was in on entry
+    included; index (n_blocks,) -- the 1-based in-block index of the drawn final particle; lml, ess, resampled (n_blocks, T) as BlockRun.  A block with
+    NaN / +Inf weights is skipped by every resample and propagated anyway (index 0, NaN path); the call then raises "Invalid weights (NaN)." after the
+    whole sweep."""
+    if isinstance(state, DeviceParticleFilterSubState):
+        raise ErrorException("pf_sweep_blocks works on the whole filter")
+    if int(block_size) < 1:
+        raise ErrorException("block_size < 1")
+    bs = min(int(block_size), max(state.n_particles, 1))
+    nb = (state.n_particles + bs - 1) // bs
+    obs = np.ascontiguousarray(observations, np.float64)
+    if obs.ndim == 3 and obs.shape[0] == nb and obs.shape[1] >= 1:
+        shared = False
+    elif obs.ndim == 2 and obs.shape[0] >= 1:
+        shared = True
+    else:
+        raise ErrorException(f"observations of shape ({nb}, T, n_obs), or (T, n_obs) for one series shared by all blocks, expected: got {obs.shape}")
+    T = obs.shape[0] if shared else obs.shape[1]
+    ref = np.ascontiguousarray(reference, np.float64)
+    if ref.ndim != 3 or ref.shape[:2] != (nb, T):
+        raise ErrorException(f"a reference of shape ({nb}, {T}, dim) expected -- the retained path of every block at the steps being entered: got {ref.shape}")
+    path, idx = np.empty((nb, T + 1, ref.shape[2])), np.zeros(nb, np.int64)
+    ess, lml, res = np.empty((T, nb)), np.empty((T, nb)), np.zeros((T, nb), np.int32)
+    inv = C.c_int32(0)
+    st = state._L.gpf_sweep_blocks(state._h, _pd(obs), obs.shape[-1], T, int(shared), _pd(ref), ref.shape[2], int(block_size), int(bool(ancestor_sampling)),
+                                   float("nan") if ess_frac is None else float(ess_frac), _pd(path), _pi64(idx), _pd(ess), _pd(lml),
+                                   res.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(inv))
+    if st != _lib.OK:
+        raise ErrorException(state._L.gpf_last_error(state._h).decode())
+    state._n_blocks_last = 0                                     # (no pf_resample_blocks for block_resampled to refer to, as after the loop's last update)
+    return BlockSweep(path, idx, lml.T, ess.T, (res & 1).astype(bool).T)
+
+
 def pf_rejuvenate_blocks(state, kern=None, kern_args: tuple = (), n_iters: int = 1, *, method: str = "move", only_resampled: bool = False,
                          count: bool = False):
     """for b in blocks: pf_rejuvenate!(state[b], ...) with the block's own latest observation; only_resampled: only the blocks the last

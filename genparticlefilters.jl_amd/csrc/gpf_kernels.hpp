@@ -29,3 +29,4 @@
 #include "gpf_k_block_forward.hpp"
 #include "gpf_k_block_map.hpp"
 #include "gpf_k_block_run.hpp"
+#include "gpf_k_block_sweep.hpp"

@@ -311,6 +311,44 @@ gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, 
 gpf_status gpf_run_blocks(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs,
                           int64_t block_size, int32_t method, int32_t sort_particles, double ess_frac,
                           double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid);
+/* One conditional SMC sweep per block in ONE launch: the conditional filter of particle Gibbs (Andrieu, Doucet & Holenstein 2010), with ancestor
+ * sampling (PGAS; Lindsten, Jordan & Schoen 2014) where ancestor_sampling != 0, and the one path per block that the sweep exists to draw,
+ *     for t in 1:n_steps
+ *         ancestor_sampling ? gpf_resample_blocks_ancestor(h, GPF_RESAMPLE_MULTINOMIAL, block_size, ess_frac, GPF_CHECK_FALSE, obs[:, t], n_obs, ref[:, t], n_ref, NULL, NULL)
+ *                           : gpf_resample_blocks_conditional(h, GPF_RESAMPLE_MULTINOMIAL, block_size, ess_frac, GPF_CHECK_FALSE, NULL, NULL)       epoch E + 2(t-1)
+ *         gpf_update_blocks_ref(h, obs[:, t], n_obs, block_size, ref[:, t], n_ref)                                                              epoch E + 2(t-1) + 1
+ *     end
+ *     gpf_block_sample_trajectories(h, block_size, 1, 1, n_steps + 1, path_out, idx_out)                                                       epoch E + 2 n_steps
+ * on a filter initialised with gpf_initialize_blocks_ref (the initial step stays a call of its own).  The filter needs NO trajectory store: the sweep
+ * keeps its genealogy -- every step's rows and 16-bit block-local parents -- in scratch of the call, 8 W (n_steps + 1) + 2 n_steps bytes per particle.
+ * That scratch (1.8 GB at 10^6 particles, W = 2, n_steps = 100) is kept on the handle for the next call and freed only by gpf_destroy.
+ * One team per block (a wave up to 512 particles, a workgroup up to 2048) runs all steps of its block, draws its path and walks it back.
+ *   contract  on a filter at epoch E the call leaves EXACTLY what the loop leaves on a twin with a block-wise store of n_steps + 1 steps: rows,
+ *             log-weights, parents (block-local, written only when a block resamples, the last write stands), the per-block observation rows of the
+ *             last step, the block size, "no gpf_resample_blocks to refer to", the epoch E + 2 n_steps + 1 -- bit for bit, so every later call
+ *             continues identically and sweeps of T1 and T2 steps leave the state of T1 + T2 steps run the same way.  Resample slot
+ *             gid0 + b block_size + j draws under epoch E + 2(t-1), slot 0's own counter serves the ancestor draw, the propagate of particle gid runs
+ *             under E + 2(t-1) + 1, the final draw of block b reads slot b of epoch E + 2 n_steps.  Per-block parameters (gpf_set_block_params) are
+ *             used as gpf_update_blocks_ref and gpf_resample_blocks_ancestor use them.
+ *   obs       HOST, [n_blocks][n_steps][n_obs], or shared_obs != 0: [n_steps][n_obs], ONE series for all blocks.  All values finite, n_obs the model's.
+ *   ref       HOST, [n_blocks][n_steps][n_ref]: the retained path's values at the n_steps steps being entered, always per block, all finite, n_ref the
+ *             model's dimension.  obs and ref are copied to the device once per call.
+ *   outputs   HOST, each may be NULL: path_out [n_blocks][n_steps + 1][dim] -- one drawn path per block, the step the filter was in on entry included;
+ *             idx_out [n_blocks] -- the 1-based index, inside the block, of the drawn final particle; ess_out, lml_out, resampled_out [n_steps][n_blocks]
+ *             and *invalid as in gpf_run_blocks.
+ *   ess_frac  as in gpf_resample_blocks; NaN: every block resamples at every step.  A block that does not resample draws no ancestor.
+ *   weights   a block whose weights hold a NaN or +Inf is skipped by every resample and propagated anyway; it reads index 0 and a NaN path, and after the
+ *             whole sweep the call returns GPF_ERR_INVALID_WEIGHTS ("Invalid weights (NaN).").  An all -Inf block resamples with uniform weights where
+ *             its gate lets it and sets *invalid.  Ancestor weights that are invalid or all -Inf -- a reference no particle leads to -- keep ancestor 0.
+ *   timing    the launch is booked under GPF_K_STEP (gpf_kernel_timing).
+ *   refused   nothing changed, epoch included.  GPF_ERR_STATE: a sub-state view, a shard, a trajectory store of either kind, forward smoothing per
+ *             block, a keep_prev filter, strata set on the filter; GPF_ERR_INVALID_ARGUMENT: block_size < 1, a clamped block_size > 2048 or other than
+ *             the per-block parameters', n_steps < 1 or > 4096, more than 2^31 input words on the device, obs NULL, n_obs not the model's, ref NULL,
+ *             n_ref not the model's dimension, a non-finite observation or reference value; GPF_ERR_HIP: scratch that cannot be allocated.  Not offered
+ *             inside the sweep: more than one path per block, backward simulation, rejuvenation, proposals, feeding the handle's store. */
+gpf_status gpf_sweep_blocks(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs,
+                            const double* ref, int32_t n_ref, int64_t block_size, int32_t ancestor_sampling, double ess_frac,
+                            double* path_out, int64_t* idx_out, double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid);
 /* Conditional SMC, the propagation half: gpf_initialize_blocks / gpf_update_blocks with ONE PARTICLE PER BLOCK PINNED to a given value -- the
  * conditional filter of Andrieu, Doucet & Holenstein (2010), section 4.3 (step (a) / (b): "set X_n^{B_n} = the retained path, sample the other
  * N - 1 particles"), on the reference's per-view loop

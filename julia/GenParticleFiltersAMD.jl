@@ -415,6 +415,25 @@ function pf_run_blocks!(s::DeviceParticleFilterState, observations::Union{Array{
                      ess_frac === nothing ? NaN : Float64(ess_frac), ess, lml, words, invalid))
     return lml, ess, (words .& Int32(1)) .!= 0
 end
+# One conditional SMC sweep per block in ONE launch (gpf.h gpf_sweep_blocks): bit for bit T iterations of the conditional resample (with ancestor
+# sampling towards reference[:, t, b] where ancestor_sampling) and the update pinned to reference[:, t, b], then the one path per block that
+# block_sample_trajectories would draw -- on a state without a trajectory store.  observations: (n_obs, T, n_blocks), or a (n_obs, T) Matrix shared by all
+# blocks; reference: (dim, T, n_blocks), the retained paths at the T steps being entered.  Returns (path, index, lml, ess, resampled): path
+# (dim, T + 1, n_blocks), index (n_blocks) 1-based inside the block, the rest (n_blocks, T) as pf_run_blocks!.
+function pf_sweep_blocks!(s::DeviceParticleFilterState, observations::Union{Array{Float64,3},Matrix{Float64}}, reference::Array{Float64,3}, block_size::Int;
+                          ancestor_sampling::Bool=true, ess_frac=0.5)
+    nb = cld(s.n_particles, min(block_size, s.n_particles)); T = size(observations, 2)
+    shared = ndims(observations) == 2
+    shared || size(observations, 3) == nb || error("one series per block expected: observations of size (n_obs, T, $nb)")
+    (size(reference, 2) == T && size(reference, 3) == nb) || error("one retained path per block expected: reference of size (dim, $T, $nb)")
+    path = Array{Float64,3}(undef, size(reference, 1), T + 1, nb); index = Vector{Int64}(undef, nb)
+    ess = Matrix{Float64}(undef, nb, T); lml = Matrix{Float64}(undef, nb, T); words = Matrix{Int32}(undef, nb, T)
+    invalid = Ref{Cint}(0)
+    _status(s, ccall((:gpf_sweep_blocks, libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Cint, Ptr{Cdouble}, Cint, Int64, Cint, Cdouble, Ptr{Cdouble}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}),
+                     s.handle, observations, size(observations, 1), T, shared ? 1 : 0, reference, size(reference, 1), block_size, ancestor_sampling ? 1 : 0,
+                     ess_frac === nothing ? NaN : Float64(ess_frac), path, index, ess, lml, words, invalid))
+    return path, index, lml, ess, (words .& Int32(1)) .!= 0
+end
 # for b in blocks: the model arguments of state[b] (src/update.jl:12-25 on a sub-state with new_args_b) -- gpf.h gpf_set_block_params.  params: a
 # (n_params, n_blocks) Matrix, column b = block b's parameter vector in the layout of csrc/gpf_models.hpp (derived constants included), or a
 # Vector of NativeModel descriptors of the state's model; `nothing` clears them.  While set, the block-wise calls use column b for block b (this
