@@ -757,6 +757,54 @@ def pf_run_blocks(state, observations, block_size: int, method: str = "multinomi
     return BlockRun(lml.T, ess.T, (res & 1).astype(bool).T)      # (views of the library's [T][n_blocks] arrays: no transposed copies)
 
 
+BlockRunMoves = namedtuple("BlockRunMoves", ["lml", "ess", "resampled", "accepted"])
+
+
+def pf_run_blocks_rejuvenate(state, observations, block_size: int, method: str = "multinomial", *, rejuvenate: str = "move", n_iters: int = 1,
+                             ess_frac=0.5, sort_particles: bool = True) -> BlockRunMoves:
+    """The whole README loop per block in ONE launch (gpf.h gpf_run_blocks_rejuvenate) -- bit for bit the loop
+
+        for t in range(T):
+            pf_resample_blocks(state, block_size, method, ess_frac=ess_frac, sort_particles=sort_particles, check=False)
+            pf_rejuvenate_blocks(state, None, (), n_iters, method=rejuvenate, only_resampled=True)
+            pf_update_blocks(state, (t,), (None,), observations[:, t], block_size)
+
+    on a keep_prev=True state whose last step was block-wise with this block size (pf_initialize_blocks, pf_update_blocks, or this call): full rows,
+    log-weights, parents, the RNG epoch (+ 3 T) and the per-block observations are what the loop leaves, so every later call continues identically and
+    runs of T1 and T2 steps compose.  The move of step t runs in the blocks that resampled at step t, on their latest observation.  observations,
+    ess_frac, sort_particles and invalid weights as in pf_run_blocks; rejuvenate: "move" (MH accept) or "reweight".
+    Returns BlockRunMoves(lml, ess, resampled, accepted), each (n_blocks, T): the first three as BlockRun; accepted (int64) -- the proposals block b
+    accepted at step t ("reweight": its particles x n_iters), 0 where it did not resample.  accepted.sum(axis=0) is what the loop's
+    pf_rejuvenate_blocks(..., count=True) returns."""
+    if method not in ("multinomial", "residual", "stratified"):
+        raise ErrorException(f"Resampling method {method} not recognized.")
+    if rejuvenate not in REJUVENATE_METHODS:
+        raise ErrorException(f"Method {rejuvenate} not recognized.")
+    if isinstance(state, DeviceParticleFilterSubState):
+        raise ErrorException("pf_run_blocks_rejuvenate works on the whole filter")
+    if int(block_size) < 1:
+        raise ErrorException("block_size < 1")
+    bs = min(int(block_size), max(state.n_particles, 1))
+    nb = (state.n_particles + bs - 1) // bs
+    obs = np.ascontiguousarray(observations, np.float64)
+    if obs.ndim == 3 and obs.shape[0] == nb and obs.shape[1] >= 1:
+        shared = False
+    elif obs.ndim == 2 and obs.shape[0] >= 1:
+        shared = True
+    else:
+        raise ErrorException(f"observations of shape ({nb}, T, n_obs), or (T, n_obs) for one series shared by all blocks, expected: got {obs.shape}")
+    T = obs.shape[0] if shared else obs.shape[1]
+    ess, lml, res, acc = np.empty((T, nb)), np.empty((T, nb)), np.zeros((T, nb), np.int32), np.zeros((T, nb), np.int64)
+    inv = C.c_int32(0)
+    st = state._L.gpf_run_blocks_rejuvenate(state._h, _pd(obs), obs.shape[-1], T, int(shared), int(block_size), RESAMPLE_METHODS[method], int(sort_particles),
+                                            float("nan") if ess_frac is None else float(ess_frac), REJUVENATE_METHODS[rejuvenate], int(n_iters),
+                                            _pd(ess), _pd(lml), res.ctypes.data_as(C.POINTER(C.c_int32)), _pi64(acc), C.byref(inv))
+    if st != _lib.OK:
+        raise ErrorException(state._L.gpf_last_error(state._h).decode())
+    state._n_blocks_last = 0                                     # (no pf_resample_blocks for block_resampled to refer to, as after the loop's last update)
+    return BlockRunMoves(lml.T, ess.T, (res & 1).astype(bool).T, acc.T)
+
+
 BlockSweep = namedtuple("BlockSweep", ["path", "index", "lml", "ess", "resampled"])
 
 

@@ -274,6 +274,7 @@ struct __attribute__((visibility("hidden"))) gpf_filter : gpfh::Bufs {
     // packed into, and its outputs [ess | lml] x [n_steps][n_blocks], [n_steps][n_blocks] resample words.  Scratch of one call (it ends with a
     // synchronisation), kept for the next
     Dev<double> run_in, run_stats; Pinned<double> h_run_in; Dev<int32_t> run_words;
+    Dev<int64_t> run_acc;                // gpf_run_blocks_rejuvenate: [n_steps][n_blocks] accepted proposals, where the caller asks for them
     // gpf_sweep_blocks (which also uses the four above, with [... | n_blocks x n_steps x dim reference] behind the observations): the genealogy slabs
     // [n_steps + 1][n][W] rows and [n_steps][n] 16-bit block-local parents, and the outputs [n_blocks][n_steps + 1][dim] path, [n_blocks] index.  Scratch
     // of one call, kept for the next
@@ -739,6 +740,8 @@ void launch_block_map(gpf_filter* h, const MapArgs& a, const AncArgs& x);       
 void launch_block_run(gpf_filter* h, const RunArgs& a, int method);               // k_block_run<model, W, method, TEAM, ITEMS> by team_dispatch; method 0 | 1 | 2
 // ---- defined in libgpf_sweep.hip
 void launch_block_sweep(gpf_filter* h, const SweepArgs& a, bool ancestor_sampling);   // k_block_sweep<model, W, AS, TEAM, ITEMS> by team_dispatch
+// ---- defined in libgpf_run_move.hip
+void launch_block_run_move(gpf_filter* h, const RunMoveArgs& a, int method, bool reweight);   // k_block_run_move<model, W, method, reweight, TEAM, ITEMS> by team_dispatch
 // ---- defined in libgpf_forward.hip: the forward-only smoother's records (hist_begin_step / hist_on_resample call the first two) and launches
 gpf_status fwd_begin_step(gpf_filter* h, bool first);             // first: step 1 begins, the statistics are reset; else the step that ends is closed in its final order
 gpf_status fwd_on_resample(gpf_filter* h, int64_t block_size);    // this call's parents into the current step's map (block_size > 0: block-local, h->blk_mask says which)

@@ -30,3 +30,4 @@
 #include "gpf_k_block_map.hpp"
 #include "gpf_k_block_run.hpp"
 #include "gpf_k_block_sweep.hpp"
+#include "gpf_k_block_run_move.hpp"

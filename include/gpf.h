@@ -311,6 +311,36 @@ gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, 
 gpf_status gpf_run_blocks(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs,
                           int64_t block_size, int32_t method, int32_t sort_particles, double ess_frac,
                           double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid);
+/* The whole README loop per block in ONE launch: gpf_run_blocks with the rejuvenation moves inside the `if` (README.md:60-79),
+ *     for t in 1:n_steps
+ *         gpf_resample_blocks(h, method, block_size, NaN, sort_particles, ess_frac, GPF_CHECK_FALSE, NULL, NULL);      epoch E + 3(t-1)
+ *         gpf_rejuvenate_blocks(h, rejuvenate_method, n_iters, 1, &acc_t);                                             epoch E + 3(t-1) + 1
+ *         gpf_update_blocks(h, obs[:, t], n_obs, block_size);                                                          epoch E + 3(t-1) + 2
+ *     end
+ * on a keep_prev = 1 filter whose per-block observations of this block size are in force (its last step was gpf_initialize_blocks, gpf_update_blocks
+ * or one of these runs with this block size).  One team per block as in gpf_run_blocks; a slot loads its ancestor's row [x | x_{t-1}] once, moves x in
+ * registers, propagates from the moved x and stores [x_new | moved x] once.
+ *   contract  the call leaves EXACTLY what the loop leaves, bit for bit: full rows (latent and x_{t-1} columns), log-weights, parents (block-local, the
+ *             last write stands), the epoch E + 3 n_steps, has_prev, the per-block observation rows of the last step, the block size, "no
+ *             gpf_resample_blocks to refer to", the forgotten weight summary -- so later calls continue identically and runs of T1 and T2 steps equal
+ *             one of T1 + T2.  The move of step t runs in every block that resampled at step t, and only there (a block that did not is untouched by
+ *             it; the epoch advances all the same); it conditions on the block's latest observation -- obs[:, t-1], at t = 1 the handle's per-block
+ *             row -- with has_prev the handle's at t = 1 and true afterwards (right after gpf_initialize_blocks the first move re-draws from the
+ *             prior).  RNG counters and floating-point order are gpf_rejuvenate_blocks' (the selection variant): particle gid, move-accept under
+ *             TAG_MOVE with proposal block it (NBLK + 1) and uniform block + NBLK, move-reweight under TAG_REWEIGHT with block it NBLK and
+ *             lw = (new weight + sum of relative weights) + log-likelihood.  Per-block parameters (gpf_set_block_params) serve move and propagate.
+ *   obs, ess_out, lml_out, resampled_out, invalid, ess_frac, weights, timing   as in gpf_run_blocks.
+ *   accepted_out  HOST int64 [n_steps][n_blocks], may be NULL: block b's share of the loop's acc_t -- the accepted proposals for GPF_REJUVENATE_MOVE,
+ *             (particles of the block) x n_iters for GPF_REJUVENATE_REWEIGHT where the block resampled; 0 where it did not.
+ *   n_iters   >= 0; 0 moves nothing, as in the loop.
+ *   refused   nothing changed, epoch included.  Everything gpf_run_blocks refuses, with its status codes, except keep_prev; GPF_ERR_STATE: keep_prev = 0
+ *             (gpf_rejuvenate_blocks' text), no per-block observations in force or ones of another block size; GPF_ERR_UNKNOWN_METHOD: rejuvenate_method
+ *             ("Method not recognized."); GPF_ERR_INVALID_ARGUMENT: n_iters < 0.  Not offered inside the run: native move proposals
+ *             (gpf_rejuvenate_with_proposal), moves outside the `if` (only_resampled = 0), a store, strata, a reference path. */
+gpf_status gpf_run_blocks_rejuvenate(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs,
+                                     int64_t block_size, int32_t method, int32_t sort_particles, double ess_frac,
+                                     int32_t rejuvenate_method, int32_t n_iters,
+                                     double* ess_out, double* lml_out, int32_t* resampled_out, int64_t* accepted_out, int32_t* invalid);
 /* One conditional SMC sweep per block in ONE launch: the conditional filter of particle Gibbs (Andrieu, Doucet & Holenstein 2010), with ancestor
  * sampling (PGAS; Lindsten, Jordan & Schoen 2014) where ancestor_sampling != 0, and the one path per block that the sweep exists to draw,
  *     for t in 1:n_steps

@@ -415,6 +415,25 @@ function pf_run_blocks!(s::DeviceParticleFilterState, observations::Union{Array{
                      ess_frac === nothing ? NaN : Float64(ess_frac), ess, lml, words, invalid))
     return lml, ess, (words .& Int32(1)) .!= 0
 end
+# The whole README loop per block in ONE launch (gpf.h gpf_run_blocks_rejuvenate): pf_run_blocks! with
+#     pf_rejuvenate_blocks!(s, nothing, (), n_iters; method=rejuvenate, only_resampled=true)
+# between the resample and the update of every step, on a keep_prev state whose last step was block-wise with this block size.  Returns
+# (lml, ess, resampled, accepted), each (n_blocks, T); accepted: the proposals block b accepted at step t (:reweight: its particles x n_iters), 0 where
+# it did not resample.
+function pf_run_blocks_rejuvenate!(s::DeviceParticleFilterState, observations::Union{Array{Float64,3},Matrix{Float64}}, block_size::Int, method::Symbol=:multinomial;
+                                   rejuvenate::Symbol=:move, n_iters::Int=1, ess_frac=0.5, sort_particles::Bool=true)
+    m = method == :multinomial ? 0 : method == :residual ? 1 : method == :stratified ? 2 : error("Resampling method $method not recognized.")
+    r = rejuvenate == :move ? 0 : rejuvenate == :reweight ? 1 : error("Method $rejuvenate not recognized.")
+    nb = cld(s.n_particles, min(block_size, s.n_particles)); T = size(observations, 2)
+    shared = ndims(observations) == 2
+    shared || size(observations, 3) == nb || error("one series per block expected: observations of size (n_obs, T, $nb)")
+    ess = Matrix{Float64}(undef, nb, T); lml = Matrix{Float64}(undef, nb, T); words = Matrix{Int32}(undef, nb, T); accepted = Matrix{Int64}(undef, nb, T)
+    invalid = Ref{Cint}(0)
+    _status(s, ccall((:gpf_run_blocks_rejuvenate, libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Cint, Int64, Cint, Cint, Cdouble, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Int64}, Ptr{Cint}),
+                     s.handle, observations, size(observations, 1), T, shared ? 1 : 0, block_size, m, sort_particles ? 1 : 0,
+                     ess_frac === nothing ? NaN : Float64(ess_frac), r, n_iters, ess, lml, words, accepted, invalid))
+    return lml, ess, (words .& Int32(1)) .!= 0, accepted
+end
 # One conditional SMC sweep per block in ONE launch (gpf.h gpf_sweep_blocks): bit for bit T iterations of the conditional resample (with ancestor
 # sampling towards reference[:, t, b] where ancestor_sampling) and the update pinned to reference[:, t, b], then the one path per block that
 # block_sample_trajectories would draw -- on a state without a trajectory store.  observations: (n_obs, T, n_blocks), or a (n_obs, T) Matrix shared by all
