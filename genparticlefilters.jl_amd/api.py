@@ -826,8 +826,14 @@ def pf_sweep_blocks(state, observations, reference, block_size: int, *, ancestor
     included; index (n_blocks,) -- the 1-based in-block index of the drawn final particle; lml, ess, resampled (n_blocks, T) as BlockRun.  A block with
     NaN / +Inf weights is skipped by every resample and propagated anyway (index 0, NaN path); the call then raises "Invalid weights (NaN)." after the
     whole sweep."""
+    path, idx, lml, ess, res = _sweep_call(state, "pf_sweep_blocks", observations, reference, block_size, ancestor_sampling, ess_frac, False)
+    return BlockSweep(path, idx, lml, ess, res)
+
+
+def _sweep_call(state, who, observations, reference, block_size, ancestor_sampling, ess_frac, backward):
+    """The argument checks and the library call pf_sweep_blocks and pf_sweep_blocks_backward share; backward: an index per step, not one per block."""
     if isinstance(state, DeviceParticleFilterSubState):
-        raise ErrorException("pf_sweep_blocks works on the whole filter")
+        raise ErrorException(f"{who} works on the whole filter")
     if int(block_size) < 1:
         raise ErrorException("block_size < 1")
     bs = min(int(block_size), max(state.n_particles, 1))
@@ -843,16 +849,37 @@ def pf_sweep_blocks(state, observations, reference, block_size: int, *, ancestor
     ref = np.ascontiguousarray(reference, np.float64)
     if ref.ndim != 3 or ref.shape[:2] != (nb, T):
         raise ErrorException(f"a reference of shape ({nb}, {T}, dim) expected -- the retained path of every block at the steps being entered: got {ref.shape}")
-    path, idx = np.empty((nb, T + 1, ref.shape[2])), np.zeros(nb, np.int64)
+    path, idx = np.empty((nb, T + 1, ref.shape[2])), np.zeros((nb, T + 1) if backward else nb, np.int64)
     ess, lml, res = np.empty((T, nb)), np.empty((T, nb)), np.zeros((T, nb), np.int32)
     inv = C.c_int32(0)
-    st = state._L.gpf_sweep_blocks(state._h, _pd(obs), obs.shape[-1], T, int(shared), _pd(ref), ref.shape[2], int(block_size), int(bool(ancestor_sampling)),
-                                   float("nan") if ess_frac is None else float(ess_frac), _pd(path), _pi64(idx), _pd(ess), _pd(lml),
-                                   res.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(inv))
+    fn = state._L.gpf_sweep_blocks_backward if backward else state._L.gpf_sweep_blocks
+    st = fn(state._h, _pd(obs), obs.shape[-1], T, int(shared), _pd(ref), ref.shape[2], int(block_size), int(bool(ancestor_sampling)),
+            float("nan") if ess_frac is None else float(ess_frac), _pd(path), _pi64(idx), _pd(ess), _pd(lml),
+            res.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(inv))
     if st != _lib.OK:
         raise ErrorException(state._L.gpf_last_error(state._h).decode())
     state._n_blocks_last = 0                                     # (no pf_resample_blocks for block_resampled to refer to, as after the loop's last update)
-    return BlockSweep(path, idx, lml.T, ess.T, (res & 1).astype(bool).T)
+    return path, idx, lml.T, ess.T, (res & 1).astype(bool).T
+
+
+BlockSweepBackward = namedtuple("BlockSweepBackward", ["path", "indices", "lml", "ess", "resampled"])
+
+
+def pf_sweep_blocks_backward(state, observations, reference, block_size: int, *, ancestor_sampling: bool = True, ess_frac=0.5) -> BlockSweepBackward:
+    """One sweep of particle Gibbs with backward simulation per block in ONE launch (gpf.h gpf_sweep_blocks_backward) -- bit for bit pf_sweep_blocks'
+    loop followed by
+
+        path, indices = block_backward_trajectories(state, block_size, 1, return_indices=True)      # [:, 0] of both
+
+    on a twin made with pf_initialize_blocks(..., history=T + 1, history_weights=True, reference=x_1) -- on a state WITHOUT a trajectory store: beside the
+    sweep's genealogy the call keeps every step's log-weights in its scratch.  The path's particle at every step below the last is drawn among all of
+    the block's particles of that step with weights w_s^i f(x_{s+1} | x_s^i), not taken from the recorded parents, so the paths of a block whose
+    genealogy has coalesced still differ in their early steps.  ancestor_sampling=False: the plain conditional filter and the backward draw, the
+    classic PGBS.  Arguments as pf_sweep_blocks; the state and the RNG epoch (+ 3 T + 1) are what the twin is left with.
+    Returns BlockSweepBackward(path, indices, lml, ess, resampled): path (n_blocks, T + 1, dim); indices (n_blocks, T + 1) -- 1-based and global, in each
+    step's final order; lml, ess, resampled (n_blocks, T) as BlockSweep.  Backward weights that are invalid or all -Inf at a step: the recorded parent.
+    A block with NaN / +Inf weights reads indices 0 and a NaN path; the call then raises "Invalid weights (NaN)." after the whole sweep."""
+    return BlockSweepBackward(*_sweep_call(state, "pf_sweep_blocks_backward", observations, reference, block_size, ancestor_sampling, ess_frac, True))
 
 
 def pf_rejuvenate_blocks(state, kern=None, kern_args: tuple = (), n_iters: int = 1, *, method: str = "move", only_resampled: bool = False,

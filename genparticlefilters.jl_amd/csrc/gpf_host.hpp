@@ -279,6 +279,8 @@ struct __attribute__((visibility("hidden"))) gpf_filter : gpfh::Bufs {
     // [n_steps + 1][n][W] rows and [n_steps][n] 16-bit block-local parents, and the outputs [n_blocks][n_steps + 1][dim] path, [n_blocks] index.  Scratch
     // of one call, kept for the next
     Dev<double> sweep_rows, sweep_path; Dev<uint16_t> sweep_par; Dev<int64_t> sweep_idx;
+    // gpf_sweep_blocks_backward (which uses the four above, the index as [n_blocks][n_steps + 1]): the log-weight slabs [n_steps][n] beside the rows
+    Dev<double> sweep_lws;
     // gpf_resample_across_blocks: the planner filter of n_blocks particles whose log-weights are the blocks' log-ML estimates (its ancestors name the
     // source block of every block; it runs on this filter's stream), the second buffers the per-block rows are gathered into (swapped with
     // blk_params / blk_obs), and the 1-based block ancestors of the last call that fired with the buffers they refer to (gpf_block_ancestors)
@@ -740,6 +742,8 @@ void launch_block_map(gpf_filter* h, const MapArgs& a, const AncArgs& x);       
 void launch_block_run(gpf_filter* h, const RunArgs& a, int method);               // k_block_run<model, W, method, TEAM, ITEMS> by team_dispatch; method 0 | 1 | 2
 // ---- defined in libgpf_sweep.hip
 void launch_block_sweep(gpf_filter* h, const SweepArgs& a, bool ancestor_sampling);   // k_block_sweep<model, W, AS, TEAM, ITEMS> by team_dispatch
+// ---- defined in libgpf_sweep_back.hip
+void launch_block_sweep_back(gpf_filter* h, const SweepBackArgs& a, bool ancestor_sampling);   // k_block_sweep_back<model, W, AS, TEAM, ITEMS> by team_dispatch
 // ---- defined in libgpf_run_move.hip
 void launch_block_run_move(gpf_filter* h, const RunMoveArgs& a, int method, bool reweight);   // k_block_run_move<model, W, method, reweight, TEAM, ITEMS> by team_dispatch
 // ---- defined in libgpf_forward.hip: the forward-only smoother's records (hist_begin_step / hist_on_resample call the first two) and launches

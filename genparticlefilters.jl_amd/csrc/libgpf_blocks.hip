@@ -541,6 +541,54 @@ gpf_status series_finish(gpf_filter* h, int64_t block_size, int64_t nblocks, siz
     return GPF_OK;
 }
 
+// gpf_sweep_blocks and gpf_sweep_blocks_backward: one order of checks, one upload, one launch.  backward: the path is the backward-simulation draw --
+// both outputs are needed, the log-weight slabs join the scratch, the index is per step and the draw takes n_steps + 1 epochs instead of one
+gpf_status sweep_impl(gpf_handle h, const std::string& who, bool backward, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs,
+                      const double* ref, int32_t n_ref, int64_t block_size, int32_t ancestor_sampling, double ess_frac, double* path_out, int64_t* idx_out,
+                      double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid)
+{
+    gpf_status s = block_gate(h, block_size, who.c_str(), GATE_SERIES);
+    if (s || (s = series_checks(h, who, "sweep", "gpf_resample_blocks_ancestor / gpf_update_blocks_ref, which records one", block_size, n_steps))) return s;
+    if (backward && (!path_out || !idx_out)) return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": null path / index output");
+    const int64_t nblocks = (h->n + block_size - 1) / block_size, obs_blocks = shared_obs ? 1 : nblocks;
+    if ((s = block_obs_check(h, obs, n_obs))) return s;          // (as gpf_update_blocks_ref refuses them)
+    const int dim = model_dim(h->cfg.model);
+    if (!ref || n_ref != dim)                                    // (block_ref_checks' refusal)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": the reference has " + std::to_string(dim) + " values per block (the model's latent columns)");
+    const int64_t obs_words = (int64_t)n_steps * obs_blocks * n_obs, ref_words = (int64_t)n_steps * nblocks * dim;
+    if (obs_words + ref_words > ((int64_t)1 << 31))
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": the observations and the reference of the call exceed 2^31 words on the device: fewer steps per call");
+    // ---- the call's input [MAX_PARAMS parameters | observations | reference] into the pinned buffer
+    const size_t in_words = (size_t)MAX_PARAMS + (size_t)obs_words + (size_t)ref_words, cells = (size_t)n_steps * (size_t)nblocks;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if ((s = h->h_run_in.grow(h, in_words)) || (s = series_obs_in(h, who, obs, obs_words, n_obs, n_steps, shared_obs != 0))) return s;
+    if (const int64_t k = copy_finite(h->h_run_in + MAX_PARAMS + obs_words, ref, ref_words); k >= 0)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": the reference of block " + std::to_string(k / dim / n_steps) + " is not finite (step " +
+                    std::to_string(k / dim % n_steps + 1) + ")");
+    if (h->W != 2 && h->W != 4) return fail(h, GPF_ERR_STATE, "row width");
+    if ((s = check_ready(h)) || (s = materialize(h))) return s;
+    // ---- device scratch: the genealogy slabs (rows and 16-bit parents; backward: log-weights) and the two outputs of the draw, then what every series has
+    const size_t path_words = (size_t)nblocks * ((size_t)n_steps + 1) * (size_t)dim, idx_words = backward ? (size_t)nblocks * ((size_t)n_steps + 1) : (size_t)nblocks;
+    if ((s = h->sweep_rows.grow(h, ((size_t)n_steps + 1) * (size_t)h->n * (size_t)h->W)) || (s = h->sweep_par.grow(h, (size_t)n_steps * (size_t)h->n)) ||
+        (backward && (s = h->sweep_lws.grow(h, (size_t)n_steps * (size_t)h->n))) ||
+        (s = h->sweep_path.grow(h, path_words)) || (s = h->sweep_idx.grow(h, idx_words)) || (s = series_upload(h, nblocks, in_words, cells))) return s;
+    SweepBackArgs ab{};
+    SweepArgs& a = ab.s;
+    a.rows = h->rows[h->cur]; a.slabs = h->sweep_rows; a.par = h->sweep_par; a.lw = h->lw; a.anc = h->anc;
+    a.n = h->n; a.nb = block_size; a.nblocks = nblocks; a.gid0 = h->cfg.gid0; a.seed = h->cfg.seed; a.epoch = h->epoch; a.n_steps = n_steps;
+    a.ess_frac = ess_frac == ess_frac ? ess_frac : -1.0;
+    a.P = h->run_in; a.blk_params = h->bp_size > 0 ? h->blk_params.p : nullptr;
+    a.obs = h->run_in + MAX_PARAMS; a.obs_blocks = obs_blocks; a.n_obs = n_obs; a.ref = h->run_in + MAX_PARAMS + obs_words;
+    a.lml_est = &h->sc->lml_est;
+    a.ess_out = h->run_stats; a.lml_out = h->run_stats + cells; a.res_out = h->run_words; a.flags_out = h->blk_mask; a.blk_obs = h->blk_obs;
+    a.path = h->sweep_path; a.idx_out = h->sweep_idx;
+    ab.lws = backward ? h->sweep_lws.p : nullptr;
+    if ((s = timed(h, GPF_K_STEP, [&] { if (backward) launch_block_sweep_back(h, ab, ancestor_sampling != 0); else launch_block_sweep(h, a, ancestor_sampling != 0); }))) return s;
+    // (the loop's 2 n_steps epochs, then one for the ancestral draw; the backward draw takes one more per step below the last)
+    return series_finish(h, block_size, nblocks, cells, (backward ? 3u : 2u) * (uint32_t)n_steps + 1u, {h->sweep_path, path_out, path_words * sizeof(double)},
+                         {h->sweep_idx, idx_out, idx_words * sizeof(int64_t)}, ess_out, lml_out, resampled_out, invalid);
+}
+
 } // namespace
 } // namespace gpfh
 
@@ -800,42 +848,17 @@ gpf_status gpf_sweep_blocks(gpf_handle h, const double* obs, int32_t n_obs, int3
                             int64_t block_size, int32_t ancestor_sampling, double ess_frac, double* path_out, int64_t* idx_out,
                             double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid)
 {
-    const std::string who = "gpf_sweep_blocks";
-    gpf_status s = block_gate(h, block_size, who.c_str(), GATE_SERIES);
-    if (s || (s = series_checks(h, who, "sweep", "gpf_resample_blocks_ancestor / gpf_update_blocks_ref, which records one", block_size, n_steps))) return s;
-    const int64_t nblocks = (h->n + block_size - 1) / block_size, obs_blocks = shared_obs ? 1 : nblocks;
-    if ((s = block_obs_check(h, obs, n_obs))) return s;          // (as gpf_update_blocks_ref refuses them)
-    const int dim = model_dim(h->cfg.model);
-    if (!ref || n_ref != dim)                                    // (block_ref_checks' refusal)
-        return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": the reference has " + std::to_string(dim) + " values per block (the model's latent columns)");
-    const int64_t obs_words = (int64_t)n_steps * obs_blocks * n_obs, ref_words = (int64_t)n_steps * nblocks * dim;
-    if (obs_words + ref_words > ((int64_t)1 << 31))
-        return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": the observations and the reference of the call exceed 2^31 words on the device: fewer steps per call");
-    // ---- the call's input [MAX_PARAMS parameters | observations | reference] into the pinned buffer
-    const size_t in_words = (size_t)MAX_PARAMS + (size_t)obs_words + (size_t)ref_words, cells = (size_t)n_steps * (size_t)nblocks;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if ((s = h->h_run_in.grow(h, in_words)) || (s = series_obs_in(h, who, obs, obs_words, n_obs, n_steps, shared_obs != 0))) return s;
-    if (const int64_t k = copy_finite(h->h_run_in + MAX_PARAMS + obs_words, ref, ref_words); k >= 0)
-        return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": the reference of block " + std::to_string(k / dim / n_steps) + " is not finite (step " +
-                    std::to_string(k / dim % n_steps + 1) + ")");
-    if (h->W != 2 && h->W != 4) return fail(h, GPF_ERR_STATE, "row width");
-    if ((s = check_ready(h)) || (s = materialize(h))) return s;
-    // ---- device scratch: the genealogy slabs (rows and 16-bit parents) and the two outputs of the draw, then what every series has
-    const size_t path_words = (size_t)nblocks * ((size_t)n_steps + 1) * (size_t)dim;
-    if ((s = h->sweep_rows.grow(h, ((size_t)n_steps + 1) * (size_t)h->n * (size_t)h->W)) || (s = h->sweep_par.grow(h, (size_t)n_steps * (size_t)h->n)) ||
-        (s = h->sweep_path.grow(h, path_words)) || (s = h->sweep_idx.grow(h, (size_t)nblocks)) || (s = series_upload(h, nblocks, in_words, cells))) return s;
-    SweepArgs a{};
-    a.rows = h->rows[h->cur]; a.slabs = h->sweep_rows; a.par = h->sweep_par; a.lw = h->lw; a.anc = h->anc;
-    a.n = h->n; a.nb = block_size; a.nblocks = nblocks; a.gid0 = h->cfg.gid0; a.seed = h->cfg.seed; a.epoch = h->epoch; a.n_steps = n_steps;
-    a.ess_frac = ess_frac == ess_frac ? ess_frac : -1.0;
-    a.P = h->run_in; a.blk_params = h->bp_size > 0 ? h->blk_params.p : nullptr;
-    a.obs = h->run_in + MAX_PARAMS; a.obs_blocks = obs_blocks; a.n_obs = n_obs; a.ref = h->run_in + MAX_PARAMS + obs_words;
-    a.lml_est = &h->sc->lml_est;
-    a.ess_out = h->run_stats; a.lml_out = h->run_stats + cells; a.res_out = h->run_words; a.flags_out = h->blk_mask; a.blk_obs = h->blk_obs;
-    a.path = h->sweep_path; a.idx_out = h->sweep_idx;
-    if ((s = timed(h, GPF_K_STEP, [&] { launch_block_sweep(h, a, ancestor_sampling != 0); }))) return s;
-    return series_finish(h, block_size, nblocks, cells, 2u * (uint32_t)n_steps + 1u, {h->sweep_path, path_out, path_words * sizeof(double)},
-                         {h->sweep_idx, idx_out, (size_t)nblocks * sizeof(int64_t)}, ess_out, lml_out, resampled_out, invalid);
+    return sweep_impl(h, "gpf_sweep_blocks", false, obs, n_obs, n_steps, shared_obs, ref, n_ref, block_size, ancestor_sampling, ess_frac, path_out, idx_out,
+                      ess_out, lml_out, resampled_out, invalid);
+}
+// the same sweep with the path drawn by backward simulation -- gpf_block_backward_sample with n_samples = 1 on a store that records weights -- inside
+// the launch (k_block_sweep_back, libgpf_sweep_back.hip) -- gpf.h.  One more slab of scratch, an index per step, n_steps more epochs
+gpf_status gpf_sweep_blocks_backward(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs, const double* ref, int32_t n_ref,
+                                     int64_t block_size, int32_t ancestor_sampling, double ess_frac, double* path_out, int64_t* idx_out,
+                                     double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid)
+{
+    return sweep_impl(h, "gpf_sweep_blocks_backward", true, obs, n_obs, n_steps, shared_obs, ref, n_ref, block_size, ancestor_sampling, ess_frac, path_out,
+                      idx_out, ess_out, lml_out, resampled_out, invalid);
 }
 gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, int32_t only_resampled, uint64_t* n_accepted)
 {

@@ -379,6 +379,27 @@ gpf_status gpf_run_blocks_rejuvenate(gpf_handle h, const double* obs, int32_t n_
 gpf_status gpf_sweep_blocks(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs,
                             const double* ref, int32_t n_ref, int64_t block_size, int32_t ancestor_sampling, double ess_frac,
                             double* path_out, int64_t* idx_out, double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid);
+/* The same sweep with the path drawn by BACKWARD SIMULATION (Whiteley 2010; Lindsten & Schoen 2013): particle Gibbs with backward simulation, with
+ * ancestor sampling in the forward part where ancestor_sampling != 0 and the classic PGBS where it is 0.  gpf_sweep_blocks' loop, then
+ *     gpf_block_backward_sample(block_size, n_samples = 1, steps 1 .. n_steps + 1)
+ * in ONE launch, on a filter WITHOUT a store: beside gpf_sweep_blocks' genealogy the call keeps every step's log-weights, 8 n_steps bytes per
+ * particle more scratch.  After the last step the block's team draws the final particle from the weights and then, per step down, draws the
+ * particle of the step below among ALL of the block's particles of that step, with weights w_s^i f(x_{s+1} | x_s^i) -- not its recorded parent.
+ *   contract  on a filter at epoch E the call leaves EXACTLY what gpf_sweep_blocks' loop followed by gpf_block_backward_sample leaves on a twin with
+ *             a block-wise store of n_steps + 1 steps that records weights (gpf_history_enable_blocks_weights): the handle state as gpf_sweep_blocks
+ *             describes it, with the epoch E + 3 n_steps + 1; the path and the indices of draw 0 of every block.  The forward part uses
+ *             gpf_sweep_blocks' counters; the final draw of block b reads slot b of epoch E + 2 n_steps, the draw of the particle of store step s
+ *             (0-based) slot b of epoch E + 2 n_steps + (n_steps - s).
+ *   arguments as gpf_sweep_blocks, except
+ *   outputs   path_out [n_blocks][n_steps + 1][dim] and idx_out [n_blocks][n_steps + 1] -- the 1-based GLOBAL index, in each step's final order, of the
+ *             path's particle (gpf_block_backward_sample's idx_out) -- are both needed; the others may be NULL.
+ *   weights   backward weights of a step that are invalid or all -Inf: the path takes the recorded parent there (where the block resampled at that
+ *             step; the same particle where it did not).  A block whose final weights hold a NaN or +Inf reads indices 0 and a NaN path, and the
+ *             call returns GPF_ERR_INVALID_WEIGHTS after the whole sweep.
+ *   refused   nothing changed: everything gpf_sweep_blocks refuses, and GPF_ERR_INVALID_ARGUMENT for path_out or idx_out NULL. */
+gpf_status gpf_sweep_blocks_backward(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs,
+                                     const double* ref, int32_t n_ref, int64_t block_size, int32_t ancestor_sampling, double ess_frac,
+                                     double* path_out, int64_t* idx_out, double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid);
 /* Conditional SMC, the propagation half: gpf_initialize_blocks / gpf_update_blocks with ONE PARTICLE PER BLOCK PINNED to a given value -- the
  * conditional filter of Andrieu, Doucet & Holenstein (2010), section 4.3 (step (a) / (b): "set X_n^{B_n} = the retained path, sample the other
  * N - 1 particles"), on the reference's per-view loop

@@ -453,6 +453,23 @@ function pf_sweep_blocks!(s::DeviceParticleFilterState, observations::Union{Arra
                      ess_frac === nothing ? NaN : Float64(ess_frac), path, index, ess, lml, words, invalid))
     return path, index, lml, ess, (words .& Int32(1)) .!= 0
 end
+# The same sweep with the path drawn by backward simulation (gpf.h gpf_sweep_blocks_backward): pf_sweep_blocks!' loop followed by
+# block_backward_trajectories(s, block_size, 1) on a twin whose store records weights, in ONE launch and without a store.  Arguments as pf_sweep_blocks!.
+# Returns (path, indices, lml, ess, resampled): indices (T + 1, n_blocks), 1-based and global, in each step's final order.
+function pf_sweep_blocks_backward!(s::DeviceParticleFilterState, observations::Union{Array{Float64,3},Matrix{Float64}}, reference::Array{Float64,3}, block_size::Int;
+                                   ancestor_sampling::Bool=true, ess_frac=0.5)
+    nb = cld(s.n_particles, min(block_size, s.n_particles)); T = size(observations, 2)
+    shared = ndims(observations) == 2
+    shared || size(observations, 3) == nb || error("one series per block expected: observations of size (n_obs, T, $nb)")
+    (size(reference, 2) == T && size(reference, 3) == nb) || error("one retained path per block expected: reference of size (dim, $T, $nb)")
+    path = Array{Float64,3}(undef, size(reference, 1), T + 1, nb); indices = Matrix{Int64}(undef, T + 1, nb)
+    ess = Matrix{Float64}(undef, nb, T); lml = Matrix{Float64}(undef, nb, T); words = Matrix{Int32}(undef, nb, T)
+    invalid = Ref{Cint}(0)
+    _status(s, ccall((:gpf_sweep_blocks_backward, libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Cint, Ptr{Cdouble}, Cint, Int64, Cint, Cdouble, Ptr{Cdouble}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}),
+                     s.handle, observations, size(observations, 1), T, shared ? 1 : 0, reference, size(reference, 1), block_size, ancestor_sampling ? 1 : 0,
+                     ess_frac === nothing ? NaN : Float64(ess_frac), path, indices, ess, lml, words, invalid))
+    return path, indices, lml, ess, (words .& Int32(1)) .!= 0
+end
 # for b in blocks: the model arguments of state[b] (src/update.jl:12-25 on a sub-state with new_args_b) -- gpf.h gpf_set_block_params.  params: a
 # (n_params, n_blocks) Matrix, column b = block b's parameter vector in the layout of csrc/gpf_models.hpp (derived constants included), or a
 # Vector of NativeModel descriptors of the state's model; `nothing` clears them.  While set, the block-wise calls use column b for block b (this
