@@ -731,10 +731,21 @@ def pf_run_blocks(state, observations, block_size: int, method: str = "multinomi
     Returns BlockRun(lml, ess, resampled), each (n_blocks, T): log_ml_estimate(state[b]) and effective_sample_size(state[b]) after step t's
     update (block_stats) and whether block b resampled at step t (block_resampled).  Blocks with NaN / +Inf weights are left alone by the
     resample and propagated anyway; the call then raises "Invalid weights (NaN)." after the whole run."""
+    return _run_blocks("pf_run_blocks", "gpf_run_blocks", state, observations, block_size, method, ess_frac, sort_particles)
+
+
+def pf_run_blocks_wide(state, observations, block_size: int, method: str = "multinomial", *, ess_frac=0.5, sort_particles: bool = True) -> BlockRun:
+    """pf_run_blocks for blocks of up to 8192 particles (gpf.h gpf_run_blocks_wide): the same arguments, result and contract.  Up to 2048 particles per
+    block it is pf_run_blocks' launch; above, where the loop runs pf_resample_blocks through sub-state views, one team of 512 threads per block runs
+    all T steps out of LDS -- bit for bit what the loop leaves.  One block per compute unit: fewer than 256 blocks leave part of the chip idle."""
+    return _run_blocks("pf_run_blocks_wide", "gpf_run_blocks_wide", state, observations, block_size, method, ess_frac, sort_particles)
+
+
+def _run_blocks(who, entry, state, observations, block_size, method, ess_frac, sort_particles) -> BlockRun:
     if method not in ("multinomial", "residual", "stratified"):
         raise ErrorException(f"Resampling method {method} not recognized.")
     if isinstance(state, DeviceParticleFilterSubState):
-        raise ErrorException("pf_run_blocks works on the whole filter")
+        raise ErrorException(f"{who} works on the whole filter")
     if int(block_size) < 1:
         raise ErrorException("block_size < 1")
     nb = (state.n_particles + min(int(block_size), max(state.n_particles, 1)) - 1) // min(int(block_size), max(state.n_particles, 1))
@@ -748,9 +759,9 @@ def pf_run_blocks(state, observations, block_size: int, method: str = "multinomi
     T = obs.shape[0] if shared else obs.shape[1]
     ess, lml, res = np.empty((T, nb)), np.empty((T, nb)), np.zeros((T, nb), np.int32)
     inv = C.c_int32(0)
-    st = state._L.gpf_run_blocks(state._h, _pd(obs), obs.shape[-1], T, int(shared), int(block_size), RESAMPLE_METHODS[method], int(sort_particles),
-                                 float("nan") if ess_frac is None else float(ess_frac), _pd(ess), _pd(lml),
-                                 res.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(inv))
+    st = getattr(state._L, entry)(state._h, _pd(obs), obs.shape[-1], T, int(shared), int(block_size), RESAMPLE_METHODS[method], int(sort_particles),
+                                  float("nan") if ess_frac is None else float(ess_frac), _pd(ess), _pd(lml),
+                                  res.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(inv))
     if st != _lib.OK:
         raise ErrorException(state._L.gpf_last_error(state._h).decode())
     state._n_blocks_last = 0                                     # (no pf_resample_blocks for block_resampled to refer to, as after the loop's last update)

@@ -740,6 +740,8 @@ void launch_block_pairs(gpf_filter* h, const PairArgs& a, const AncArgs& x);    
 void launch_block_map(gpf_filter* h, const MapArgs& a, const AncArgs& x);         // k_block_map<model, TEAM, ITEMS> by team_dispatch
 // ---- defined in libgpf_run.hip
 void launch_block_run(gpf_filter* h, const RunArgs& a, int method);               // k_block_run<model, W, method, TEAM, ITEMS> by team_dispatch; method 0 | 1 | 2
+// ---- defined in libgpf_run_wide.hip
+gpf_status launch_block_run_wide(gpf_filter* h, const RunArgs& a, int method);    // k_block_run_wide<model, W, method>: a 512-thread team per block of 2049 .. BLK_WIDE_MAX particles
 // ---- defined in libgpf_sweep.hip
 void launch_block_sweep(gpf_filter* h, const SweepArgs& a, bool ancestor_sampling);   // k_block_sweep<model, W, AS, TEAM, ITEMS> by team_dispatch
 // ---- defined in libgpf_sweep_back.hip

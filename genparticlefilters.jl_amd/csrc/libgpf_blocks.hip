@@ -475,14 +475,17 @@ gpf_status across_planner(gpf_filter* h, int64_t nblocks)
 // ------------------------------------------------------------------ a whole series per block in one launch: what gpf_run_blocks and gpf_sweep_blocks share
 constexpr unsigned GATE_SERIES = GATE_VIEW | GATE_SHARD | GATE_SIZE | GATE_CLAMP | GATE_MAX | GATE_PARAMS | GATE_FWD;
 // the refusals behind the gate, each with the state untouched.  what: "run" | "sweep"; loop: the calls of the loop the call stands for; moves: the
-// series has the rejuvenation moves inside, so it needs the x_{t-1} columns the other two refuse
-gpf_status series_checks(gpf_filter* h, const std::string& who, const std::string& what, const char* loop, int64_t block_size, int32_t n_steps, bool moves = false)
+// series has the rejuvenation moves inside, so it needs the x_{t-1} columns the other two refuse; max_block: the largest block the call's kernel serves
+gpf_status series_checks(gpf_filter* h, const std::string& who, const std::string& what, const char* loop, int64_t block_size, int32_t n_steps, bool moves = false,
+                         int64_t max_block = BLK_MAX)
 {
     if (h->hist_on) return fail(h, GPF_ERR_STATE, who + " on a filter with a trajectory store: recording a step is host bookkeeping per step (run the loop of " + loop + ")");
     if (h->fwd_on) return fail(h, GPF_ERR_STATE, who + ": forward smoothing per block is on (gpf_forward_enable_blocks): its statistics are closed by a call per step");
     if (moves && !h->cfg.keep_prev) return fail(h, GPF_ERR_STATE, "gpf_rejuvenate needs keep_prev = 1 (x_{t-1} must travel with the particle)");   // (gpf_rejuvenate_blocks' refusal)
     if (!moves && h->cfg.keep_prev) return fail(h, GPF_ERR_STATE, who + " on a keep_prev filter: x_{t-1} serves only the rejuvenation moves, and the " + what + " has none");
-    if (block_size > BLK_MAX) return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": blocks of more than " + std::to_string(BLK_MAX) + " particles are not the work of one team");
+    if (block_size > max_block)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": blocks of more than " + std::to_string(max_block) + " particles are not the work of one team" +
+                    (max_block == BLK_MAX ? "" : ", the wide one included (run the loop of gpf_resample_blocks / gpf_update_blocks)"));
     if (h->args.n_strata > 0) return fail(h, GPF_ERR_STATE, who + ": strata are set on this filter; the " + what + " extends every block with the default proposal only");
     if (n_steps < 1 || n_steps > 4096) return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": need 1 <= n_steps <= 4096 (longer series: call it in chunks, they compose)");
     return GPF_OK;
@@ -587,6 +590,45 @@ gpf_status sweep_impl(gpf_handle h, const std::string& who, bool backward, const
     // (the loop's 2 n_steps epochs, then one for the ancestral draw; the backward draw takes one more per step below the last)
     return series_finish(h, block_size, nblocks, cells, (backward ? 3u : 2u) * (uint32_t)n_steps + 1u, {h->sweep_path, path_out, path_words * sizeof(double)},
                          {h->sweep_idx, idx_out, idx_words * sizeof(int64_t)}, ess_out, lml_out, resampled_out, invalid);
+}
+
+
+// gpf_run_blocks and gpf_run_blocks_wide: for t in 1:n_steps; gpf_resample_blocks(check = false); gpf_update_blocks(obs[:, t]); end in one launch -- gpf.h.
+// One order of checks, one upload, one launch: k_block_run (libgpf_run.hip) for blocks of up to BLK_MAX particles, which is all gpf_run_blocks accepts
+// (max_block), k_block_run_wide (libgpf_run_wide.hip) above.  Everything up to the input's upload is a check or scratch of the call: a refused call
+// changes nothing
+gpf_status run_blocks_impl(gpf_handle h, const std::string& who, int64_t max_block, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs,
+                           int64_t block_size, int32_t method, int32_t sort_particles, double ess_frac, double* ess_out, double* lml_out,
+                           int32_t* resampled_out, int32_t* invalid)
+{
+    gpf_status s = block_gate(h, block_size, who.c_str(), GATE_SERIES);
+    if (s || (s = series_checks(h, who, "run", "gpf_resample_blocks / gpf_update_blocks", block_size, n_steps, false, max_block))) return s;
+    const int64_t nblocks = (h->n + block_size - 1) / block_size, obs_blocks = shared_obs ? 1 : nblocks;
+    if (method != GPF_RESAMPLE_MULTINOMIAL && method != GPF_RESAMPLE_RESIDUAL && method != GPF_RESAMPLE_STRATIFIED)
+        return fail(h, GPF_ERR_UNKNOWN_METHOD, "Resampling method not recognized.");          // resample.jl:28
+    if ((s = block_obs_check(h, obs, n_obs))) return s;          // (as gpf_update_blocks refuses them: every step's rows have the one width)
+    const int64_t obs_words = (int64_t)n_steps * obs_blocks * n_obs;
+    if (obs_words > ((int64_t)1 << 31)) return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": the observations of the call exceed 2^31 words on the device: fewer steps per call");
+    // ---- the call's input [MAX_PARAMS parameters | the observations in the caller's layout] into the pinned buffer (copy_finite).  Scratch: a call
+    //      refused here or below has changed nothing
+    const size_t in_words = (size_t)MAX_PARAMS + (size_t)obs_words, cells = (size_t)n_steps * (size_t)nblocks;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if ((s = h->h_run_in.grow(h, in_words)) || (s = series_obs_in(h, who, obs, obs_words, n_obs, n_steps, shared_obs != 0))) return s;
+    if (h->W != 2 && h->W != 4) return fail(h, GPF_ERR_STATE, "row width");
+    if ((s = check_ready(h)) || (s = materialize(h)) || (s = series_upload(h, nblocks, in_words, cells))) return s;
+    RunArgs a{};
+    a.rows[0] = h->rows[h->cur]; a.rows[1] = h->rows[1 - h->cur]; a.lw = h->lw; a.anc = h->anc;
+    a.n = h->n; a.nb = block_size; a.nblocks = nblocks; a.gid0 = h->cfg.gid0; a.seed = h->cfg.seed; a.epoch = h->epoch; a.n_steps = n_steps;
+    a.sorted = method == GPF_RESAMPLE_STRATIFIED && sort_particles ? 1 : 0;
+    a.ess_frac = ess_frac == ess_frac ? ess_frac : -1.0;
+    a.P = h->run_in; a.blk_params = h->bp_size > 0 ? h->blk_params.p : nullptr;
+    a.obs = h->run_in + MAX_PARAMS; a.obs_blocks = obs_blocks; a.n_obs = n_obs;
+    a.lml_est = &h->sc->lml_est;
+    a.ess_out = h->run_stats; a.lml_out = h->run_stats + cells; a.res_out = h->run_words; a.flags_out = h->blk_mask; a.blk_obs = h->blk_obs;
+    const int m_id = method == GPF_RESAMPLE_MULTINOMIAL ? 0 : (method == GPF_RESAMPLE_RESIDUAL ? 1 : 2);
+    gpf_status ls = GPF_OK;
+    if ((s = timed(h, GPF_K_STEP, [&] { if (block_size > BLK_MAX) ls = launch_block_run_wide(h, a, m_id); else launch_block_run(h, a, m_id); })) || (s = ls)) return s;
+    return series_finish(h, block_size, nblocks, cells, 2u * (uint32_t)n_steps, {}, {}, ess_out, lml_out, resampled_out, invalid);
 }
 
 } // namespace
@@ -763,39 +805,17 @@ gpf_status gpf_update_blocks_proposal(gpf_handle h, const double* obs, int32_t n
     if (!proposal_valid(h, proposal) || !model_caps(h).proposal) return fail(h, GPF_ERR_INVALID_ARGUMENT, "this model has no such native proposal");
     return block_update_impl(h, obs, n_obs, block_size, 4, use_proposal);
 }
-// for t in 1:n_steps; gpf_resample_blocks(check = false); gpf_update_blocks(obs[:, t]); end in one launch (k_block_run, libgpf_run.hip) -- gpf.h.
-// Everything up to the input's upload is a check or scratch of the call: a refused call changes nothing
 gpf_status gpf_run_blocks(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs, int64_t block_size, int32_t method,
                           int32_t sort_particles, double ess_frac, double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid)
 {
-    const std::string who = "gpf_run_blocks";
-    gpf_status s = block_gate(h, block_size, who.c_str(), GATE_SERIES);
-    if (s || (s = series_checks(h, who, "run", "gpf_resample_blocks / gpf_update_blocks", block_size, n_steps))) return s;
-    const int64_t nblocks = (h->n + block_size - 1) / block_size, obs_blocks = shared_obs ? 1 : nblocks;
-    if (method != GPF_RESAMPLE_MULTINOMIAL && method != GPF_RESAMPLE_RESIDUAL && method != GPF_RESAMPLE_STRATIFIED)
-        return fail(h, GPF_ERR_UNKNOWN_METHOD, "Resampling method not recognized.");          // resample.jl:28
-    if ((s = block_obs_check(h, obs, n_obs))) return s;          // (as gpf_update_blocks refuses them: every step's rows have the one width)
-    const int64_t obs_words = (int64_t)n_steps * obs_blocks * n_obs;
-    if (obs_words > ((int64_t)1 << 31)) return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": the observations of the call exceed 2^31 words on the device: fewer steps per call");
-    // ---- the call's input [MAX_PARAMS parameters | the observations in the caller's layout] into the pinned buffer (copy_finite).  Scratch: a call
-    //      refused here or below has changed nothing
-    const size_t in_words = (size_t)MAX_PARAMS + (size_t)obs_words, cells = (size_t)n_steps * (size_t)nblocks;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if ((s = h->h_run_in.grow(h, in_words)) || (s = series_obs_in(h, who, obs, obs_words, n_obs, n_steps, shared_obs != 0))) return s;
-    if (h->W != 2 && h->W != 4) return fail(h, GPF_ERR_STATE, "row width");
-    if ((s = check_ready(h)) || (s = materialize(h)) || (s = series_upload(h, nblocks, in_words, cells))) return s;
-    RunArgs a{};
-    a.rows[0] = h->rows[h->cur]; a.rows[1] = h->rows[1 - h->cur]; a.lw = h->lw; a.anc = h->anc;
-    a.n = h->n; a.nb = block_size; a.nblocks = nblocks; a.gid0 = h->cfg.gid0; a.seed = h->cfg.seed; a.epoch = h->epoch; a.n_steps = n_steps;
-    a.sorted = method == GPF_RESAMPLE_STRATIFIED && sort_particles ? 1 : 0;
-    a.ess_frac = ess_frac == ess_frac ? ess_frac : -1.0;
-    a.P = h->run_in; a.blk_params = h->bp_size > 0 ? h->blk_params.p : nullptr;
-    a.obs = h->run_in + MAX_PARAMS; a.obs_blocks = obs_blocks; a.n_obs = n_obs;
-    a.lml_est = &h->sc->lml_est;
-    a.ess_out = h->run_stats; a.lml_out = h->run_stats + cells; a.res_out = h->run_words; a.flags_out = h->blk_mask; a.blk_obs = h->blk_obs;
-    const int m_id = method == GPF_RESAMPLE_MULTINOMIAL ? 0 : (method == GPF_RESAMPLE_RESIDUAL ? 1 : 2);
-    if ((s = timed(h, GPF_K_STEP, [&] { launch_block_run(h, a, m_id); }))) return s;
-    return series_finish(h, block_size, nblocks, cells, 2u * (uint32_t)n_steps, {}, {}, ess_out, lml_out, resampled_out, invalid);
+    return run_blocks_impl(h, "gpf_run_blocks", BLK_MAX, obs, n_obs, n_steps, shared_obs, block_size, method, sort_particles, ess_frac, ess_out, lml_out, resampled_out, invalid);
+}
+// gpf_run_blocks for blocks of up to BLK_WIDE_MAX = 8192 particles: the same call, contract and refusals; above BLK_MAX the wide team's kernel -- gpf.h
+gpf_status gpf_run_blocks_wide(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs, int64_t block_size, int32_t method,
+                               int32_t sort_particles, double ess_frac, double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid)
+{
+    return run_blocks_impl(h, "gpf_run_blocks_wide", BLK_WIDE_MAX, obs, n_obs, n_steps, shared_obs, block_size, method, sort_particles, ess_frac, ess_out, lml_out,
+                           resampled_out, invalid);
 }
 // for t in 1:n_steps; gpf_resample_blocks(check = false); gpf_rejuvenate_blocks(only_resampled = 1); gpf_update_blocks(obs[:, t]); end in one launch
 // (k_block_run_move, libgpf_run_move.hip) -- gpf.h.  gpf_run_blocks on a keep_prev filter, with the move's arguments, the handle's per-block observation

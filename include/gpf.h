@@ -311,6 +311,16 @@ gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, 
 gpf_status gpf_run_blocks(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs,
                           int64_t block_size, int32_t method, int32_t sort_particles, double ess_frac,
                           double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid);
+/* gpf_run_blocks for blocks of up to 8192 particles: arguments, outputs, contract, weights, timing and refusals are gpf_run_blocks', for clamped block
+ * sizes 1 .. 8192.  Up to 2048 it IS gpf_run_blocks' launch.  Above, where the loop runs gpf_resample_blocks through sub-state views (full-size launches
+ * and a pinned-memory wait per block and step), one team of 512 threads per block runs all steps with the block's fixed-point weights, CDFs, sort
+ * keys and order resident in LDS (64 | 128 | 144 kB at 8192 for multinomial | residual | stratified with sort_particles); the call leaves bit for bit
+ * what n_steps iterations of gpf_resample_blocks(check = false); gpf_update_blocks leave, parents as the loop over views leaves them (block-local).
+ * One block per workgroup and CU: fewer than 256 blocks leave CUs idle.
+ *   refused   as gpf_run_blocks, with GPF_ERR_INVALID_ARGUMENT for a clamped block_size > 8192 (the loop of calls serves any size). */
+gpf_status gpf_run_blocks_wide(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs,
+                               int64_t block_size, int32_t method, int32_t sort_particles, double ess_frac,
+                               double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid);
 /* The whole README loop per block in ONE launch: gpf_run_blocks with the rejuvenation moves inside the `if` (README.md:60-79),
  *     for t in 1:n_steps
  *         gpf_resample_blocks(h, method, block_size, NaN, sort_particles, ess_frac, GPF_CHECK_FALSE, NULL, NULL);      epoch E + 3(t-1)

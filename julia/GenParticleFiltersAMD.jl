@@ -415,6 +415,21 @@ function pf_run_blocks!(s::DeviceParticleFilterState, observations::Union{Array{
                      ess_frac === nothing ? NaN : Float64(ess_frac), ess, lml, words, invalid))
     return lml, ess, (words .& Int32(1)) .!= 0
 end
+# pf_run_blocks! for blocks of up to 8192 particles (gpf.h gpf_run_blocks_wide): the same arguments, results and contract; above 2048 particles per
+# block one team of 512 threads per block runs all steps out of LDS instead of the loop's sub-state views.
+function pf_run_blocks_wide!(s::DeviceParticleFilterState, observations::Union{Array{Float64,3},Matrix{Float64}}, block_size::Int, method::Symbol=:multinomial;
+                             ess_frac=0.5, sort_particles::Bool=true)
+    m = method == :multinomial ? 0 : method == :residual ? 1 : method == :stratified ? 2 : error("Resampling method $method not recognized.")
+    nb = cld(s.n_particles, min(block_size, s.n_particles)); T = size(observations, 2)
+    shared = ndims(observations) == 2
+    shared || size(observations, 3) == nb || error("one series per block expected: observations of size (n_obs, T, $nb)")
+    ess = Matrix{Float64}(undef, nb, T); lml = Matrix{Float64}(undef, nb, T); words = Matrix{Int32}(undef, nb, T)
+    invalid = Ref{Cint}(0)
+    _status(s, ccall((:gpf_run_blocks_wide, libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Cint, Int64, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}),
+                     s.handle, observations, size(observations, 1), T, shared ? 1 : 0, block_size, m, sort_particles ? 1 : 0,
+                     ess_frac === nothing ? NaN : Float64(ess_frac), ess, lml, words, invalid))
+    return lml, ess, (words .& Int32(1)) .!= 0
+end
 # The whole README loop per block in ONE launch (gpf.h gpf_run_blocks_rejuvenate): pf_run_blocks! with
 #     pf_rejuvenate_blocks!(s, nothing, (), n_iters; method=rejuvenate, only_resampled=true)
 # between the resample and the update of every step, on a keep_prev state whose last step was block-wise with this block size.  Returns

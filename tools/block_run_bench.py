@@ -12,7 +12,10 @@ synchronisation; median, minimum, maximum over --reps after --warmup.  Kernel ti
 further calls with the timers on: the loop's is k_block_resample (GPF_K_SEARCH) + k_step (GPF_K_STEP), the run's k_block_run (booked under GPF_K_STEP);
 the loop's staging kernels are not in it.
 
-    python tools/block_run_bench.py [--reps 7] [--warmup 2] [--kreps 2] [--cases 0,1,2] [--out FILE.jsonl]
+--wide: the cases of gpf_run_blocks_wide (blocks of 4096 and 8192 particles) with pf_run_blocks_wide as the one call.  Above 2048 particles per block the
+loop's resample runs through sub-state views, whose kernels are booked on the views' own timers: the loop's kernel time then holds the propagate alone.
+
+    python tools/block_run_bench.py [--wide] [--reps 7] [--warmup 2] [--kreps 2] [--cases 0,1,2] [--out FILE.jsonl]
 """
 import argparse
 import ctypes as C
@@ -27,6 +30,7 @@ from block_smooth_bench import data, model_of, stats
 
 # (model, n_blocks, block_size, T, method, also the shared-series form)
 CASES = [("lgssm2", 10_000, 100, 100, "residual", True), ("bearings4", 10_000, 100, 100, "residual", False), ("lgssm2", 64, 2048, 32, "residual", False)]
+WIDE_CASES = [("lgssm2", 64, 8192, 32, "residual", False), ("lgssm2", 256, 4096, 100, "residual", False)]
 K_STEP, K_SEARCH = 0, 3
 NAN = float("nan")
 
@@ -35,7 +39,8 @@ def pd(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
-def case(g, name, n_blocks, nb, T, method, with_shared, reps, warmup, kreps, out):
+def case(g, name, n_blocks, nb, T, method, with_shared, reps, warmup, kreps, out, wide=False):
+    run_blocks = g.pf_run_blocks_wide if wide else g.pf_run_blocks
     m = model_of(g, name)
     ys = np.ascontiguousarray(data(g, m, n_blocks, T + 1))
     y0, yrun = np.ascontiguousarray(ys[:, 0]), np.ascontiguousarray(ys[:, 1:])
@@ -60,9 +65,9 @@ def case(g, name, n_blocks, nb, T, method, with_shared, reps, warmup, kreps, out
             st._check(L.gpf_update_blocks(h, pd(ysteps[t]), n_obs, nb))
         st.synchronize()
 
-    calls = {"loop": loop, "loop_c": loop_c, "run": lambda: g.pf_run_blocks(st, yrun, nb, method, ess_frac=0.5)}
+    calls = {"loop": loop, "loop_c": loop_c, "run": lambda: run_blocks(st, yrun, nb, method, ess_frac=0.5)}
     if with_shared:
-        calls["run_shared"] = lambda: g.pf_run_blocks(st, yshared, nb, method, ess_frac=0.5)
+        calls["run_shared"] = lambda: run_blocks(st, yshared, nb, method, ess_frac=0.5)
     times = {c: [] for c in calls}
     for r in range(warmup + reps):
         for c, f in calls.items():
@@ -87,7 +92,7 @@ def case(g, name, n_blocks, nb, T, method, with_shared, reps, warmup, kreps, out
     for t in range(T):
         g.pf_resample_blocks(p, nb, method, ess_frac=0.5, check=False)
         g.pf_update_blocks(p, (t + 2,), (None,), ysteps[t], nb)
-    r = g.pf_run_blocks(q, yrun, nb, method, ess_frac=0.5)
+    r = run_blocks(q, yrun, nb, method, ess_frac=0.5)
     same = bool(np.array_equal(p.log_weights, q.log_weights) and np.array_equal(p.traces, q.traces) and np.array_equal(p.parents, q.parents)
                 and np.array_equal(g.block_stats(p, nb)[1], r.lml[:, -1]))
     p.close(); q.close()
@@ -107,14 +112,16 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--kreps", type=int, default=2)
-    ap.add_argument("--cases", default="0,1,2")
+    ap.add_argument("--cases", default=None)
+    ap.add_argument("--wide", action="store_true")
     ap.add_argument("--out", default=os.devnull)
     a = ap.parse_args()
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import gpf_amd as g
     with open(a.out, "a") as out:
-        for k in (int(c) for c in a.cases.split(",")):
-            case(g, *CASES[k], a.reps, a.warmup, a.kreps, out)
+        cases = WIDE_CASES if a.wide else CASES
+        for k in (int(c) for c in a.cases.split(",")) if a.cases else range(len(cases)):
+            case(g, *cases[k], a.reps, a.warmup, a.kreps, out, a.wide)
 
 
 if __name__ == "__main__":
