@@ -741,6 +741,15 @@ def pf_run_blocks_wide(state, observations, block_size: int, method: str = "mult
     return _run_blocks("pf_run_blocks_wide", "gpf_run_blocks_wide", state, observations, block_size, method, ess_frac, sort_particles)
 
 
+def pf_run_blocks_history(state, observations, block_size: int, method: str = "multinomial", *, ess_frac=0.5, sort_particles: bool = True) -> BlockRun:
+    """pf_run_blocks on a state made with pf_initialize_blocks(..., history=T[, history_weights=True]) (gpf.h gpf_run_blocks_history): the same arguments,
+    result and contract for blocks of up to 2048 particles, and the launch records the trajectory store as the loop's calls would -- every query
+    (history_column, block_moments(step=t), block_sample_trajectories, block_backward_trajectories, block_smoothed_moments, block_smoothed_pair_moments,
+    block_map_trajectories) answers with the bits it gives after the loop.  The store grows by T steps; runs compose with each other and with
+    iterations of the loop.  A call that does not fit the store's remaining steps is refused as a whole, with nothing changed."""
+    return _run_blocks("pf_run_blocks_history", "gpf_run_blocks_history", state, observations, block_size, method, ess_frac, sort_particles)
+
+
 def _run_blocks(who, entry, state, observations, block_size, method, ess_frac, sort_particles) -> BlockRun:
     if method not in ("multinomial", "residual", "stratified"):
         raise ErrorException(f"Resampling method {method} not recognized.")

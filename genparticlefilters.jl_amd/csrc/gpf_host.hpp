@@ -748,6 +748,8 @@ void launch_block_sweep(gpf_filter* h, const SweepArgs& a, bool ancestor_samplin
 void launch_block_sweep_back(gpf_filter* h, const SweepBackArgs& a, bool ancestor_sampling);   // k_block_sweep_back<model, W, AS, TEAM, ITEMS> by team_dispatch
 // ---- defined in libgpf_run_move.hip
 void launch_block_run_move(gpf_filter* h, const RunMoveArgs& a, int method, bool reweight);   // k_block_run_move<model, W, method, reweight, TEAM, ITEMS> by team_dispatch
+// ---- defined in libgpf_run_hist.hip
+void launch_block_run_hist(gpf_filter* h, const RunArgs& a, const RunHistArgs& hs, int method, bool weights);   // k_block_run_hist<model, W, method, TEAM, ITEMS, weights> by team_dispatch
 // ---- defined in libgpf_forward.hip: the forward-only smoother's records (hist_begin_step / hist_on_resample call the first two) and launches
 gpf_status fwd_begin_step(gpf_filter* h, bool first);             // first: step 1 begins, the statistics are reset; else the step that ends is closed in its final order
 gpf_status fwd_on_resample(gpf_filter* h, int64_t block_size);    // this call's parents into the current step's map (block_size > 0: block-local, h->blk_mask says which)

@@ -475,11 +475,14 @@ gpf_status across_planner(gpf_filter* h, int64_t nblocks)
 // ------------------------------------------------------------------ a whole series per block in one launch: what gpf_run_blocks and gpf_sweep_blocks share
 constexpr unsigned GATE_SERIES = GATE_VIEW | GATE_SHARD | GATE_SIZE | GATE_CLAMP | GATE_MAX | GATE_PARAMS | GATE_FWD;
 // the refusals behind the gate, each with the state untouched.  what: "run" | "sweep"; loop: the calls of the loop the call stands for; moves: the
-// series has the rejuvenation moves inside, so it needs the x_{t-1} columns the other two refuse; max_block: the largest block the call's kernel serves
+// series has the rejuvenation moves inside, so it needs the x_{t-1} columns the other two refuse; max_block: the largest block the call's kernel serves;
+// store: the call records the block-wise trajectory store (gpf_run_blocks_history) -- it needs one, with room for the whole call
 gpf_status series_checks(gpf_filter* h, const std::string& who, const std::string& what, const char* loop, int64_t block_size, int32_t n_steps, bool moves = false,
-                         int64_t max_block = BLK_MAX)
+                         int64_t max_block = BLK_MAX, bool store = false)
 {
-    if (h->hist_on) return fail(h, GPF_ERR_STATE, who + " on a filter with a trajectory store: recording a step is host bookkeeping per step (run the loop of " + loop + ")");
+    if (store && !(h->hist_on && h->hist_blocks))
+        return fail(h, GPF_ERR_STATE, who + " needs the block-wise trajectory store (gpf_history_enable_blocks before gpf_initialize_blocks); without a store: gpf_run_blocks");
+    if (!store && h->hist_on) return fail(h, GPF_ERR_STATE, who + " on a filter with a trajectory store: recording a step is host bookkeeping per step (run the loop of " + loop + ")");
     if (h->fwd_on) return fail(h, GPF_ERR_STATE, who + ": forward smoothing per block is on (gpf_forward_enable_blocks): its statistics are closed by a call per step");
     if (moves && !h->cfg.keep_prev) return fail(h, GPF_ERR_STATE, "gpf_rejuvenate needs keep_prev = 1 (x_{t-1} must travel with the particle)");   // (gpf_rejuvenate_blocks' refusal)
     if (!moves && h->cfg.keep_prev) return fail(h, GPF_ERR_STATE, who + " on a keep_prev filter: x_{t-1} serves only the rejuvenation moves, and the " + what + " has none");
@@ -488,6 +491,8 @@ gpf_status series_checks(gpf_filter* h, const std::string& who, const std::strin
                     (max_block == BLK_MAX ? "" : ", the wide one included (run the loop of gpf_resample_blocks / gpf_update_blocks)"));
     if (h->args.n_strata > 0) return fail(h, GPF_ERR_STATE, who + ": strata are set on this filter; the " + what + " extends every block with the default proposal only");
     if (n_steps < 1 || n_steps > 4096) return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": need 1 <= n_steps <= 4096 (longer series: call it in chunks, they compose)");
+    // (the whole call or nothing: the loop would stop at the iteration that fills the store)
+    if (store && (int64_t)h->hist_x.size() + n_steps > h->hist_cap) return fail(h, GPF_ERR_STATE, "trajectory store full: raise max_steps of gpf_history_enable");
     return GPF_OK;
 }
 // an input array of the call into the pinned buffer, in the caller's layout: ONE pass, which is also its check (the exponent fields, branch-free as in
@@ -593,16 +598,89 @@ gpf_status sweep_impl(gpf_handle h, const std::string& who, bool backward, const
 }
 
 
+// ---- gpf_run_blocks_history: the store's bookkeeping of the loop's n_steps iterations -- per iteration one hist_on_resample (a fresh map for the current
+// step) and one hist_begin_step (the current step's snapshot, a new current step) -- in one place before the launch.  The call works on store steps
+// s0 = hist_step .. s0 + n_steps - 1 and leaves s0 + n_steps current: no snapshot and no map yet, as the loop leaves it.
+// One Dev per step and kind, as hist_snapshot and hist_on_resample allocate them: hist_clear, gpf_destroy and every query see the store they know.
+struct RunStore {
+    std::vector<Dev<double>> slabs;                               // [n_steps] columns | log-weights | observation rows; slabs[0] stays empty where step s0 has one
+    std::vector<Dev<int32_t>> maps;                               // [n_steps]
+    Dev<int32_t> old_map;                                         // the composed map step s0 had on entry: the launch reads it
+    RunHistArgs hs{};
+};
+// everything that can fail: on an error nothing of the filter or the store has changed
+gpf_status run_store_alloc(gpf_filter* h, int64_t block_size, int64_t nblocks, int32_t n_steps, RunStore& rs)
+{
+    if (h->hist_step < 0) return fail(h, GPF_ERR_STATE, "the trajectory store has no current step");
+    const int s0 = h->hist_step;
+    const size_t cols = (size_t)h->n * (size_t)h->d;
+    // step s0 keeps the observation rows it was entered with: of its own block size, which a whole-filter call (0) or another blocking may have set
+    const int64_t bs0 = h->hist_weights ? h->hist_bsize[s0] : 0;
+    const size_t obs0_words = bs0 > 0 ? (size_t)((h->n + bs0 - 1) / bs0) * MAX_OBS : 0;
+    rs.slabs.resize((size_t)n_steps); rs.maps.resize((size_t)n_steps);
+    gpf_status s;
+    for (int t = 0; t < n_steps; ++t) {
+        const size_t words = cols + (h->hist_weights ? (size_t)h->n + (t == 0 ? obs0_words : (size_t)nblocks * MAX_OBS) : 0);
+        if (!(t == 0 && h->hist_x[s0]) && (s = rs.slabs[t].alloc(h, words))) return s;
+        if ((s = rs.maps[t].alloc(h, (size_t)h->n))) return s;
+    }
+    rs.hs.obs0 = h->hist_weights && bs0 == block_size ? 1 : 0;
+    if (h->hist_weights && !rs.hs.obs0 && obs0_words) {          // (another blocking: k_hist_record's copy of the rows, before series_upload may regrow blk_obs)
+        double* const x0 = h->hist_x[s0] ? h->hist_x[s0].p : rs.slabs[0].p;
+        HIP_TRY(h, hipMemcpyAsync(x0 + cols + h->n, h->blk_obs.p, obs0_words * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    }
+    return GPF_OK;
+}
+// the vectors' entries and the call's rows of the device pointer tables (through the pinned input: no host temporary to wait for)
+gpf_status run_store_commit(gpf_filter* h, int64_t block_size, int32_t n_steps, size_t in_words, RunStore& rs)
+{
+    const int s0 = h->hist_step;
+    const size_t cols = (size_t)h->n * (size_t)h->d;
+    if (!h->hist_x[s0]) h->hist_x[s0] = std::move(rs.slabs[0]);
+    rs.old_map = std::move(h->hist_map[s0]);
+    h->hist_map[s0] = std::move(rs.maps[0]);
+    if (h->hist_weights) {
+        h->hist_lw[s0] = h->hist_x[s0] + cols;
+        h->hist_obs[s0] = h->hist_bsize[s0] > 0 ? h->hist_lw[s0] + h->n : nullptr;
+    }
+    for (int t = 1; t <= n_steps; ++t) {                         // (t = n_steps: the step the call leaves current)
+        if (t < n_steps) { h->hist_x.emplace_back(std::move(rs.slabs[t])); h->hist_map.emplace_back(std::move(rs.maps[t])); }
+        else { h->hist_x.emplace_back(); h->hist_map.emplace_back(); }
+        if (h->hist_weights) {
+            double* const lw = t < n_steps ? h->hist_x.back() + cols : nullptr;
+            h->hist_lw.push_back(lw); h->hist_obs.push_back(lw ? lw + h->n : nullptr); h->hist_bsize.push_back(block_size);
+        }
+    }
+    h->hist_step = s0 + n_steps;
+    static_assert(sizeof(void*) == sizeof(double), "the tables travel in the pinned input");
+    void** const tab = reinterpret_cast<void**>(h->h_run_in + in_words);
+    const size_t T = (size_t)n_steps, bytes = T * sizeof(void*);
+    for (size_t t = 0; t < T; ++t) {
+        tab[t] = h->hist_x[s0 + t].p; tab[T + t] = h->hist_map[s0 + t].p;
+        if (h->hist_weights) { tab[2 * T + t] = h->hist_lw[s0 + t]; tab[3 * T + t] = h->hist_obs[s0 + t]; }
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_x + s0, tab, bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->hist_dev_maps + s0, tab + T, bytes, hipMemcpyHostToDevice, h->stream));
+    if (h->hist_weights) {
+        HIP_TRY(h, hipMemcpyAsync(h->hist_dev_lw + s0, tab + 2 * T, bytes, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->hist_dev_obs + s0, tab + 3 * T, bytes, hipMemcpyHostToDevice, h->stream));
+    }
+    rs.hs.hx = const_cast<double* const*>(h->hist_dev_x.p); rs.hs.maps = const_cast<int32_t* const*>(h->hist_dev_maps.p);
+    rs.hs.hlw = const_cast<double* const*>(h->hist_dev_lw.p); rs.hs.hobs = const_cast<double* const*>(h->hist_dev_obs.p);
+    rs.hs.map0 = rs.old_map; rs.hs.s0 = s0;
+    return GPF_OK;
+}
+
 // gpf_run_blocks and gpf_run_blocks_wide: for t in 1:n_steps; gpf_resample_blocks(check = false); gpf_update_blocks(obs[:, t]); end in one launch -- gpf.h.
 // One order of checks, one upload, one launch: k_block_run (libgpf_run.hip) for blocks of up to BLK_MAX particles, which is all gpf_run_blocks accepts
 // (max_block), k_block_run_wide (libgpf_run_wide.hip) above.  Everything up to the input's upload is a check or scratch of the call: a refused call
-// changes nothing
+// changes nothing.  store: gpf_run_blocks_history -- the same call on a filter with the block-wise store, which k_block_run_hist (libgpf_run_hist.hip) records
 gpf_status run_blocks_impl(gpf_handle h, const std::string& who, int64_t max_block, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs,
                            int64_t block_size, int32_t method, int32_t sort_particles, double ess_frac, double* ess_out, double* lml_out,
-                           int32_t* resampled_out, int32_t* invalid)
+                           int32_t* resampled_out, int32_t* invalid, bool store = false)
 {
     gpf_status s = block_gate(h, block_size, who.c_str(), GATE_SERIES);
-    if (s || (s = series_checks(h, who, "run", "gpf_resample_blocks / gpf_update_blocks", block_size, n_steps, false, max_block))) return s;
+    if (s || (s = series_checks(h, who, "run", "gpf_resample_blocks / gpf_update_blocks", block_size, n_steps, false, max_block, store))) return s;
     const int64_t nblocks = (h->n + block_size - 1) / block_size, obs_blocks = shared_obs ? 1 : nblocks;
     if (method != GPF_RESAMPLE_MULTINOMIAL && method != GPF_RESAMPLE_RESIDUAL && method != GPF_RESAMPLE_STRATIFIED)
         return fail(h, GPF_ERR_UNKNOWN_METHOD, "Resampling method not recognized.");          // resample.jl:28
@@ -613,9 +691,13 @@ gpf_status run_blocks_impl(gpf_handle h, const std::string& who, int64_t max_blo
     //      refused here or below has changed nothing
     const size_t in_words = (size_t)MAX_PARAMS + (size_t)obs_words, cells = (size_t)n_steps * (size_t)nblocks;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if ((s = h->h_run_in.grow(h, in_words)) || (s = series_obs_in(h, who, obs, obs_words, n_obs, n_steps, shared_obs != 0))) return s;
+    // (store: the pinned input has room for the call's rows of the four pointer tables behind the observations)
+    if ((s = h->h_run_in.grow(h, in_words + (store ? 4 * (size_t)n_steps : 0))) || (s = series_obs_in(h, who, obs, obs_words, n_obs, n_steps, shared_obs != 0))) return s;
     if (h->W != 2 && h->W != 4) return fail(h, GPF_ERR_STATE, "row width");
-    if ((s = check_ready(h)) || (s = materialize(h)) || (s = series_upload(h, nblocks, in_words, cells))) return s;
+    RunStore rs;
+    if ((s = check_ready(h)) || (s = materialize(h)) || (store && (s = run_store_alloc(h, block_size, nblocks, n_steps, rs))) ||
+        (s = series_upload(h, nblocks, in_words, cells))) return s;
+    if (store && (s = run_store_commit(h, block_size, n_steps, in_words, rs))) return s;
     RunArgs a{};
     a.rows[0] = h->rows[h->cur]; a.rows[1] = h->rows[1 - h->cur]; a.lw = h->lw; a.anc = h->anc;
     a.n = h->n; a.nb = block_size; a.nblocks = nblocks; a.gid0 = h->cfg.gid0; a.seed = h->cfg.seed; a.epoch = h->epoch; a.n_steps = n_steps;
@@ -627,7 +709,12 @@ gpf_status run_blocks_impl(gpf_handle h, const std::string& who, int64_t max_blo
     a.ess_out = h->run_stats; a.lml_out = h->run_stats + cells; a.res_out = h->run_words; a.flags_out = h->blk_mask; a.blk_obs = h->blk_obs;
     const int m_id = method == GPF_RESAMPLE_MULTINOMIAL ? 0 : (method == GPF_RESAMPLE_RESIDUAL ? 1 : 2);
     gpf_status ls = GPF_OK;
-    if ((s = timed(h, GPF_K_STEP, [&] { if (block_size > BLK_MAX) ls = launch_block_run_wide(h, a, m_id); else launch_block_run(h, a, m_id); })) || (s = ls)) return s;
+    if ((s = timed(h, GPF_K_STEP, [&] {
+             if (store) launch_block_run_hist(h, a, rs.hs, m_id, h->hist_weights);
+             else if (block_size > BLK_MAX) ls = launch_block_run_wide(h, a, m_id);
+             else launch_block_run(h, a, m_id);
+         })) || (s = ls)) return s;
+    // (store: rs.old_map, which the launch read, is freed on return -- behind the synchronisation of series_finish, and hipFree waits in any case)
     return series_finish(h, block_size, nblocks, cells, 2u * (uint32_t)n_steps, {}, {}, ess_out, lml_out, resampled_out, invalid);
 }
 
@@ -809,6 +896,13 @@ gpf_status gpf_run_blocks(gpf_handle h, const double* obs, int32_t n_obs, int32_
                           int32_t sort_particles, double ess_frac, double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid)
 {
     return run_blocks_impl(h, "gpf_run_blocks", BLK_MAX, obs, n_obs, n_steps, shared_obs, block_size, method, sort_particles, ess_frac, ess_out, lml_out, resampled_out, invalid);
+}
+// gpf_run_blocks on a filter with the block-wise trajectory store, which the launch records as the loop's calls would -- gpf.h
+gpf_status gpf_run_blocks_history(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs, int64_t block_size, int32_t method,
+                                  int32_t sort_particles, double ess_frac, double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid)
+{
+    return run_blocks_impl(h, "gpf_run_blocks_history", BLK_MAX, obs, n_obs, n_steps, shared_obs, block_size, method, sort_particles, ess_frac, ess_out, lml_out,
+                           resampled_out, invalid, true);
 }
 // gpf_run_blocks for blocks of up to BLK_WIDE_MAX = 8192 particles: the same call, contract and refusals; above BLK_MAX the wide team's kernel -- gpf.h
 gpf_status gpf_run_blocks_wide(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs, int64_t block_size, int32_t method,

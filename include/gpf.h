@@ -321,6 +321,29 @@ gpf_status gpf_run_blocks(gpf_handle h, const double* obs, int32_t n_obs, int32_
 gpf_status gpf_run_blocks_wide(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs,
                                int64_t block_size, int32_t method, int32_t sort_particles, double ess_frac,
                                double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid);
+/* gpf_run_blocks on a filter with the block-wise trajectory store (gpf_history_enable_blocks[_weights] before gpf_initialize_blocks), recorded inside
+ * the launch: arguments, outputs, weights and timing are gpf_run_blocks', for clamped block sizes 1 .. 2048.  The call leaves what n_steps iterations of
+ *     gpf_resample_blocks(check = false); gpf_update_blocks(obs[:, t])
+ * leave on that filter: rows, log-weights, parents, the RNG epoch (+ 2 n_steps), the per-block observation rows and the three outputs as gpf_run_blocks,
+ * and a store that answers every query -- gpf_history_column, gpf_block_history_moments / _proportion, gpf_block_sample_trajectories,
+ * gpf_block_backward_sample, gpf_block_smooth, gpf_block_smooth_pairs, gpf_block_map_path -- with the bits the loop's store gives.
+ * With s0 the store's current step on entry, iteration t (0-based) works on step s = s0 + t:
+ *   map       g[j] = block start + the slot's parent where the block resampled, j where it did not; where step s0 already has a composed map B (a
+ *             gpf_resample_across_blocks came before the call) its new map is B[g[j]], in a fresh buffer.  Every step of the call has a map, the
+ *             identity where no block resampled (as after a gpf_resample_blocks that resampled none);
+ *   snapshot  in the step's final order -- after this iteration's resample, before its propagate -- the latent columns of the row the slot propagates
+ *             from; with the weight records also the log-weight gpf_resample_blocks leaves the slot and the observation row the block entered the step
+ *             with: the handle's at t = 0, obs[b][t - 1] zero-padded afterwards.  The steps the call begins are recorded under block_size.
+ * On return gpf_history_steps has grown by n_steps; the last step is current -- no snapshot or map yet, taken at query time or by the next update, as the
+ * loop leaves it.  Later calls continue identically; runs of T1 and T2 steps compose with each other and with iterations of the loop in between.
+ * One deviation from the loop: a call whose n_steps do not fit the store's max_steps is refused as a whole, before anything changes (the loop stops at
+ * the iteration that fills the store).
+ *   refused   as gpf_run_blocks -- forward smoothing per block, a keep_prev filter, strata, a clamped block_size > 2048 among them --; GPF_ERR_STATE on
+ *             a filter without the block-wise store (gpf_run_blocks serves it) and for a store without room for n_steps more steps.  If a device
+ *             allocation fails, the filter and the store are as they were. */
+gpf_status gpf_run_blocks_history(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs,
+                                  int64_t block_size, int32_t method, int32_t sort_particles, double ess_frac,
+                                  double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid);
 /* The whole README loop per block in ONE launch: gpf_run_blocks with the rejuvenation moves inside the `if` (README.md:60-79),
  *     for t in 1:n_steps
  *         gpf_resample_blocks(h, method, block_size, NaN, sort_particles, ess_frac, GPF_CHECK_FALSE, NULL, NULL);      epoch E + 3(t-1)

@@ -430,6 +430,21 @@ function pf_run_blocks_wide!(s::DeviceParticleFilterState, observations::Union{A
                      ess_frac === nothing ? NaN : Float64(ess_frac), ess, lml, words, invalid))
     return lml, ess, (words .& Int32(1)) .!= 0
 end
+# pf_run_blocks! on a filter with the block-wise trajectory store (gpf.h gpf_run_blocks_history): the same arguments, results and contract for blocks of
+# up to 2048 particles; the launch records the store as the loop's calls would, and a call that does not fit the store is refused as a whole.
+function pf_run_blocks_history!(s::DeviceParticleFilterState, observations::Union{Array{Float64,3},Matrix{Float64}}, block_size::Int, method::Symbol=:multinomial;
+                                ess_frac=0.5, sort_particles::Bool=true)
+    m = method == :multinomial ? 0 : method == :residual ? 1 : method == :stratified ? 2 : error("Resampling method $method not recognized.")
+    nb = cld(s.n_particles, min(block_size, s.n_particles)); T = size(observations, 2)
+    shared = ndims(observations) == 2
+    shared || size(observations, 3) == nb || error("one series per block expected: observations of size (n_obs, T, $nb)")
+    ess = Matrix{Float64}(undef, nb, T); lml = Matrix{Float64}(undef, nb, T); words = Matrix{Int32}(undef, nb, T)
+    invalid = Ref{Cint}(0)
+    _status(s, ccall((:gpf_run_blocks_history, libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Cint, Int64, Cint, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}),
+                     s.handle, observations, size(observations, 1), T, shared ? 1 : 0, block_size, m, sort_particles ? 1 : 0,
+                     ess_frac === nothing ? NaN : Float64(ess_frac), ess, lml, words, invalid))
+    return lml, ess, (words .& Int32(1)) .!= 0
+end
 # The whole README loop per block in ONE launch (gpf.h gpf_run_blocks_rejuvenate): pf_run_blocks! with
 #     pf_rejuvenate_blocks!(s, nothing, (), n_iters; method=rejuvenate, only_resampled=true)
 # between the resample and the update of every step, on a keep_prev state whose last step was block-wise with this block size.  Returns
