@@ -739,17 +739,17 @@ void launch_block_pairs(gpf_filter* h, const PairArgs& a, const AncArgs& x);    
 // ---- defined in libgpf_map.hip
 void launch_block_map(gpf_filter* h, const MapArgs& a, const AncArgs& x);         // k_block_map<model, TEAM, ITEMS> by team_dispatch
 // ---- defined in libgpf_run.hip
-void launch_block_run(gpf_filter* h, const RunArgs& a, int method);               // k_block_run<model, W, method, TEAM, ITEMS> by team_dispatch; method 0 | 1 | 2
+void launch_block_run(gpf_filter* h, const RunArgs& a, int method);               // k_block_series<model, W, method, TEAM, ITEMS, RunPlain> by team_dispatch; method 0 | 1 | 2
 // ---- defined in libgpf_run_wide.hip
 gpf_status launch_block_run_wide(gpf_filter* h, const RunArgs& a, int method);    // k_block_run_wide<model, W, method>: a 512-thread team per block of 2049 .. BLK_WIDE_MAX particles
 // ---- defined in libgpf_sweep.hip
-void launch_block_sweep(gpf_filter* h, const SweepArgs& a, bool ancestor_sampling);   // k_block_sweep<model, W, AS, TEAM, ITEMS> by team_dispatch
+void launch_block_sweep(gpf_filter* h, const SweepArgs& a, bool ancestor_sampling);   // k_block_sweep<model, W, AS, TEAM, ITEMS, false> by team_dispatch
 // ---- defined in libgpf_sweep_back.hip
-void launch_block_sweep_back(gpf_filter* h, const SweepBackArgs& a, bool ancestor_sampling);   // k_block_sweep_back<model, W, AS, TEAM, ITEMS> by team_dispatch
+void launch_block_sweep_back(gpf_filter* h, const SweepArgs& a, bool ancestor_sampling);   // k_block_sweep<model, W, AS, TEAM, ITEMS, true> by team_dispatch
 // ---- defined in libgpf_run_move.hip
 void launch_block_run_move(gpf_filter* h, const RunMoveArgs& a, int method, bool reweight);   // k_block_run_move<model, W, method, reweight, TEAM, ITEMS> by team_dispatch
 // ---- defined in libgpf_run_hist.hip
-void launch_block_run_hist(gpf_filter* h, const RunArgs& a, const RunHistArgs& hs, int method, bool weights);   // k_block_run_hist<model, W, method, TEAM, ITEMS, weights> by team_dispatch
+void launch_block_run_hist(gpf_filter* h, const RunArgs& a, const RunHistArgs& hs, int method, bool weights);   // k_block_series<model, W, method, TEAM, ITEMS, RunHist<weights>> by team_dispatch
 // ---- defined in libgpf_forward.hip: the forward-only smoother's records (hist_begin_step / hist_on_resample call the first two) and launches
 gpf_status fwd_begin_step(gpf_filter* h, bool first);             // first: step 1 begins, the statistics are reset; else the step that ends is closed in its final order
 gpf_status fwd_on_resample(gpf_filter* h, int64_t block_size);    // this call's parents into the current step's map (block_size > 0: block-local, h->blk_mask says which)

@@ -1,4 +1,5 @@
-// K11f: a whole series per block in one launch  (part of gpf_kernels.hpp; include that header, not this file)
+// K11f: a whole series per block in one launch, plain or recording the block-wise trajectory store
+// (part of gpf_kernels.hpp; include that header, not this file)
 #pragma once
 
 namespace gpf {
@@ -29,6 +30,15 @@ namespace gpf {
 // waves share their CU's L1, which serves the vector memory operations of the CU in issue order, so a load issued behind the barrier is behind the
 // store issued in front of it; that is the guarantee every store -> __syncthreads -> load through global memory in a HIP program rests on.  No spin
 // waits, nothing between workgroups; every loop is bounded by n_steps, cnt or the network's size.
+//
+// One kernel template, k_block_series, serves two entry points.  The variant is the type of its second argument; what a variant adds stands inside
+// `if constexpr` at the place of the step where it happens, and everything else is written once (profiles/block_series_kernels.md: the instantiations'
+// code is what the two separate kernels' was):
+//   RunPlain          gpf_run_blocks: the step above and nothing else;
+//   RunHist<WEIGHTS>  gpf_run_blocks_history: the same loop on a filter with the block-wise trajectory store.  Between the search and
+//                     the propagate the slot writes the store's records of the step; nothing recorded is read inside the launch, so there is no
+//                     synchronisation beyond the plain step's.
+// k_block_run_move (gpf_k_block_run_move.hpp) is not a variant: written this way its code came out differently (profiles/block_series_kernels.md).
 struct RunArgs {
     double* rows[2];                               // [n][W]; rows[0] holds the rows on entry and on exit
     double* lw;                                    // [n]
@@ -48,6 +58,19 @@ struct RunArgs {
     int32_t* flags_out;                            // [nblocks]: (OR of the block's validity flags over the steps) << 8 (k_block_summary folds them)
     double* blk_obs;                               // [nblocks][MAX_OBS] the handle's per-block observation rows: the last step's
 };
+// ---- the variants: what k_block_series takes beside RunArgs, and the flags its `if constexpr` blocks read
+struct RunPlain { static constexpr bool HIST = false, WEIGHTS = false; };
+// the store's slab and map pointers come from its own device tables (hist_dev_x / _lw / _obs / _maps of the handle), read with the team-uniform step index
+struct RunHistArgs {
+    double* const* hx;                             // [>= s0 + n_steps] the steps' snapshots, [n][D]
+    double* const* hlw;                            // ... their log-weights [n] (WEIGHTS)
+    double* const* hobs;                           // ... their observation rows [nblocks][MAX_OBS] (WEIGHTS)
+    int32_t* const* maps;                          // ... their ancestor maps [n]
+    const int32_t* map0;                           // the composed map step s0 has on entry, or null
+    int32_t s0;                                    // the store's current step on entry
+    int32_t obs0;                                  // WEIGHTS: the kernel writes step s0's observation rows (it was entered with this block size)
+};
+template <bool WEIGHTS_> struct RunHist : RunHistArgs { static constexpr bool HIST = true, WEIGHTS = WEIGHTS_; };
 template <int TEAM>
 __device__ __forceinline__ void run_sync()
 {
@@ -74,8 +97,9 @@ __device__ __forceinline__ void run_summary(const double* lw_blk, int cnt, int K
     const unsigned __int128 Qt = ((unsigned __int128)v4[2] << 64) + ((unsigned __int128)v4[1] << 32) + v4[0];
     ess = ess_from(S, (uint64_t)(Qt >> 64), (uint64_t)Qt);
 }
-template <int M, int W, int METHOD, int TEAM, int ITEMS>    // METHOD 0 multinomial, 1 residual, 2 stratified; W = row_width(Model<M>::D, false)
-__global__ __launch_bounds__(BLOCK) void k_block_run(RunArgs a)
+// METHOD 0 multinomial, 1 residual, 2 stratified; W = row_width(Model<M>::D, false); V = RunPlain | RunHist<WEIGHTS>
+template <int M, int W, int METHOD, int TEAM, int ITEMS, class V>
+__global__ __launch_bounds__(BLOCK) void k_block_series(RunArgs a, V v)
 {
     using Mo = Model<M>;
     constexpr int D = Mo::D;
@@ -174,12 +198,29 @@ __global__ __launch_bounds__(BLOCK) void k_block_run(RunArgs a)
         // (resample.jl:205-211: every particle of a block that resampled carries the block's average weight)
         const double new_lw = go ? lse_from(m, S, K, f) - log_((double)cnt) : 0.0;
         const uint64_t sB = METHOD == 2 && go ? S / (uint64_t)cnt : 0, srem = METHOD == 2 && go ? S % (uint64_t)cnt : 0;
-        // ================ the slots: ancestor (resample), then k_step's default proposal under epoch E + 2t + 1
+        // ================ the slots: ancestor (resample), the variant's part, then k_step's default proposal under epoch E + 2t + 1
         double ob[MAX_OBS];                                        // (team-uniform: the block's row of step t, zero-padded as the staged rows of gpf_update_blocks)
         {
             const double* const orow = obs_b + (size_t)t * (size_t)a.n_obs;
 #pragma unroll
             for (int k = 0; k < MAX_OBS; ++k) ob[k] = k < a.n_obs ? orow[k] : 0.0;
+        }
+        // RunHist: what the loop's store does between the two calls of an iteration -- hist_on_resample's compose launch and hist_begin_step's snapshot
+        // launches (libgpf_core.hip) -- done with stores alone.  Iteration t works on store step s = s0 + t.
+        double* hx = nullptr; int32_t* hmap = nullptr; const int32_t* map0 = nullptr; double* hlw = nullptr;
+        if constexpr (V::HIST) {
+            const int s = v.s0 + t;                                // (team-uniform: the four table reads are scalar loads)
+            hx = v.hx[s] + b0 * D;
+            hmap = v.maps[s] + b0;
+            map0 = t == 0 ? v.map0 : nullptr;
+            if (V::WEIGHTS) {
+                hlw = v.hlw[s] + b0;
+                // the observation: the first MAX_OBS lanes of the team write the block's row the step was ENTERED with to hobs[s][blk]: at t = 0 the
+                // handle's blk_obs row as it stands (obs0; the host copies it where step s0 was entered under another block size), at t > 0 the series'
+                // row t - 1, zero-padded.  blk_obs is written by the same lanes behind the loop.
+                if (tl < MAX_OBS && (t > 0 || v.obs0))
+                    v.hobs[s][blk * MAX_OBS + tl] = t == 0 ? a.blk_obs[blk * MAX_OBS + tl] : (tl < a.n_obs ? obs_b[(size_t)(t - 1) * (size_t)a.n_obs + tl] : 0.0);
+            }
         }
         const double* const rows_in = a.rows[side] + b0 * W;
         double* const rows_out = a.rows[go ? 1 - side : side] + b0 * W;
@@ -203,9 +244,30 @@ __global__ __launch_bounds__(BLOCK) void k_block_run(RunArgs a)
             {
                 const double2* src = reinterpret_cast<const double2*>(rows_in + (size_t)anc * W);
 #pragma unroll
-                for (int c = 0; c < (D + 1) / 2; ++c) { const double2 v = src[c]; r[2 * c] = v.x; r[2 * c + 1] = v.y; }
+                for (int c = 0; c < (D + 1) / 2; ++c) { const double2 v2 = src[c]; r[2 * c] = v2.x; r[2 * c + 1] = v2.y; }
             }
             const double lw_in = go ? new_lw : lw[j];
+            if constexpr (V::HIST) {
+                // ---- the store: step s's records of slot j, from the registers the propagate reads
+                //   the map         g = b0 + anc where the block resampled, b0 + j where not: one 4-byte store to maps[s][b0 + j].  Only at t = 0 with a
+                //                   composed map B already on step s0 (a gpf_resample_across_blocks came before) the word is B[g]: one dependent load through
+                //                   memory the launch does not write -- the new map is a fresh buffer (k_hist_compose_blocks never composes in place either);
+                //   the snapshot    the row's D latent columns go to hx[s][(b0 + j) D ..], in 16-byte pieces where D is even: the step's final order, after
+                //                   this iteration's resample and before its propagate.  A block that does not resample propagates in place, and its slot
+                //                   holds its OWN row here, before it overwrites it: nothing is read twice and there is no in-place hazard;
+                //   the weight      WEIGHTS: the log-weight pf_resample_blocks leaves the slot -- the block's average where it resampled, else its own.
+                const int32_t g = (int32_t)(b0 + anc);             // (anc = j where the block did not resample)
+                hmap[j] = map0 ? map0[g] : g;
+                if (D % 2 == 0) {
+                    double2* dst = reinterpret_cast<double2*>(hx + (size_t)j * D);
+#pragma unroll
+                    for (int c = 0; c < D / 2; ++c) dst[c] = make_double2(r[2 * c], r[2 * c + 1]);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < D; ++k) hx[(size_t)j * D + k] = r[k];
+                }
+                if (V::WEIGHTS) hlw[j] = lw_in;
+            }
             double xn[MAX_DIM];
             Mo::sample(P, false, r, ob, a.seed, slot, 0, ep_u, TAG_UPDATE, xn);
             const double ll = Mo::loglik(P, xn, ob);

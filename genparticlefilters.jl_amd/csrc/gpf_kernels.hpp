@@ -30,7 +30,5 @@
 #include "gpf_k_block_map.hpp"
 #include "gpf_k_block_run.hpp"
 #include "gpf_k_block_sweep.hpp"
-#include "gpf_k_block_sweep_back.hpp"
 #include "gpf_k_block_run_move.hpp"
 #include "gpf_k_block_run_wide.hpp"
-#include "gpf_k_block_run_hist.hpp"

@@ -580,8 +580,7 @@ gpf_status sweep_impl(gpf_handle h, const std::string& who, bool backward, const
     if ((s = h->sweep_rows.grow(h, ((size_t)n_steps + 1) * (size_t)h->n * (size_t)h->W)) || (s = h->sweep_par.grow(h, (size_t)n_steps * (size_t)h->n)) ||
         (backward && (s = h->sweep_lws.grow(h, (size_t)n_steps * (size_t)h->n))) ||
         (s = h->sweep_path.grow(h, path_words)) || (s = h->sweep_idx.grow(h, idx_words)) || (s = series_upload(h, nblocks, in_words, cells))) return s;
-    SweepBackArgs ab{};
-    SweepArgs& a = ab.s;
+    SweepArgs a{};
     a.rows = h->rows[h->cur]; a.slabs = h->sweep_rows; a.par = h->sweep_par; a.lw = h->lw; a.anc = h->anc;
     a.n = h->n; a.nb = block_size; a.nblocks = nblocks; a.gid0 = h->cfg.gid0; a.seed = h->cfg.seed; a.epoch = h->epoch; a.n_steps = n_steps;
     a.ess_frac = ess_frac == ess_frac ? ess_frac : -1.0;
@@ -590,8 +589,8 @@ gpf_status sweep_impl(gpf_handle h, const std::string& who, bool backward, const
     a.lml_est = &h->sc->lml_est;
     a.ess_out = h->run_stats; a.lml_out = h->run_stats + cells; a.res_out = h->run_words; a.flags_out = h->blk_mask; a.blk_obs = h->blk_obs;
     a.path = h->sweep_path; a.idx_out = h->sweep_idx;
-    ab.lws = backward ? h->sweep_lws.p : nullptr;
-    if ((s = timed(h, GPF_K_STEP, [&] { if (backward) launch_block_sweep_back(h, ab, ancestor_sampling != 0); else launch_block_sweep(h, a, ancestor_sampling != 0); }))) return s;
+    a.lws = backward ? h->sweep_lws.p : nullptr;
+    if ((s = timed(h, GPF_K_STEP, [&] { if (backward) launch_block_sweep_back(h, a, ancestor_sampling != 0); else launch_block_sweep(h, a, ancestor_sampling != 0); }))) return s;
     // (the loop's 2 n_steps epochs, then one for the ancestral draw; the backward draw takes one more per step below the last)
     return series_finish(h, block_size, nblocks, cells, (backward ? 3u : 2u) * (uint32_t)n_steps + 1u, {h->sweep_path, path_out, path_words * sizeof(double)},
                          {h->sweep_idx, idx_out, idx_words * sizeof(int64_t)}, ess_out, lml_out, resampled_out, invalid);
@@ -672,9 +671,9 @@ gpf_status run_store_commit(gpf_filter* h, int64_t block_size, int32_t n_steps, 
 }
 
 // gpf_run_blocks and gpf_run_blocks_wide: for t in 1:n_steps; gpf_resample_blocks(check = false); gpf_update_blocks(obs[:, t]); end in one launch -- gpf.h.
-// One order of checks, one upload, one launch: k_block_run (libgpf_run.hip) for blocks of up to BLK_MAX particles, which is all gpf_run_blocks accepts
+// One order of checks, one upload, one launch: k_block_series<.., RunPlain> (libgpf_run.hip) for blocks of up to BLK_MAX particles, which is all gpf_run_blocks accepts
 // (max_block), k_block_run_wide (libgpf_run_wide.hip) above.  Everything up to the input's upload is a check or scratch of the call: a refused call
-// changes nothing.  store: gpf_run_blocks_history -- the same call on a filter with the block-wise store, which k_block_run_hist (libgpf_run_hist.hip) records
+// changes nothing.  store: gpf_run_blocks_history -- the same call on a filter with the block-wise store, which k_block_series<.., RunHist> (libgpf_run_hist.hip) records
 gpf_status run_blocks_impl(gpf_handle h, const std::string& who, int64_t max_block, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs,
                            int64_t block_size, int32_t method, int32_t sort_particles, double ess_frac, double* ess_out, double* lml_out,
                            int32_t* resampled_out, int32_t* invalid, bool store = false)
@@ -966,7 +965,7 @@ gpf_status gpf_sweep_blocks(gpf_handle h, const double* obs, int32_t n_obs, int3
                       ess_out, lml_out, resampled_out, invalid);
 }
 // the same sweep with the path drawn by backward simulation -- gpf_block_backward_sample with n_samples = 1 on a store that records weights -- inside
-// the launch (k_block_sweep_back, libgpf_sweep_back.hip) -- gpf.h.  One more slab of scratch, an index per step, n_steps more epochs
+// the launch (k_block_sweep<.., BACK = true>, libgpf_sweep_back.hip) -- gpf.h.  One more slab of scratch, an index per step, n_steps more epochs
 gpf_status gpf_sweep_blocks_backward(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs, const double* ref, int32_t n_ref,
                                      int64_t block_size, int32_t ancestor_sampling, double ess_frac, double* path_out, int64_t* idx_out,
                                      double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid)

@@ -1,7 +1,7 @@
-// libgpf_run_hist.hip -- the kernels of the whole series per block that records the block-wise trajectory store (gpf_k_block_run_hist.hpp; gpf.h
+// libgpf_run_hist.hip -- the kernels of the whole series per block that records the block-wise trajectory store (k_block_series<.., RunHist<WEIGHTS>>, gpf_k_block_run.hpp; gpf.h
 // gpf_run_blocks_history, whose host side is in libgpf_blocks.hip).  A translation unit of their own, for the reason libgpf_run.hip is one: ninety
-// instantiations -- k_block_run's forty-five with and without the store's weight records -- and every other unit's device code stays what it was
-// (tools/isa_diff.py), k_block_run and the loop's kernels among them.
+// instantiations -- the plain run's forty-five with and without the store's weight records -- and every other unit's device code stays what it was
+// (tools/isa_diff.py), the plain run's and the loop's kernels among them.
 #include "gpf_host.hpp"
 
 using namespace gpf;
@@ -14,7 +14,7 @@ static void launch_block_run_hist_as(gpf_filter* h, const RunArgs& a, const RunH
 {
     constexpr int Wc = row_width(Model<M>::D, false);            // (a keep_prev state is refused, as by gpf_run_blocks)
     team_dispatch(a.nb, a.nblocks, [&](auto TEAM, auto ITEMS, dim3 grid) {
-        GPF_LAUNCH((k_block_run_hist<M, Wc, METHOD, TEAM, ITEMS, WEIGHTS>), grid, dim3(BLOCK), 0, h->stream, a, hs);
+        GPF_LAUNCH((k_block_series<M, Wc, METHOD, TEAM, ITEMS, RunHist<WEIGHTS>>), grid, dim3(BLOCK), 0, h->stream, a, RunHist<WEIGHTS>{hs});
     });
 }
 void launch_block_run_hist(gpf_filter* h, const RunArgs& a, const RunHistArgs& hs, int method, bool weights)

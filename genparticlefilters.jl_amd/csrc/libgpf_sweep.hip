@@ -14,7 +14,7 @@ static void launch_block_sweep_as(gpf_filter* h, const SweepArgs& a)
 {
     constexpr int Wc = row_width(Model<M>::D, false);            // (a keep_prev state is refused: x_{t-1} serves only the moves)
     team_dispatch(a.nb, a.nblocks, [&](auto TEAM, auto ITEMS, dim3 grid) {
-        GPF_LAUNCH((k_block_sweep<M, Wc, AS, TEAM, ITEMS>), grid, dim3(BLOCK), 0, h->stream, a);
+        GPF_LAUNCH((k_block_sweep<M, Wc, AS, TEAM, ITEMS, false>), grid, dim3(BLOCK), 0, h->stream, a);
     });
 }
 void launch_block_sweep(gpf_filter* h, const SweepArgs& a, bool ancestor_sampling)

@@ -23,7 +23,7 @@ def test_the_entry_point_in_every_layer(g):
     table = {s[0]: s for s in g._lib.SYMBOLS}
     assert table[NAME][1:] == table["gpf_sweep_blocks"][1:]
     assert "libgpf_sweep_back.hip" in ge.HIP_UNITS and os.path.exists(os.path.join(ge.CSRC, "libgpf_sweep_back.hip"))
-    assert '#include "gpf_k_block_sweep_back.hpp"' in open(os.path.join(ge.CSRC, "gpf_kernels.hpp")).read()
+    assert '#include "gpf_k_block_sweep.hpp"' in open(os.path.join(ge.CSRC, "gpf_kernels.hpp")).read()
     jl = open(os.path.join(ROOT, "julia", "GenParticleFiltersAMD.jl")).read()
     assert "ccall((:" + NAME + ", libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Cint, Ptr{Cdouble}, Cint, Int64, Cint, Cdouble, " \
            "Ptr{Cdouble}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint})" in jl and "\nfunction pf_sweep_blocks_backward!(s::DeviceParticleFilterState, " in jl

@@ -1,5 +1,5 @@
 """The whole series per block in one launch on a filter with the block-wise trajectory store: gpf_run_blocks_history / pf_run_blocks_history
-(gpf_k_block_run_hist.hpp) against the loop it stands for -- pf_resample_blocks(check=False); pf_update_blocks -- on a twin from the same seed.  The state,
+(k_block_series<.., RunHist>, gpf_k_block_run.hpp) against the loop it stands for -- pf_resample_blocks(check=False); pf_update_blocks -- on a twin from the same seed.  The state,
 the three outputs and every query of the store must be the loop's, bit for bit: every comparison is np.array_equal."""
 import ctypes as C
 
@@ -65,6 +65,53 @@ def test_lockstep_with_the_loop(g, name, n, bs, method, sort_particles, ess_frac
         g.pf_resample_blocks(st, bs, method, check=False)
         g.pf_update_blocks(st, (T + 2,), (None,), ys[:, T + 1], bs)
     assert same_state(g, a, b, bs) and same_store(g, a, b, bs, weights)
+    a.close(); b.close()
+
+
+def answers(g, st, bs):
+    """the store's answers with a refusal's text in place of an answer that is refused (invalid weights): twins must answer or refuse alike"""
+    out = []
+    for t in range(1, history_steps(st) + 1):
+        out += [st.history_column(t, c) for c in range(st.model.dim)]
+    for q in (lambda: g.block_sample_trajectories(st, bs, 2, return_indices=True), lambda: g.block_backward_trajectories(st, bs, 2, return_indices=True),
+              lambda: g.block_smoothed_moments(st, bs, return_weights=True), lambda: g.block_map_trajectories(st, bs, return_indices=True, return_log_density=True)):
+        try:
+            out += list(q())
+        except g.ErrorException as e:
+            out.append(np.frombuffer(str(e).encode(), np.uint8))
+    return out
+
+
+# one block size per team shape (64 x 2, 64 x 8, 256 x 8), each with its own resampler
+@pytest.mark.parametrize("ess_frac", [None, 0.5])
+@pytest.mark.parametrize("bs,method", [(100, "multinomial"), (129, "residual"), (600, "stratified")])
+def test_invalid_weights_at_entry(g, bs, method, ess_frac):
+    """block 0 with a NaN, block 1 with a +Inf (both skipped by every resample, propagated anyway), block 2 all -Inf (the uniform fallback where the gate
+    lets it resample), block 3 healthy: the loop with every iteration's exception caught, against one call through the C ABI -- status, message, the
+    resample words, outputs, state and the store's answers, bit for bit"""
+    n, steps = 4 * bs, 3
+    m = g.models.lgssm2()
+    ys = data(g, m, n, bs, steps=steps + 1)
+    a, b = (g.pf_initialize_blocks(m, (1,), ys[:, 0], n, bs, seed=13, history=steps + 1, history_weights=True) for _ in range(2))
+    lw = a.log_weights.copy()
+    lw[3] = np.nan; lw[bs + 5] = np.inf; lw[2 * bs:3 * bs] = -np.inf
+    a.log_weights = lw; b.log_weights = lw
+    want, errs = device_loop(g, a, bs, ys[:, 1:], method, ess_frac, True)
+    obs = np.ascontiguousarray(ys[:, 1:])
+    ess, lml, res, inv = np.empty((steps, 4)), np.empty((steps, 4)), np.zeros((steps, 4), np.int32), C.c_int32(-1)
+    st = b._L.gpf_run_blocks_history(b._h, pd(obs), obs.shape[2], steps, 0, bs, {"multinomial": 0, "residual": 1, "stratified": 2}[method], 1,
+                                     float("nan") if ess_frac is None else ess_frac, pd(ess), pd(lml), res.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(inv))
+    if ess_frac is None:
+        # every block resamples: the NaN and +Inf blocks are reported and left alone at every step, the all -Inf block resamples uniformly (flag 4)
+        assert len(errs) == steps and st != 0 and b._L.gpf_last_error(b._h).decode() in errs and inv.value != 0
+        assert (res[:, :2] & 1 == 0).all() and (res[:, :2] >> 8 != 0).all() and (res[:, 2] == (4 << 8 | 1)).all() and (res[:, 3] == 1).all()
+    else:
+        # behind an ESS gate invalid weights have a NaN ESS: the comparison is false, the block keeps its particles and nothing is reported
+        assert errs == [] and st == 0 and inv.value == 0 and (res[:, :3] == 0).all()
+    assert same_run(type(want)(lml.T, ess.T, (res & 1).astype(bool).T), want)
+    assert np.isnan(lml[:, :2]).all() and np.isnan(ess[:, :3]).all() and (lml[:, 2] == -np.inf).all() and np.isfinite(lml[:, 3]).all() and np.isfinite(ess[:, 3]).all()
+    assert same_state(g, a, b, bs)
+    assert history_steps(a) == history_steps(b) == steps + 1 and all(eq(x, y) for x, y in zip(answers(g, a, bs), answers(g, b, bs), strict=True))
     a.close(); b.close()
 
 

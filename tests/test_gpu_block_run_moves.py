@@ -116,6 +116,52 @@ def test_per_block_parameters_and_the_shared_series(g):
     a.close(); b.close()
 
 
+# ----------------------------------------------------------------------------- 3b. weights at entry
+# one block size per team shape (64 x 2, 64 x 8, 256 x 8), each with its own resampler
+@pytest.mark.parametrize("ess_frac", [None, 0.5])
+@pytest.mark.parametrize("kind", ["move", "reweight"])
+@pytest.mark.parametrize("bs,method", [(100, "multinomial"), (129, "residual"), (600, "stratified")])
+def test_invalid_weights_at_entry(g, bs, method, kind, ess_frac):
+    """block 0 with a NaN, block 1 with a +Inf (both skipped by every resample, never moved, propagated anyway), block 2 all -Inf (the uniform fallback
+    where the gate lets it resample), block 3 healthy: the loop with every resample's exception caught, against one call through the C ABI -- status,
+    message, the resample words, outputs, accept counts and state, bit for bit"""
+    import ctypes as C
+    from test_gpu_block_run import pd
+    n, steps = 4 * bs, 3
+    m = g.models.lgssm2()
+    ys = data(g, m, n, bs, steps=steps + 1)
+    a, b = twins(g, m, ys, n, bs, seed=13)
+    lw = a.log_weights.copy()
+    lw[3] = np.nan; lw[bs + 5] = np.inf; lw[2 * bs:3 * bs] = -np.inf
+    a.log_weights = lw; b.log_weights = lw
+    w_lml, w_ess, w_res, w_acc, errs = np.empty((4, steps)), np.empty((4, steps)), np.zeros((4, steps), bool), np.zeros(steps, np.int64), []
+    for t in range(steps):
+        try:
+            g.pf_resample_blocks(a, bs, method, ess_frac=ess_frac, sort_particles=True, check=False)
+        except g.ErrorException as e:
+            errs.append(str(e))
+        w_res[:, t] = g.block_resampled(a)
+        w_acc[t] = g.pf_rejuvenate_blocks(a, None, (), N_ITERS, method=kind, only_resampled=True, count=True)
+        g.pf_update_blocks(a, (t + 2,), (None,), ys[:, t + 1], bs)
+        w_ess[:, t], w_lml[:, t] = g.block_stats(a, bs)
+    obs = np.ascontiguousarray(ys[:, 1:])
+    ess, lml, res, acc, inv = np.empty((steps, 4)), np.empty((steps, 4)), np.zeros((steps, 4), np.int32), np.zeros((steps, 4), np.int64), C.c_int32(-1)
+    st = b._L.gpf_run_blocks_rejuvenate(b._h, pd(obs), obs.shape[2], steps, 0, bs, {"multinomial": 0, "residual": 1, "stratified": 2}[method], 1,
+                                        float("nan") if ess_frac is None else ess_frac, {"move": 0, "reweight": 1}[kind], N_ITERS, pd(ess), pd(lml),
+                                        res.ctypes.data_as(C.POINTER(C.c_int32)), acc.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(inv))
+    if ess_frac is None:
+        assert len(errs) == steps and st != 0 and b._L.gpf_last_error(b._h).decode() in errs and inv.value != 0
+        assert (res[:, :2] & 1 == 0).all() and (res[:, :2] >> 8 != 0).all() and (res[:, 2] == (4 << 8 | 1)).all() and (res[:, 3] == 1).all()
+    else:
+        assert errs == [] and st == 0 and inv.value == 0 and (res[:, :3] == 0).all()
+    got_res = (res & 1).astype(bool).T
+    assert np.array_equal(got_res, w_res) and np.array_equal(lml.T, w_lml, equal_nan=True) and np.array_equal(ess.T, w_ess, equal_nan=True)
+    assert np.array_equal(acc.sum(axis=1), w_acc) and not acc.T[~got_res].any()
+    assert np.isnan(lml[:, :2]).all() and np.isnan(ess[:, :3]).all() and np.isfinite(lml[:, 3]).all() and np.isfinite(ess[:, 3]).all()
+    assert same_state(g, a, b, bs)
+    a.close(); b.close()
+
+
 # ----------------------------------------------------------------------------- 4. refusals: nothing changed, the epoch included
 def test_refusals_leave_the_state_alone(g):
     n, bs = 300, 100

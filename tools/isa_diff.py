@@ -1,6 +1,6 @@
 """Per-kernel ISA diff of two --save-temps builds: the check that a change leaves the kernels' code alone.
 
-    python tools/isa_diff.py BEFORE AFTER [--shift OFF]
+    python tools/isa_diff.py BEFORE AFTER [--shift OFF] [--rename REGEX REPL]...
 
 BEFORE / AFTER: the device assembly of one build each -- a .s file, or several separated by commas (the units' *-hip-amdgcn-amd-amdhsa-gfx950.s:
 a kernel may change translation unit).  Normalised: the kernel's own name, label numbers, comments.  Reports every kernel that differs, every
@@ -8,7 +8,10 @@ kernel of BEFORE missing from AFTER and every kernel new in AFTER, and exits non
 
 --shift OFF compares against the parent of the per-block parameter change: kernels of BEFORE map to the AFTER kernel whose template argument list
 gained a trailing `false` (Lb0E, the defaulted BP flag), and in kernels that take ModelArgs the kernarg offsets (loads, address arithmetic on the
-kernarg pointer) at or behind OFF move back by 8 (ModelArgs grew by one pointer) and the kernarg size by 8."""
+kernarg pointer) at or behind OFF move back by 8 (ModelArgs grew by one pointer) and the kernarg size by 8.
+
+--rename REGEX REPL (repeatable) compares renamed kernels: every (mangled) kernel name of AFTER goes through re.sub(REGEX, REPL, name), in the order
+given, before it is matched with BEFORE's."""
 import difflib
 import re
 import sys
@@ -43,10 +46,17 @@ def norm(lines, name, off):
 
 
 def main(argv):
+    renames = []
+    while len(argv) >= 5 and argv[-3] == "--rename":
+        renames.insert(0, (argv[-2], argv[-1])); argv = argv[:-3]
     if len(argv) not in (2, 4) or (len(argv) == 4 and argv[2] != "--shift"):
         sys.exit(__doc__)
     off = int(argv[3], 16) if len(argv) == 4 else None
-    b, a = funcs(argv[0]), funcs(argv[1])
+    b, a, old = funcs(argv[0]), {}, {}
+    for n, body in funcs(argv[1]).items():
+        o = n
+        for rx, repl in renames: o = re.sub(rx, repl, o)
+        a[o], old[o] = body, n
     same = diff = 0
     missing, matched = [], set()
     for n, body in sorted(b.items()):
@@ -56,7 +66,7 @@ def main(argv):
         if m not in a:
             missing.append(n); continue
         matched.add(m)
-        x, y = norm(body, n, None), norm(a[m], m, off if off is not None and "ModelArgs" in n else None)
+        x, y = norm(body, n, None), norm(a[m], old[m], off if off is not None and "ModelArgs" in n else None)
         if x == y: same += 1
         else:
             diff += 1
