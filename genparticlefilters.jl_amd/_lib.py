@@ -66,6 +66,8 @@ SYMBOLS = [
     ("gpf_run_blocks_history", C.c_int, [_H, _pd, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_double, _pd, _pd, _pi32, _pi32]),
     ("gpf_run_blocks_rejuvenate", C.c_int, [_H, _pd, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32,
                                             _pd, _pd, _pi32, C.POINTER(C.c_int64), _pi32]),
+    ("gpf_pmmh_blocks", C.c_int, [_H, _pd, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _pd, C.c_int32, _pd, C.c_int64, C.c_uint64, C.c_int32, C.c_int32,
+                                  C.c_double, C.c_int32, _pi32, _pd]),
     ("gpf_sweep_blocks", C.c_int, [_H, _pd, C.c_int32, C.c_int32, C.c_int32, _pd, C.c_int32, C.c_int64, C.c_int32, C.c_double, _pd, C.POINTER(C.c_int64),
                                    _pd, _pd, _pi32, _pi32]),
     ("gpf_sweep_blocks_backward", C.c_int, [_H, _pd, C.c_int32, C.c_int32, C.c_int32, _pd, C.c_int32, C.c_int64, C.c_int32, C.c_double, _pd,

@@ -777,6 +777,65 @@ def _run_blocks(who, entry, state, observations, block_size, method, ess_frac, s
     return BlockRun(lml.T, ess.T, (res & 1).astype(bool).T)      # (views of the library's [T][n_blocks] arrays: no transposed copies)
 
 
+BlockPmmh = namedtuple("BlockPmmh", ["accepted", "lml"])
+
+
+def pf_pmmh_blocks(state, observations, params, log_threshold, block_size: int, method: str = "multinomial", *, seed: int, ess_frac=0.5,
+                   sort_particles: bool = True, keep_mass: bool = True) -> BlockPmmh:
+    """The particle-marginal MH move per block in ONE launch (gpf.h gpf_pmmh_blocks) -- the step SMC^2, parallel particle-marginal MH and a
+    likelihood surface over a parameter grid repeat.  Bit for bit the loop
+
+        twin = pf_initialize_blocks(state.model, (), observations[:, 0], state.n_particles, block_size, seed=seed, params=params)
+        if T > 1: pf_run_blocks(twin, observations[:, 1:], block_size, method, ess_frac=ess_frac, sort_particles=sort_particles)   # its NaN error ignored
+        Lp = block_stats(twin, block_size)[1]
+        accepted = Lp > log_threshold                                         # strict; NaN compares false
+        for b where accepted[b]: rows, parents, parameter row and observation row of state's block b <- twin's block b
+                                 log-weights of b <- twin's                                   (keep_mass=False)
+                                                  <- twin's + (lme_state_b - lme_twin_b)      (keep_mass=True)
+
+    with lme = logsumexp(block log-weights) - log(block particles): the block keeps the mass it stands for at the outer level, as after
+    pf_resample_across_blocks, and takes the proposal's inner weights.  The twin lives inside the launch only.
+    state: a whole block-wise filter with per-block parameters of this block size in force (pf_initialize_blocks(..., params=...) / set_block_params),
+    at most 2048 particles per block, no keep_prev, store, forward mode or strata.  observations: (n_blocks, T, n_obs), or (T, n_obs) shared by all
+    blocks, T >= 1 -- the WHOLE series, row 0 being the observation of the initial step.  params: (n_blocks, n_params) proposed rows or a list of
+    NativeModel descriptors (block_params_rows); accepted rows are what get_block_params then returns.  log_threshold: (n_blocks,) doubles, -inf
+    (always replace where the proposal's estimate is finite) and +inf (never) allowed, NaN refused -- the caller's log u - log prior / proposal ratio
+    + current estimate.  seed: the proposal filter's, required: pass a FRESH one per call, and one different from the state's -- the twin's streams
+    are (seed, particle id, its epochs), and a repeated seed repeats the proposal filter's noise.
+    Blocks that are not accepted are untouched bit for bit, and so are the state's RNG epoch and seed.  A proposal block with invalid final weights is
+    never accepted; with keep_mass a state block with invalid weights is never replaced; neither raises.
+    Returns BlockPmmh(accepted, lml): (n_blocks,) bool and the proposal filters' log-ML estimates."""
+    if method not in ("multinomial", "residual", "stratified"):
+        raise ErrorException(f"Resampling method {method} not recognized.")
+    if isinstance(state, DeviceParticleFilterSubState):
+        raise ErrorException("pf_pmmh_blocks works on the whole filter")
+    if int(block_size) < 1:
+        raise ErrorException("block_size < 1")
+    bs = min(int(block_size), max(state.n_particles, 1))
+    nb = (state.n_particles + bs - 1) // bs
+    obs = np.ascontiguousarray(observations, np.float64)
+    if obs.ndim == 3 and obs.shape[0] == nb and obs.shape[1] >= 1:
+        shared = False
+    elif obs.ndim == 2 and obs.shape[0] >= 1:
+        shared = True
+    else:
+        raise ErrorException(f"observations of shape ({nb}, T, n_obs), or (T, n_obs) for one series shared by all blocks, expected: got {obs.shape}")
+    T = obs.shape[0] if shared else obs.shape[1]
+    thr = np.ascontiguousarray(log_threshold, np.float64)
+    if thr.shape != (nb,):
+        raise ErrorException(f"one log-threshold per block expected: shape ({nb},), got {thr.shape}")
+    rows = block_params_rows(state.model, params, state.n_particles, block_size)
+    acc, lml = np.zeros(nb, np.int32), np.empty(nb)
+    st = state._L.gpf_pmmh_blocks(state._h, _pd(obs), obs.shape[-1], T, int(shared), int(block_size), _pd(rows), rows.shape[1], _pd(thr), nb,
+                                  int(seed) & 0xFFFFFFFFFFFFFFFF, RESAMPLE_METHODS[method], int(sort_particles),
+                                  float("nan") if ess_frac is None else float(ess_frac), int(bool(keep_mass)),
+                                  acc.ctypes.data_as(C.POINTER(C.c_int32)), _pd(lml))
+    if st != _lib.OK:
+        raise ErrorException(state._L.gpf_last_error(state._h).decode())
+    state._n_blocks_last = 0                                     # (no pf_resample_blocks for block_resampled to refer to)
+    return BlockPmmh(acc.astype(bool), lml)
+
+
 BlockRunMoves = namedtuple("BlockRunMoves", ["lml", "ess", "resampled", "accepted"])
 
 

@@ -275,6 +275,10 @@ struct __attribute__((visibility("hidden"))) gpf_filter : gpfh::Bufs {
     // synchronisation), kept for the next
     Dev<double> run_in, run_stats; Pinned<double> h_run_in; Dev<int32_t> run_words;
     Dev<int64_t> run_acc;                // gpf_run_blocks_rejuvenate: [n_steps][n_blocks] accepted proposals, where the caller asks for them
+    // gpf_pmmh_blocks (which uses run_in as [observations | n_blocks x MAX_PARAMS proposed rows | n_blocks thresholds], run_stats and run_words as its
+    // two outputs): the proposal filter of the blocks that do not keep it in LDS -- [2][n][W] rows, [n] log-weights -- and its [n] parents.  Scratch of
+    // one call, grown on demand, kept for the next
+    Dev<double> pmmh_rows; Dev<int32_t> pmmh_par;
     // gpf_sweep_blocks (which also uses the four above, with [... | n_blocks x n_steps x dim reference] behind the observations): the genealogy slabs
     // [n_steps + 1][n][W] rows and [n_steps][n] 16-bit block-local parents, and the outputs [n_blocks][n_steps + 1][dim] path, [n_blocks] index.  Scratch
     // of one call, kept for the next
@@ -750,6 +754,9 @@ void launch_block_sweep_back(gpf_filter* h, const SweepArgs& a, bool ancestor_sa
 void launch_block_run_move(gpf_filter* h, const RunMoveArgs& a, int method, bool reweight);   // k_block_run_move<model, W, method, reweight, TEAM, ITEMS> by team_dispatch
 // ---- defined in libgpf_run_hist.hip
 void launch_block_run_hist(gpf_filter* h, const RunArgs& a, const RunHistArgs& hs, int method, bool weights);   // k_block_series<model, W, method, TEAM, ITEMS, RunHist<weights>> by team_dispatch
+// ---- defined in libgpf_pmmh.hip
+void launch_block_pmmh(gpf_filter* h, const PmmhArgs& a, int method);             // k_block_pmmh<model, W, method, TEAM, ITEMS> by team_dispatch; method 0 | 1 | 2
+bool block_pmmh_in_lds(int64_t block_size, int W);                                // the proposal filter of a block of this size lives in LDS: no device scratch
 // ---- defined in libgpf_forward.hip: the forward-only smoother's records (hist_begin_step / hist_on_resample call the first two) and launches
 gpf_status fwd_begin_step(gpf_filter* h, bool first);             // first: step 1 begins, the statistics are reset; else the step that ends is closed in its final order
 gpf_status fwd_on_resample(gpf_filter* h, int64_t block_size);    // this call's parents into the current step's map (block_size > 0: block-local, h->blk_mask says which)

@@ -954,6 +954,76 @@ gpf_status gpf_run_blocks_rejuvenate(gpf_handle h, const double* obs, int32_t n_
     return series_finish(h, block_size, nblocks, cells, 3u * (uint32_t)n_steps, {h->run_acc, accepted_out, cells * sizeof(int64_t)}, {},
                          ess_out, lml_out, resampled_out, invalid);
 }
+// The particle-marginal MH move per block in one launch (k_block_pmmh, libgpf_pmmh.hip) -- gpf.h: a proposal filter per block under the proposed
+// parameter rows and `seed`, run over the whole series inside the launch, replaces the block where its estimate beats the block's threshold.
+// gpf_run_blocks' order of checks, then the call's own; one pass over each input, which is its check and its copy into the pinned buffer
+// [MAX_PARAMS | observations | n_blocks x MAX_PARAMS proposed rows | n_blocks thresholds]; one upload, one launch, the two outputs read back.
+// Nothing of the state's RNG is used: seed and epoch stay.
+gpf_status gpf_pmmh_blocks(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs, int64_t block_size,
+                           const double* params, int32_t n_params, const double* log_threshold, int64_t n_blocks, uint64_t seed, int32_t method,
+                           int32_t sort_particles, double ess_frac, int32_t keep_mass, int32_t* accepted_out, double* lml_out)
+{
+    const std::string who = "gpf_pmmh_blocks";
+    gpf_status s = block_gate(h, block_size, who.c_str(), GATE_SERIES);
+    // (n_steps counts the initial step: the run behind it has n_steps - 1, and series_checks' range is [1, 4096])
+    if (s || (s = series_checks(h, who, "proposal filter", "gpf_initialize_blocks / gpf_run_blocks on a second filter", block_size, n_steps > 1 ? n_steps - 1 : n_steps))) return s;
+    if (h->bp_size != block_size)
+        return fail(h, GPF_ERR_STATE, who + ": the move replaces a block's parameter row: per-block parameters of this block size must be in force (gpf_set_block_params with block_size " +
+                    std::to_string(block_size) + " first)");
+    if (h->blk_obs_size != block_size)
+        return fail(h, GPF_ERR_STATE, who + ": the move replaces a block's observation row: per-block observations of this block size must be in force (gpf_initialize_blocks / "
+                    "gpf_update_blocks with block_size " + std::to_string(block_size) + " first)");
+    const int64_t nblocks = (h->n + block_size - 1) / block_size, obs_blocks = shared_obs ? 1 : nblocks;
+    if (method != GPF_RESAMPLE_MULTINOMIAL && method != GPF_RESAMPLE_RESIDUAL && method != GPF_RESAMPLE_STRATIFIED)
+        return fail(h, GPF_ERR_UNKNOWN_METHOD, "Resampling method not recognized.");          // resample.jl:28
+    if ((s = block_obs_check(h, obs, n_obs))) return s;
+    if (!params || n_params < 1 || n_params > MAX_PARAMS || !log_threshold || n_blocks != nblocks)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": need [" + std::to_string(nblocks) + "][1 <= n_params <= " + std::to_string(MAX_PARAMS) + "] proposed parameters and " +
+                    std::to_string(nblocks) + " log-thresholds");
+    const int64_t obs_words = (int64_t)n_steps * obs_blocks * n_obs;
+    if (obs_words > ((int64_t)1 << 31)) return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": the observations of the call exceed 2^31 words on the device: fewer steps per call");
+    const size_t par_off = (size_t)MAX_PARAMS + (size_t)obs_words, thr_off = par_off + (size_t)nblocks * MAX_PARAMS, in_words = thr_off + (size_t)nblocks;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if ((s = h->h_run_in.grow(h, in_words)) || (s = series_obs_in(h, who, obs, obs_words, n_obs, n_steps, shared_obs != 0))) return s;
+    {   // the proposed rows, zero-padded to MAX_PARAMS, and the thresholds: the exponent fields as in copy_finite; a threshold may be +-Inf, not NaN
+        double* const rows = h->h_run_in + par_off; double* const thr = h->h_run_in + thr_off;
+        uint64_t bad = 0;
+        for (int64_t b = 0; b < nblocks; ++b)
+            for (int i = 0; i < MAX_PARAMS; ++i) {
+                const double v = i < n_params ? params[b * n_params + i] : 0.0;
+                uint64_t u; memcpy(&u, &v, sizeof(u)); bad |= (uint64_t)(((u >> 52) & 0x7ffu) == 0x7ffu);
+                rows[b * MAX_PARAMS + i] = v;
+            }
+        if (bad)
+            for (int64_t k = 0; k < nblocks * n_params; ++k)
+                if (!(params[k] - params[k] == 0.0)) return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": a proposed parameter of block " + std::to_string(k / n_params) + " is not finite");
+        for (int64_t b = 0; b < nblocks; ++b) {
+            if (log_threshold[b] != log_threshold[b]) return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": the log-threshold of block " + std::to_string(b) + " is NaN");
+            thr[b] = log_threshold[b];
+        }
+    }
+    if (h->W != 2 && h->W != 4) return fail(h, GPF_ERR_STATE, "row width");
+    const bool in_lds = block_pmmh_in_lds(block_size, h->W);
+    if ((s = check_ready(h)) || (s = materialize(h)) ||
+        (!in_lds && ((s = h->pmmh_rows.grow(h, (size_t)h->n * (2 * (size_t)h->W + 1))) || (s = h->pmmh_par.grow(h, (size_t)h->n)))) ||
+        (s = series_upload(h, nblocks, in_words, (size_t)nblocks))) return s;
+    PmmhArgs a{};
+    a.rows = h->rows[h->cur]; a.lw = h->lw; a.anc = h->anc; a.blk_params = h->blk_params; a.blk_obs = h->blk_obs;
+    a.srows = h->pmmh_rows; a.slw = in_lds ? nullptr : h->pmmh_rows + 2 * (size_t)h->n * (size_t)h->W; a.spar = h->pmmh_par;
+    a.n = h->n; a.nb = block_size; a.nblocks = nblocks; a.gid0 = h->cfg.gid0; a.seed = seed; a.n_steps = n_steps;
+    a.sorted = method == GPF_RESAMPLE_STRATIFIED && sort_particles ? 1 : 0;
+    a.ess_frac = ess_frac == ess_frac ? ess_frac : -1.0;
+    a.params = h->run_in + par_off; a.obs = h->run_in + MAX_PARAMS; a.obs_blocks = obs_blocks; a.n_obs = n_obs; a.thr = h->run_in + thr_off;
+    a.keep_mass = keep_mass ? 1 : 0;
+    a.acc_out = h->run_words; a.lml_out = h->run_stats;
+    const int m_id = method == GPF_RESAMPLE_MULTINOMIAL ? 0 : (method == GPF_RESAMPLE_RESIDUAL ? 1 : 2);
+    if ((s = timed(h, GPF_K_STEP, [&] { launch_block_pmmh(h, a, m_id); }))) return s;
+    HIP_TRY(h, hipGetLastError());
+    // (as after gpf_run_blocks: no gpf_resample_blocks to refer to, every cached weight summary forgotten; the epoch and the seed are the state's own)
+    h->blk_last = 0;
+    weights_written(h, false);
+    return block_out(h, {{h->run_words, accepted_out, (size_t)nblocks * sizeof(int32_t)}, {h->run_stats, lml_out, (size_t)nblocks * sizeof(double)}});
+}
 // one conditional SMC sweep per block -- n_steps x (gpf_resample_blocks_ancestor | _conditional with check = false, gpf_update_blocks_ref), then the one
 // path gpf_block_sample_trajectories would draw -- in one launch and without a store (k_block_sweep, libgpf_sweep.hip) -- gpf.h.  gpf_run_blocks with a
 // reference behind the observations, the genealogy slabs as scratch and two more outputs

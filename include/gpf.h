@@ -374,6 +374,46 @@ gpf_status gpf_run_blocks_rejuvenate(gpf_handle h, const double* obs, int32_t n_
                                      int64_t block_size, int32_t method, int32_t sort_particles, double ess_frac,
                                      int32_t rejuvenate_method, int32_t n_iters,
                                      double* ess_out, double* lml_out, int32_t* resampled_out, int64_t* accepted_out, int32_t* invalid);
+/* The particle-marginal MH move per block in ONE launch -- the step SMC^2, parallel particle-marginal MH and a likelihood surface over a parameter grid
+ * repeat: propose theta'_b, filter y_1:T again from the prior under theta'_b, compare the estimate of p(y_1:T | theta'_b) with a threshold, replace the
+ * block where it wins.  With `twin` a fresh filter of this model, size and gid0 created under `seed`, the rows `params` set as its per-block parameters,
+ * the call leaves bit for bit what this loop of calls leaves:
+ *     gpf_initialize_blocks(twin, obs[:, 0], n_obs, block_size);                                                       the twin's epoch 0
+ *     if n_steps > 1: gpf_run_blocks(twin, obs[:, 1:], n_obs, n_steps - 1, shared_obs, block_size, method, sort_particles, ess_frac, ...)   epochs 1 ..
+ *                     (its GPF_ERR_INVALID_WEIGHTS ignored)
+ *     gpf_block_stats(twin, block_size, NULL, Lp);                                                                     lml_out = Lp
+ *     accepted_out[b] = Lp[b] > log_threshold[b]      (strict; a NaN estimate compares false)
+ *     for every accepted b: rows, parents, parameter row and per-block observation row of h's block b <- the twin's block b;
+ *                           log-weights of b <- the twin's                                   (keep_mass = 0)
+ *                                            <- the twin's + (lme_h[b] - lme_twin[b])        (keep_mass != 0)
+ * lme = logsumexp(block log-weights) - log(block particles), gpf_block_stats' value without the filter's constant; the shift is ONE double per block,
+ * formed once and added per particle in that order -- the lw + (M - L[a]) of gpf_resample_across_blocks: the block keeps the mass it stands for at the
+ * outer level and takes the proposal's inner weights.  The twin exists only inside the launch: one team per block (a wave up to 512 particles, a
+ * workgroup up to 2048) runs the initial step and all later steps of its block; for blocks of up to 128 particles its rows, weights and parents never
+ * leave LDS, larger blocks keep them in device scratch of the call (16 W + 12 bytes per particle, kept on the handle).
+ *   h         a whole filter (no view, no shard) with per-block parameters AND per-block observations of this block size in force, clamped
+ *             block_size 1 .. 2048, no keep_prev, no trajectory store, no forward smoothing, no strata.
+ *   untouched blocks that are not accepted, bit for bit; h's RNG epoch and seed (nothing is drawn from h's streams).  As after gpf_run_blocks there is
+ *             no gpf_resample_blocks to refer to and the cached weight summary is forgotten.
+ *   obs       HOST, [n_blocks][n_steps][n_obs], or shared_obs != 0: [n_steps][n_obs].  The WHOLE series: row 0 is the observation of the initial
+ *             step.  All values finite, n_obs the model's, 1 <= n_steps <= 4097.
+ *   params    HOST, [n_blocks][n_params] proposed rows (gpf_set_block_params' layout), all finite.  An accepted row becomes the block's row
+ *             (gpf_get_block_params returns it).
+ *   log_threshold  HOST, [n_blocks]; -Inf: always replace where the estimate is finite, +Inf: never.  The caller's log u - log prior / proposal
+ *             ratio + current estimate.  n_blocks must be the filter's number of blocks.
+ *   seed      the proposal filter's.  Pass a fresh one per call, and one different from h's: the twin's streams are (seed, particle id, its epochs).
+ *   invalid   a proposal block whose final weights are invalid (NaN, +Inf, all -Inf) is never accepted, its lml_out is what gpf_block_stats reports;
+ *             with keep_mass a block of h with invalid weights is never replaced.  Neither is an error: the call returns GPF_OK.
+ *   outputs   HOST, each may be NULL: accepted_out int32 [n_blocks] (0 | 1), lml_out [n_blocks].
+ *   refused   nothing changed.  Everything gpf_run_blocks refuses, with its status codes; GPF_ERR_STATE: no per-block parameters, or no per-block
+ *             observations, of this block size in force; GPF_ERR_INVALID_ARGUMENT: params / log_threshold NULL, n_params outside 1 .. 24, n_blocks not
+ *             the filter's, a parameter that is not finite, a NaN threshold.  Not offered: proposals or rejuvenation inside the proposal filter, a
+ *             store or keep_prev on h, blocks of more than 2048 particles, the accept uniforms and the parameter proposal on the device, shards.
+ *   timing    the launch is booked under GPF_K_STEP. */
+gpf_status gpf_pmmh_blocks(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs, int64_t block_size,
+                           const double* params, int32_t n_params, const double* log_threshold, int64_t n_blocks, uint64_t seed,
+                           int32_t method, int32_t sort_particles, double ess_frac, int32_t keep_mass,
+                           int32_t* accepted_out, double* lml_out);
 /* One conditional SMC sweep per block in ONE launch: the conditional filter of particle Gibbs (Andrieu, Doucet & Holenstein 2010), with ancestor
  * sampling (PGAS; Lindsten, Jordan & Schoen 2014) where ancestor_sampling != 0, and the one path per block that the sweep exists to draw,
  *     for t in 1:n_steps

@@ -464,6 +464,24 @@ function pf_run_blocks_rejuvenate!(s::DeviceParticleFilterState, observations::U
                      ess_frac === nothing ? NaN : Float64(ess_frac), r, n_iters, ess, lml, words, accepted, invalid))
     return lml, ess, (words .& Int32(1)) .!= 0, accepted
 end
+# The particle-marginal MH move per block in ONE launch (gpf.h gpf_pmmh_blocks): a proposal filter per block under the proposed parameter rows
+# params (n_params, n_blocks) and `seed` -- pass a fresh one per call, different from the state's -- is initialised with observations[:, 1, b], run over
+# the rest of the series inside the launch, and replaces block b (rows, parents, parameter row, observation row; the log-weights shifted so that the
+# block keeps its mass where keep_mass) where its log-ML estimate exceeds log_threshold[b].  observations: (n_obs, T, n_blocks), or a (n_obs, T) Matrix
+# shared by all blocks -- the WHOLE series.  Blocks that are not accepted, the state's epoch and its seed are untouched.  Returns (accepted, lml).
+function pf_pmmh_blocks!(s::DeviceParticleFilterState, observations::Union{Array{Float64,3},Matrix{Float64}}, params::Matrix{Float64}, log_threshold::Vector{Float64},
+                         block_size::Int, method::Symbol=:multinomial; seed::Integer, ess_frac=0.5, sort_particles::Bool=true, keep_mass::Bool=true)
+    m = method == :multinomial ? 0 : method == :residual ? 1 : method == :stratified ? 2 : error("Resampling method $method not recognized.")
+    nb = cld(s.n_particles, min(block_size, s.n_particles)); T = size(observations, 2)
+    shared = ndims(observations) == 2
+    shared || size(observations, 3) == nb || error("one series per block expected: observations of size (n_obs, T, $nb)")
+    (size(params, 2) == nb && length(log_threshold) == nb) || error("one proposed parameter column and one log-threshold per block expected: $nb")
+    accepted = Vector{Int32}(undef, nb); lml = Vector{Float64}(undef, nb)
+    _status(s, ccall((:gpf_pmmh_blocks, libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Cint, Int64, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Int64, UInt64, Cint, Cint, Cdouble, Cint, Ptr{Cint}, Ptr{Cdouble}),
+                     s.handle, observations, size(observations, 1), T, shared ? 1 : 0, block_size, params, size(params, 1), log_threshold, nb, UInt64(seed), m,
+                     sort_particles ? 1 : 0, ess_frac === nothing ? NaN : Float64(ess_frac), keep_mass ? 1 : 0, accepted, lml))
+    return accepted .!= 0, lml
+end
 # One conditional SMC sweep per block in ONE launch (gpf.h gpf_sweep_blocks): bit for bit T iterations of the conditional resample (with ancestor
 # sampling towards reference[:, t, b] where ancestor_sampling) and the update pinned to reference[:, t, b], then the one path per block that
 # block_sample_trajectories would draw -- on a state without a trajectory store.  observations: (n_obs, T, n_blocks), or a (n_obs, T) Matrix shared by all
