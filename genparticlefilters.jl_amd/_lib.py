@@ -72,6 +72,8 @@ SYMBOLS = [
                                    _pd, _pd, _pi32, _pi32]),
     ("gpf_sweep_blocks_backward", C.c_int, [_H, _pd, C.c_int32, C.c_int32, C.c_int32, _pd, C.c_int32, C.c_int64, C.c_int32, C.c_double, _pd,
                                             C.POINTER(C.c_int64), _pd, _pd, _pi32, _pi32]),
+    ("gpf_gibbs_blocks", C.c_int, [_H, _pd, C.c_int32, C.c_int32, C.c_int32, _pd, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_double,
+                                   C.POINTER(C.c_uint64), C.c_int32, C.c_int32, _pd, _pd]),
     ("gpf_set_block_params", C.c_int, [_H, _pd, C.c_int32, C.c_int64]),
     ("gpf_get_block_params", C.c_int, [_H, _pd, C.c_int32, C.c_int64]),
     ("gpf_resample_across_blocks", C.c_int, [_H, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32, _pi32, _pi32, _pd]),

@@ -961,6 +961,65 @@ def pf_sweep_blocks_backward(state, observations, reference, block_size: int, *,
     return BlockSweepBackward(*_sweep_call(state, "pf_sweep_blocks_backward", observations, reference, block_size, ancestor_sampling, ess_frac, True))
 
 
+BlockGibbs = namedtuple("BlockGibbs", ["paths", "lml"])
+
+
+def pf_gibbs_blocks(state, observations, reference, block_size: int, seeds, *, ancestor_sampling: bool = True, backward: bool = False, ess_frac=0.5,
+                    thin: int = 1) -> BlockGibbs:
+    """The particle Gibbs chain per block in ONE launch (gpf.h gpf_gibbs_blocks) -- sweep, take the drawn path as the next retained path, sweep again;
+    PGAS used as a smoother is the same chain.  Bit for bit the loop, with K = len(seeds),
+
+        for k in range(K):
+            tw = pf_initialize_blocks(state.model, (), observations[:, 0], state.n_particles, block_size, seed=seeds[k],
+                                      params=<the state's per-block rows, if in force>, reference=reference[:, 0])
+            sw = (pf_sweep_blocks_backward if backward else pf_sweep_blocks)(tw, observations[:, 1:], reference[:, 1:], block_size,
+                                                                            ancestor_sampling=ancestor_sampling, ess_frac=ess_frac)
+            lml[:, k] = sw.lml[:, -1];  reference = sw.path
+            if (k + 1) % thin == 0: kept.append(sw.path)
+
+    without a fresh handle per sweep and without the path crossing the bus between sweeps: the filters exist only inside the launch.
+    state: the carrier of model, size, device, parameters and per-block parameters -- a whole block-wise filter, at most 2048 particles per block, no
+    keep_prev, store, forward mode or strata.  The call writes NOTHING of it: state.checkpoint() gives the same bytes before and after.
+    observations: (n_blocks, T, n_obs), or (T, n_obs) shared by all blocks -- the WHOLE series, row 0 being the observation of the initial step, T >= 2.
+    reference: (n_blocks, T, dim), the whole initial retained path of every block, all finite.  seeds: K unsigned 64-bit values, a fresh one per
+    sweep and different from the state's -- sweep k's streams are (seeds[k], particle id, its epochs).  thin >= 1 keeps every thin-th path.
+    Returns BlockGibbs(paths, lml): paths (n_blocks, K // thin, T, dim) -- paths[:, -1] is the next call's reference: chains compose; lml (n_blocks, K),
+    the log-ML estimate of every sweep's filter.  A block whose sweep ends with NaN / +Inf weights reads NaN in that and every later kept path and
+    lml entry; the other blocks are unaffected and nothing is raised."""
+    if isinstance(state, DeviceParticleFilterSubState):
+        raise ErrorException("pf_gibbs_blocks works on the whole filter")
+    if int(block_size) < 1:
+        raise ErrorException("block_size < 1")
+    bs = min(int(block_size), max(state.n_particles, 1))
+    nb = (state.n_particles + bs - 1) // bs
+    obs = np.ascontiguousarray(observations, np.float64)
+    if obs.ndim == 3 and obs.shape[0] == nb:
+        shared = False
+    elif obs.ndim == 2:
+        shared = True
+    else:
+        raise ErrorException(f"observations of shape ({nb}, T, n_obs), or (T, n_obs) for one series shared by all blocks, expected: got {obs.shape}")
+    T = obs.shape[0] if shared else obs.shape[1]
+    if T < 2:
+        raise ErrorException(f"the whole series expected -- the initial step and at least one step of the sweep: T = {T}")
+    ref = np.ascontiguousarray(reference, np.float64)
+    if ref.ndim != 3 or ref.shape[:2] != (nb, T):
+        raise ErrorException(f"a reference of shape ({nb}, {T}, dim) expected -- the whole retained path of every block: got {ref.shape}")
+    sd =np.ascontiguousarray([int(s) & 0xFFFFFFFFFFFFFFFF for s in np.asarray(seeds, dtype=object).ravel()], np.uint64)
+    if sd.size < 1:
+        raise ErrorException("seeds: one fresh seed per sweep expected, got none")
+    if int(thin) < 1:
+        raise ErrorException("thin < 1")
+    K = int(sd.size)
+    paths, lml = np.empty((nb, K // int(thin), T, ref.shape[2])), np.empty((nb, K))
+    st = state._L.gpf_gibbs_blocks(state._h, _pd(obs), obs.shape[-1], T, int(shared), _pd(ref), ref.shape[2], int(block_size), int(bool(ancestor_sampling)),
+                                   int(bool(backward)), float("nan") if ess_frac is None else float(ess_frac), sd.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                   K, int(thin), _pd(paths), _pd(lml))
+    if st != _lib.OK:
+        raise ErrorException(state._L.gpf_last_error(state._h).decode())
+    return BlockGibbs(paths, lml)
+
+
 def pf_rejuvenate_blocks(state, kern=None, kern_args: tuple = (), n_iters: int = 1, *, method: str = "move", only_resampled: bool = False,
                          count: bool = False):
     """for b in blocks: pf_rejuvenate!(state[b], ...) with the block's own latest observation; only_resampled: only the blocks the last

@@ -285,6 +285,10 @@ struct __attribute__((visibility("hidden"))) gpf_filter : gpfh::Bufs {
     Dev<double> sweep_rows, sweep_path; Dev<uint16_t> sweep_par; Dev<int64_t> sweep_idx;
     // gpf_sweep_blocks_backward (which uses the four above, the index as [n_blocks][n_steps + 1]): the log-weight slabs [n_steps][n] beside the rows
     Dev<double> sweep_lws;
+    // gpf_gibbs_blocks (which uses the sweep's slabs, parents and weight slabs for T - 1 steps, run_in as [observations | n_blocks x T x dim retained
+    // paths, overwritten in place by every sweep | K seeds], run_words as the resample words and run_stats as [n_blocks][K] estimates): the [n]
+    // log-weights of the filter that exists only inside the launch, and the kept paths [n_blocks][K / thin][T][dim].  Scratch of one call, kept for the next
+    Dev<double> gibbs_lw, gibbs_paths;
     // gpf_resample_across_blocks: the planner filter of n_blocks particles whose log-weights are the blocks' log-ML estimates (its ancestors name the
     // source block of every block; it runs on this filter's stream), the second buffers the per-block rows are gathered into (swapped with
     // blk_params / blk_obs), and the 1-based block ancestors of the last call that fired with the buffers they refer to (gpf_block_ancestors)
@@ -757,6 +761,8 @@ void launch_block_run_hist(gpf_filter* h, const RunArgs& a, const RunHistArgs& h
 // ---- defined in libgpf_pmmh.hip
 void launch_block_pmmh(gpf_filter* h, const PmmhArgs& a, int method);             // k_block_pmmh<model, W, method, TEAM, ITEMS> by team_dispatch; method 0 | 1 | 2
 bool block_pmmh_in_lds(int64_t block_size, int W);                                // the proposal filter of a block of this size lives in LDS: no device scratch
+// ---- defined in libgpf_gibbs.hip
+void launch_block_gibbs(gpf_filter* h, const GibbsArgs& a, bool ancestor_sampling, bool backward);   // k_block_gibbs<model, W, AS, TEAM, ITEMS, BACK> by team_dispatch
 // ---- defined in libgpf_forward.hip: the forward-only smoother's records (hist_begin_step / hist_on_resample call the first two) and launches
 gpf_status fwd_begin_step(gpf_filter* h, bool first);             // first: step 1 begins, the statistics are reset; else the step that ends is closed in its final order
 gpf_status fwd_on_resample(gpf_filter* h, int64_t block_size);    // this call's parents into the current step's map (block_size > 0: block-local, h->blk_mask says which)

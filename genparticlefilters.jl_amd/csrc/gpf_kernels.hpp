@@ -33,3 +33,4 @@
 #include "gpf_k_block_run_move.hpp"
 #include "gpf_k_block_run_wide.hpp"
 #include "gpf_k_block_pmmh.hpp"
+#include "gpf_k_block_gibbs.hpp"

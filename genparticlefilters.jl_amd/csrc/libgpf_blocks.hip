@@ -1043,6 +1043,66 @@ gpf_status gpf_sweep_blocks_backward(gpf_handle h, const double* obs, int32_t n_
     return sweep_impl(h, "gpf_sweep_blocks_backward", true, obs, n_obs, n_steps, shared_obs, ref, n_ref, block_size, ancestor_sampling, ess_frac, path_out,
                       idx_out, ess_out, lml_out, resampled_out, invalid);
 }
+// The particle Gibbs chain per block in one launch (k_block_gibbs, libgpf_gibbs.hip) -- gpf.h: n_sweeps times (a fresh filter under seeds[k], initialised
+// with its slot 0 pinned to the retained path, swept over the rest of the series, its drawn path the next retained one), the filter existing only inside
+// the launch.  sweep_impl's gate and checks, then the call's own; one pass over each input, which is its check and its copy into the pinned buffer
+// [MAX_PARAMS | observations | pad to an even word | n_blocks x n_steps x dim retained paths | n_sweeps seeds]; one upload, one launch, the two outputs
+// read back.  The handle is the carrier of model, size, gid0, device and parameters: nothing of it is written, neither epoch nor weight-summary cache
+// nor block bookkeeping -- every buffer the launch writes is scratch of the call.
+gpf_status gpf_gibbs_blocks(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs, const double* ref, int32_t n_ref,
+                            int64_t block_size, int32_t ancestor_sampling, int32_t backward, double ess_frac, const uint64_t* seeds, int32_t n_sweeps,
+                            int32_t thin, double* paths_out, double* lml_out)
+{
+    const std::string who = "gpf_gibbs_blocks";
+    gpf_status s = block_gate(h, block_size, who.c_str(), GATE_SERIES);
+    // (n_steps counts the initial step: the sweep behind it has n_steps - 1, and series_checks' range is [1, 4096])
+    if (s || (s = series_checks(h, who, "sweep", "gpf_initialize_blocks_ref / gpf_sweep_blocks on a second filter", block_size, n_steps > 2 ? n_steps - 1 : 1))) return s;
+    if (n_steps < 2) return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": need 2 <= n_steps <= 4097: the initial step and at least one step of the sweep");
+    if (!seeds || n_sweeps < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": need n_sweeps >= 1 seeds, a fresh one per sweep");
+    if (thin < 1) return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": thin < 1");
+    if (!paths_out || !lml_out) return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": null paths / lml output");
+    const int64_t nblocks = (h->n + block_size - 1) / block_size, obs_blocks = shared_obs ? 1 : nblocks;
+    if ((s = block_obs_check(h, obs, n_obs))) return s;
+    const int dim = model_dim(h->cfg.model);
+    if (!ref || n_ref != dim)                                    // (block_ref_checks' refusal)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": the reference has " + std::to_string(dim) + " values per block and step (the model's latent columns)");
+    const int64_t obs_words = (int64_t)n_steps * obs_blocks * n_obs, ref_words = (int64_t)n_steps * nblocks * dim;
+    if (obs_words + ref_words > ((int64_t)1 << 31))
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": the observations and the reference of the call exceed 2^31 words on the device: a shorter series");
+    // (the retained paths are stored as 16-byte column pairs: they begin at an even word)
+    const size_t ref_off = ((size_t)MAX_PARAMS + (size_t)obs_words + 1) & ~(size_t)1, seed_off = ref_off + (size_t)ref_words, in_words = seed_off + (size_t)n_sweeps;
+    const int32_t n_kept = n_sweeps / thin;
+    const size_t path_words = (size_t)nblocks * (size_t)n_kept * (size_t)n_steps * (size_t)dim, lml_words = (size_t)nblocks * (size_t)n_sweeps;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if ((s = h->h_run_in.grow(h, in_words)) || (s = series_obs_in(h, who, obs, obs_words, n_obs, n_steps, shared_obs != 0))) return s;
+    if (ref_off > (size_t)MAX_PARAMS + (size_t)obs_words) h->h_run_in[ref_off - 1] = 0.0;       // (the pad word: never read)
+    if (const int64_t k = copy_finite(h->h_run_in + ref_off, ref, ref_words); k >= 0)
+        return fail(h, GPF_ERR_INVALID_ARGUMENT, who + ": the reference of block " + std::to_string(k / dim / n_steps) + " is not finite (step " +
+                    std::to_string(k / dim % n_steps + 1) + ")");
+    memcpy(h->h_run_in + seed_off, seeds, (size_t)n_sweeps * sizeof(uint64_t));       // (64-bit words among the doubles: the kernel reads them as such)
+    for (int i = 0; i < MAX_PARAMS; ++i) h->h_run_in[i] = h->args.P[i];
+    if (h->W != 2 && h->W != 4) return fail(h, GPF_ERR_STATE, "row width");
+    if ((s = check_ready(h, true))) return s;                    // (a lazy move stays pending: the call reads no particle)
+    // ---- device scratch: the sweep's slabs for n_steps - 1 steps, reused by every sweep; the filter's weights; the outputs
+    const size_t ns = (size_t)n_steps - 1;
+    if ((s = h->sweep_rows.grow(h, (size_t)n_steps * (size_t)h->n * (size_t)h->W)) || (s = h->sweep_par.grow(h, ns * (size_t)h->n)) ||
+        (backward && (s = h->sweep_lws.grow(h, ns * (size_t)h->n))) || (s = h->gibbs_lw.grow(h, (size_t)h->n)) ||
+        (s = h->gibbs_paths.grow(h, std::max<size_t>(path_words, 1))) || (s = h->run_in.grow(h, in_words)) || (s = h->run_stats.grow(h, lml_words)) ||
+        (s = h->run_words.grow(h, ns * (size_t)nblocks))) return s;
+    HIP_TRY(h, hipMemcpyAsync(h->run_in, h->h_run_in, in_words * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    GibbsArgs a{};
+    a.slabs = h->sweep_rows; a.par = h->sweep_par; a.res = h->run_words; a.lws = backward ? h->sweep_lws.p : nullptr; a.lw = h->gibbs_lw;
+    a.cur = h->run_in + ref_off;
+    a.n = h->n; a.nb = block_size; a.nblocks = nblocks; a.gid0 = h->cfg.gid0;
+    a.seeds = reinterpret_cast<const uint64_t*>(h->run_in + seed_off); a.n_sweeps = n_sweeps; a.thin = thin; a.n_kept = n_kept; a.n_steps = n_steps;
+    a.ess_frac = ess_frac == ess_frac ? ess_frac : -1.0;
+    a.P = h->run_in; a.blk_params = h->bp_size > 0 ? h->blk_params.p : nullptr;
+    a.obs = h->run_in + MAX_PARAMS; a.obs_blocks = obs_blocks; a.n_obs = n_obs;
+    a.paths = h->gibbs_paths; a.lml = h->run_stats;
+    if ((s = timed(h, GPF_K_STEP, [&] { launch_block_gibbs(h, a, ancestor_sampling != 0, backward != 0); }))) return s;
+    HIP_TRY(h, hipGetLastError());
+    return block_out(h, {{h->gibbs_paths, path_words ? paths_out : nullptr, path_words * sizeof(double)}, {h->run_stats, lml_out, lml_words * sizeof(double)}});
+}
 gpf_status gpf_rejuvenate_blocks(gpf_handle h, int32_t method, int32_t n_iters, int32_t only_resampled, uint64_t* n_accepted)
 {
     gpf_status s = check_ready(h);

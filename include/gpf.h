@@ -473,6 +473,44 @@ gpf_status gpf_sweep_blocks(gpf_handle h, const double* obs, int32_t n_obs, int3
 gpf_status gpf_sweep_blocks_backward(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs,
                                      const double* ref, int32_t n_ref, int64_t block_size, int32_t ancestor_sampling, double ess_frac,
                                      double* path_out, int64_t* idx_out, double* ess_out, double* lml_out, int32_t* resampled_out, int32_t* invalid);
+/* The particle Gibbs chain per block in ONE launch: sweep, take the drawn path as the retained one, sweep again, n_sweeps times -- what particle Gibbs
+ * (and PGAS used as a smoother) repeats.  Bit for bit
+ *     for k in 0 .. n_sweeps - 1
+ *         twin = a fresh filter of h's size, model, gid0 and parameters under seeds[k] (h's per-block parameter rows where they are in force)
+ *         gpf_initialize_blocks_ref(twin, obs[:, 0], n_obs, block_size, ref[:, 0], n_ref)                                  epoch 0
+ *         (backward ? gpf_sweep_blocks_backward : gpf_sweep_blocks)(twin, obs[:, 1:], ..., ref[:, 1:], ..., ancestor_sampling, ess_frac) -> path, lml
+ *         lml_out[:, k] = lml[n_steps - 2][:];  ref = path;  (k + 1) % thin == 0: paths_out[:, (k + 1) / thin - 1] = path
+ *     end
+ * without any twin: one team per block (a wave up to 512 particles, a workgroup up to 2048) runs all n_sweeps sweeps of its block inside the launch --
+ * the initial step with slot 0 pinned, the n_steps - 1 steps of the conditional filter, the path draw --, and the retained path stays on the device:
+ * every sweep reads it as the reference and overwrites it with its draw.  Scratch is that of ONE sweep (gpf_sweep_blocks: 8 W n_steps + 2 (n_steps - 1)
+ * bytes per particle, backward: 8 (n_steps - 1) more), reused by every sweep, plus 8 bytes per particle and the outputs; kept on the handle.
+ *   streams   twin k's are (seeds[k], gid0 + particle, epoch): epoch 0 the initial step; step t = 0 .. n_steps - 2 of the sweep resamples under 1 + 2t
+ *             (slot 0's own counter serves the ancestor draw) and propagates under 2 + 2t; the path draw of block b reads slot b of epoch
+ *             1 + 2 (n_steps - 1), the backward draws the epochs behind it, as gpf_sweep_blocks_backward counts them.  Pass fresh seeds, different
+ *             from h's: a repeated seed repeats a sweep's noise.
+ *   h         the carrier of model, size, gid0, device, parameters and per-block parameters, and of the call's scratch: a whole initialised filter (no
+ *             view, no shard), clamped block_size 1 .. 2048, no keep_prev, no trajectory store, no forward smoothing, no strata.  NOTHING of it is
+ *             written: rows, log-weights, parents, epoch, seed, per-block observations, the cached weight summary and "the gpf_resample_blocks to
+ *             refer to" stay as they are -- gpf_checkpoint gives the same bytes before and after.
+ *   obs       HOST, [n_blocks][n_steps][n_obs], or shared_obs != 0: [n_steps][n_obs].  The WHOLE series: row 0 is the observation of the initial
+ *             step.  All values finite, n_obs the model's, 2 <= n_steps <= 4097.
+ *   ref       HOST, [n_blocks][n_steps][n_ref]: the whole initial retained path of every block, all finite, n_ref the model's dimension.
+ *   seeds     HOST, [n_sweeps] -- one per sweep.  thin >= 1: every thin-th path is kept, n_kept = n_sweeps / thin.
+ *   outputs   HOST, both needed: paths_out [n_blocks][n_kept][n_steps][dim] -- the last kept path is the next call's ref: chains compose --,
+ *             lml_out [n_blocks][n_sweeps] -- the log-ML estimate of every sweep's filter (gpf_block_stats on the twin behind its last step).
+ *   ess_frac  as in gpf_sweep_blocks; NaN: every block resamples at every step.
+ *   weights   a block whose sweep ends with final weights that hold a NaN or +Inf -- the loop would read a NaN path and refuse it as the next
+ *             reference -- has NaN in that and every later kept path and lml entry and does no further work; the other blocks are unaffected and
+ *             the call returns GPF_OK.
+ *   timing    the launch is booked under GPF_K_STEP.
+ *   refused   nothing changed.  Everything gpf_sweep_blocks refuses, with its status codes; GPF_ERR_INVALID_ARGUMENT: n_steps < 2, seeds NULL or
+ *             n_sweeps < 1, thin < 1, an output NULL.  Not offered: blocks of more than 2048 particles, rejuvenation, proposals or strata inside the
+ *             sweeps, residual / stratified conditional schemes, a parameter update between sweeps, shards, more than one path per sweep. */
+gpf_status gpf_gibbs_blocks(gpf_handle h, const double* obs, int32_t n_obs, int32_t n_steps, int32_t shared_obs,
+                            const double* ref, int32_t n_ref, int64_t block_size, int32_t ancestor_sampling, int32_t backward,
+                            double ess_frac, const uint64_t* seeds, int32_t n_sweeps, int32_t thin,
+                            double* paths_out, double* lml_out);
 /* Conditional SMC, the propagation half: gpf_initialize_blocks / gpf_update_blocks with ONE PARTICLE PER BLOCK PINNED to a given value -- the
  * conditional filter of Andrieu, Doucet & Holenstein (2010), section 4.3 (step (a) / (b): "set X_n^{B_n} = the retained path, sample the other
  * N - 1 particles"), on the reference's per-view loop

@@ -518,6 +518,26 @@ function pf_sweep_blocks_backward!(s::DeviceParticleFilterState, observations::U
                      ess_frac === nothing ? NaN : Float64(ess_frac), path, indices, ess, lml, words, invalid))
     return path, indices, lml, ess, (words .& Int32(1)) .!= 0
 end
+# The particle Gibbs chain per block in ONE launch (gpf.h gpf_gibbs_blocks): length(seeds) times (a fresh filter under seeds[k], initialised with slot 0
+# pinned to reference[:, 1, b], swept over the rest of the series as pf_sweep_blocks! / pf_sweep_blocks_backward! sweep it, its drawn path the next
+# retained path) inside the launch.  The state only carries model, size, device and parameters: nothing of it is written.  observations:
+# (n_obs, T, n_blocks), or a (n_obs, T) Matrix shared by all blocks -- the WHOLE series; reference: (dim, T, n_blocks), the whole initial retained paths.
+# Returns (paths, lml): paths (dim, T, length(seeds) ÷ thin, n_blocks) -- every thin-th path; the last one is the next call's reference --, lml
+# (length(seeds), n_blocks).
+function pf_gibbs_blocks!(s::DeviceParticleFilterState, observations::Union{Array{Float64,3},Matrix{Float64}}, reference::Array{Float64,3}, block_size::Int,
+                          seeds::Vector{UInt64}; ancestor_sampling::Bool=true, backward::Bool=false, ess_frac=0.5, thin::Int=1)
+    nb = cld(s.n_particles, min(block_size, s.n_particles)); T = size(observations, 2)
+    shared = ndims(observations) == 2
+    shared || size(observations, 3) == nb || error("one series per block expected: observations of size (n_obs, T, $nb)")
+    (size(reference, 2) == T && size(reference, 3) == nb) || error("one retained path per block expected: reference of size (dim, $T, $nb)")
+    (T >= 2 && length(seeds) >= 1 && thin >= 1) || error("the whole series (T >= 2), one seed per sweep and thin >= 1 expected")
+    K = length(seeds)
+    paths = Array{Float64,4}(undef, size(reference, 1), T, K ÷ thin, nb); lml = Matrix{Float64}(undef, K, nb)
+    _status(s, ccall((:gpf_gibbs_blocks, libgpf), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Cint, Ptr{Cdouble}, Cint, Int64, Cint, Cint, Cdouble, Ptr{UInt64}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+                     s.handle, observations, size(observations, 1), T, shared ? 1 : 0, reference, size(reference, 1), block_size, ancestor_sampling ? 1 : 0,
+                     backward ? 1 : 0, ess_frac === nothing ? NaN : Float64(ess_frac), seeds, K, thin, paths, lml))
+    return paths, lml
+end
 # for b in blocks: the model arguments of state[b] (src/update.jl:12-25 on a sub-state with new_args_b) -- gpf.h gpf_set_block_params.  params: a
 # (n_params, n_blocks) Matrix, column b = block b's parameter vector in the layout of csrc/gpf_models.hpp (derived constants included), or a
 # Vector of NativeModel descriptors of the state's model; `nothing` clears them.  While set, the block-wise calls use column b for block b (this
